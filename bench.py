@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5] [--strong] ...
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5] [--strong] [--full] [--dump-outputs DIR] ...
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up the batch, runs W warm-up and K timed steps, and prints the line: the headline (`value`, `ms_per_step`)
+and the rooflines, which are arithmetic on the stats of those steps.  --full adds what takes work of its own after the
+timed region: device clocks, the collection, the CPU baseline with the parity sample, the invariants and `parity_full`
+(config 2), `e2e`, and the `secondary` lines of configs 4 / 5 / 5x and the chromosome pairs (config 2 at its default size).
+--dump-outputs DIR writes what the last timed step computed (rank 0's batch) as DIR/<name>.npy, float32 or float64.
 
 Workloads (BASELINE.json `configs`):
   --config 2 (default, the headline; configs[1] at N=1, configs[2] sharded at N>1): per GPU 1,000,000 synthetic
@@ -65,6 +71,8 @@ CONFIGS = {
 }
 PATH_CONFIGS = (5, 6)
 TARGET_LEN, READ_LEN = 5_000_000, 150
+DUMP_LIMIT_BYTES = 60 * 10**6               # --dump-outputs: the arrays of all files together (64 MB with room for the headers)
+DUMP_SAMPLE_SEED = 12351
 
 
 # ------------------------------------------------------------------------------------------ launch
@@ -480,6 +488,43 @@ def run_step(cfg_id, batch):
     return st
 
 
+def last_step_outputs(cfg_id, batch):
+    """what a caller of the timed path receives from its last step: every array of the results view and, for the PATH
+    workloads, both CIGAR formats (the NUL-terminated strings one after the other, and their offsets).  A task without
+    paths has no op bytes: its alnOff / alignment are left out."""
+    out = {k: v for k, v in batch.results_flat(copy=True).items() if v is not None}
+    if out["alignment"].size == 0:
+        del out["alnOff"], out["alignment"]
+    if cfg_id in PATH_CONFIGS:
+        for name, extended in (("cigar_extended", True), ("cigar_standard", False)):
+            out[name + "_chars"], out[name + "_off"] = batch.cigars(extended, copy=True)
+    return out
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Every non-empty (integer) array as <outdir>/<name>.npy: float32 where each value is exact in it, float64 otherwise.
+    When the whole would pass `limit` bytes, each array larger than an even share of it is cut to a fixed, seeded sample of
+    its elements (the same positions for the same length), and the positions go beside it as <name>.index.npy."""
+    def float_type(a):
+        exact32 = max(-int(a.min()), int(a.max())) < 2 ** 24
+        return np.dtype(np.float32 if exact32 else np.float64)
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if np.asarray(v).size > 0}
+    types = {k: float_type(a) for k, a in arrays.items()}
+    sample = sum(a.size * types[k].itemsize for k, a in arrays.items()) > limit
+    share = limit // max(1, len(arrays))
+    files = {}
+    for name, a in arrays.items():
+        t = types[name]
+        if sample and a.size * t.itemsize > share:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=share // (t.itemsize + 8), replace=False))
+            files[name], files[name + ".index"] = a[idx].astype(t), idx.astype(float_type(idx))
+        else:
+            files[name] = a.astype(t)
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def device_cigars(batch):
     """both CIGAR formats of the batch as the concatenation of the strings (no terminators), made by the library over the
     whole batch (edlibAmdBatchCigarView)"""
@@ -535,7 +580,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the configs 4 / 5 lines that a default (config 2, full size, 1 GPU) run appends")
+                    help="skip the configs 4 / 5 lines that a --full config-2 run (full size, 1 GPU) appends")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline: clocks, collection, "
+                         "CPU baseline + parity, invariants, parity_full, e2e, the secondary configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--parity-sample", type=int, default=None,
                     help="units checked against the reference (default: 20000 for config 2, the whole batch for 4 / 5)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo with --share-gpu)")
@@ -602,7 +652,9 @@ def main():
     dt_local = time.perf_counter() - t0
     sync()
     dt_sync = time.perf_counter() - t0
-    clocks_after = device_clocks(device) if rank == 0 else None          # (outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(args.config, batch))
+    clocks_after = device_clocks(device) if rank == 0 and args.full else None          # (outside the timed region)
     from edlib_amd.parallel import aggregate_throughput, gather_int_results
     # whole-job cells (SUM over ranks) and the slowest rank's time (MAX over ranks, barrier included)
     cells_all, dt = aggregate_throughput(st["cells"] * args.steps, dt_sync, dist, coll_dev)
@@ -615,9 +667,9 @@ def main():
         devices = [x[1] for x in tl]
     flat = None
     coll_note = None
-    # (rank 0 also at world > 1: the line of a multi-rank run carries the reference baseline and the parity check of rank 0's
+    # (rank 0 also at world > 1: the --full line of a multi-rank run carries the reference baseline and the parity check of rank 0's
     # OWN shard -- taken after the timed region, while the other ranks wait at the closing barrier)
-    if args.dump or (rank == 0 and not args.no_cpu_baseline):
+    if args.dump or (rank == 0 and args.full and not args.no_cpu_baseline):
         coll_note, flat = measure_collection(args.config, batch, round(dt_sync / max(1, args.steps) * 1e3, 2))
     if args.dump:
         total = units if args.strong else units * world
@@ -633,14 +685,15 @@ def main():
             if not coll_note.get("inside_step"):
                 coll_note["ms_per_step_plus_one_collection"] = round(out["ms_per_step"] + coll_note["results_flat_ms"], 3)
             out["collection"] = coll_note
-        out["clocks"] = {"right_after_the_timed_steps": clocks_after, "after_the_run": device_clocks(device),
-                         "source": "rocm-smi --showclocks --showpower --showtemp (rank 0's device)"}
+        if args.full:
+            out["clocks"] = {"right_after_the_timed_steps": clocks_after, "after_the_run": device_clocks(device),
+                             "source": "rocm-smi --showclocks --showpower --showtemp (rank 0's device)"}
         out["per_rank_ms_per_step"] = per_rank_ms
         out["devices"] = devices
         out["devices_distinct"] = len(set(devices))
         if args.share_gpu:
             out["dry_run_shared_gpu"] = True
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             sample = args.parity_sample if args.parity_sample is not None else (20000 if args.config == 2 else (10000 if args.config == 6 else w["n"]))
             base, parity = cpu_baseline_and_parity(w, flat, sample, batch if args.config == 5 else None)
             if world > 1:
@@ -650,7 +703,7 @@ def main():
             out["parity_sample"] = parity
             if args.config == 2:
                 out["invariants"] = invariants_config2(w, flat)
-                # the WHOLE batch against the reference's committed answers (tests/golden/c2_full_ref.npz), when this is the
+                # the WHOLE batch against the reference's committed answers (tests/golden/c2_full_ref/), when this is the
                 # batch they were made for (1,000,000 reads, rank 0, weak scaling)
                 try:
                     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -660,7 +713,7 @@ def main():
                         out["parity_full"] = pf
                 except Exception as e:                                 # the headline line must survive
                     out["parity_full"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and args.config == 2 and not args.no_e2e:
+        if args.full and world == 1 and args.config == 2 and not args.no_e2e:
             r = e2e_config2(w)
             if isinstance(r, tuple):
                 out["e2e"] = r[0]
@@ -673,8 +726,8 @@ def main():
     batch.close()
     del batch, w, flat
     # BASELINE configs 4 and 5 at their full sizes, AFTER the headline's timed region and on the same device: every
-    # default run carries a driver-visible line for them (value, rooflines, reference baseline, whole-batch parity)
-    if rank == 0 and world == 1 and args.config == 2 and args.units is None and not args.no_secondary and not args.no_cpu_baseline:
+    # --full config-2 run carries a driver-visible line for them (value, rooflines, reference baseline, whole-batch parity)
+    if args.full and rank == 0 and world == 1 and args.config == 2 and args.units is None and not args.no_secondary and not args.no_cpu_baseline:
         out["secondary"] = {}
         for cid in (4, 5, 6):
             try:

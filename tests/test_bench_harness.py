@@ -62,6 +62,28 @@ def test_checker_arithmetic(ref):
     assert par["bit_exact"] == 64 and par["cigar_extended_equal"] and par["cigar_standard_equal"] and par["op_bytes_equal"]
 
 
+def test_dump_outputs_float_types_and_seeded_sample(tmp_path):
+    """--dump-outputs writes float32 where every value is exact in it, float64 otherwise; over the size limit, the same
+    seeded positions of every large array, with the positions beside it"""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(-5, 1000, dtype=np.int32)
+    big = np.array([0, 2 ** 24, 3 * 10 ** 9], dtype=np.int64)
+    bench.dump_outputs(str(tmp_path / "whole"), {"small": small, "big": big, "empty": np.zeros(0, dtype=np.uint8)})
+    a, b = (np.load(str(tmp_path / "whole" / (n + ".npy"))) for n in ("small", "big"))
+    assert a.dtype == np.float32 and np.array_equal(a, small)
+    assert b.dtype == np.float64 and np.array_equal(b, big)
+    assert sorted(os.listdir(str(tmp_path / "whole"))) == ["big.npy", "small.npy"]          # no empty outputs
+    long_ = np.arange(100000, dtype=np.int32) * 7
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"long": long_, "short": small}, limit=80000)
+    v, i = np.load(str(tmp_path / "s1" / "long.npy")), np.load(str(tmp_path / "s1" / "long.index.npy"))
+    assert 0 < len(v) == len(i) < len(long_) and np.array_equal(v, long_[i.astype(np.int64)])
+    assert np.array_equal(v, np.load(str(tmp_path / "s2" / "long.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "short.npy")), small)
+    assert sum(os.path.getsize(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))) < 80000 + 4 * 256
+
+
 # ------------------------------------------------------------------------------------------ GPU
 
 @pytest.mark.gpu
@@ -96,7 +118,7 @@ def test_gpus_2_without_a_second_device_fails_loudly():
 @pytest.mark.gpu
 @pytest.mark.parametrize("cfg,units", [(2, 4096), (4, 600), (5, 1500)])
 def test_config_lines_carry_full_parity(cfg, units):
-    out = _line(_run(["--config", str(cfg), "--units", str(units), "--steps", "1", "--warmup", "1", "--parity-sample", str(units)]))
+    out = _line(_run(["--config", str(cfg), "--units", str(units), "--steps", "1", "--warmup", "1", "--parity-sample", str(units), "--full"]))
     assert out["config"]["baseline_config"] == cfg and out["n_gpus"] == 1
     for key in ("roofline", "valu_roofline", "cpu_baseline", "parity_sample"):
         assert key in out
@@ -117,7 +139,7 @@ def test_eight_ranks_dry_run_on_one_device(strong):
     run finishes well inside two minutes"""
     import time
     args = ["--reads", "64000" if strong else "8000", "--steps", "2", "--warmup", "1", "--parity-sample", "400", "--no-e2e",
-            "--gpus", "8", "--share-gpu"] + (["--strong"] if strong else [])
+            "--gpus", "8", "--share-gpu", "--full"] + (["--strong"] if strong else [])
     t0 = time.time()
     out = _line(_run(args, timeout=300))
     wall = time.time() - t0
@@ -129,3 +151,30 @@ def test_eight_ranks_dry_run_on_one_device(strong):
     assert out["parity_sample"]["checked"] >= 400 and out["parity_sample"]["bit_exact"] == out["parity_sample"]["checked"]
     assert out["parity_sample"]["shard"] == "rank 0 of 8" and all(v is True for k, v in out["invariants"].items() if k != "planted_position_reads_checked")
     assert wall < 150, wall
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg,units", [(2, 4096), (5, 300)])
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path, cfg, units):
+    """a plain line holds the headline of exactly --steps timed steps and none of --full's extras; --dump-outputs writes
+    the results of the last step as floats, the same from run to run"""
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        out = _line(_run(["--config", str(cfg), "--units", str(units), "--steps", "2", "--warmup", "1", "--dump-outputs", d,
+                          "--dump", str(tmp_path / "ed.npy")]))
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "GCUPS" and out["higher_is_better"] is True and out["dtype"] == "u32"
+        for key in ("cpu_baseline", "parity_sample", "e2e", "secondary", "clocks"):
+            assert key not in out
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert all(n + ".npy" in names for n in ("status", "editDistance", "numLocations", "alphabetLength", "locOff", "ends"))
+    if cfg == 5:
+        assert all(n + ".npy" in names for n in ("starts", "alnOff", "alignment", "cigar_extended_chars", "cigar_standard_off"))
+    else:                                       # TASK_DISTANCE: no op bytes, so no path arrays
+        assert "alignment.npy" not in names and "alnOff.npy" not in names
+    for n in names:
+        a, b = np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n))
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.array_equal(a, b), n
+    ed = np.load(os.path.join(dirs[0], "editDistance.npy"))
+    assert len(ed) == units and np.array_equal(ed, np.load(str(tmp_path / "ed.npy")))

@@ -124,7 +124,20 @@ def leg_compare(args):
         json.dump(out, open(args.json, "w"), indent=1)
 
 
-FIXTURE = os.path.join(ROOT, "tests", "golden", "c2_full_ref.npz")
+# the fixture is kept as shards of consecutive units (part_0.npz, part_1.npz, ...): no committed file passes 1 MiB
+FIXTURE = os.path.join(ROOT, "tests", "golden", "c2_full_ref")
+FIXTURE_PARTS = 8
+
+
+def load_fixture(fixture=FIXTURE):
+    """the shards of the fixture joined into one dict of arrays; None when it is absent"""
+    parts = [os.path.join(fixture, "part_%d.npz" % p) for p in range(FIXTURE_PARTS)]
+    if not all(os.path.exists(p) for p in parts):
+        return None
+    fs = [np.load(p) for p in parts]
+    out = {k: np.concatenate([f[k] for f in fs]) for k in ("editDistance", "numLocations", "alphabetLength", "ends")}
+    out["sha256"], out["note"] = fs[0]["sha256"], fs[0]["note"]
+    return out
 
 
 def leg_fixture(args):
@@ -138,20 +151,29 @@ def leg_fixture(args):
         assert (r["status"] == 0).all()
         ed.append(r["editDistance"].astype(np.int16)); nl.append(r["numLocations"].astype(np.int32))
         al.append(r["alphabetLength"].astype(np.uint8)); ends.append(r["ends"].astype(np.int32))
-    out = args.out if args.out and args.out.endswith(".npz") else FIXTURE
-    np.savez_compressed(out, editDistance=np.concatenate(ed), numLocations=np.concatenate(nl), alphabetLength=np.concatenate(al),
-                        ends=np.concatenate(ends), sha256=np.frombuffer(meta["sha256"].encode(), dtype=np.uint8),
-                        note=np.frombuffer(b"edlibAlign(HW, DISTANCE, k = -1) of the UNMODIFIED reference (oracle/_ref) over bench.py's config-2 "
-                                           b"batch, rank 0, weak scaling (target seed 12345, reads seed 12346); made by tools/full_parity_c2.py ref + fixture", dtype=np.uint8))
-    print("[fixture] %d units -> %s (%.1f MB)" % (n, out, os.path.getsize(out) / 1e6))
+    out = args.out or FIXTURE
+    ed, nl, al, ends = np.concatenate(ed), np.concatenate(nl), np.concatenate(al), np.concatenate(ends)
+    roff = np.concatenate([[0], np.cumsum(nl.astype(np.int64))])
+    step = n // FIXTURE_PARTS
+    os.makedirs(out, exist_ok=True)
+    size = 0
+    for p in range(FIXTURE_PARTS):
+        a, b = p * step, (n if p == FIXTURE_PARTS - 1 else (p + 1) * step)
+        path = os.path.join(out, "part_%d.npz" % p)
+        np.savez_compressed(path, editDistance=ed[a:b], numLocations=nl[a:b], alphabetLength=al[a:b], ends=ends[roff[a]:roff[b]],
+                            sha256=np.frombuffer(meta["sha256"].encode(), dtype=np.uint8),
+                            note=np.frombuffer(b"edlibAlign(HW, DISTANCE, k = -1) of the UNMODIFIED reference (oracle/_ref) over bench.py's config-2 "
+                                               b"batch, rank 0, weak scaling (target seed 12345, reads seed 12346); made by tools/full_parity_c2.py ref + fixture", dtype=np.uint8))
+        size += os.path.getsize(path)
+    print("[fixture] %d units -> %s/part_*.npz (%.1f MB)" % (n, out, size / 1e6))
 
 
 def compare_with_fixture(flat, target, reads, fixture=FIXTURE):
     """whole-batch comparison of results_flat() arrays with the committed reference answers; None when the fixture is absent
     or was made for other inputs"""
-    if not os.path.exists(fixture):
+    f = load_fixture(fixture)
+    if f is None:
         return None
-    f = np.load(fixture)
     n = len(f["editDistance"])
     if len(reads) != n or bytes(f["sha256"]).decode() != digest(target, np.ascontiguousarray(reads)):
         return {"checked": 0, "note": "fixture is for other inputs"}
@@ -170,7 +192,7 @@ def compare_with_fixture(flat, target, reads, fixture=FIXTURE):
                 bad[i] = True
     return {"checked": int(n), "bit_exact": int((~bad).sum()), "failing_units": [int(i) for i in np.nonzero(bad)[0][:20]],
             "fields": "status, editDistance, numLocations, alphabetLength, every endLocation",
-            "reference": "tests/golden/c2_full_ref.npz: the unmodified reference over the whole batch (tools/full_parity_c2.py ref, CPU hours)"}
+            "reference": "tests/golden/c2_full_ref/: the unmodified reference over the whole batch (tools/full_parity_c2.py ref, CPU hours)"}
 
 
 def main():

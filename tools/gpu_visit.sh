@@ -4,7 +4,7 @@
 # Stages run in the order given; every GPU command runs under `timeout`.  Output: gpurun_out/visit_$R/ (copy what
 # should be judged into profiles/).  Stages:
 #   tests        pytest -m gpu (PYTEST_ARGS) + smoke
-#   bench        the default bench.py line (config 2 + `secondary` configs 4 / 5), BENCH_ARGS appended
+#   bench        the bench.py --full line (config 2 + `secondary` configs 4 / 5), BENCH_ARGS appended
 #   bench4|bench5  one config on its own (--config N)
 #   parity       whole-batch config-2 results for tools/full_parity_c2.py compare (gpurun_out/c2gpu.npz)
 #   trace        rocprofv3 --kernel-trace --stats of bench.py for configs 2, 4, 5 (TRACE_CFGS)
@@ -47,10 +47,10 @@ for stage in "$@"; do
       timeout 2700 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS:-} 2>&1 | tail -15 | tee $OUT/${R}_pytest_gpu.log
       timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3 | tee $OUT/${R}_smoke.log ;;
     bench)
-      timeout 1500 python bench.py ${BENCH_ARGS:-} 2> $OUT/bench.err | tee $OUT/${R}_bench_default.json | cut -c1-3000; tail -3 $OUT/bench.err | cut -c1-300 ;;
+      timeout 1500 python bench.py --full ${BENCH_ARGS:-} 2> $OUT/bench.err | tee $OUT/${R}_bench_default.json | cut -c1-3000; tail -3 $OUT/bench.err | cut -c1-300 ;;
     bench4|bench5)
       c=${stage#bench}
-      timeout 900 python bench.py --config $c ${BENCH_ARGS:-} 2> $OUT/bench_c$c.err | tee $OUT/${R}_bench_c$c.json | cut -c1-3000; tail -3 $OUT/bench_c$c.err | cut -c1-300 ;;
+      timeout 900 python bench.py --config $c --full ${BENCH_ARGS:-} 2> $OUT/bench_c$c.err | tee $OUT/${R}_bench_c$c.json | cut -c1-3000; tail -3 $OUT/bench_c$c.err | cut -c1-300 ;;
     parity)
       timeout 600 python tools/full_parity_c2.py gpu --out gpurun_out/c2gpu.npz 2>&1 | tail -3 ;;
     trace)
