@@ -4,8 +4,8 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 ``getNiceAlignment()`` have the same arguments, defaults, result dictionary and
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
-``align_batch()`` / ``align_pairs()`` and the resident ``SharedBatch`` / ``PairBatch``
-sessions over include/edlib_amd.h.
+``align_batch()`` / ``align_pairs()`` / ``align_cross()`` and the resident ``SharedBatch`` /
+``PairBatch`` / ``CrossBatch`` sessions over include/edlib_amd.h.
 
 There is no CPU path in here: everything calls ``libedlib.so`` (built by
 ``__graft_entry__.build()`` / ``make``), and a missing library or a missing GPU
@@ -58,6 +58,16 @@ class ResultsView(C.Structure):          # edlib_amd.h EdlibAmdResultsView
                 ("alignment", C.POINTER(C.c_ubyte))]
 
 
+class CrossView(C.Structure):            # edlib_amd.h EdlibAmdCrossView
+    _fields_ = [("numQueries", C.c_int), ("numTargets", C.c_int)] + [
+        (f, C.POINTER(C.c_int)) for f in ("editDistance", "numLocations", "endLocation",
+                                          "bestQuery", "bestQueryDistance", "secondQueryDistance",
+                                          "bestTarget", "bestTargetDistance", "secondTargetDistance")]
+
+
+CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
+CROSS_BEST = 2                            # EDLIB_AMD_CROSS_BEST
+
 _lib = None
 
 
@@ -86,6 +96,10 @@ def lib():
         L.edlibAmdBatchCreatePairs.restype = C.c_void_p
         L.edlibAmdBatchCreatePairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                AlignConfig, C.c_int]
+        L.edlibAmdBatchCreateCross.restype = C.c_void_p
+        L.edlibAmdBatchCreateCross.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                               AlignConfig, C.c_int]
+        L.edlibAmdBatchCrossView.argtypes = [C.c_void_p, C.c_int, C.POINTER(CrossView)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -424,6 +438,70 @@ class PairBatch(_Batch):
         h = lib().edlibAmdBatchCreatePairs(qd.ctypes.data, qo.ctypes.data, td.ctypes.data, to.ctypes.data,
                                            len(qo) - 1, cfg, device)
         super().__init__(h, len(qo) - 1, keep)
+
+
+class CrossBatch(_Batch):
+    """Every query against every target, distances only (edlibAmdBatchCreateCross): the loop
+    ``for t in targets: for q in queries: edlib.align(q, t, mode)`` as one resident batch.  Results come as a
+    matrix of shape (numTargets, numQueries) and as best hits per target and per query."""
+
+    def __init__(self, queries, targets, mode="HW", k=-1, additionalEqualities=None, device=0):
+        qd, qo = _pack(queries)
+        td, to = _pack(targets)
+        cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
+        self.numQueries, self.numTargets = len(qo) - 1, len(to) - 1
+        h = lib().edlibAmdBatchCreateCross(qd.ctypes.data, qo.ctypes.data, self.numQueries,
+                                           td.ctypes.data, to.ctypes.data, self.numTargets, cfg, device)
+        super().__init__(h, self.numQueries * self.numTargets, keep)
+
+    def _view(self, what):
+        v = CrossView()
+        if lib().edlibAmdBatchCrossView(self._h, what, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: cross view failed: " + last_error())
+        return v
+
+    @staticmethod
+    def _arr(ptr, shape, copy):
+        if not ptr:
+            return None
+        if int(np.prod(shape)) == 0:
+            return np.zeros(shape, dtype=np.int32)
+        a = np.ctypeslib.as_array(ptr, shape=shape)
+        return a.copy() if copy else a
+
+    def matrix(self, copy=True):
+        """{editDistance, numLocations, endLocation}: int32 arrays of shape (numTargets, numQueries).
+        copy=False: views of the batch's pinned memory, valid until its next run() / close()."""
+        v = self._view(CROSS_MATRIX)
+        shape = (self.numTargets, self.numQueries)
+        return {f: self._arr(getattr(v, f), shape, copy) for f in ("editDistance", "numLocations", "endLocation")}
+
+    def best(self, copy=True):
+        """Best hits: bestQuery / bestQueryDistance / secondQueryDistance [numTargets] and bestTarget /
+        bestTargetDistance / secondTargetDistance [numQueries]; ties go to the lowest index, -1 where no cell is within k."""
+        v = self._view(CROSS_BEST)
+        out = {}
+        for f in ("bestQuery", "bestQueryDistance", "secondQueryDistance"):
+            out[f] = self._arr(getattr(v, f), (self.numTargets,), copy)
+        for f in ("bestTarget", "bestTargetDistance", "secondTargetDistance"):
+            out[f] = self._arr(getattr(v, f), (self.numQueries,), copy)
+        return out
+
+    def results(self, raw=True):
+        raise RuntimeError("edlib_amd: a cross batch has no per-unit results: use matrix() / best()")
+
+
+def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None):
+    """Every query against every target in one device batch: the matrix() arrays (shape (numTargets, numQueries))
+    and the best() arrays of CrossBatch in one dictionary."""
+    b = CrossBatch(queries, targets, mode, k, additionalEqualities)
+    try:
+        b.run()
+        out = b.matrix()
+        out.update(b.best())
+        return out
+    finally:
+        b.close()
 
 
 def align_batch(queries, target, mode="HW", task="distance", k=-1, additionalEqualities=None, raw=False):

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <system_error>
@@ -15,7 +16,13 @@
 
 using namespace edlib_amd;
 
-struct EdlibAmdBatch { Batch impl; };
+struct EdlibAmdBatch { Batch impl; std::unique_ptr<CrossBatch> cross; };      // cross: a cross batch (impl unused)
+
+static int not_on_cross(EdlibAmdBatch* b, const char* what) {
+    if (!b->cross) return 0;
+    set_error("%s: not available on a cross batch (edlibAmdBatchCrossView has its results)", what);
+    return 1;
+}
 
 static void fail_loudly(const char* where) {
     fprintf(stderr, "edlib (MI355X engine): %s failed: %s\n", where, last_error().c_str());
@@ -143,13 +150,37 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreatePairs(const char* queries, const lon
     return b;
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(const char* queries, const long long* queryOffsets, int numQueries,
+                                                  const char* targets, const long long* targetOffsets, int numTargets,
+                                                  EdlibAlignConfig config, int device) {
+    EdlibAmdBatch* b = guarded("edlibAmdBatchCreateCross", static_cast<EdlibAmdBatch*>(nullptr), [] {
+        EdlibAmdBatch* x = new EdlibAmdBatch;
+        x->cross.reset(new CrossBatch);
+        return x;
+    });
+    if (!b) return nullptr;
+    if (guarded("edlibAmdBatchCreateCross", 1, [&] {
+            return b->cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device); })) {
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* b, int what, EdlibAmdCrossView* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->cross) { set_error("edlibAmdBatchCrossView: not a cross batch"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchCrossView", 1, [&] { return b->cross->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchRun(EdlibAmdBatch* b) {
     if (!b) { set_error("null batch"); return EDLIB_STATUS_ERROR; }
-    return guarded("edlibAmdBatchRun", 1, [&] { return b->impl.run(); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+    return guarded("edlibAmdBatchRun", 1, [&] { return b->cross ? b->cross->run() : b->impl.run(); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchResults(EdlibAmdBatch* b, EdlibAlignResult* results) {
     if (!b || !results) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_cross(b, "edlibAmdBatchResults")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchResults", 1, [&] { return b->impl.results(results); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
@@ -157,6 +188,7 @@ EDLIB_API int edlibAmdBatchResultsFlat(EdlibAmdBatch* b, int* status, int* editD
                                        int* alphabetLength, long long* locOffsets, int** endLocations,
                                        int** startLocations, long long* alnOffsets, unsigned char** alignment) {
     if (!b) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_cross(b, "edlibAmdBatchResultsFlat")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchResultsFlat", 1, [&] {
                return b->impl.resultsFlat(status, editDistance, numLocations, alphabetLength, locOffsets, endLocations,
                                           startLocations, alnOffsets, alignment); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
@@ -164,11 +196,13 @@ EDLIB_API int edlibAmdBatchResultsFlat(EdlibAmdBatch* b, int* status, int* editD
 
 EDLIB_API int edlibAmdBatchResultsView(EdlibAmdBatch* b, EdlibAmdResultsView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_cross(b, "edlibAmdBatchResultsView")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchResultsView", 1, [&] { return b->impl.resultsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchCigarView(EdlibAmdBatch* b, EdlibCigarFormat cigarFormat, const char** chars, const long long** offsets) {
     if (!b) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_cross(b, "edlibAmdBatchCigarView")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchCigarView", 1, [&] { return b->impl.cigarView((int)cigarFormat, chars, offsets); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
@@ -184,6 +218,7 @@ EDLIB_API void edlibAmdTrim(void) { (void)guarded("edlibAmdTrim", 0, [] { pool_t
 
 EDLIB_API int edlibAmdBatchStats(EdlibAmdBatch* b, EdlibAmdBatchStats* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (b->cross) { *out = b->cross->stats; return EDLIB_STATUS_OK; }
     (void)guarded("edlibAmdBatchStats", 0, [&] { b->impl.finishStats(); return 0; });
     *out = b->impl.stats;
     return EDLIB_STATUS_OK;

@@ -1,0 +1,81 @@
+// cross_kernels.hpp -- launch interface of the cross kernels (every query against every target, DISTANCE only):
+// the 4-bit target pack, the lane-per-cell scan, the best-hit reductions and the scatter of cells computed elsewhere.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace edlib_amd {
+
+constexpr int kCrossMaxQueryWords = 8;          // queries up to 256 symbols (kernel A's word groups)
+constexpr int kCrossMaxTarget = 65536;          // longer targets take the shared-target engine
+constexpr int kCrossMaxSyms = 16;               // union target alphabet of the cross kernel
+
+// Result of one cell from what its scan left: the rules of finalize_global / finalize_semiglobal (engine.hip), with the
+// empty-sequence case of the reference (edlib.cpp:167-183) in front.  HW / SHW: best = smallest bottom-row score over the
+// target columns, cnt = number of columns at it, first = the first of them (best > every threshold when n == 0).
+// NW: best = score of the last column.
+__host__ __device__ inline void cross_cell_result(int mode, int kcfg, int m, int n, int best, int cnt, int first,
+                                                  int& ed, int& nloc, int& end)
+{
+    if (m == 0 || n == 0) {
+        if (mode == 0) { ed = m > n ? m : n; nloc = 1; end = n - 1; }
+        else { ed = m; nloc = 1; end = -1; }
+        return;
+    }
+    if (mode == 0) {
+        if (kcfg >= 0 && best > kcfg) { ed = -1; nloc = 0; end = -1; }
+        else { ed = best; nloc = 1; end = n - 1; }
+        return;
+    }
+    // candidates score <= min(k, m): HW clamps k to m, SHW's best never exceeds m; the empty target prefix (-1) takes
+    // part when the reference's padded last block sees it (W > 0)
+    const int thr = (kcfg < 0 || kcfg > m) ? m : kcfg;
+    const int W = ((m + 63) / 64) * 64 - m;
+    const bool kAllowsM = (kcfg < 0 || kcfg >= m);
+    if (best > thr) {
+        if (W > 0 && kAllowsM) { ed = m; nloc = 1; end = -1; }
+        else { ed = -1; nloc = 0; end = -1; }
+        return;
+    }
+    const bool lead = W > 0 && best == m;
+    ed = best;
+    nloc = cnt + (lead ? 1 : 0);
+    end = lead ? -1 : first;
+}
+
+// Best and second best of a row of distances (-1 = not within k): key = (distance << 32) | index, the smaller key wins,
+// so ties go to the lowest index whatever the order of the reduction.  ~0 = none.
+struct CrossBest2 { unsigned long long b, s; };
+
+// What the scan of one query group needs.  The group's slots are tiles of `qt` queries; lane l of a wave takes query slot
+// tile * qt + l % qt against sorted target tile * (64 / qt) + l / qt.
+struct CrossScanArgs {
+    const uint32_t* peq;        // the group's Peq, [slot / 64][S][NWD][slot % 64] (build_peq_reads_kernel)
+    const int* qlen;            // [slots]
+    const int* qperm;           // [slots] slot -> query index, -1 for a padding slot
+    int qt;                     // queries per tile: 64, 32, ..., 1
+    int numQueryTiles;
+    const uint32_t* tpk;        // target pool, 4 bits per column, 8 columns per dword, each target from a dword boundary
+    const long long* tdw;       // [numSorted] first dword of sorted target i
+    const int* tlen;            // [numSorted]
+    const int* tperm;           // [numSorted] sorted target -> target index
+    int numSorted;
+    int numQueries;             // row length of the matrix
+    int kcfg;
+    int* ed; int* nloc; int* end;   // [numTargets][numQueries]
+};
+
+hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, const int* tperm, const long long* tdw,
+                                     int numSorted, const uint8_t* tlut, uint32_t* tpk, hipStream_t stream);
+// nwords 1..8, syms 4 / 8 / 16, mode 0 NW / 1 SHW / 2 HW; ysplit: waves per query tile (each strides over target tiles)
+hipError_t launch_scan_cross(int nwords, int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream);
+// per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are
+// best index / best distance / second distance
+hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,
+                             int* bestQ, int* bestQD, int* secondQD, int* bestT, int* bestTD, int* secondTD,
+                             CrossBest2* partial, int targetChunk, hipStream_t stream);
+// cells computed by other engines: ed / nloc / end of cell[i] (index into the matrix)
+hipError_t launch_cross_scatter(const long long* cell, const int* vals, long long n, int* ed, int* nloc, int* end,
+                                hipStream_t stream);
+
+}  // namespace edlib_amd

@@ -69,7 +69,7 @@ static long long first_outside_ssse3(const uint8_t* p, long long from, long long
 }
 #endif
 
-static void build_tables(Tables& tab, const uint8_t* targets, long long totalTargetBytes,
+void build_tables(Tables& tab, const uint8_t* targets, long long totalTargetBytes,
                          const EdlibEqualityPair* eqs, int neq) {
     memset(tab.presence, 0, sizeof tab.presence);
     memset(tab.tlut, 0, sizeof tab.tlut);

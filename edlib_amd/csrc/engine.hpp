@@ -7,6 +7,7 @@
 #include "pair_kernels.hpp"
 #include "lanepair.hpp"
 #include "reads_kernels.hpp"
+#include "cross_kernels.hpp"
 
 #include <chrono>
 #include <deque>
@@ -368,6 +369,57 @@ private:
     int ensureCollected();                       // results of the last run that are still on the device -> results_
 };
 
+// Every query against every target (engine_cross.hip, DESIGN.md "Cross batches"): DISTANCE only, results as a
+// target-major matrix and best hits, both made on the device.  Cells inside the cross kernel's envelope run on it; each
+// other target runs through an internal shared-target Batch over all queries, longer queries against the rest through
+// one internal pair Batch, and their results are scattered into the matrix.
+class CrossBatch {
+public:
+    ~CrossBatch();
+    int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
+             EdlibAlignConfig cfg, int device);
+    int run();
+    int view(int what, EdlibAmdCrossView* out);
+    EdlibAmdBatchStats stats{};
+
+private:
+    struct Group {
+        int words = 0, qt = 64, tiles = 0, slots = 0, ysplit = 1;
+        long long liveWords = 0;                  // sum of the words of its real queries
+        DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;
+        DevBuf<uint32_t> d_peq;
+    };
+    EdlibAlignConfig cfg_{};
+    std::vector<EdlibEqualityPair> eqs_;
+    int device_ = 0, nq_ = 0, nt_ = 0, syms_ = 4;
+    size_t cells_ = 0;
+    hipStream_t stream_ = nullptr;
+    Tables tab_;
+    std::vector<std::unique_ptr<Group>> groups_;
+    int numSorted_ = 0;                           // targets on the cross kernel
+    long long sortedCols_ = 0;                    // their columns
+    DevBuf<uint8_t> d_qpool_;
+    DevBuf<long long> d_qoff_, d_tdw_;
+    DevBuf<uint16_t> d_eqtbl_;
+    DevBuf<uint32_t> d_presence_, d_tpk_;
+    DevBuf<int> d_tperm_, d_tlen_;
+    DevBuf<int> d_mat_;                           // [3][nt][nq]: editDistance, numLocations, endLocation
+    DevBuf<int> d_best_;                          // [3][nt] then [3][nq]
+    DevBuf<CrossBest2> d_partial_;
+    int targetChunk_ = 1024;
+    // cells of the other engines: each out-of-envelope target's column (shared Batch), the long queries' cells (pair Batch)
+    std::vector<std::unique_ptr<Batch>> outShared_;
+    std::vector<int> outTargets_;
+    std::unique_ptr<Batch> longPairs_;
+    std::vector<long long> longCells_;
+    long long otherCells_ = 0;
+    DevBuf<long long> d_cells_; DevBuf<int> d_vals_; PinBuf h_vals_;
+    Event evScan0_, evScan1_;
+    PinBuf h_mat_, h_best_;
+    bool haveRun_ = false, matFetched_ = false, bestFetched_ = false;
+    int gather(Batch& b, size_t n, int* vals);
+};
+
 // single-pair convenience used by edlibAlign()
 int align_one(const char* q, int qn, const char* t, int tn, EdlibAlignConfig cfg, EdlibAlignResult* out);
 // one small pair in one kernel launch (one_pair.hip): 0 = answered, 1 = error, 2 = not handled here (take align_one)
@@ -400,6 +452,8 @@ void plan_segments(int nlanes, int T, int mode, int warmFull, long long wantWave
 // a SIMD: one per SIMD of 256 CUs (swept in round 4: DESIGN.md 3c)
 inline long long tall_round_waves() { return 1024; }
 void finalize_semiglobal(UnitResult& r, int kcfg, int m, int best, const int* pos, long long npos);
+// target alphabet and equality tables of a batch (engine.hip)
+void build_tables(Tables& tab, const uint8_t* targets, long long totalTargetBytes, const EdlibEqualityPair* eqs, int neq);
 
 int device_count();
 int host_threads(int cap);

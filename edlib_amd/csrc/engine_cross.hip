@@ -1,0 +1,315 @@
+// engine_cross.hip -- host side of cross batches: every query against every target, DISTANCE only (DESIGN.md "Cross
+// batches").  Create sorts the queries into word groups (kernel A's groups, each sorted by length) and the targets by
+// length, packs the targets to 4-bit codes once and chooses each group's tile; a Run builds the Peq rows of every query
+// (build_peq_reads_kernel over the union target alphabet), scans every group on the cross kernel, lets the internal
+// sessions of the cells outside the kernel's envelope run meanwhile, scatters their results into the matrix and reduces
+// it to the best hits.  Results stay in HBM until view() asks for a part of them.
+#include "engine.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <numeric>
+
+namespace edlib_amd {
+
+CrossBatch::~CrossBatch()
+{
+    DeviceGuard guard(device_);
+    if (stream_) { (void)hipStreamSynchronize(stream_); pool_stream_release(stream_); }
+}
+
+// lanes a tile shape leaves idle decide it; on a tie the wider query tile (fewer Peq stagings)
+static int choose_qt(long long nq, long long nt)
+{
+    int bestQt = 64; long long bestLanes = -1;
+    for (int qt = 64; qt >= 1; qt >>= 1) {
+        const long long tpt = 64 / qt;
+        const long long lanes = ((nq + qt - 1) / qt) * qt * ((nt + tpt - 1) / tpt) * tpt;
+        if (bestLanes < 0 || lanes < bestLanes) { bestLanes = lanes; bestQt = qt; }
+    }
+    return bestQt;
+}
+
+int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const char* targets,
+                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device)
+{
+    if (cfg.task != EDLIB_TASK_DISTANCE) {
+        set_error("cross batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
+                  "for locations or paths");
+        return 1;
+    }
+    if (cfg.mode != EDLIB_MODE_NW && cfg.mode != EDLIB_MODE_SHW && cfg.mode != EDLIB_MODE_HW) { set_error("unknown mode"); return 1; }
+    if (nq < 0 || nt < 0 || (nq > 0 && !qoffIn) || (nt > 0 && !toffIn)) { set_error("bad batch shape"); return 1; }
+    const int ndev = device_count();
+    if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
+    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
+    cfg_ = cfg;
+    if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0)
+        eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
+    cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
+    cfg_.additionalEqualitiesLength = (int)eqs_.size();
+    device_ = device; nq_ = nq; nt_ = nt;
+    std::vector<long long> qoff(nq + 1, 0), toff(nt + 1, 0);
+    if (nq > 0) qoff.assign(qoffIn, qoffIn + nq + 1);
+    if (nt > 0) toff.assign(toffIn, toffIn + nt + 1);
+    for (int i = 0; i < nq; ++i)
+        if (qoff[i + 1] < qoff[i] || qoff[i + 1] - qoff[i] > 0x7fffffffLL) { set_error("bad query offsets"); return 1; }
+    for (int i = 0; i < nt; ++i)
+        if (toff[i + 1] < toff[i] || toff[i + 1] - toff[i] > 0x7fffffffLL) { set_error("bad target offsets"); return 1; }
+    const long long qb = qoff[0], tb = toff[0];
+    const long long qbytes = qoff[nq] - qb, tbytes = toff[nt] - tb;
+    auto qlen = [&](int q) { return (int)(qoff[q + 1] - qoff[q]); };
+    auto tlen = [&](int t) { return (int)(toff[t + 1] - toff[t]); };
+    cells_ = (size_t)nq * (size_t)nt;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = qbytes * tbytes;
+
+    // the union alphabet of all targets decides the Peq rows (and whether the kernel can take any cell)
+    build_tables(tab_, reinterpret_cast<const uint8_t*>(targets) + tb, tbytes, eqs_.data(), (int)eqs_.size());
+    const bool wide = tab_.sigmaT > kCrossMaxSyms;
+    syms_ = tab_.sigmaT <= 4 ? 4 : (tab_.sigmaT <= 8 ? 8 : 16);
+    std::vector<int> inT, longQ;
+    for (int t = 0; t < nt; ++t) {
+        if (!wide && tlen(t) <= kCrossMaxTarget) inT.push_back(t);
+        else outTargets_.push_back(t);
+    }
+    for (int q = 0; q < nq; ++q)
+        if (qlen(q) > 32 * kCrossMaxQueryWords) longQ.push_back(q);
+
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    EDLIB_AMD_HIP(pool_stream(&stream_));
+    EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
+    EDLIB_AMD_HIP(d_mat_.alloc(3 * std::max<size_t>(cells_, 1)));
+    EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
+    targetChunk_ = std::max(1024, (nt + 32767) / 32768);
+    EDLIB_AMD_HIP(d_partial_.alloc((size_t)std::max(1, (nt + targetChunk_ - 1) / targetChunk_) * (size_t)std::max(nq, 1)));
+
+    // ---- the cross kernel's share
+    if (!inT.empty() && (int)longQ.size() < nq) {
+        std::stable_sort(inT.begin(), inT.end(), [&](int a, int b) { return tlen(a) < tlen(b); });
+        numSorted_ = (int)inT.size();
+        std::vector<long long> tdw(numSorted_);
+        std::vector<int> tl(numSorted_);
+        long long dw = 0;
+        for (int i = 0; i < numSorted_; ++i) {
+            tdw[i] = dw; tl[i] = tlen(inT[i]);
+            dw += (tl[i] + 7) / 8;
+            sortedCols_ += tl[i];
+        }
+        EDLIB_AMD_HIP(d_tpk_.alloc((size_t)std::max(dw, 1LL)));
+        EDLIB_AMD_HIP(d_tdw_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tperm_.alloc(numSorted_));
+        EDLIB_AMD_HIP(hipMemcpy(d_tdw_.p, tdw.data(), numSorted_ * sizeof(long long), hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, tl.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_tperm_.p, inT.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
+        {   // the raw target pool is only needed by the pack
+            DevBuf<uint8_t> d_traw, d_tlut; DevBuf<long long> d_toff;
+            std::vector<long long> toffR(toff);
+            for (auto& v : toffR) v -= tb;
+            EDLIB_AMD_HIP(d_traw.alloc((size_t)tbytes + 16)); EDLIB_AMD_HIP(d_tlut.alloc(256)); EDLIB_AMD_HIP(d_toff.alloc(nt + 1));
+            if (tbytes) EDLIB_AMD_HIP(hipMemcpy(d_traw.p, targets + tb, (size_t)tbytes, hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(d_tlut.p, tab_.tlut, 256, hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(d_toff.p, toffR.data(), (nt + 1) * sizeof(long long), hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(launch_pack_cross_targets(d_traw.p, d_toff.p, d_tperm_.p, d_tdw_.p, numSorted_, d_tlut.p, d_tpk_.p, stream_));
+            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        }
+        // queries (rebased), their tables
+        std::vector<long long> qoffR(qoff);
+        for (auto& v : qoffR) v -= qb;
+        EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
+        if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
+        EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
+        // word groups, each sorted by length; empty queries ride in the one-word group
+        std::vector<std::vector<int>> byWords(kCrossMaxQueryWords + 1);
+        for (int q = 0; q < nq; ++q) {
+            const int m = qlen(q);
+            if (m > 32 * kCrossMaxQueryWords) continue;
+            byWords[std::max(1, (m + 31) / 32)].push_back(q);
+        }
+        for (int w = 1; w <= kCrossMaxQueryWords; ++w) {
+            auto& qs = byWords[w];
+            if (qs.empty()) continue;
+            std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return qlen(a) < qlen(b); });
+            std::unique_ptr<Group> g(new Group);
+            g->words = w;
+            g->qt = choose_qt((long long)qs.size(), numSorted_);
+            g->tiles = ((int)qs.size() + g->qt - 1) / g->qt;
+            g->slots = g->tiles * g->qt;
+            g->liveWords = (long long)qs.size() * w;
+            const int tpt = 64 / g->qt;
+            const long long targetTiles = (numSorted_ + tpt - 1) / tpt;
+            // about 8,192 waves per launch (256 CUs), each persistent over a strided range of target tiles
+            g->ysplit = (int)std::min<long long>({targetTiles, std::max(1LL, (8192LL + g->tiles - 1) / g->tiles), 65535LL});
+            std::vector<int> perm(g->slots, -1);
+            std::copy(qs.begin(), qs.end(), perm.begin());
+            const size_t blocks = (size_t)(g->slots + 63) / 64;
+            EDLIB_AMD_HIP(g->d_perm.alloc(g->slots)); EDLIB_AMD_HIP(g->d_qlen.alloc(g->slots));
+            EDLIB_AMD_HIP(g->d_kinit.alloc(g->slots)); EDLIB_AMD_HIP(g->d_alpha.alloc(g->slots));
+            EDLIB_AMD_HIP(g->d_peq.alloc(blocks * syms_ * w * 64));
+            EDLIB_AMD_HIP(hipMemcpy(g->d_perm.p, perm.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
+            groups_.push_back(std::move(g));
+        }
+    }
+
+    // ---- the other engines' share
+    if (nq > 0) {
+        for (int t : outTargets_) {
+            std::unique_ptr<Batch> b(new Batch);
+            const long long to[2] = {toff[t], toff[t + 1]};
+            if (b->init(queries, qoffIn, nq, targets, to, 1, cfg_, device)) return 1;
+            outShared_.push_back(std::move(b));
+            otherCells_ += nq;
+        }
+        if (!longQ.empty() && !inT.empty()) {
+            // every long query against every target the kernel takes, as pairs (their bytes replicated per cell)
+            std::vector<char> qp, tp;
+            std::vector<long long> qo(1, 0), to(1, 0);
+            for (int t : inT)
+                for (int q : longQ) {
+                    qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
+                    tp.insert(tp.end(), targets + toff[t], targets + toff[t + 1]);
+                    qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
+                    longCells_.push_back((long long)t * nq + q);
+                }
+            longPairs_.reset(new Batch);
+            if (longPairs_->init(qp.data(), qo.data(), (int)longCells_.size(), tp.data(), to.data(), (int)longCells_.size(),
+                                 cfg_, device)) return 1;
+            otherCells_ += (long long)longCells_.size();
+        }
+        if (otherCells_ > 0) {
+            std::vector<long long> cellIdx;
+            cellIdx.reserve((size_t)otherCells_);
+            for (int t : outTargets_)
+                for (int q = 0; q < nq; ++q) cellIdx.push_back((long long)t * nq + q);
+            cellIdx.insert(cellIdx.end(), longCells_.begin(), longCells_.end());
+            EDLIB_AMD_HIP(d_cells_.alloc((size_t)otherCells_)); EDLIB_AMD_HIP(d_vals_.alloc(3 * (size_t)otherCells_));
+            EDLIB_AMD_HIP(h_vals_.alloc(3 * (size_t)otherCells_ * sizeof(int)));
+            EDLIB_AMD_HIP(hipMemcpy(d_cells_.p, cellIdx.data(), (size_t)otherCells_ * sizeof(long long), hipMemcpyHostToDevice));
+        }
+    }
+    return 0;
+}
+
+// editDistance / numLocations / first end location of the n units of an internal session's last run
+int CrossBatch::gather(Batch& b, size_t n, int* vals)
+{
+    EdlibAmdResultsView v{};
+    if (b.resultsView(&v)) return 1;
+    for (size_t i = 0; i < n; ++i) {
+        if (v.status[i] != EDLIB_STATUS_OK) { set_error("cross batch: an internal alignment failed"); return 1; }
+        vals[3 * i] = v.editDistance[i];
+        vals[3 * i + 1] = v.numLocations[i];
+        vals[3 * i + 2] = v.numLocations[i] > 0 ? v.endLocations[v.locOffsets[i]] : -1;
+    }
+    return 0;
+}
+
+int CrossBatch::run()
+{
+    pool_quarantine(false);
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    haveRun_ = matFetched_ = bestFetched_ = false;
+    const long long cells = stats.cells;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = cells;
+    int* ed = d_mat_.p; int* nloc = d_mat_.p + cells_; int* end = d_mat_.p + 2 * cells_;
+    const int mode = (int)cfg_.mode;
+
+    // the cross kernel: Peq of every query, then one scan per word group
+    if (!groups_.empty()) {
+        for (auto& g : groups_)
+            EDLIB_AMD_HIP(launch_build_peq_reads(g->words, syms_, d_qpool_.p, d_qoff_.p, g->d_perm.p, g->slots, d_eqtbl_.p,
+                                                 d_presence_.p, cfg_.k, g->d_peq.p, g->d_qlen.p, g->d_kinit.p, g->d_alpha.p,
+                                                 stream_));
+        EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
+        for (auto& g : groups_) {
+            CrossScanArgs a{};
+            a.peq = g->d_peq.p; a.qlen = g->d_qlen.p; a.qperm = g->d_perm.p; a.qt = g->qt; a.numQueryTiles = g->tiles;
+            a.tpk = d_tpk_.p; a.tdw = d_tdw_.p; a.tlen = d_tlen_.p; a.tperm = d_tperm_.p; a.numSorted = numSorted_;
+            a.numQueries = nq_; a.kcfg = cfg_.k; a.ed = ed; a.nloc = nloc; a.end = end;
+            EDLIB_AMD_HIP(launch_scan_cross(g->words, syms_, mode, a, g->ysplit, stream_));
+            ++stats.scan_launches;
+            stats.word_steps += g->liveWords * sortedCols_;
+        }
+        EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
+        stats.path |= 8;
+    }
+    // the other engines run on their own streams meanwhile
+    if (otherCells_ > 0) {
+        int* vals = reinterpret_cast<int*>(h_vals_.p);
+        size_t at = 0;
+        for (auto& b : outShared_) {
+            if (b->run()) return 1;
+            if (gather(*b, (size_t)nq_, vals + 3 * at)) return 1;
+            at += (size_t)nq_;
+            b->finishStats();
+            stats.word_steps += b->stats.word_steps; stats.scan_launches += b->stats.scan_launches;
+            stats.path |= b->stats.path; stats.overflow_units += b->stats.overflow_units; stats.wide_retries += b->stats.wide_retries;
+        }
+        if (longPairs_) {
+            if (longPairs_->run()) return 1;
+            if (gather(*longPairs_, longCells_.size(), vals + 3 * at)) return 1;
+            longPairs_->finishStats();
+            const EdlibAmdBatchStats& s = longPairs_->stats;
+            stats.word_steps += s.word_steps; stats.scan_launches += s.scan_launches;
+            stats.path |= s.path; stats.overflow_units += s.overflow_units; stats.wide_retries += s.wide_retries;
+        }
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, 3 * (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(launch_cross_scatter(d_cells_.p, d_vals_.p, otherCells_, ed, nloc, end, stream_));
+    }
+    int* bq = d_best_.p; int* bt = d_best_.p + 3 * (size_t)nt_;
+    EDLIB_AMD_HIP(launch_cross_best(ed, nq_, nt_, bq, bq + nt_, bq + 2 * (size_t)nt_, bt, bt + nq_, bt + 2 * (size_t)nq_,
+                                    d_partial_.p, targetChunk_, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (!groups_.empty()) {
+        float ms = 0.f;
+        EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evScan0_.e, evScan1_.e));
+        stats.scan_ms = ms;
+    }
+    stats.algo_bytes = 0;
+    stats.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    haveRun_ = true;
+    return 0;
+}
+
+int CrossBatch::view(int what, EdlibAmdCrossView* out)
+{
+    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    if (what & ~(EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST)) { set_error("cross view: unknown parts %d", what); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    const size_t matBytes = 3 * cells_ * sizeof(int), bestBytes = (3 * (size_t)nt_ + 3 * (size_t)nq_) * sizeof(int);
+    if ((what & EDLIB_AMD_CROSS_MATRIX) && !matFetched_) {
+        if (h_mat_.n < matBytes || !h_mat_.p) EDLIB_AMD_HIP(h_mat_.alloc(matBytes));
+        if (matBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_mat_.p, d_mat_.p, matBytes, hipMemcpyDeviceToHost, stream_));
+    }
+    if ((what & EDLIB_AMD_CROSS_BEST) && !bestFetched_) {
+        if (h_best_.n < bestBytes || !h_best_.p) EDLIB_AMD_HIP(h_best_.alloc(bestBytes));
+        if (bestBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_best_.p, d_best_.p, bestBytes, hipMemcpyDeviceToHost, stream_));
+    }
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (what & EDLIB_AMD_CROSS_MATRIX) matFetched_ = true;
+    if (what & EDLIB_AMD_CROSS_BEST) bestFetched_ = true;
+    memset(out, 0, sizeof *out);
+    out->numQueries = nq_; out->numTargets = nt_;
+    if (what & EDLIB_AMD_CROSS_MATRIX) {
+        const int* m = reinterpret_cast<const int*>(h_mat_.p);
+        out->editDistance = m; out->numLocations = m + cells_; out->endLocation = m + 2 * cells_;
+    }
+    if (what & EDLIB_AMD_CROSS_BEST) {
+        const int* b = reinterpret_cast<const int*>(h_best_.p);
+        out->bestQuery = b; out->bestQueryDistance = b + nt_; out->secondQueryDistance = b + 2 * (size_t)nt_;
+        b += 3 * (size_t)nt_;
+        out->bestTarget = b; out->bestTargetDistance = b + nq_; out->secondTargetDistance = b + 2 * (size_t)nq_;
+    }
+    return 0;
+}
+
+}  // namespace edlib_amd

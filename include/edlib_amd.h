@@ -71,6 +71,22 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreatePairs(
     const char* targets, const long long* targetOffsets, int numPairs,
     EdlibAlignConfig config, int device);
 
+/* numQueries queries against numTargets targets, every pair (a cross batch): replaces
+ * `for t: for q: d[t][q] = edlibAlign(queries[q], .., targets[t], .., config).editDistance`
+ * (barcode / primer demultiplexing, all-against-all distance matrices, reads against several contigs) without
+ * replicating a byte per cell.  config.task must be EDLIB_TASK_DISTANCE (otherwise NULL; align the chosen pairs
+ * with a pair batch for locations or paths); NW, SHW and HW, any k, additionalEqualities.  Cells of queries up to
+ * 256 bases and targets up to 65,536 bases over at most 16 target symbols (all targets together) run on the cross
+ * kernel; every other target runs through the shared-target engine over all queries (one internal session per
+ * such target: right for long contigs, slow for thousands of short targets over a wide alphabet), and longer
+ * queries against the remaining targets through one internal pair batch.
+ * Run, Stats and Destroy work as for the other batches (Stats.path bit 3: the cross kernel; Stats.cells the sum of
+ * queryLength * targetLength over all cells); Results, ResultsFlat, ResultsView and CigarView fail. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* targets, const long long* targetOffsets, int numTargets,
+    EdlibAlignConfig config, int device);
+
 /* One pass of the device path over the resident batch (encode target, build
  * the query profiles, scan, merge; for LOC/PATH also start locations and
  * traceback), then wait for it.  Results stay on the device. */
@@ -116,6 +132,28 @@ EDLIB_API int edlibAmdBatchResultsView(EdlibAmdBatch* batch, EdlibAmdResultsView
 EDLIB_API int edlibAmdBatchCigarView(EdlibAmdBatch* batch, EdlibCigarFormat cigarFormat,
                                      const char** chars, const long long** offsets);
 
+/* Results of the last Run of a cross batch, as pointers into pinned host memory the batch owns (valid until the next
+ * Run / Destroy).  Only the parts asked for in `what` (EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST) cross the link;
+ * the others are NULL.  Cell (q, t) of the matrix is at [t * numQueries + q] and equals edlibAlign(query q, target t,
+ * config) in editDistance (-1: above k), numLocations and the first end location (-1 when there is none).
+ * Best hits: per target over the queries and per query over the targets, the lowest index wins a tie; the second
+ * distance is the smallest over the other indices (equal to the best on a tie); -1 where no cell is within k. */
+typedef struct {
+    int numQueries, numTargets;
+    const int* editDistance;          /* [numTargets * numQueries]                                  */
+    const int* numLocations;          /* [numTargets * numQueries]                                  */
+    const int* endLocation;           /* [numTargets * numQueries] endLocations[0], else -1         */
+    const int* bestQuery;             /* [numTargets]                                               */
+    const int* bestQueryDistance;     /* [numTargets]                                               */
+    const int* secondQueryDistance;   /* [numTargets]                                               */
+    const int* bestTarget;            /* [numQueries]                                               */
+    const int* bestTargetDistance;    /* [numQueries]                                               */
+    const int* secondTargetDistance;  /* [numQueries]                                               */
+} EdlibAmdCrossView;
+#define EDLIB_AMD_CROSS_MATRIX 1
+#define EDLIB_AMD_CROSS_BEST   2
+EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* batch, int what, EdlibAmdCrossView* out);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
@@ -132,7 +170,7 @@ typedef struct {
     long long cells;        /* sum over units of queryLength * targetLength (GCUPS numerator)*/
     long long word_steps;   /* 32-row word-column updates the scan kernels executed          */
     long long algo_bytes;   /* algorithmic bytes: target+query+Peq+results    */
-    int path;               /* bit 0 reads-per-lane kernel, bit 1 block-per-lane kernel, bit 2 piece filter (long HW reads) */
+    int path;               /* bit 0 reads-per-lane kernel, bit 1 block-per-lane kernel, bit 2 piece filter (long HW reads), bit 3 cross kernel */
     int overflow_units;     /* units whose end-location list needed the exact second pass    */
     int wide_retries;       /* launches of the many-wave kernel that gave up (not resident together / stalled) and were run again with one slot per unit */
 } EdlibAmdBatchStats;
