@@ -65,6 +65,12 @@ class CrossView(C.Structure):            # edlib_amd.h EdlibAmdCrossView
                                           "bestTarget", "bestTargetDistance", "secondTargetDistance")]
 
 
+class CrossHits(C.Structure):            # edlib_amd.h EdlibAmdCrossHits
+    _fields_ = [("numQueries", C.c_int), ("numTargets", C.c_int), ("numHits", C.c_longlong),
+                ("targetOffsets", C.POINTER(C.c_longlong))] + [
+        (f, C.POINTER(C.c_int)) for f in ("query", "editDistance", "numLocations", "endLocation")]
+
+
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
 CROSS_BEST = 2                            # EDLIB_AMD_CROSS_BEST
 
@@ -100,6 +106,9 @@ def lib():
         L.edlibAmdBatchCreateCross.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                AlignConfig, C.c_int]
         L.edlibAmdBatchCrossView.argtypes = [C.c_void_p, C.c_int, C.POINTER(CrossView)]
+        L.edlibAmdBatchCreateCrossHits.restype = C.c_void_p
+        L.edlibAmdBatchCreateCrossHits.argtypes = L.edlibAmdBatchCreateCross.argtypes
+        L.edlibAmdBatchCrossHits.argtypes = [C.c_void_p, C.POINTER(CrossHits)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -443,15 +452,18 @@ class PairBatch(_Batch):
 class CrossBatch(_Batch):
     """Every query against every target, distances only (edlibAmdBatchCreateCross): the loop
     ``for t in targets: for q in queries: edlib.align(q, t, mode)`` as one resident batch.  Results come as a
-    matrix of shape (numTargets, numQueries) and as best hits per target and per query."""
+    matrix of shape (numTargets, numQueries) and as best hits per target and per query.
+    hits=True (edlibAmdBatchCreateCrossHits, k >= 0): no matrix; hits() lists the cells within k per target."""
 
-    def __init__(self, queries, targets, mode="HW", k=-1, additionalEqualities=None, device=0):
+    def __init__(self, queries, targets, mode="HW", k=-1, additionalEqualities=None, device=0, hits=False):
         qd, qo = _pack(queries)
         td, to = _pack(targets)
         cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
         self.numQueries, self.numTargets = len(qo) - 1, len(to) - 1
-        h = lib().edlibAmdBatchCreateCross(qd.ctypes.data, qo.ctypes.data, self.numQueries,
-                                           td.ctypes.data, to.ctypes.data, self.numTargets, cfg, device)
+        self.is_hits = bool(hits)
+        create = lib().edlibAmdBatchCreateCrossHits if hits else lib().edlibAmdBatchCreateCross
+        h = create(qd.ctypes.data, qo.ctypes.data, self.numQueries, td.ctypes.data, to.ctypes.data, self.numTargets,
+                   cfg, device)
         super().__init__(h, self.numQueries * self.numTargets, keep)
 
     def _view(self, what):
@@ -472,6 +484,9 @@ class CrossBatch(_Batch):
     def matrix(self, copy=True):
         """{editDistance, numLocations, endLocation}: int32 arrays of shape (numTargets, numQueries).
         copy=False: views of the batch's pinned memory, valid until its next run() / close()."""
+        if self.is_hits:
+            raise RuntimeError("edlib_amd: a hit-list cross batch keeps no matrix: use hits(), or create the batch "
+                               "without hits=True")
         v = self._view(CROSS_MATRIX)
         shape = (self.numTargets, self.numQueries)
         return {f: self._arr(getattr(v, f), shape, copy) for f in ("editDistance", "numLocations", "endLocation")}
@@ -487,17 +502,31 @@ class CrossBatch(_Batch):
             out[f] = self._arr(getattr(v, f), (self.numQueries,), copy)
         return out
 
+    def hits(self, copy=True):
+        """The cells within k of a hits=True batch, grouped by target (CSR), ascending query inside a target:
+        targetOffsets int64 [numTargets + 1] (target t: [targetOffsets[t], targetOffsets[t + 1])) and query /
+        editDistance / numLocations / endLocation int32 [numHits].  copy=False: views of the batch's pinned memory,
+        valid until its next run() / close()."""
+        v = CrossHits()
+        if lib().edlibAmdBatchCrossHits(self._h, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: cross hits failed: " + last_error())
+        n = int(v.numHits)
+        out = {"targetOffsets": self._arr(v.targetOffsets, (self.numTargets + 1,), copy).astype(np.int64, copy=False)}
+        for f in ("query", "editDistance", "numLocations", "endLocation"):
+            out[f] = self._arr(getattr(v, f), (n,), copy) if n else np.zeros(0, dtype=np.int32)
+        return out
+
     def results(self, raw=True):
         raise RuntimeError("edlib_amd: a cross batch has no per-unit results: use matrix() / best()")
 
 
-def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None):
+def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hits=False):
     """Every query against every target in one device batch: the matrix() arrays (shape (numTargets, numQueries))
-    and the best() arrays of CrossBatch in one dictionary."""
-    b = CrossBatch(queries, targets, mode, k, additionalEqualities)
+    and the best() arrays of CrossBatch in one dictionary; hits=True (k >= 0): the hits() arrays instead of the matrix."""
+    b = CrossBatch(queries, targets, mode, k, additionalEqualities, hits=hits)
     try:
         b.run()
-        out = b.matrix()
+        out = b.hits() if hits else b.matrix()
         out.update(b.best())
         return out
     finally:

@@ -150,27 +150,48 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreatePairs(const char* queries, const lon
     return b;
 }
 
-EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(const char* queries, const long long* queryOffsets, int numQueries,
-                                                  const char* targets, const long long* targetOffsets, int numTargets,
-                                                  EdlibAlignConfig config, int device) {
-    EdlibAmdBatch* b = guarded("edlibAmdBatchCreateCross", static_cast<EdlibAmdBatch*>(nullptr), [] {
+static EdlibAmdBatch* create_cross(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
+                                   const char* targets, const long long* targetOffsets, int numTargets,
+                                   EdlibAlignConfig config, int device, bool hits) {
+    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
         EdlibAmdBatch* x = new EdlibAmdBatch;
         x->cross.reset(new CrossBatch);
         return x;
     });
     if (!b) return nullptr;
-    if (guarded("edlibAmdBatchCreateCross", 1, [&] {
-            return b->cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device); })) {
+    if (guarded(where, 1, [&] {
+            return b->cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device,
+                                  hits); })) {
         delete b;
         return nullptr;
     }
     return b;
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(const char* queries, const long long* queryOffsets, int numQueries,
+                                                  const char* targets, const long long* targetOffsets, int numTargets,
+                                                  EdlibAlignConfig config, int device) {
+    return create_cross("edlibAmdBatchCreateCross", queries, queryOffsets, numQueries, targets, targetOffsets, numTargets,
+                        config, device, false);
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHits(const char* queries, const long long* queryOffsets, int numQueries,
+                                                      const char* targets, const long long* targetOffsets, int numTargets,
+                                                      EdlibAlignConfig config, int device) {
+    return create_cross("edlibAmdBatchCreateCrossHits", queries, queryOffsets, numQueries, targets, targetOffsets,
+                        numTargets, config, device, true);
+}
+
 EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* b, int what, EdlibAmdCrossView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
     if (!b->cross) { set_error("edlibAmdBatchCrossView: not a cross batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchCrossView", 1, [&] { return b->cross->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->cross) { set_error("edlibAmdBatchCrossHits: not a cross batch"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchCrossHits", 1, [&] { return b->cross->hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchRun(EdlibAmdBatch* b) {

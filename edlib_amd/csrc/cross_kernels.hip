@@ -75,7 +75,10 @@ __device__ __forceinline__ void cross_column(const u32* __restrict__ rows, int s
     }
 }
 
-template <int NWD, int S, int MODE>
+// HITS: the epilogue appends the cells within k to the hit list (one 64-bit atomicAdd per target-tile step of a wave that
+// has any) instead of writing the matrix.  Every lane reaches it with a flag: padding slots and target slots past the end
+// take part as non-hits.
+template <int NWD, int S, int MODE, bool HITS>
 __global__ void __launch_bounds__(64)
 scan_cross_kernel(CrossScanArgs a)
 {
@@ -99,75 +102,107 @@ scan_cross_kernel(CrossScanArgs a)
     const int q = a.qperm[slot];
     const int m = a.qlen[slot];
     const int sh = (m - 1) & 31;
-    if (q < 0) return;                                  // (no barrier below)
+    if (!HITS && q < 0) return;                         // (no barrier or ballot below)
     const int numTT = (a.numSorted + tpt - 1) / tpt;
-    for (int tt = blockIdx.y; tt < numTT; tt += gridDim.y) {
+    for (int tt = blockIdx.y; tt < numTT; tt += gridDim.y) {   // wave-uniform trip count
         const int ts = tt * tpt + ti;
-        if (ts >= a.numSorted) continue;
-        const int n = a.tlen[ts];
-        const u32* __restrict__ tp = a.tpk + a.tdw[ts];
-        u32 Pv[NWD], Mv[NWD];
+        const bool live = q >= 0 && ts < a.numSorted;
+        int ed = -1, nloc = 0, end = -1;
+        if (live) {
+            const int n = a.tlen[ts];
+            int score = m, best = 0x7fffffff, cnt = 0, first = -1;
+            if (!cross_nw_outside(MODE, a.kcfg, m, n)) {
+                const u32* __restrict__ tp = a.tpk + a.tdw[ts];
+                u32 Pv[NWD], Mv[NWD];
 #pragma unroll
-        for (int d = 0; d < NWD; ++d) { Pv[d] = ~0u; Mv[d] = 0u; }
-        int score = m, best = 0x7fffffff, cnt = 0, first = -1;
-        auto step = [&](u32 c, int j) {
-            cross_column<NWD, MODE>(s_peq + c * (NWD * qt) + qi, qt, Pv, Mv, sh, score);
-            if (MODE != 0) {
-                if (score < best) { best = score; cnt = 1; first = j; }
-                else if (score == best) ++cnt;
+                for (int d = 0; d < NWD; ++d) { Pv[d] = ~0u; Mv[d] = 0u; }
+                auto step = [&](u32 c, int j) {
+                    cross_column<NWD, MODE>(s_peq + c * (NWD * qt) + qi, qt, Pv, Mv, sh, score);
+                    if (MODE != 0) {
+                        if (score < best) { best = score; cnt = 1; first = j; }
+                        else if (score == best) ++cnt;
+                    }
+                };
+                int j = 0;
+                for (; j + 8 <= n; j += 8) {
+                    u32 w = tp[j >> 3];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) { step(w & 15u, j + c); w >>= 4; }
+                }
+                if (j < n) {
+                    u32 w = tp[j >> 3];
+                    for (; j < n; ++j) { step(w & 15u, j); w >>= 4; }
+                }
             }
-        };
-        int j = 0;
-        for (; j + 8 <= n; j += 8) {
-            u32 w = tp[j >> 3];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) { step(w & 15u, j + c); w >>= 4; }
+            cross_cell_result(MODE, a.kcfg, m, n, MODE == 0 ? score : best, cnt, first, ed, nloc, end);
         }
-        if (j < n) {
-            u32 w = tp[j >> 3];
-            for (; j < n; ++j) { step(w & 15u, j); w >>= 4; }
+        if (!HITS) {
+            if (live) {
+                const size_t at = (size_t)a.tperm[ts] * (size_t)a.numQueries + (size_t)q;
+                a.ed[at] = ed; a.nloc[at] = nloc; a.end[at] = end;
+            }
+            continue;
         }
-        int ed, nloc, end;
-        cross_cell_result(MODE, a.kcfg, m, n, MODE == 0 ? score : best, cnt, first, ed, nloc, end);
-        const size_t at = (size_t)a.tperm[ts] * (size_t)a.numQueries + (size_t)q;
-        a.ed[at] = ed; a.nloc[at] = nloc; a.end[at] = end;
+        const bool hit = live && ed != -1;
+        const u64 mask = __ballot(hit);
+        if (mask == 0) continue;                        // a sparse batch issues almost no atomics
+        const int leader = __ffsll((long long)mask) - 1;    // a lane with a hit: active
+        u64 base = 0;
+        if (lane == leader) base = atomicAdd(a.hitCount, (u64)__popcll(mask));
+        base = __shfl(base, leader, 64);
+        if (hit) {
+            const u64 at = base + __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
+            if (at < a.hitCap) {
+                a.hitKey[at] = ((u64)(u32)a.tperm[ts] << 32) | (u32)q;
+                a.hitVal[at] = ed; a.hitVal[a.hitCap + at] = nloc; a.hitVal[2 * a.hitCap + at] = end;
+            }
+        }
     }
 }
 
-template <int NWD, int S>
+template <int NWD, int S, bool HITS>
 static hipError_t launch_scan_cross_ws(int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
 {
     const dim3 grid((unsigned)a.numQueryTiles, (unsigned)ysplit);
-    if (mode == 0) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 0>), grid, dim3(64), 0, stream, a);
-    else if (mode == 1) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 1>), grid, dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 2>), grid, dim3(64), 0, stream, a);
+    if (mode == 0) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 0, HITS>), grid, dim3(64), 0, stream, a);
+    else if (mode == 1) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 1, HITS>), grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 2, HITS>), grid, dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 
-template <int NWD>
+template <int NWD, bool HITS>
 static hipError_t launch_scan_cross_w(int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
 {
-    if (syms == 4) return launch_scan_cross_ws<NWD, 4>(mode, a, ysplit, stream);
-    if (syms == 8) return launch_scan_cross_ws<NWD, 8>(mode, a, ysplit, stream);
-    return launch_scan_cross_ws<NWD, 16>(mode, a, ysplit, stream);
+    if (syms == 4) return launch_scan_cross_ws<NWD, 4, HITS>(mode, a, ysplit, stream);
+    if (syms == 8) return launch_scan_cross_ws<NWD, 8, HITS>(mode, a, ysplit, stream);
+    return launch_scan_cross_ws<NWD, 16, HITS>(mode, a, ysplit, stream);
 }
 
-hipError_t launch_scan_cross(int nwords, int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
+template <bool HITS>
+static hipError_t launch_scan_cross_h(int nwords, int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
+{
+    switch (nwords) {
+    case 1: return launch_scan_cross_w<1, HITS>(syms, mode, a, ysplit, stream);
+    case 2: return launch_scan_cross_w<2, HITS>(syms, mode, a, ysplit, stream);
+    case 3: return launch_scan_cross_w<3, HITS>(syms, mode, a, ysplit, stream);
+    case 4: return launch_scan_cross_w<4, HITS>(syms, mode, a, ysplit, stream);
+    case 5: return launch_scan_cross_w<5, HITS>(syms, mode, a, ysplit, stream);
+    case 6: return launch_scan_cross_w<6, HITS>(syms, mode, a, ysplit, stream);
+    case 7: return launch_scan_cross_w<7, HITS>(syms, mode, a, ysplit, stream);
+    case 8: return launch_scan_cross_w<8, HITS>(syms, mode, a, ysplit, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
+                             hipStream_t stream)
 {
     if (a.numQueryTiles == 0 || a.numSorted == 0) return hipSuccess;
     if ((syms != 4 && syms != 8 && syms != 16) || mode < 0 || mode > 2 || a.qt < 1 || a.qt > 64 || (64 % a.qt) != 0)
         return hipErrorInvalidValue;
-    switch (nwords) {
-    case 1: return launch_scan_cross_w<1>(syms, mode, a, ysplit, stream);
-    case 2: return launch_scan_cross_w<2>(syms, mode, a, ysplit, stream);
-    case 3: return launch_scan_cross_w<3>(syms, mode, a, ysplit, stream);
-    case 4: return launch_scan_cross_w<4>(syms, mode, a, ysplit, stream);
-    case 5: return launch_scan_cross_w<5>(syms, mode, a, ysplit, stream);
-    case 6: return launch_scan_cross_w<6>(syms, mode, a, ysplit, stream);
-    case 7: return launch_scan_cross_w<7>(syms, mode, a, ysplit, stream);
-    case 8: return launch_scan_cross_w<8>(syms, mode, a, ysplit, stream);
-    default: return hipErrorInvalidValue;
-    }
+    if (hits && (!a.hitCount || !a.hitKey || !a.hitVal)) return hipErrorInvalidValue;
+    return hits ? launch_scan_cross_h<true>(nwords, syms, mode, a, ysplit, stream)
+                : launch_scan_cross_h<false>(nwords, syms, mode, a, ysplit, stream);
 }
 
 // -------------------------------------------------------------- best hits
@@ -182,15 +217,6 @@ __device__ __forceinline__ void best2_merge(CrossBest2& r, const CrossBest2& o)
 {
     if (o.b < r.b) { r.s = r.b < o.s ? r.b : o.s; r.b = o.b; }
     else { r.s = r.s < o.b ? r.s : o.b; }
-}
-
-__device__ __forceinline__ u64 cross_key(int ed, int idx) { return ed < 0 ? ~0ull : (((u64)(u32)ed << 32) | (u32)idx); }
-
-__device__ __forceinline__ void best2_store(const CrossBest2& r, int* best, int* bestD, int* secondD, int i)
-{
-    best[i] = r.b == ~0ull ? -1 : (int)(u32)r.b;
-    bestD[i] = r.b == ~0ull ? -1 : (int)(r.b >> 32);
-    secondD[i] = r.s == ~0ull ? -1 : (int)(r.s >> 32);
 }
 
 // per target over its queries: one wave per row of the matrix

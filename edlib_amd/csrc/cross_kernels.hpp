@@ -14,6 +14,13 @@ constexpr int kCrossMaxSyms = 16;               // union target alphabet of the 
 // empty-sequence case of the reference (edlib.cpp:167-183) in front.  HW / SHW: best = smallest bottom-row score over the
 // target columns, cnt = number of columns at it, first = the first of them (best > every threshold when n == 0).
 // NW: best = score of the last column.
+// NW with k >= 0: a cell whose lengths differ by more than k is above k without a scan (the reference's own early exit,
+// edlib.cpp:744); the kernel skips the columns of such a cell and cross_cell_result() answers -1 for it.
+__host__ __device__ inline bool cross_nw_outside(int mode, int kcfg, int m, int n)
+{
+    return mode == 0 && kcfg >= 0 && (m > n ? m - n : n - m) > kcfg;
+}
+
 __host__ __device__ inline void cross_cell_result(int mode, int kcfg, int m, int n, int best, int cnt, int first,
                                                   int& ed, int& nloc, int& end)
 {
@@ -22,6 +29,7 @@ __host__ __device__ inline void cross_cell_result(int mode, int kcfg, int m, int
         else { ed = m; nloc = 1; end = -1; }
         return;
     }
+    if (cross_nw_outside(mode, kcfg, m, n)) { ed = -1; nloc = 0; end = -1; return; }
     if (mode == 0) {
         if (kcfg >= 0 && best > kcfg) { ed = -1; nloc = 0; end = -1; }
         else { ed = best; nloc = 1; end = n - 1; }
@@ -47,6 +55,18 @@ __host__ __device__ inline void cross_cell_result(int mode, int kcfg, int m, int
 // so ties go to the lowest index whatever the order of the reduction.  ~0 = none.
 struct CrossBest2 { unsigned long long b, s; };
 
+__device__ __forceinline__ unsigned long long cross_key(int ed, int idx)
+{
+    return ed < 0 ? ~0ull : (((unsigned long long)(uint32_t)ed << 32) | (uint32_t)idx);
+}
+
+__device__ __forceinline__ void best2_store(const CrossBest2& r, int* best, int* bestD, int* secondD, int i)
+{
+    best[i] = r.b == ~0ull ? -1 : (int)(uint32_t)r.b;
+    bestD[i] = r.b == ~0ull ? -1 : (int)(r.b >> 32);
+    secondD[i] = r.s == ~0ull ? -1 : (int)(r.s >> 32);
+}
+
 // What the scan of one query group needs.  The group's slots are tiles of `qt` queries; lane l of a wave takes query slot
 // tile * qt + l % qt against sorted target tile * (64 / qt) + l / qt.
 struct CrossScanArgs {
@@ -62,13 +82,21 @@ struct CrossScanArgs {
     int numSorted;
     int numQueries;             // row length of the matrix
     int kcfg;
-    int* ed; int* nloc; int* end;   // [numTargets][numQueries]
+    int* ed; int* nloc; int* end;   // [numTargets][numQueries] (dense batches)
+    // hit-list batches: every cell whose editDistance is not -1 is appended at slot atomicAdd(hitCount) as the key
+    // (target << 32) | query and its ed / nloc / end; slots at or past hitCap are counted but not written
+    unsigned long long* hitCount;
+    unsigned long long hitCap;
+    unsigned long long* hitKey;  // [hitCap]
+    int* hitVal;                // [3][hitCap]: editDistance, numLocations, endLocation
 };
 
 hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, const int* tperm, const long long* tdw,
                                      int numSorted, const uint8_t* tlut, uint32_t* tpk, hipStream_t stream);
-// nwords 1..8, syms 4 / 8 / 16, mode 0 NW / 1 SHW / 2 HW; ysplit: waves per query tile (each strides over target tiles)
-hipError_t launch_scan_cross(int nwords, int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream);
+// nwords 1..8, syms 4 / 8 / 16, mode 0 NW / 1 SHW / 2 HW; ysplit: waves per query tile (each strides over target tiles);
+// hits: append the cells within k to the hit list instead of writing the matrix
+hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
+                             hipStream_t stream);
 // per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are
 // best index / best distance / second distance
 hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,
@@ -77,5 +105,19 @@ hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,
 // cells computed by other engines: ed / nloc / end of cell[i] (index into the matrix)
 hipError_t launch_cross_scatter(const long long* cell, const int* vals, long long n, int* ed, int* nloc, int* end,
                                 hipStream_t stream);
+
+// ---- hit lists (cross_hits.hip)
+// temporary bytes of the sort of up to n hits
+hipError_t cross_hits_sort_bytes(long long n, int numTargets, size_t* bytes);
+// idx[i] = i for i < n
+hipError_t launch_cross_hits_iota(uint32_t* idx, long long n, hipStream_t stream);
+// The n hits (key, val [3][cap]) into CSR order: sorted by key (target-major, ascending query inside a target) into
+// skey / sidx, gathered into out [4][n] (query, editDistance, numLocations, endLocation), targetOffsets [nt + 1] from the
+// boundaries of the sorted keys; best hits per target and per query from the list into best ([3][nt] then [3][nq], the
+// layout of launch_cross_best) through bkey ([2][nt + nq]).
+hipError_t launch_cross_hits_finish(const unsigned long long* key, const int* val, long long cap, long long n,
+                                    int numQueries, int numTargets, const uint32_t* idx, unsigned long long* skey,
+                                    uint32_t* sidx, void* tmp, size_t tmpBytes, long long* targetOffsets, int* out,
+                                    unsigned long long* bkey, int* best, hipStream_t stream);
 
 }  // namespace edlib_amd

@@ -373,19 +373,23 @@ private:
 // target-major matrix and best hits, both made on the device.  Cells inside the cross kernel's envelope run on it; each
 // other target runs through an internal shared-target Batch over all queries, longer queries against the rest through
 // one internal pair Batch, and their results are scattered into the matrix.
+// A hit-list batch (hits: k >= 0) keeps no matrix: the scan appends the cells within k to a list, the internal sessions'
+// cells within k are appended behind them, and the list is sorted on the device into CSR order (per target, ascending
+// query) and reduced to the same best hits.
 class CrossBatch {
 public:
     ~CrossBatch();
     int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
-             EdlibAlignConfig cfg, int device);
+             EdlibAlignConfig cfg, int device, bool hits = false);
     int run();
     int view(int what, EdlibAmdCrossView* out);
+    int hitsView(EdlibAmdCrossHits* out);
     EdlibAmdBatchStats stats{};
 
 private:
     struct Group {
         int words = 0, qt = 64, tiles = 0, slots = 0, ysplit = 1;
-        long long liveWords = 0;                  // sum of the words of its real queries
+        long long wordSteps = 0;                  // word-steps of its scanned cells (NW, k >= 0: inside the length window)
         DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;
         DevBuf<uint32_t> d_peq;
     };
@@ -417,7 +421,23 @@ private:
     Event evScan0_, evScan1_;
     PinBuf h_mat_, h_best_;
     bool haveRun_ = false, matFetched_ = false, bestFetched_ = false;
+    // hit-list batches: nothing here scales with numQueries x numTargets; the list starts at max(2^20, nq + nt) entries
+    // and grows to the count of a Run that overflowed it (that Run scans again)
+    bool hits_ = false, hitsFetched_ = false;
+    long long hitCap_ = 0, numHits_ = 0;
+    DevBuf<unsigned long long> d_hcount_, d_hkey_, d_skey_, d_bkey_;
+    DevBuf<int> d_hval_, d_hout_;                 // [3][hitCap_] as appended; [4][numHits_] in CSR order
+    DevBuf<uint32_t> d_hidx_, d_sidx_;
+    DevBuf<uint8_t> d_sortTmp_;
+    DevBuf<long long> d_htoff_;                   // [nt + 1]
+    PinBuf h_hcount_, h_hits_;
+    std::vector<long long> otherCellIdx_;         // cells of the internal sessions (t * nq + q), host side
+    std::vector<unsigned long long> xKey_;        // their cells within k of the last Run
+    std::vector<int> xVal_;
     int gather(Batch& b, size_t n, int* vals);
+    int scanGroups();
+    int growHits(long long cap);
+    int finishHits();
 };
 
 // single-pair convenience used by edlibAlign()

@@ -3,7 +3,9 @@
 // length, packs the targets to 4-bit codes once and chooses each group's tile; a Run builds the Peq rows of every query
 // (build_peq_reads_kernel over the union target alphabet), scans every group on the cross kernel, lets the internal
 // sessions of the cells outside the kernel's envelope run meanwhile, scatters their results into the matrix and reduces
-// it to the best hits.  Results stay in HBM until view() asks for a part of them.
+// it to the best hits.  Results stay in HBM until view() asks for a part of them.  A hit-list batch appends the cells
+// within k instead (the scan, then the internal sessions' cells behind them) and finishes the list on the device
+// (cross_hits.hip): sorted into CSR order, target offsets, best hits from the list.
 #include "engine.hpp"
 
 #include <algorithm>
@@ -31,11 +33,16 @@ static int choose_qt(long long nq, long long nt)
 }
 
 int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const char* targets,
-                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device)
+                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device, bool hits)
 {
     if (cfg.task != EDLIB_TASK_DISTANCE) {
         set_error("cross batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
                   "for locations or paths");
+        return 1;
+    }
+    if (hits && cfg.k < 0) {
+        set_error("hit-list cross batches need config.k >= 0 (every cell is a hit at k = %d: use edlibAmdBatchCreateCross "
+                  "for the dense matrix)", cfg.k);
         return 1;
     }
     if (cfg.mode != EDLIB_MODE_NW && cfg.mode != EDLIB_MODE_SHW && cfg.mode != EDLIB_MODE_HW) { set_error("unknown mode"); return 1; }
@@ -48,7 +55,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
     cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
     cfg_.additionalEqualitiesLength = (int)eqs_.size();
-    device_ = device; nq_ = nq; nt_ = nt;
+    device_ = device; nq_ = nq; nt_ = nt; hits_ = hits;
     std::vector<long long> qoff(nq + 1, 0), toff(nt + 1, 0);
     if (nq > 0) qoff.assign(qoffIn, qoffIn + nq + 1);
     if (nt > 0) toff.assign(toffIn, toffIn + nt + 1);
@@ -81,23 +88,41 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     EDLIB_AMD_HIP(guard.status);
     EDLIB_AMD_HIP(pool_stream(&stream_));
     EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
-    EDLIB_AMD_HIP(d_mat_.alloc(3 * std::max<size_t>(cells_, 1)));
     EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
-    targetChunk_ = std::max(1024, (nt + 32767) / 32768);
-    EDLIB_AMD_HIP(d_partial_.alloc((size_t)std::max(1, (nt + targetChunk_ - 1) / targetChunk_) * (size_t)std::max(nq, 1)));
+    if (!hits_) {
+        EDLIB_AMD_HIP(d_mat_.alloc(3 * std::max<size_t>(cells_, 1)));
+        targetChunk_ = std::max(1024, (nt + 32767) / 32768);
+        EDLIB_AMD_HIP(d_partial_.alloc((size_t)std::max(1, (nt + targetChunk_ - 1) / targetChunk_) * (size_t)std::max(nq, 1)));
+    } else {
+        EDLIB_AMD_HIP(d_hcount_.alloc(1)); EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
+        EDLIB_AMD_HIP(d_htoff_.alloc((size_t)nt + 1));
+        EDLIB_AMD_HIP(d_bkey_.alloc(2 * ((size_t)nt + (size_t)nq)));
+        if (growHits(std::max<long long>(1LL << 20, (long long)nq + nt))) return 1;
+    }
 
     // ---- the cross kernel's share
     if (!inT.empty() && (int)longQ.size() < nq) {
         std::stable_sort(inT.begin(), inT.end(), [&](int a, int b) { return tlen(a) < tlen(b); });
         numSorted_ = (int)inT.size();
-        std::vector<long long> tdw(numSorted_);
+        std::vector<long long> tdw(numSorted_), colsBelow(numSorted_ + 1, 0);
         std::vector<int> tl(numSorted_);
         long long dw = 0;
         for (int i = 0; i < numSorted_; ++i) {
             tdw[i] = dw; tl[i] = tlen(inT[i]);
             dw += (tl[i] + 7) / 8;
             sortedCols_ += tl[i];
+            colsBelow[i + 1] = sortedCols_;
         }
+        // columns the kernel scans for a query of length m: all of them, or under NW with k >= 0 those of the targets in
+        // the length window [m - k, m + k] (cross_nw_outside), a range of the sorted lengths
+        auto scannedCols = [&](int m) -> long long {
+            if (cfg.mode == EDLIB_MODE_NW && cfg.k >= 0) {
+                const long long lo = std::lower_bound(tl.begin(), tl.end(), (long long)m - cfg.k) - tl.begin();
+                const long long hi = std::upper_bound(tl.begin(), tl.end(), (long long)m + cfg.k) - tl.begin();
+                return colsBelow[hi] - colsBelow[lo];
+            }
+            return sortedCols_;
+        };
         EDLIB_AMD_HIP(d_tpk_.alloc((size_t)std::max(dw, 1LL)));
         EDLIB_AMD_HIP(d_tdw_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tperm_.alloc(numSorted_));
         EDLIB_AMD_HIP(hipMemcpy(d_tdw_.p, tdw.data(), numSorted_ * sizeof(long long), hipMemcpyHostToDevice));
@@ -139,7 +164,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
             g->qt = choose_qt((long long)qs.size(), numSorted_);
             g->tiles = ((int)qs.size() + g->qt - 1) / g->qt;
             g->slots = g->tiles * g->qt;
-            g->liveWords = (long long)qs.size() * w;
+            for (int q : qs) g->wordSteps += (long long)w * scannedCols(qlen(q));
             const int tpt = 64 / g->qt;
             const long long targetTiles = (numSorted_ + tpt - 1) / tpt;
             // about 8,192 waves per launch (256 CUs), each persistent over a strided range of target tiles
@@ -186,9 +211,12 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
             for (int t : outTargets_)
                 for (int q = 0; q < nq; ++q) cellIdx.push_back((long long)t * nq + q);
             cellIdx.insert(cellIdx.end(), longCells_.begin(), longCells_.end());
-            EDLIB_AMD_HIP(d_cells_.alloc((size_t)otherCells_)); EDLIB_AMD_HIP(d_vals_.alloc(3 * (size_t)otherCells_));
             EDLIB_AMD_HIP(h_vals_.alloc(3 * (size_t)otherCells_ * sizeof(int)));
-            EDLIB_AMD_HIP(hipMemcpy(d_cells_.p, cellIdx.data(), (size_t)otherCells_ * sizeof(long long), hipMemcpyHostToDevice));
+            if (hits_) otherCellIdx_.swap(cellIdx);            // their hits are appended from the host
+            else {
+                EDLIB_AMD_HIP(d_cells_.alloc((size_t)otherCells_)); EDLIB_AMD_HIP(d_vals_.alloc(3 * (size_t)otherCells_));
+                EDLIB_AMD_HIP(hipMemcpy(d_cells_.p, cellIdx.data(), (size_t)otherCells_ * sizeof(long long), hipMemcpyHostToDevice));
+            }
         }
     }
     return 0;
@@ -208,18 +236,95 @@ int CrossBatch::gather(Batch& b, size_t n, int* vals)
     return 0;
 }
 
+// one scan per word group (the Peq is built); a hit-list batch counts its hits from 0
+int CrossBatch::scanGroups()
+{
+    if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
+    for (auto& g : groups_) {
+        CrossScanArgs a{};
+        a.peq = g->d_peq.p; a.qlen = g->d_qlen.p; a.qperm = g->d_perm.p; a.qt = g->qt; a.numQueryTiles = g->tiles;
+        a.tpk = d_tpk_.p; a.tdw = d_tdw_.p; a.tlen = d_tlen_.p; a.tperm = d_tperm_.p; a.numSorted = numSorted_;
+        a.numQueries = nq_; a.kcfg = cfg_.k;
+        if (hits_) {
+            a.hitCount = d_hcount_.p; a.hitCap = (unsigned long long)hitCap_; a.hitKey = d_hkey_.p; a.hitVal = d_hval_.p;
+        } else {
+            a.ed = d_mat_.p; a.nloc = d_mat_.p + cells_; a.end = d_mat_.p + 2 * cells_;
+        }
+        EDLIB_AMD_HIP(launch_scan_cross(g->words, syms_, (int)cfg_.mode, hits_, a, g->ysplit, stream_));
+        ++stats.scan_launches;
+        stats.word_steps += g->wordSteps;
+    }
+    return 0;
+}
+
+// the hit list and its sort / CSR buffers for `cap` hits (what they held is gone)
+int CrossBatch::growHits(long long cap)
+{
+    hitCap_ = 0;
+    size_t tmp = 0;
+    hipError_t e = d_hkey_.alloc((size_t)cap);
+    if (e == hipSuccess) e = d_hval_.alloc(3 * (size_t)cap);
+    if (e == hipSuccess) e = d_hidx_.alloc((size_t)cap);
+    if (e == hipSuccess) e = d_skey_.alloc((size_t)cap);
+    if (e == hipSuccess) e = d_sidx_.alloc((size_t)cap);
+    if (e == hipSuccess) e = d_hout_.alloc(4 * (size_t)cap);
+    if (e == hipSuccess) e = cross_hits_sort_bytes(cap, nt_, &tmp);
+    if (e == hipSuccess) e = d_sortTmp_.alloc(tmp);
+    if (e == hipSuccess) e = launch_cross_hits_iota(d_hidx_.p, cap, stream_);
+    if (e != hipSuccess) {
+        set_error("cross batch: no room on the device for a hit list of %lld hits (%s)", cap, hipGetErrorString(e));
+        return 1;
+    }
+    hitCap_ = cap;
+    return 0;
+}
+
+// after the scans and the internal sessions: the kernel's count (the sort needs it anyway); a count past capacity grows
+// the list to it and scans again, so later Runs of the batch fit.  Then the internal sessions' hits behind the kernel's,
+// and the list finished on the device.
+int CrossBatch::finishHits()
+{
+    unsigned long long* hc = reinterpret_cast<unsigned long long*>(h_hcount_.p);
+    EDLIB_AMD_HIP(hipMemcpyAsync(hc, d_hcount_.p, sizeof *hc, hipMemcpyDeviceToHost, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    const long long kernelHits = (long long)*hc, extra = (long long)xKey_.size(), total = kernelHits + extra;
+    if (total > 0xffffffffLL) {
+        set_error("cross batch: %lld hits, more than a hit list holds (2^32 - 1): lower k or split the batch", total);
+        return 1;
+    }
+    if (total > hitCap_) {
+        if (growHits(total)) return 1;
+        if (kernelHits > 0 && scanGroups()) return 1;
+    }
+    if (extra > 0) {
+        const size_t cap = (size_t)hitCap_;
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_hkey_.p + kernelHits, xKey_.data(), (size_t)extra * sizeof(unsigned long long),
+                                     hipMemcpyHostToDevice, stream_));
+        for (int f = 0; f < 3; ++f)
+            EDLIB_AMD_HIP(hipMemcpyAsync(d_hval_.p + f * cap + kernelHits, xVal_.data() + f * (size_t)extra,
+                                         (size_t)extra * sizeof(int), hipMemcpyHostToDevice, stream_));
+    }
+    size_t tmp = 0;
+    EDLIB_AMD_HIP(cross_hits_sort_bytes(total, nt_, &tmp));
+    if (tmp > d_sortTmp_.n) EDLIB_AMD_HIP(d_sortTmp_.alloc(tmp));
+    EDLIB_AMD_HIP(launch_cross_hits_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nq_, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
+                                           d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, d_bkey_.p, d_best_.p, stream_));
+    numHits_ = total;
+    return 0;
+}
+
 int CrossBatch::run()
 {
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    haveRun_ = matFetched_ = bestFetched_ = false;
+    haveRun_ = matFetched_ = bestFetched_ = hitsFetched_ = false;
     const long long cells = stats.cells;
     stats = EdlibAmdBatchStats{};
     stats.cells = cells;
-    int* ed = d_mat_.p; int* nloc = d_mat_.p + cells_; int* end = d_mat_.p + 2 * cells_;
-    const int mode = (int)cfg_.mode;
+    int* ed = d_mat_.p; int* nloc = hits_ ? nullptr : ed + cells_; int* end = hits_ ? nullptr : ed + 2 * cells_;
+    if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
 
     // the cross kernel: Peq of every query, then one scan per word group
     if (!groups_.empty()) {
@@ -228,19 +333,12 @@ int CrossBatch::run()
                                                  d_presence_.p, cfg_.k, g->d_peq.p, g->d_qlen.p, g->d_kinit.p, g->d_alpha.p,
                                                  stream_));
         EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
-        for (auto& g : groups_) {
-            CrossScanArgs a{};
-            a.peq = g->d_peq.p; a.qlen = g->d_qlen.p; a.qperm = g->d_perm.p; a.qt = g->qt; a.numQueryTiles = g->tiles;
-            a.tpk = d_tpk_.p; a.tdw = d_tdw_.p; a.tlen = d_tlen_.p; a.tperm = d_tperm_.p; a.numSorted = numSorted_;
-            a.numQueries = nq_; a.kcfg = cfg_.k; a.ed = ed; a.nloc = nloc; a.end = end;
-            EDLIB_AMD_HIP(launch_scan_cross(g->words, syms_, mode, a, g->ysplit, stream_));
-            ++stats.scan_launches;
-            stats.word_steps += g->liveWords * sortedCols_;
-        }
+        if (scanGroups()) return 1;
         EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
         stats.path |= 8;
     }
     // the other engines run on their own streams meanwhile
+    xKey_.clear(); xVal_.clear();
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
         size_t at = 0;
@@ -260,12 +358,28 @@ int CrossBatch::run()
             stats.word_steps += s.word_steps; stats.scan_launches += s.scan_launches;
             stats.path |= s.path; stats.overflow_units += s.overflow_units; stats.wide_retries += s.wide_retries;
         }
-        EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, 3 * (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
-        EDLIB_AMD_HIP(launch_cross_scatter(d_cells_.p, d_vals_.p, otherCells_, ed, nloc, end, stream_));
+        if (!hits_) {
+            EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, 3 * (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
+            EDLIB_AMD_HIP(launch_cross_scatter(d_cells_.p, d_vals_.p, otherCells_, ed, nloc, end, stream_));
+        } else {
+            // their cells within k, as [key], [ed][nloc][end]
+            std::vector<int> e3[3];
+            for (long long i = 0; i < otherCells_; ++i) {
+                if (vals[3 * i] == -1) continue;
+                const long long c = otherCellIdx_[(size_t)i];
+                xKey_.push_back(((unsigned long long)(c / nq_) << 32) | (unsigned long long)(c % nq_));
+                for (int f = 0; f < 3; ++f) e3[f].push_back(vals[3 * i + f]);
+            }
+            for (int f = 0; f < 3; ++f) xVal_.insert(xVal_.end(), e3[f].begin(), e3[f].end());
+        }
     }
-    int* bq = d_best_.p; int* bt = d_best_.p + 3 * (size_t)nt_;
-    EDLIB_AMD_HIP(launch_cross_best(ed, nq_, nt_, bq, bq + nt_, bq + 2 * (size_t)nt_, bt, bt + nq_, bt + 2 * (size_t)nq_,
-                                    d_partial_.p, targetChunk_, stream_));
+    if (hits_) {
+        if (finishHits()) return 1;
+    } else {
+        int* bq = d_best_.p; int* bt = d_best_.p + 3 * (size_t)nt_;
+        EDLIB_AMD_HIP(launch_cross_best(ed, nq_, nt_, bq, bq + nt_, bq + 2 * (size_t)nt_, bt, bt + nq_, bt + 2 * (size_t)nq_,
+                                        d_partial_.p, targetChunk_, stream_));
+    }
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     if (!groups_.empty()) {
         float ms = 0.f;
@@ -282,6 +396,11 @@ int CrossBatch::view(int what, EdlibAmdCrossView* out)
 {
     if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
     if (what & ~(EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST)) { set_error("cross view: unknown parts %d", what); return 1; }
+    if (hits_ && (what & EDLIB_AMD_CROSS_MATRIX)) {
+        set_error("cross view: a hit-list batch keeps no matrix (edlibAmdBatchCrossHits has its cells within k; "
+                  "create the batch with edlibAmdBatchCreateCross for EDLIB_AMD_CROSS_MATRIX)");
+        return 1;
+    }
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
@@ -309,6 +428,35 @@ int CrossBatch::view(int what, EdlibAmdCrossView* out)
         b += 3 * (size_t)nt_;
         out->bestTarget = b; out->bestTargetDistance = b + nq_; out->secondTargetDistance = b + 2 * (size_t)nq_;
     }
+    return 0;
+}
+
+int CrossBatch::hitsView(EdlibAmdCrossHits* out)
+{
+    if (!hits_) {
+        set_error("edlibAmdBatchCrossHits: not a hit-list batch (create it with edlibAmdBatchCreateCrossHits; a dense cross "
+                  "batch has edlibAmdBatchCrossView)");
+        return 1;
+    }
+    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    const size_t offBytes = ((size_t)nt_ + 1) * sizeof(long long), listBytes = 4 * (size_t)numHits_ * sizeof(int);
+    if (!hitsFetched_) {
+        if (h_hits_.n < offBytes + listBytes || !h_hits_.p) EDLIB_AMD_HIP(h_hits_.alloc(offBytes + listBytes));
+        EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p, d_htoff_.p, offBytes, hipMemcpyDeviceToHost, stream_));
+        if (listBytes)
+            EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p + offBytes, d_hout_.p, listBytes, hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        hitsFetched_ = true;
+    }
+    memset(out, 0, sizeof *out);
+    out->numQueries = nq_; out->numTargets = nt_; out->numHits = numHits_;
+    out->targetOffsets = reinterpret_cast<const long long*>(h_hits_.p);
+    const int* l = reinterpret_cast<const int*>(h_hits_.p + offBytes);
+    const size_t n = (size_t)numHits_;
+    out->query = l; out->editDistance = l + n; out->numLocations = l + 2 * n; out->endLocation = l + 3 * n;
     return 0;
 }
 

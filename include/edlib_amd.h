@@ -154,6 +154,33 @@ typedef struct {
 #define EDLIB_AMD_CROSS_BEST   2
 EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* batch, int what, EdlibAmdCrossView* out);
 
+/* A cross batch whose results are the cells within k as a list, without a numQueries x numTargets matrix anywhere
+ * (device or host).  Same inputs, routing, modes and additionalEqualities as edlibAmdBatchCreateCross; config.task
+ * must be EDLIB_TASK_DISTANCE and config.k >= 0 (otherwise NULL, with the reason in edlibAmdLastError()).
+ * Run, Stats and Destroy work as for a dense cross batch; edlibAmdBatchCrossView gives EDLIB_AMD_CROSS_BEST (equal to
+ * a dense batch's) and refuses EDLIB_AMD_CROSS_MATRIX; Results, ResultsFlat, ResultsView and CigarView fail.
+ * The device list starts at max(2^20, numQueries + numTargets) hits; a Run that finds more grows it to its count and
+ * scans once more (later Runs of the batch fit); a list that does not fit in device memory fails the Run with the count
+ * in the message. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHits(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* targets, const long long* targetOffsets, int numTargets,
+    EdlibAlignConfig config, int device);
+
+/* The hits of the last Run of such a batch: every cell whose editDistance is not -1, i.e. exactly the cells of the
+ * dense batch's matrix that are not -1, grouped by target (CSR) and by ascending query index inside a target.
+ * Pointers into pinned memory the batch owns, valid until the next Run / Destroy. */
+typedef struct {
+    int numQueries, numTargets;
+    long long numHits;
+    const long long* targetOffsets;   /* [numTargets + 1]: hits of target t are [targetOffsets[t], targetOffsets[t+1]) */
+    const int* query;                 /* [numHits] */
+    const int* editDistance;          /* [numHits] */
+    const int* numLocations;          /* [numHits] */
+    const int* endLocation;           /* [numHits] endLocations[0], else -1 */
+} EdlibAmdCrossHits;
+EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* batch, EdlibAmdCrossHits* out);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 

@@ -1,9 +1,12 @@
 """Cross batches (every query against every target) on one device: resident run ms and view ms (BEST only, then MATRIX)
 for the demultiplexing shape (96 x 24 bp barcodes against 1M x 150 bp read heads, HW, k = -1) and the all-against-all
 shape (2,000 x 150 bp amplicons, NW), and the same cells through PairBatch at a size both routes hold (96 x 20,000),
-with a sample of cells checked against the reference.  Prints one JSON line.
+with a sample of cells checked against the reference.  Hit-list batches ("hits"): run ms, hits-view ms and numHits of
+200,000 x 200,000 32 bp sequences (2,000 families of 100, NW, k = 2), of the 2,000 amplicons at NW k = 8 and of the demux
+shape at HW k = 3 (each beside the dense batch's run + MATRIX view), and of 2,000 amplicons of 100-200 bp at NW k = 5
+(the length window decides most cells).  Prints one JSON line.
 
-    python tools/bench_cross.py [--reads 1000000] [--amplicons 2000] [--runs 5]
+    python tools/bench_cross.py [--reads 1000000] [--amplicons 2000] [--runs 5] [--families 2000]
 """
 import argparse
 import json
@@ -38,8 +41,8 @@ def amplicons(rng, n, length=150):
     return a
 
 
-def time_cross(queries, targets, mode, runs):
-    b = edlib_amd.CrossBatch(queries, targets, mode=mode, k=-1)
+def time_cross(queries, targets, mode, runs, k=-1):
+    b = edlib_amd.CrossBatch(queries, targets, mode=mode, k=k)
     b.run()                                                 # warm-up
     ms, scan = [], []
     for _ in range(runs):
@@ -52,6 +55,72 @@ def time_cross(queries, targets, mode, runs):
     out = {"run_ms": float(np.median(ms)), "scan_ms": float(np.median(scan)), "view_best_ms": best_ms,
            "view_matrix_ms": mat_ms, "cells": st["cells"], "word_steps": st["word_steps"], "path": st["path"]}
     return b, out, {k: v.copy() for k, v in mat.items()}, {k: v.copy() for k, v in best.items()}
+
+
+def time_hits(queries, targets, mode, k, runs):
+    """A hit-list batch: median resident run ms (scan ms), then the hits view and the BEST view of the last run."""
+    b = edlib_amd.CrossBatch(queries, targets, mode=mode, k=k, hits=True)
+    st = b.run()                                            # warm-up (a first run past the list's capacity grows it)
+    first_ms = st["run_ms"]
+    ms, scan = [], []
+    for _ in range(runs):
+        t = time.perf_counter()
+        st = b.run()
+        ms.append((time.perf_counter() - t) * 1e3)
+        scan.append(st["scan_ms"])
+    t = time.perf_counter(); h = b.hits(copy=False); hits_ms = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter(); b.best(copy=False); best_ms = (time.perf_counter() - t) * 1e3
+    out = {"run_ms": float(np.median(ms)), "scan_ms": float(np.median(scan)), "first_run_ms": first_ms,
+           "view_hits_ms": hits_ms, "view_best_ms": best_ms, "numHits": int(len(h["query"])),
+           "cells": st["cells"], "word_steps": st["word_steps"], "path": st["path"]}
+    h = {f: v.copy() for f, v in h.items()}
+    b.close()
+    return out, h
+
+
+def families(rng, nfam, kids, length=32):
+    """nfam random parents with kids children each at 0-2 substitutions."""
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    seqs = np.repeat(rng.choice(acgt, size=(nfam, length)).astype(np.uint8), kids, axis=0)
+    for p in (0.8, 0.5):
+        hit = rng.random(len(seqs)) < p
+        pos = rng.integers(0, length, size=len(seqs))
+        seqs[hit, pos[hit]] = rng.choice(acgt, size=int(hit.sum()))
+    return seqs
+
+
+def check_hits(queries, targets, mode, k, h, n, rng):
+    """Sampled hits against the reference: mismatching editDistance values."""
+    from oracle import oracle as O
+    nh = len(h["query"])
+    if nh == 0:
+        return 0
+    idx = rng.choice(nh, size=min(n, nh), replace=False)
+    t_ = np.searchsorted(h["targetOffsets"], idx, side="right") - 1
+    qs = [bytes(queries[int(h["query"][i])]) for i in idx]
+    ts = [bytes(targets[int(t)]) for t in t_]
+
+    def pack(s):
+        off = np.zeros(len(s) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(x) for x in s])
+        return np.frombuffer(b"".join(s) + b"\0", dtype=np.uint8), off
+    qp, qo = pack(qs)
+    tp, to = pack(ts)
+    r = O.pool_align(qp, qo, tp, to, False, mode, "distance", k)
+    return int(np.sum(np.asarray(r["editDistance"]) != h["editDistance"][idx]))
+
+
+def hits_beside_dense(queries, targets, mode, k, runs, check, rng):
+    res, h = time_hits(queries, targets, mode, k, runs)
+    b, dense, _, _ = time_cross(queries, targets, mode, runs, k=k)
+    b.close()
+    res["dense_run_ms"] = dense["run_ms"]
+    res["dense_view_matrix_ms"] = dense["view_matrix_ms"]
+    res["dense_word_steps"] = dense["word_steps"]
+    res["shape"] = [len(queries), len(targets)]
+    res["k"] = k
+    res["sample_mismatches"] = check_hits(queries, targets, mode, k, h, check, rng)
+    return res
 
 
 def check_sample(queries, targets, mode, mat, n, rng):
@@ -79,6 +148,8 @@ def main():
     ap.add_argument("--pair-reads", type=int, default=20_000)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--check", type=int, default=2000)
+    ap.add_argument("--families", type=int, default=2000, help="families of 100 in the 32 bp all-against-all shape")
+    ap.add_argument("--no-hits", action="store_true", help="only the dense shapes")
     a = ap.parse_args()
     rng = np.random.default_rng(1)
     res = {"metric": "bench_cross"}
@@ -113,6 +184,23 @@ def main():
                              "pairs_run_ms": float(np.median(ms)),
                              "speedup": float(np.median(ms)) / max(cross_small["run_ms"], 1e-9),
                              "mismatches": int(np.sum(f["editDistance"] != mat["editDistance"].reshape(-1)))}
+    del mat
+
+    if not a.no_hits:
+        hits = res["hits"] = {}
+        seqs = families(rng, a.families, 100)
+        r, h = time_hits(seqs, seqs, "NW", 2, max(1, min(a.runs, 3)))
+        r["shape"] = [len(seqs), len(seqs)]
+        r["k"] = 2
+        r["sample_mismatches"] = check_hits(seqs, seqs, "NW", 2, h, a.check, rng)
+        hits["all_against_all_32"] = r
+        del h
+        hits["amplicons_150"] = hits_beside_dense(amp, amp, "NW", 8, a.runs, a.check, rng)
+        acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+        var = [bytes(amp[i % len(amp)][:int(n)]) + bytes(rng.choice(acgt, size=max(0, int(n) - 150)))
+               for i, n in enumerate(rng.integers(100, 201, size=a.amplicons))]
+        hits["amplicons_100_200"] = hits_beside_dense(var, var, "NW", 5, a.runs, a.check, rng)
+        hits["demux"] = hits_beside_dense(bc, reads, "HW", 3, a.runs, a.check, rng)
     print(json.dumps(res))
 
 
