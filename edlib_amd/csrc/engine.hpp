@@ -158,7 +158,7 @@ private:
 
     // ---- reads-per-lane path
     struct ReadGroup {
-        int nwords = 0, nslots = 0, numSegments = 1, segLen = 0, warm = 0;
+        int nwords = 0, nslots = 0, numSegments = 1, segLen = 0, warm = 0, mMin = 0;   // mMin: the shortest query
         std::vector<int> perm;                 // slot -> unit (or -1)
         DevBuf<int> d_perm, d_qlen, d_kinit, d_alphaExtra, d_segBest, d_segCnt, d_segPos;
         DevBuf<int> d_best, d_total, d_pos, d_flags;
@@ -181,6 +181,12 @@ private:
     int runGroupScans(ReadGroup& g, bool fullOnly);
     int runGroupExact(ReadGroup& g);
     int collectGroup(ReadGroup& g, std::vector<UnitResult>& res);
+    // ---- exact k-mer seed filter in place of the banded first pass (reads_seed.hip)
+    int seedThreshold(const ReadGroup& g, bool fullOnly) const;   // k_f of the group, -1: the group takes the banded pass
+    int buildSeedIndex();                                         // buckets of the shared target (every run, after packTarget)
+    int runSeedPass(ReadGroup& g, int k);                         // pass 1 at threshold k, hand-backs through the banded kernel
+    DevBuf<uint32_t> d_seedCnt_, d_seedOff_, d_seedPos_;          // [4^12 + 1] counts, [4^12 + 1] bucket offsets, [T] positions
+    DevBuf<uint8_t> d_seedTmp_;                                   // rocPRIM scan scratch
     // ---- long HW queries: piece filter on the reads-per-lane kernel + window verification on kernel W (long_reads.hip)
     struct Piece { long long off; int len; int thr; };           // rows [off, off + len) of the query pool, threshold of its scan
     int scanPieces(const std::vector<Piece>& pieces, bool filter, std::vector<std::pair<int, int>>* cand,

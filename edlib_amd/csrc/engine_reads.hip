@@ -103,6 +103,9 @@ int Batch::runReads()
 {
     if (groups_.empty()) return 0;
     stats.path |= 1;
+    bool seed = false;
+    for (auto& gp : groups_) seed = seed || seedThreshold(*gp, false) >= 0;
+    if (seed && buildSeedIndex()) return 1;
     for (auto& gp : groups_) if (runGroupScans(*gp, false)) return 1;
     for (auto& gp : groups_) if (runGroupExact(*gp)) return 1;
     return 0;
@@ -125,8 +128,11 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
     // first threshold of the k-doubling (edlib.cpp:197-217 starts at 64): 8 up to 512 bases; the groups of 24 / 32
     // words take 12 / 16 -- at 1 % error a 1024-base read has distance ~10, and a read that fails the first level
     // pays the full 32-word height over the whole target
-    const int kFirstMax = std::max(8, g.nwords / 2);
-    int kFirst = kFirstMax;
+    // Groups the exact seed filter takes start at its threshold k_f instead: pass 1 costs them the lookups and
+    // the windows, not a band over every column, and the probe below only prices the levels after it.
+    const int kSeed = seedThreshold(g, fullOnly);
+    const int kFirstMax = kSeed >= 0 ? kSeed : std::max(8, g.nwords / 2);
+    int kFirst = (kSeed >= 0 && cfg_.k >= 0) ? std::min(kSeed, cfg_.k) : kFirstMax;
     bool twoPass = !fullOnly && banded && (cfg_.k < 0 || cfg_.k > kFirst) && 32 * g.nwords > kFirst;
     std::vector<int> ladder;                    // thresholds of the banded passes between the first and the full one
     if (twoPass && g.nslots >= 16384) {
@@ -178,12 +184,12 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
         // unrelated sequence that score hovers around 13, so every unit of k below 8 keeps the second
         // word out more often.  Take the smallest threshold (>= 4) that still resolves 99.5 % of what 8
         // resolves: the few reads above it just join pass 2.
-        if (resolved > 0) {
+        if (resolved > 0 && kSeed < 0) {
             int acc = 0, kq = kFirstMax;
             for (int d = 0; d <= kFirstMax; ++d) { acc += hist[d]; if (acc * 1000LL >= resolved * 995LL) { kq = d; break; } }
             kFirst = std::max(4, std::min(kFirstMax, kq));
         }
-        if (real > 0 && resolved * 10 < real * 3) twoPass = false;
+        if (kSeed < 0 && real > 0 && resolved * 10 < real * 3) twoPass = false;   // (the seed pass costs little whatever resolves)
         // ---- the levels between the first and the full threshold (the reference doubles k: edlib.cpp:197-217).  When
         // more than a tenth of the probe is still open, the open probe reads are scanned once more with thresholds
         // capped at 64: their distances say which intermediate thresholds pay.  A level at threshold t costs every
@@ -222,11 +228,15 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             }
         }
     }
-    if (scanGroup(g, mode, nullptr, g.nslots, twoPass ? kFirst : kNoCap, g.d_kinit.p, g.numSegments, g.segLen,
-                  g.warm, g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, 8, nullptr, nullptr, /*unbanded=*/fullOnly)) return 1;
-    EDLIB_AMD_HIP(launch_merge_segments(g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, g.numSegments, 8,
-                                        g.nslots, nullptr, 16, g.d_best.p, g.d_total.p, g.d_pos.p,
-                                        g.d_flags.p, stream_));
+    if (kSeed >= 0) {
+        if (runSeedPass(g, kFirst)) return 1;
+    } else {
+        if (scanGroup(g, mode, nullptr, g.nslots, twoPass ? kFirst : kNoCap, g.d_kinit.p, g.numSegments, g.segLen,
+                      g.warm, g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, 8, nullptr, nullptr, /*unbanded=*/fullOnly)) return 1;
+        EDLIB_AMD_HIP(launch_merge_segments(g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, g.numSegments, 8,
+                                            g.nslots, nullptr, 16, g.d_best.p, g.d_total.p, g.d_pos.p,
+                                            g.d_flags.p, stream_));
+    }
     // ---- the next levels (k-doubling): slots with nothing <= the last threshold are rescanned with the next one,
     // the last time with their full threshold
     ladder.push_back(kNoCap);
@@ -328,6 +338,85 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
         hipLaunchKernelGGL(count_flags_kernel, dim3((g.nslots + 255) / 256), dim3(256), 0, stream_,
                            g.d_flags.p, g.nslots, counter);
     }
+    return 0;
+}
+
+// ------------------------------------------------------- exact k-mer seed filter (reads_seed.hip)
+
+// k_f of a group: the largest k <= 16 whose k + 1 pieces of the shortest read hold at least kSeedQ symbols each and whose
+// expected random exact hits per read on a uniform target, (k + 1) T / 4^L, stay at or below 1/8 (150-base reads against
+// 5 Mb: k_f = 9, ten pieces of 15 symbols, 0.05 random windows per read).  -1: the group takes the banded first pass.
+int Batch::seedThreshold(const ReadGroup& g, bool fullOnly) const
+{
+    const long long T = tlen(0);
+    if (fullOnly || !banded_ || cfg_.mode != EDLIB_MODE_HW || syms_ != 4 || cfg_.additionalEqualitiesLength > 0 ||
+        g.nwords > kMaxReadWords || chain_.in != nullptr || chain_.out != nullptr)
+        return -1;
+    // The index costs every run 0.5 ms at 5 Mb (measured: count 0.19, rocPRIM scan of the 4^12 counts 0.08, fill 0.23 ms), the
+    // banded pass 888 ms per 5e12 read-columns: it pays from ~1e9 read-columns and ~600 reads at 5 Mb.  Smaller batches, and
+    // targets shorter than 64 columns per query row, keep the banded pass.
+    if (T < 64LL * 32 * g.nwords || g.nslots < 1024 || (long long)g.nslots * T < (1LL << 30)) return -1;
+    int kf = -1;
+    for (int k = 16; k >= 0 && kf < 0; --k) {
+        const int L = g.mMin / (k + 1);
+        if (L >= kSeedQ && (double)(k + 1) * (double)T <= std::ldexp(1.0, 2 * L) / 8.0) kf = k;
+    }
+    // a k_f below the banded pass's first threshold (8) would leave more reads to the full-height pass than that pass does
+    // (short reads against long targets: 40 bases against 5 Mb give k_f = 1), unless the caller's k is no higher
+    return (kf >= 0 && kf >= std::min(8, cfg_.k >= 0 ? cfg_.k : 8)) ? kf : -1;
+}
+
+// the buckets of the shared target: rebuilt in every run, as d_tpk_ is (a step does all of its target-dependent work)
+int Batch::buildSeedIndex()
+{
+    const int T = tlen(0);
+    EDLIB_AMD_HIP(d_seedCnt_.ensure((size_t)kSeedBuckets + 1));
+    EDLIB_AMD_HIP(d_seedOff_.ensure((size_t)kSeedBuckets + 1));
+    EDLIB_AMD_HIP(d_seedPos_.ensure((size_t)T));
+    size_t tmp = 0;
+    EDLIB_AMD_HIP(seed_index_scratch_bytes(&tmp));
+    EDLIB_AMD_HIP(d_seedTmp_.ensure(tmp));
+    scanTimerStart();
+    EDLIB_AMD_HIP(launch_build_seed_index(d_tpk_.p, T, d_seedCnt_.p, d_seedOff_.p, d_seedPos_.p, d_seedTmp_.p,
+                                          d_seedTmp_.bytes(), stream_));
+    scanTimerStop();
+    return 0;
+}
+
+// Pass 1 of a seed group at threshold k: every slot gets merge_segments_kernel's record (best or -1, the number of end
+// locations, the first 16, the overflow flag) from its windows; the slots the filter hands back are scanned with the banded
+// kernel over the whole target at the same threshold and merged through the slot map.
+int Batch::runSeedPass(ReadGroup& g, int k)
+{
+    const int T = tlen(0);
+    DevBuf<int> d_back;                                        // [nslots] handed-back slots, then their number
+    EDLIB_AMD_HIP(d_back.alloc((size_t)g.nslots + 1));
+    int* backCount = d_back.p + g.nslots;
+    EDLIB_AMD_HIP(hipMemsetAsync(backCount, 0, sizeof(int), stream_));
+    SeedArgs a{};
+    a.peq = g.d_peq.p; a.qlen = g.d_qlen.p; a.perm = g.d_perm.p; a.tpk = d_tpk_.p; a.targetLength = T;
+    a.seedOff = d_seedOff_.p; a.seedPos = d_seedPos_.p; a.nslots = g.nslots; a.k = k;
+    a.best = g.d_best.p; a.total = g.d_total.p; a.pos = g.d_pos.p; a.flags = g.d_flags.p;
+    a.backSlots = d_back.p; a.backCount = backCount; a.wordSteps = d_wordSteps_.p;
+    scanTimerStart();
+    EDLIB_AMD_HIP(launch_seed_verify(g.nwords, a, stream_));
+    scanTimerStop();
+    int nb = 0;
+    EDLIB_AMD_HIP(hipMemcpyAsync(&nb, backCount, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    static const bool dbg = getenv("EDLIB_AMD_DEBUG") != nullptr;
+    if (dbg) fprintf(stderr, "[edlib_amd] seed pass nwords=%d k=%d: %d of %d slots handed back\n", g.nwords, k, nb, g.nslots);
+    if (nb <= 0) return 0;
+    int S2, segLen2, warm2;
+    plan_segments(nb, T, EDLIB_MODE_HW, g.warm, 65536, S2, segLen2, warm2);
+    const size_t items = (size_t)nb * S2;
+    DevBuf<int> d_sb, d_sc, d_sp;
+    EDLIB_AMD_HIP(d_sb.alloc(items)); EDLIB_AMD_HIP(d_sc.alloc(items)); EDLIB_AMD_HIP(d_sp.alloc(items * 8));
+    if (scanGroup(g, EDLIB_MODE_HW, d_back.p, nb, k, g.d_kinit.p, S2, segLen2, warm2, d_sb.p, d_sc.p, d_sp.p, 8,
+                  nullptr, nullptr)) return 1;
+    EDLIB_AMD_HIP(launch_merge_segments(d_sb.p, d_sc.p, d_sp.p, S2, 8, nb, d_back.p, 16, g.d_best.p, g.d_total.p,
+                                        g.d_pos.p, g.d_flags.p, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));            // temporaries die here
     return 0;
 }
 

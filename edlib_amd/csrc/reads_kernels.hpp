@@ -81,6 +81,35 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 hipError_t launch_collect_candidates(const int* segCnt, const int* segPos, int numSegments, int cap, int nlanes,
                                      int* out, int maxOut, int* counter, int* overflow, hipStream_t stream);
 
+// Exact k-mer seed filter, the first pass of HW groups of up to kMaxReadWords words against a target of at most four
+// symbols (reads_seed.hip).  Buckets on the first kSeedQ symbols of every target position.
+constexpr int kSeedQ = 12;
+constexpr int kSeedBuckets = 1 << (2 * kSeedQ);
+constexpr int kSeedBucketCap = 64;      // a piece whose bucket holds more target positions hands its read back
+constexpr int kSeedMaxDiag = 32;        // distinct diagonals a read may collect (LDS: 8 KB per wave)
+constexpr int kSeedMaxWindow = 1024;    // columns of one merged window
+
+struct SeedArgs {
+    const uint32_t* peq;      // the group's Peq rows, [readBlock][4][NWD][64 lanes]
+    const int* qlen;          // [slots]
+    const int* perm;          // [slots] slot -> unit, -1 = padding
+    const uint32_t* tpk;      // target, 2 bits / symbol (ReadScanArgs::tpk)
+    int targetLength;
+    const uint32_t* seedOff;  // [kSeedBuckets + 1]
+    const uint32_t* seedPos;  // [targetLength]
+    int nslots;               // multiple of 64
+    int k;                    // threshold: columns scoring <= k are found
+    int* best; int* total; int* pos; int* flags;   // the group's merged per-slot results (merge_segments_kernel's meaning)
+    int* backSlots; int* backCount;                // slots handed back to the banded scan
+    unsigned long long* wordSteps;                 // += word-columns verified
+};
+
+hipError_t seed_index_scratch_bytes(size_t* bytes);
+// cnt, off: kSeedBuckets + 1 entries; pos: targetLength entries; tmp: seed_index_scratch_bytes()
+hipError_t launch_build_seed_index(const uint32_t* tpk, int targetLength, uint32_t* cnt, uint32_t* off, uint32_t* pos,
+                                   void* tmp, size_t tmpBytes, hipStream_t stream);
+hipError_t launch_seed_verify(int nwords, const SeedArgs& a, hipStream_t stream);
+
 hipError_t launch_merge_segments(const int* segBest, const int* segCnt, const int* segPos,
                                  int numSegments, int cap, int nlanes, const int* slotmap, int capFinal,
                                  int* best, int* total, int* pos, int* flags, hipStream_t stream);

@@ -11,6 +11,57 @@ namespace edlib_amd {
 
 typedef uint32_t u32;
 
+// ------------------------------------------------- the full-height column (scan_reads_kernel, the seed filter's verification)
+
+// One column of the Myers recurrence over NWD 32-bit words held in VGPRs
+// (reference calculateBlock, edlib.cpp:412-447, with hin fixed by the top
+// boundary: 0 for HW, +1 for SHW/NW -- hin is never negative at row -1, so the
+// "Eq |= hinIsNeg" term vanishes).  Also advances the bottom-row score by the
+// horizontal delta of row m-1 (bit `sh` of the last word).
+template <int NWD, int MODE>
+__device__ __forceinline__ void column_step(const u32 (&Eq)[NWD], u32 (&Pv)[NWD], u32 (&Mv)[NWD],
+                                            int& score, const u32 sh)
+{
+    if constexpr (NWD <= 8) {
+        // one asm statement: VOP3 encodings behind an alignment fence (reads_column_asm.hpp: why)
+        u32 t_, s_, xh_, ph0_, ph1_, mh0_, mh1_, phs_, mhs_, xv_, Pn[NWD], Mn[NWD];
+        int scoreN;
+        unsigned long long cy_;
+        if constexpr (MODE == 2) { RC_COLUMN_DISPATCH(NWD, RC_WORD0_HW) } else { RC_COLUMN_DISPATCH(NWD, RC_WORD0_NW) }
+#pragma unroll
+        for (int i = 0; i < NWD; ++i) { Pv[i] = Pn[i]; Mv[i] = Mn[i]; }
+        score = scoreN;
+        return;
+    }
+    u32 Ph[NWD], Mh[NWD];
+    u32 carry = 0;
+#pragma unroll
+    for (int i = 0; i < NWD; ++i) {
+        const u32 t = Eq[i] & Pv[i];
+        u32 cout;
+        const u32 s = __builtin_addc(t, Pv[i], carry, &cout);     // v_add_co / v_addc_co chain
+        carry = cout;
+        const u32 Xh = (s ^ Pv[i]) | Eq[i];
+        Ph[i] = Mv[i] | ~(Xh | Pv[i]);
+        Mh[i] = Pv[i] & Xh;
+    }
+    score += (int)__builtin_amdgcn_ubfe(Ph[NWD - 1], sh, 1) + __builtin_amdgcn_sbfe(Mh[NWD - 1], sh, 1);
+#pragma unroll
+    for (int i = NWD - 1; i >= 0; --i) {
+        u32 ph, mh;
+        if (i > 0) {
+            ph = __builtin_amdgcn_alignbit(Ph[i], Ph[i - 1], 31);   // (Ph << 1) across words
+            mh = __builtin_amdgcn_alignbit(Mh[i], Mh[i - 1], 31);
+        } else {
+            ph = (Ph[0] << 1) | (MODE == 2 ? 0u : 1u);             // row -1: HW 0, SHW/NW +1 (edlib.cpp:584,779)
+            mh = Mh[0] << 1;
+        }
+        const u32 Xv = Eq[i] | Mv[i];
+        Pv[i] = mh | ~(Xv | ph);
+        Mv[i] = ph & Xv;
+    }
+}
+
 // ------------------------------------------------- the banded HW scan (k-doubling)
 
 // Ukkonen band + k-doubling of the reference (edlib.cpp:197-217, 562, 602-630) re-expressed per WAVE:
