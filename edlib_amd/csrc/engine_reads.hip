@@ -222,6 +222,7 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             }
             for (int q = 0; q < 6; ++q) if ((bestMask >> q) & 1) ladder.push_back(cand[q]);
             if (dbgLadder) {
+                // (tests/test_gpu_seed_filter.py reads this line)
                 fprintf(stderr, "[edlib_amd] ladder nwords=%d kFirst=%d open=%zu/%d levels:", g.nwords, kFirst, open.size(), real);
                 for (int t : ladder) fprintf(stderr, " %d(%.2f)", t, frac_le(t));
                 fprintf(stderr, " full\n");
@@ -327,6 +328,7 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             EDLIB_AMD_HIP(launch_merge_segments(d_sb.p, d_sc.p, d_sp.p, S2, 8, (int)no, d_map.p, 16,
                                                 g.d_best.p, g.d_total.p, g.d_pos.p, g.d_flags.p, stream_));
             EDLIB_AMD_HIP(hipStreamSynchronize(stream_));            // temporaries die here
+            // (tests/test_gpu_seed_filter.py reads this line)
             if (dbgLadder) fprintf(stderr, "[edlib_amd] level kcap=%d: %zu slots rescanned (plain=%d)\n", kcapL, no, (int)plain);
         }
         kDone = kcapL;
@@ -405,6 +407,7 @@ int Batch::runSeedPass(ReadGroup& g, int k)
     EDLIB_AMD_HIP(hipMemcpyAsync(&nb, backCount, sizeof(int), hipMemcpyDeviceToHost, stream_));
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     static const bool dbg = getenv("EDLIB_AMD_DEBUG") != nullptr;
+    // (tests/test_gpu_seed_filter.py reads this line)
     if (dbg) fprintf(stderr, "[edlib_amd] seed pass nwords=%d k=%d: %d of %d slots handed back\n", g.nwords, k, nb, g.nslots);
     if (nb <= 0) return 0;
     int S2, segLen2, warm2;

@@ -7,6 +7,8 @@ path against the textbook DP without a GPU:
   * lookup() finds every exact occurrence of every piece through buckets on its first q symbols (pieces holding a byte the
     target lacks cannot occur and are skipped), giving the diagonals delta = P - o;
   * windows() merges [delta - k, delta + m - 1 + k] (clipped to the target) over the sorted, distinct diagonals;
+  * predict() is what the kernel must DO for a read: whether it hands it back, how many distinct diagonals it finds and how
+    many columns its merged windows hold (the kernel's work counter adds NWD word-steps per such column);
   * seed_filter() scans every window restarted from a fresh column (filter_model.bottom_row over the window) and returns the
     least score with the columns attaining it when that is <= k, None (unresolved) otherwise, or "back" when one of the caps
     of the kernel hands the read back to the banded scan."""
@@ -39,18 +41,24 @@ def pieces(m, k):
 
 def build_index(t, q):
     """bucket of the first q symbols -> target positions"""
-    t = bytes(np.asarray(t, dtype=np.uint8))
+    t = _bytes(t)
     idx = {}
     for P in range(len(t) - q + 1):
         idx.setdefault(t[P:P + q], []).append(P)
     return idx
 
 
-def lookup(qr, t, k, q=Q, index=None, caps=True):
-    """sorted distinct diagonals of the exact piece hits, or "back" """
-    qb = bytes(np.asarray(qr, dtype=np.uint8)); tb = bytes(np.asarray(t, dtype=np.uint8))
-    present = set(tb)
-    index = build_index(t, q) if index is None else index
+def _bytes(x):
+    return x if isinstance(x, bytes) else bytes(np.asarray(x, dtype=np.uint8))
+
+
+def lookup(qr, t, k, q=Q, index=None, caps=True, present=None, info=None):
+    """sorted distinct diagonals of the exact piece hits, or "back".  `t` may be the target's bytes and `present` the set
+    of its byte values (a caller with many reads converts the target once); `info`, a dict, receives the largest bucket
+    that was looked at"""
+    qb = _bytes(qr); tb = _bytes(t)
+    present = set(tb) if present is None else present
+    index = build_index(tb, q) if index is None else index
     diags = set()
     for o, n in pieces(len(qb), k):
         if n < q:
@@ -58,7 +66,9 @@ def lookup(qr, t, k, q=Q, index=None, caps=True):
         piece = qb[o:o + n]
         if any(c not in present for c in piece):        # a byte the target lacks: the piece cannot occur
             continue
-        bucket = index.get(piece[:q], [])
+        bucket = index.get(piece[:q], ())
+        if info is not None:
+            info["bucket"] = max(info.get("bucket", 0), len(bucket))
         if caps and len(bucket) > BUCKET_CAP:
             return "back"
         for P in bucket:
@@ -79,6 +89,32 @@ def windows(diags, m, k, T):
         else:
             out.append([a, b])
     return [tuple(w) for w in out]
+
+
+def predict(read, target, k, index, present=None, q=Q):
+    """what the kernel does with one read at threshold k, caps on: {"back": handed back, "diagonals": distinct diagonals,
+    "columns": sum of the merged window lengths, "bucket": the largest bucket looked at, "window": the longest merged
+    window}; a handed-back read verifies no column.  `target` as bytes, `index` = build_index(target, q) and `present` =
+    set(target) make a batch of thousands of reads cost seconds."""
+    tb = _bytes(target)
+    info = {}
+    diags = lookup(read, tb, k, q, index, True, present, info)
+    out = {"back": True, "diagonals": 0, "columns": 0, "bucket": info.get("bucket", 0), "window": 0}
+    if diags == "back":
+        return out
+    ws = windows(diags, len(read), k, len(tb))
+    out["window"] = max([b - a + 1 for a, b in ws], default=0)
+    if out["window"] > MAX_WINDOW:
+        return out
+    out.update(back=False, diagonals=len(diags), columns=sum(b - a + 1 for a, b in ws))
+    return out
+
+
+def predict_batch(reads, target, k, q=Q):
+    """predict() for every read against one target (converted and indexed once)"""
+    tb = _bytes(target)
+    index, present = build_index(tb, q), set(tb)
+    return [predict(r, tb, k, index, present, q) for r in reads]
 
 
 def seed_filter(qr, t, k, q=Q, index=None, caps=True):

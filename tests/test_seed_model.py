@@ -169,3 +169,125 @@ def test_caps_only_hand_back():
         else:
             assert got != "back" and got[0] == 0 and len(got[1]) == copies
             assert got == SM.reference(block, t, 9)
+
+
+# ------------------------------------------------------------------------------ the planted inputs of tests/seed_cases.py
+# (shared with tests/test_gpu_seed_filter.py): on a target of a few thousand columns, with q = 12 as in the kernel, every
+# generator does what it claims -- predict() gives the claimed diagonals / columns / bucket / window / hand-back -- and every
+# read that is not handed back gets the textbook DP's answer from the filter with the caps on.
+
+import seed_cases as SC
+
+# (word count, k): k_f of the GPU batches at T = 256,000, k = 0 (one piece = the whole read), and the pairs that give piece
+# lengths 12 / 13 (1, 1), 27 .. 29 (1, 0: lengths 12 .. 32) and 43 / 44 (3, 1)
+_PLANTED = [(1, 1), (2, 3), (3, 5), (4, 7), (5, 8), (6, 11), (7, 13), (8, 16), (1, 0), (4, 0), (8, 0), (4, 1), (8, 1), (4, 6),
+            (8, 15), (3, 1)]
+
+
+def test_seed_thresholds_of_the_gpu_batches():
+    assert [SM.seed_threshold(SC.M_MIN[w], 256_000) for w in range(1, 9)] == [1, 3, 5, 7, 8, 11, 13, 16]
+    for w in range(1, 9):                                     # the same at T mod 16 = 1 and 15
+        assert SM.seed_threshold(SC.M_MIN[w], 256_001) == SM.seed_threshold(SC.M_MIN[w], 255_999) == SM.seed_threshold(SC.M_MIN[w], 256_000)
+    assert SM.seed_threshold(108, 200_000) == 8 and SM.seed_threshold(108, 256_000) == 7
+    assert SM.seed_threshold(97, 256_000) == 7 and SM.seed_threshold(12, 256_000) == 0
+
+
+def test_piece_lengths_reach_every_compare_tail():
+    """len - 12 in {0, 1, 15, 16, 17, 31, 32} over the (word count, k) pairs of the GPU tests"""
+    seen = set()
+    for nwd, k in _PLANTED:
+        mlo = max(32 * (nwd - 1) + 1, 12 * (k + 1)) if (nwd, k) not in ((1, 1), (2, 3), (3, 5), (4, 7)) else SC.M_MIN[nwd]
+        for m in range(mlo, 32 * nwd + 1):
+            seen |= {n - 12 for _, n in SM.pieces(m, k)}
+    assert {0, 1, 15, 16, 17, 31, 32} <= seen
+
+
+@pytest.mark.parametrize("gen", SC.GENERATORS)
+@pytest.mark.parametrize("nwd,k", _PLANTED)
+def test_planted_generator_does_what_it_claims(nwd, k, gen):
+    span = 32 * nwd + 2 * k + 2
+    T = 2 * SC.RESERVE + (48 * span if gen.startswith("diag") else 100 * span if gen == "compare_tails" else max(2_000, 14 * span))
+    T = T // 16 * 16 + (0, 1, 15)[(nwd + k) % 3]
+    P = SC.Planter(nwd, T, k, 500 + 17 * nwd + k)
+    getattr(P, gen)()
+    assert len(P.reads) >= (0 if (nwd, k, gen) == (1, 0, "window_1025") else 1) and len(P.target) == T and set(P.target.tolist()) <= set(b"ACGT")
+    tb = P.target.tobytes()
+    index, present = SM.build_index(tb, SM.Q), set(tb)
+    pred = [SM.predict(r, tb, k, index, present) for r in P.reads]
+    assert SC.claims_hold(P.claims, pred) == []
+    for r, c, p in zip(P.reads, P.claims, pred):
+        want = SM.reference(r, P.target, k)
+        if "found" in c:
+            assert (want is not None) == c["found"], (c, want)
+        if "dist" in c:
+            assert want[0] == c["dist"], (c, want)
+        got = SM.seed_filter(r, P.target, k, index=index, caps=True)
+        assert (got == "back") == p["back"]
+        if not p["back"]:
+            assert got == want, (c, got, want)
+
+
+def test_caps_sit_on_both_sides():
+    """32 / 33 diagonals, buckets of 64 / 65, windows of 1024 / 1025 columns: exactly, for a short and a long word count"""
+    for nwd, k in ((2, 3), (8, 16)):
+        P = SC.Planter(nwd, 2 * SC.RESERVE + 200 * (32 * nwd + 2 * k + 2), k, 600 + nwd)
+        for gen in ("diag_32", "diag_33", "bucket_64", "bucket_65", "window_1024", "window_1025"):
+            getattr(P, gen)()
+        pred = SM.predict_batch(P.reads, P.target, k)
+        assert [p["back"] for p in pred] == [False, True, False, True, False, True]
+        assert pred[0]["diagonals"] == 32 and pred[2]["bucket"] == 64 and pred[3]["bucket"] == 65
+        assert pred[4]["window"] == 1024 and pred[4]["diagonals"] >= 4 and pred[5]["window"] == 1025
+
+
+def test_predict_is_lookup_and_windows():
+    rng = np.random.default_rng(700)
+    t = _ACGT[rng.integers(0, 4, 3000)]
+    r = t[100:160].copy()
+    p = SM.predict(r, t, 3, SM.build_index(t, SM.Q))
+    assert p == {"back": False, "diagonals": 1, "columns": 66, "bucket": 1, "window": 66}
+    assert SM.predict(r[:40], t, 3, SM.build_index(t, SM.Q))["back"]          # pieces of 10 symbols
+
+
+@pytest.mark.parametrize("nwd", [1, 5, 8])
+def test_gpu_batches_keep_their_claims_at_full_size(nwd):
+    """the batches of the GPU tests (256,000 columns, no DP here): the model hands back nothing in the work-accounting batch
+    and exactly the three over-the-cap reads in the caps batch; the planted claims hold there too"""
+    k = SM.seed_threshold(SC.M_MIN[nwd], 256_000)
+    b = SC.single_group(nwd, k, mlo=SC.M_MIN[nwd])
+    pred = SM.predict_batch(b["reads"], b["target"], k)
+    assert sum(p["back"] for p in pred) == 0
+    b = SC.batch("caps:%d" % nwd)
+    pred = SM.predict_batch(b["reads"], b["target"], k)
+    assert SC.claims_hold(b["claims"], pred, keys=("back",)) == []        # (a random extra hit may add a diagonal here)
+    caps = [(c, p) for c, p in zip(b["claims"], pred) if c and (c.get("bucket", 0) >= 64 or c.get("window") or c.get("diagonals", 0) >= 32 or c["back"])]
+    assert len(caps) == 6 and SC.claims_hold([c for c, _ in caps], [p for _, p in caps]) == []
+    assert sum(p["back"] for p in pred) == sum(1 for c in b["claims"] if c and c["back"]) == 3
+
+
+@pytest.mark.parametrize("name", ["three_symbols", "two_symbols", "low_complexity"])
+def test_small_alphabet_batches_on_a_small_target(name):
+    """the same generators at 6,000 columns: the alphabet is what the name says, and every read the model does not hand back
+    gets the textbook DP's answer (a read holding a base the target lacks included)"""
+    b = getattr(SC, name)(nwd=2, k=3, T=6_000, n=48, seed=800)
+    t = b["target"]
+    assert len(set(t.tolist())) == {"three_symbols": 3, "two_symbols": 2, "low_complexity": 4}[name]
+    if name == "three_symbols":
+        assert sum(1 for r in b["reads"] if ord("T") in r.tolist()) >= 16
+    index = SM.build_index(t, SM.Q)
+    back = 0
+    for r in b["reads"]:
+        got = SM.seed_filter(r, t, 3, index=index, caps=True)
+        assert (got == "back") == SM.predict(r, t, 3, index)["back"]
+        back += got == "back"
+        if got != "back":
+            assert got == SM.reference(r, t, 3)
+    if name == "low_complexity":
+        assert 0 < back < len(b["reads"])                     # (the run and the repeat overflow a bucket, the rest does not)
+
+
+def test_two_symbol_buckets_straddle_the_cap_at_full_size():
+    """256,000 columns of two symbols: 4096 keys occur, about 62.5 positions each -- both sides of the cap of 64"""
+    b = SC.two_symbols()
+    sizes = np.array([len(v) for v in SM.build_index(b["target"], SM.Q).values()])
+    assert len(sizes) == 4096 and 55 < sizes.mean() < 70
+    assert (sizes > SM.BUCKET_CAP).sum() > 400 and (sizes <= SM.BUCKET_CAP).sum() > 400

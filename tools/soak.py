@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Differential soak of the batch entry points against the oracle (test infrastructure) for a time budget: random
 shared-target batches over every read-length group of the lane-per-read kernels and the piece filter / chained strips
-above them (1 .. 6000 bases), random pair batches over the ring sizes and the flat pair path, single edlibAlign() calls
+above them (1 .. 6000 bases), batches of the shape the exact k-mer seed filter takes, random pair batches over the ring sizes and the flat pair path, single edlibAlign() calls
 (fused one-pair kernel); every field of every unit is compared.  usage: soak.py [seconds] [seed] [max cases]"""
 import sys, os, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
@@ -92,6 +92,28 @@ def shared_case():
     qoff = np.zeros(len(reads) + 1, dtype=np.int64); qoff[1:] = np.cumsum([len(r) for r in reads])
     ref = O.pool_align(np.concatenate(reads), qoff, target, np.array([0, len(target)], dtype=np.int64), True, mode, task, k)
     return len(reads), compare(got, ref, task, "shared mode=%s task=%s k=%d tn=%d nq=%d lens=%s" % (mode, task, k, len(target), len(lens), sorted(set(lens))[:8]))
+
+
+def seed_case():
+    """a shape whose first pass is the exact k-mer seed filter: 8,192 or more reads of one word count against
+    131,072 or more columns of ACGT, a fixed k within k_f, or -1 where k_f >= 8 (five words and more)"""
+    tn = int(rng.choice([131072, 200000, 256001])); nwd = int(rng.integers(1, 9)); mlo = max(32 * (nwd - 1) + 1, 24)
+    target = synth.random_dna(int(rng.integers(1 << 30)), tn)
+    reads = []
+    for _ in range(int(rng.choice([8192, 8200, 9000]))):
+        m = int(rng.integers(mlo, 32 * nwd + 1)); s = int(rng.integers(0, tn - m - 70))
+        reads.append(mutate(target[s:s + m + 64].copy(), m, float(rng.choice([0.0, 0.01, 0.04, 0.1]))) if rng.random() < 0.95 else ACGT[rng.integers(0, 4, m)])
+    k = int(rng.choice([-1, 0, 1, 3, 8] if nwd >= 5 else [0, 1]))
+    what = "seed k=%d tn=%d nq=%d nwd=%d" % (k, tn, len(reads), nwd)
+    trace(what)
+    b = edlib_amd.SharedBatch(reads, target, mode="HW", task="distance", k=k)
+    try:
+        b.run(); got = b.results_flat()
+    finally:
+        b.close()
+    qoff = np.zeros(len(reads) + 1, dtype=np.int64); qoff[1:] = np.cumsum([len(r) for r in reads])
+    ref = O.pool_align(np.concatenate(reads), qoff, target, np.array([0, tn], dtype=np.int64), True, "HW", "distance", k)
+    return len(reads), compare(got, ref, "distance", what)
 
 
 def pair_case():
@@ -220,7 +242,8 @@ while time.time() - t0 < budget and cases < max_cases:
     if os.environ.get("SOAK_ONLY") == "lane" or x > 0.97:
         n, err = lane_case()
     else:
-        n, err = shared_case() if x < 0.5 else (pair_case() if x < 0.8 else (long_pair_case() if x < 0.9 else single_case()))
+        n, err = shared_case() if x < 0.5 else (pair_case() if x < 0.8 else (long_pair_case() if x < 0.9 else
+                                                                              (single_case() if x < 0.95 else seed_case())))
     cases += 1; units += n
     if err:
         failures.append(err); print("MISMATCH", err, file=sys.stderr)
