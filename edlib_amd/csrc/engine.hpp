@@ -166,7 +166,15 @@ private:
         bool zeroCopy = false; PinBuf hostOut;   // small groups: d_best / d_total / d_alphaExtra / d_flags / d_pos are views into pinned host memory
         // exact second pass of the last run: overflowing slots, their offsets into d_ovfPool
         std::vector<int> ovfSlots; std::vector<long long> ovfOff; DevBuf<int> d_ovfPool;
+        // segment records of the k-doubling levels (engine_reads.hip), kept from run to run; after a run whose last level
+        // ran (lvValid) they hold that level: lvMap = its lanes' slots (ascending), lvS segments, lvCap positions per segment
+        DevBuf<int> d_lvMap, d_lvBest, d_lvCnt, d_lvPos; std::vector<int> lvMap; int lvS = 0, lvCap = 0; bool lvValid = false;
+        DevBuf<int> d_list;                    // [nslots + 1] a slot list compacted on the device, then its length
+        int nreal = -1;                        // slots that hold a unit (counted when first needed)
     };
+    static constexpr int kLastLevelCap = 16;   // positions per (lane, segment) of the last level = the slot's own 16
+    int listOpenSlots(ReadGroup& g, int kDone, std::vector<int>& out);
+    DevBuf<uint8_t> d_selTmp_;                 // rocPRIM select scratch
     std::vector<std::unique_ptr<ReadGroup>> groups_;
     DevBuf<uint32_t> d_tpk_, d_trows_;
     DevBuf<unsigned long long> d_wordSteps_;

@@ -14,14 +14,6 @@
 
 namespace edlib_amd {
 
-// overflow census of the reads path: how many slots need the exact second pass
-__global__ void __launch_bounds__(256)
-count_flags_kernel(const int* __restrict__ flags, int n, int* __restrict__ counter)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && flags[i]) atomicAdd(counter, 1);
-}
-
 // full-height pass of the reads path: a lane's threshold drops to what a scan of the target's first columns found
 __global__ void __launch_bounds__(256)
 seed_thresholds_kernel(int* __restrict__ kinit, const int* __restrict__ best, const int* __restrict__ cnt, int n)
@@ -135,7 +127,72 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
     int kFirst = (kSeed >= 0 && cfg_.k >= 0) ? std::min(kSeed, cfg_.k) : kFirstMax;
     bool twoPass = !fullOnly && banded && (cfg_.k < 0 || cfg_.k > kFirst) && 32 * g.nwords > kFirst;
     std::vector<int> ladder;                    // thresholds of the banded passes between the first and the full one
-    if (twoPass && g.nslots >= 16384) {
+    g.lvValid = false;
+    // best score of the slots in `map` with thresholds capped at kc (-1: nothing <= kc)
+    auto probe_scan = [&](const std::vector<int>& map, int kc, std::vector<int>& bestOut) -> int {
+        const int nm = (int)map.size();
+        int S2, segLen2, warm2;
+        plan_segments(nm, T, mode, g.warm, 16384, S2, segLen2, warm2);
+        const size_t items = (size_t)nm * S2;
+        DevBuf<int> d_map, d_sb, d_sc;
+        EDLIB_AMD_HIP(d_map.alloc(nm)); EDLIB_AMD_HIP(d_sb.alloc(items)); EDLIB_AMD_HIP(d_sc.alloc(items));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_map.p, map.data(), nm * sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (scanGroup(g, mode, d_map.p, nm, kc, g.d_kinit.p, S2, segLen2, warm2,
+                      d_sb.p, d_sc.p, d_sb.p /*unused*/, 0, nullptr, nullptr)) return 1;
+        std::vector<int> cnts(items), bests(items);
+        EDLIB_AMD_HIP(hipMemcpyAsync(cnts.data(), d_sc.p, items * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(bests.data(), d_sb.p, items * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        bestOut.assign(nm, -1);
+        for (int i = 0; i < nm; ++i) {
+            int b = 0x7fffffff;
+            for (int sg = 0; sg < S2; ++sg)
+                if (cnts[(size_t)i * S2 + sg] > 0) b = std::min(b, bests[(size_t)i * S2 + sg]);
+            if (b <= kc) bestOut[i] = b;
+        }
+        return 0;
+    };
+    // ---- the levels between the first and the full threshold (the reference doubles k: edlib.cpp:197-217).  When
+    // more than a tenth of the reads is still open after the first threshold, a sample of the open reads is scanned once
+    // more with thresholds capped at 64: their distances say which intermediate thresholds pay.  A level at threshold t
+    // costs every read that reaches it a band of about 1 + (t - 6) / 8 words per column; it pays when what it resolves
+    // would otherwise meet a taller band.  All subsets of {12, 16, 24, 32, 48, 64} are priced; reads at
+    // Illumina-like error rates (leftovers = unrelated sequence) keep the two levels they always had.
+    // (sample: open slots to scan; nOpen of nReal: what the debug line reports)
+    auto price_ladder = [&](const std::vector<int>& sample, size_t nOpen, int nReal) -> int {
+        const int kTop = std::min(64, 32 * g.nwords - 1);
+        std::vector<int> obest;
+        if (probe_scan(sample, kTop, obest)) return 1;
+        static const int cand[6] = {12, 16, 24, 32, 48, 64};
+        auto words = [&](int t) { return std::min<double>(g.nwords, 1.0 + std::max(0, t - 6) / 8.0); };
+        auto frac_le = [&](int t) {                           // share of the open reads with distance <= t
+            size_t c = 0;
+            for (int b : obest) if (b >= 0 && b <= t) ++c;
+            return (double)c / (double)obest.size();
+        };
+        double bestCost = 1e30; int bestMask = 0;
+        for (int mask = 0; mask < 64; ++mask) {
+            double cost = 0.0, reach = 1.0; bool ok = true;
+            for (int q = 0; q < 6; ++q) {
+                if (!((mask >> q) & 1)) continue;
+                if (cand[q] <= kFirst || cand[q] > kTop) { ok = false; break; }
+                cost += reach * words(cand[q]);
+                reach = 1.0 - frac_le(cand[q]);
+            }
+            if (!ok) continue;
+            cost += reach * g.nwords;                         // what is left takes the full threshold
+            if (cost < bestCost - 1e-9) { bestCost = cost; bestMask = mask; }
+        }
+        for (int q = 0; q < 6; ++q) if ((bestMask >> q) & 1) ladder.push_back(cand[q]);
+        if (dbgLadder) {
+            // (tests/test_gpu_seed_filter.py reads this line)
+            fprintf(stderr, "[edlib_amd] ladder nwords=%d kFirst=%d open=%zu/%d levels:", g.nwords, kFirst, nOpen, nReal);
+            for (int t : ladder) fprintf(stderr, " %d(%.2f)", t, frac_le(t));
+            fprintf(stderr, " full\n");
+        }
+        return 0;
+    };
+    if (twoPass && g.nslots >= 16384 && kSeed < 0) {
         // k-doubling only pays when most units resolve at the small threshold (pass 1 costs ~2/NWD of a
         // full scan, unresolved units then pay the full scan on top).  Probe 2048 evenly strided slots
         // first (0.2 % of the work at 1M reads) and fall back to one full-threshold pass if fewer than
@@ -145,30 +202,6 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
         const int np = std::max(512, std::min(2048, g.nslots / 32));
         std::vector<int> probe(np);
         for (int i = 0; i < np; ++i) probe[i] = (int)((long long)i * g.nslots / np);
-        // best score of the probe slots in `map` with thresholds capped at kc (-1: nothing <= kc)
-        auto probe_scan = [&](const std::vector<int>& map, int kc, std::vector<int>& bestOut) -> int {
-            const int nm = (int)map.size();
-            int S2, segLen2, warm2;
-            plan_segments(nm, T, mode, g.warm, 16384, S2, segLen2, warm2);
-            const size_t items = (size_t)nm * S2;
-            DevBuf<int> d_map, d_sb, d_sc;
-            EDLIB_AMD_HIP(d_map.alloc(nm)); EDLIB_AMD_HIP(d_sb.alloc(items)); EDLIB_AMD_HIP(d_sc.alloc(items));
-            EDLIB_AMD_HIP(hipMemcpyAsync(d_map.p, map.data(), nm * sizeof(int), hipMemcpyHostToDevice, stream_));
-            if (scanGroup(g, mode, d_map.p, nm, kc, g.d_kinit.p, S2, segLen2, warm2,
-                          d_sb.p, d_sc.p, d_sb.p /*unused*/, 0, nullptr, nullptr)) return 1;
-            std::vector<int> cnts(items), bests(items);
-            EDLIB_AMD_HIP(hipMemcpyAsync(cnts.data(), d_sc.p, items * sizeof(int), hipMemcpyDeviceToHost, stream_));
-            EDLIB_AMD_HIP(hipMemcpyAsync(bests.data(), d_sb.p, items * sizeof(int), hipMemcpyDeviceToHost, stream_));
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-            bestOut.assign(nm, -1);
-            for (int i = 0; i < nm; ++i) {
-                int b = 0x7fffffff;
-                for (int sg = 0; sg < S2; ++sg)
-                    if (cnts[(size_t)i * S2 + sg] > 0) b = std::min(b, bests[(size_t)i * S2 + sg]);
-                if (b <= kc) bestOut[i] = b;
-            }
-            return 0;
-        };
         std::vector<int> pbest;
         if (probe_scan(probe, kFirst, pbest)) return 1;
         int resolved = 0, real = 0;
@@ -184,59 +217,38 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
         // unrelated sequence that score hovers around 13, so every unit of k below 8 keeps the second
         // word out more often.  Take the smallest threshold (>= 4) that still resolves 99.5 % of what 8
         // resolves: the few reads above it just join pass 2.
-        if (resolved > 0 && kSeed < 0) {
+        if (resolved > 0) {
             int acc = 0, kq = kFirstMax;
             for (int d = 0; d <= kFirstMax; ++d) { acc += hist[d]; if (acc * 1000LL >= resolved * 995LL) { kq = d; break; } }
             kFirst = std::max(4, std::min(kFirstMax, kq));
         }
-        if (kSeed < 0 && real > 0 && resolved * 10 < real * 3) twoPass = false;   // (the seed pass costs little whatever resolves)
-        // ---- the levels between the first and the full threshold (the reference doubles k: edlib.cpp:197-217).  When
-        // more than a tenth of the probe is still open, the open probe reads are scanned once more with thresholds
-        // capped at 64: their distances say which intermediate thresholds pay.  A level at threshold t costs every
-        // read that reaches it a band of about 1 + (t - 6) / 8 words per column; it pays when what it resolves
-        // would otherwise meet a taller band.  All subsets of {12, 16, 24, 32, 48, 64} are priced; reads at
-        // Illumina-like error rates (leftovers = unrelated sequence) keep the two levels they always had.
-        if (twoPass && (int)open.size() * 10 > real && open.size() >= 32) {
-            const int kTop = std::min(64, 32 * g.nwords - 1);
-            std::vector<int> obest;
-            if (probe_scan(open, kTop, obest)) return 1;
-            static const int cand[6] = {12, 16, 24, 32, 48, 64};
-            auto words = [&](int t) { return std::min<double>(g.nwords, 1.0 + std::max(0, t - 6) / 8.0); };
-            auto frac_le = [&](int t) {                           // share of the open reads with distance <= t
-                size_t c = 0;
-                for (int b : obest) if (b >= 0 && b <= t) ++c;
-                return (double)c / (double)obest.size();
-            };
-            double bestCost = 1e30; int bestMask = 0;
-            for (int mask = 0; mask < 64; ++mask) {
-                double cost = 0.0, reach = 1.0; bool ok = true;
-                for (int q = 0; q < 6; ++q) {
-                    if (!((mask >> q) & 1)) continue;
-                    if (cand[q] <= kFirst || cand[q] > kTop) { ok = false; break; }
-                    cost += reach * words(cand[q]);
-                    reach = 1.0 - frac_le(cand[q]);
-                }
-                if (!ok) continue;
-                cost += reach * g.nwords;                         // what is left takes the full threshold
-                if (cost < bestCost - 1e-9) { bestCost = cost; bestMask = mask; }
-            }
-            for (int q = 0; q < 6; ++q) if ((bestMask >> q) & 1) ladder.push_back(cand[q]);
-            if (dbgLadder) {
-                // (tests/test_gpu_seed_filter.py reads this line)
-                fprintf(stderr, "[edlib_amd] ladder nwords=%d kFirst=%d open=%zu/%d levels:", g.nwords, kFirst, open.size(), real);
-                for (int t : ladder) fprintf(stderr, " %d(%.2f)", t, frac_le(t));
-                fprintf(stderr, " full\n");
+        if (real > 0 && resolved * 10 < real * 3) twoPass = false;
+        if (twoPass && (int)open.size() * 10 > real && open.size() >= 32 && price_ladder(open, open.size(), real)) return 1;
+    }
+    std::vector<int> todo;                      // the slots of the next level, ascending
+    bool haveTodo = false;
+    if (kSeed >= 0) {
+        // The seed pass costs little whatever resolves, and it is exact at its threshold over ALL slots: what it leaves open
+        // is the probe's answer for the whole group, and the first level's slot list.
+        if (runSeedPass(g, kFirst)) return 1;
+        if (twoPass) {
+            if (listOpenSlots(g, kFirst, todo)) return 1;
+            haveTodo = true;
+            if (g.nreal < 0) { g.nreal = 0; for (int u : g.perm) g.nreal += u >= 0; }
+            if (g.nslots >= 16384 && todo.size() * 10 > (size_t)g.nreal && todo.size() >= 32) {
+                const size_t nsm = std::min<size_t>(2048, todo.size());
+                std::vector<int> sample(nsm);
+                for (size_t i = 0; i < nsm; ++i) sample[i] = todo[i * todo.size() / nsm];
+                if (price_ladder(sample, todo.size(), g.nreal)) return 1;
             }
         }
-    }
-    if (kSeed >= 0) {
-        if (runSeedPass(g, kFirst)) return 1;
     } else {
         if (scanGroup(g, mode, nullptr, g.nslots, twoPass ? kFirst : kNoCap, g.d_kinit.p, g.numSegments, g.segLen,
                       g.warm, g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, 8, nullptr, nullptr, /*unbanded=*/fullOnly)) return 1;
+        const bool chained = chain_.in != nullptr || chain_.out != nullptr;
         EDLIB_AMD_HIP(launch_merge_segments(g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, g.numSegments, 8,
                                             g.nslots, nullptr, 16, g.d_best.p, g.d_total.p, g.d_pos.p,
-                                            g.d_flags.p, stream_));
+                                            g.d_flags.p, stream_, chained ? kOvfRescan : kOvfGatherGroup));
     }
     // ---- the next levels (k-doubling): slots with nothing <= the last threshold are rescanned with the next one,
     // the last time with their full threshold
@@ -245,37 +257,32 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
     for (size_t lv = 0; twoPass && lv < ladder.size(); ++lv) {
         const int kcapL = ladder[lv];
         const bool last = kcapL == kNoCap;
-        PinBuf totalPin;                               // pinned: the copy runs at link rate
-        const int* total = g.d_total.p;
-        if (!g.zeroCopy) {
-            EDLIB_AMD_HIP(totalPin.alloc((size_t)g.nslots * sizeof(int)));
-            EDLIB_AMD_HIP(hipMemcpyAsync(totalPin.p, g.d_total.p, (size_t)g.nslots * sizeof(int), hipMemcpyDeviceToHost, stream_));
-            total = reinterpret_cast<const int*>(totalPin.p);
-        }
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        std::vector<int> todo;
-        for (int s = 0; s < g.nslots; ++s) {
-            const int u = g.perm[s];
-            if (u < 0 || total[s] > 0) continue;
-            if (std::min(qlen(u), cfg_.k < 0 ? 0x3fffffff : cfg_.k) > kDone) todo.push_back(s);   // its threshold min(k, m) is above what was tried
-        }
+        // the slots whose threshold min(k, m) is above what was tried: compacted on the device, only the list comes down
+        if (!haveTodo && listOpenSlots(g, kDone, todo)) return 1;
+        haveTodo = false;
         if (todo.empty()) break;
         {
             const size_t no = todo.size();
             int S2, segLen2, warm2;
             plan_segments((int)no, T, mode, g.warm, 65536, S2, segLen2, warm2);
             const size_t items = no * (size_t)S2;
-            DevBuf<int> d_map, d_sb, d_sc, d_sp;
-            EDLIB_AMD_HIP(d_map.alloc(no)); EDLIB_AMD_HIP(d_sb.alloc(items)); EDLIB_AMD_HIP(d_sc.alloc(items));
-            EDLIB_AMD_HIP(d_sp.alloc(items * 8));
-            EDLIB_AMD_HIP(hipMemcpyAsync(d_map.p, todo.data(), no * sizeof(int), hipMemcpyHostToDevice, stream_));
+            // The segment records of a level are the group's: they are reused from run to run (at 1M reads the positions
+            // are a block the allocator's pool does not keep), and those of the last level outlive the loop -- the exact
+            // pass gathers from them the lists that only overflowed the 16 positions of a slot.  The last level keeps 16
+            // positions per segment instead of 8, so that a segment alone rarely overflows.
+            const int capL = last ? kLastLevelCap : 8;
+            EDLIB_AMD_HIP(g.d_lvMap.ensure(no)); EDLIB_AMD_HIP(g.d_lvBest.ensure(items)); EDLIB_AMD_HIP(g.d_lvCnt.ensure(items));
+            EDLIB_AMD_HIP(g.d_lvPos.ensure(items * capL));
+            int *d_map = g.d_lvMap.p, *d_sb = g.d_lvBest.p, *d_sc = g.d_lvCnt.p, *d_sp = g.d_lvPos.p;
+            EDLIB_AMD_HIP(hipMemcpyAsync(d_map, todo.data(), no * sizeof(int), hipMemcpyHostToDevice, stream_));
             // What the last level leaves over is usually unrelated sequence whose band is the whole query; there the
             // plain full-height kernel (register-resident Peq rows, no band bookkeeping) is ~12 % faster per
-            // column than the banded one.  256 strided leftovers tell: the banded kernel reports its band
+            // column than the banded one.  64 strided leftovers tell (one wave per segment: a quarter of the work of
+            // the 256 this took before): the banded kernel reports its band
             // height (word-steps), and a band above 85 % of the words sends the pass to the plain kernel.
             bool plain = false;
             if (last && no >= 4096) {
-                const int np2 = 256;
+                const int np2 = 64;
                 std::vector<int> sub(np2);
                 for (int i = 0; i < np2; ++i) sub[i] = todo[(size_t)((long long)i * no / np2)];
                 int S3, segLen3, warm3;
@@ -324,21 +331,37 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
                 EDLIB_AMD_HIP(hipGetLastError());
             }
             if (scanGroup(g, mode, nullptr, (int)no, kcapL, d_kinit2.p, S2, segLen2, warm2,
-                          d_sb.p, d_sc.p, d_sp.p, 8, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p)) return 1;
-            EDLIB_AMD_HIP(launch_merge_segments(d_sb.p, d_sc.p, d_sp.p, S2, 8, (int)no, d_map.p, 16,
-                                                g.d_best.p, g.d_total.p, g.d_pos.p, g.d_flags.p, stream_));
+                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p)) return 1;
+            EDLIB_AMD_HIP(launch_merge_segments(d_sb, d_sc, d_sp, S2, capL, (int)no, d_map, 16,
+                                                g.d_best.p, g.d_total.p, g.d_pos.p, g.d_flags.p, stream_,
+                                                last ? kOvfGatherLevel : kOvfRescan));
             EDLIB_AMD_HIP(hipStreamSynchronize(stream_));            // temporaries die here
+            if (last) { g.lvValid = true; g.lvS = S2; g.lvCap = capL; g.lvMap.swap(todo); }
             // (tests/test_gpu_seed_filter.py reads this line)
             if (dbgLadder) fprintf(stderr, "[edlib_amd] level kcap=%d: %zu slots rescanned (plain=%d)\n", kcapL, no, (int)plain);
         }
         kDone = kcapL;
     }
-    // census of slots whose end-location list did not fit (small groups: counted on the host from the pinned flags)
-    if (!g.zeroCopy) {
-        int* counter = g.d_flags.p + g.nslots;
-        EDLIB_AMD_HIP(hipMemsetAsync(counter, 0, sizeof(int), stream_));
-        hipLaunchKernelGGL(count_flags_kernel, dim3((g.nslots + 255) / 256), dim3(256), 0, stream_,
-                           g.d_flags.p, g.nslots, counter);
+    return 0;
+}
+
+// The group's slots that are still open above kDone (launch_select_open_slots), ascending, on the host
+int Batch::listOpenSlots(ReadGroup& g, int kDone, std::vector<int>& out)
+{
+    size_t tmp = 0;
+    EDLIB_AMD_HIP(select_slots_scratch_bytes(g.nslots, &tmp));
+    EDLIB_AMD_HIP(d_selTmp_.ensure(tmp));
+    EDLIB_AMD_HIP(g.d_list.ensure((size_t)g.nslots + 1));
+    int* count = g.d_list.p + g.nslots;
+    EDLIB_AMD_HIP(launch_select_open_slots(g.d_perm.p, g.d_total.p, g.d_qlen.p, cfg_.k, kDone, g.nslots, g.d_list.p, count,
+                                           d_selTmp_.p, d_selTmp_.bytes(), stream_));
+    int n = 0;
+    EDLIB_AMD_HIP(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    out.resize((size_t)n);
+    if (n > 0) {
+        EDLIB_AMD_HIP(hipMemcpyAsync(out.data(), g.d_list.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     }
     return 0;
 }
@@ -423,9 +446,10 @@ int Batch::runSeedPass(ReadGroup& g, int k)
     return 0;
 }
 
-// exact second pass for the (rare) slots with more end locations than the first pass keeps.
-// Their best score b is already exact, so "score <= b" selects exactly the end locations:
-// (a) a counting scan over fine segments gives the number of hits of every (slot, segment),
+// Exact second pass for the (rare) slots with more end locations than the first pass keeps.  Their best score b is already
+// exact.  Where every segment that holds b kept all of its hits (the merge's flag says so), the complete list is in the
+// segment records and a gather copies it out.  The others are scanned again, "score <= b" selecting exactly the end
+// locations: (a) a counting scan over fine segments gives the number of hits of every (slot, segment),
 // (b) after a prefix sum the same scan writes them to their final place.  Fine segments keep
 // the pass parallel (a handful of slots still fills the chip).
 int Batch::runGroupExact(ReadGroup& g)
@@ -435,54 +459,109 @@ int Batch::runGroupExact(ReadGroup& g)
     const int kNoCap = 0x3fffffff;
     const size_t ns = (size_t)g.nslots;
     g.ovfSlots.clear(); g.ovfOff.assign(1, 0);
-    int novf = 0;
+    if (mode == EDLIB_MODE_NW) return 0;
+    // the flagged slots, ascending, with their flag and their number of end locations
+    std::vector<int> recs;                                    // {slot, flag, total} each
     if (g.zeroCopy) {
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        for (size_t s = 0; s < ns; ++s) novf += g.d_flags.p[s] != 0;
-    }
-    else {
-        EDLIB_AMD_HIP(hipMemcpyAsync(&novf, g.d_flags.p + g.nslots, sizeof(int), hipMemcpyDeviceToHost, stream_));
+        for (size_t s = 0; s < ns; ++s)
+            if (g.d_flags.p[s] && g.perm[s] >= 0) { recs.push_back((int)s); recs.push_back(g.d_flags.p[s]); recs.push_back(g.d_total.p[s]); }
+    } else {
+        size_t tmp = 0;
+        EDLIB_AMD_HIP(select_slots_scratch_bytes(g.nslots, &tmp));
+        EDLIB_AMD_HIP(d_selTmp_.ensure(tmp));
+        EDLIB_AMD_HIP(g.d_list.ensure(ns + 1));
+        int* count = g.d_list.p + ns;
+        EDLIB_AMD_HIP(launch_select_flagged_slots(g.d_perm.p, g.d_flags.p, g.nslots, g.d_list.p, count,
+                                                  d_selTmp_.p, d_selTmp_.bytes(), stream_));
+        int novf = 0;
+        EDLIB_AMD_HIP(hipMemcpyAsync(&novf, count, sizeof(int), hipMemcpyDeviceToHost, stream_));
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        if (novf > 0) {
+            DevBuf<int> d_recs;
+            EDLIB_AMD_HIP(d_recs.alloc((size_t)novf * 3));
+            EDLIB_AMD_HIP(launch_pick_slot_records(g.d_list.p, novf, g.d_flags.p, g.d_total.p, d_recs.p, stream_));
+            recs.resize((size_t)novf * 3);
+            EDLIB_AMD_HIP(hipMemcpyAsync(recs.data(), d_recs.p, recs.size() * sizeof(int), hipMemcpyDeviceToHost, stream_));
+            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        }
     }
-    if (novf <= 0 || mode == EDLIB_MODE_NW) return 0;
-    std::vector<int> flags(ns), total(ns);
-    if (g.zeroCopy) memcpy(flags.data(), g.d_flags.p, ns * sizeof(int));
-    else {
-        EDLIB_AMD_HIP(hipMemcpyAsync(flags.data(), g.d_flags.p, ns * sizeof(int), hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    }
-    for (size_t s = 0; s < ns; ++s)
-        if (flags[s] && g.perm[s] >= 0) g.ovfSlots.push_back((int)s);
-    const size_t no = g.ovfSlots.size();
+    const size_t no = recs.size() / 3;
     if (!no) return 0;
-    int S2, segLen2, warm2;
-    // (a handful of slots is a handful of waves per segment: the pass takes what ONE wave takes for its segment, so the
-    // segments go down to four warm-ups -- 18 slots of a 16,384-read batch: 2 x 0.83 ms at 4,112 columns)
-    plan_segments((int)no, T, mode, g.warm, 16384, S2, segLen2, warm2, no <= 256 ? 1024 : 4096);
-    const size_t items = no * (size_t)S2;
+    // who is gathered from which records (lane of the scan that left them), who is scanned again
+    std::vector<int> src(no, 0), at(no, -1);                  // 0: scan again, 1: the last level's records, 2: pass 1's
+    std::vector<int> rescan;
+    for (size_t i = 0; i < no; ++i) {
+        const int s = recs[3 * i], f = recs[3 * i + 1];
+        g.ovfSlots.push_back(s);
+        if (f == kOvfGatherLevel && g.lvValid) {
+            const auto it = std::lower_bound(g.lvMap.begin(), g.lvMap.end(), s);
+            if (it != g.lvMap.end() && *it == s) { src[i] = 1; at[i] = (int)(it - g.lvMap.begin()); }
+        } else if (f == kOvfGatherGroup) { src[i] = 2; at[i] = s; }
+        if (!src[i]) { at[i] = (int)rescan.size(); rescan.push_back(s); }
+    }
+    const size_t nr = rescan.size();
+    int S2 = 1, segLen2 = 0, warm2 = 0;
     DevBuf<int> d_map, d_caps, d_sb, d_sc; DevBuf<long long> d_off;
-    EDLIB_AMD_HIP(d_map.alloc(no)); EDLIB_AMD_HIP(d_sb.alloc(items)); EDLIB_AMD_HIP(d_sc.alloc(items));
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_map.p, g.ovfSlots.data(), no * sizeof(int), hipMemcpyHostToDevice, stream_));
-    // (a) count; threshold = the exact best (d_best), so the band is as narrow as it gets
-    if (scanGroup(g, mode, d_map.p, (int)no, kNoCap, g.d_best.p, S2, segLen2, warm2,
-                  d_sb.p, d_sc.p, d_sb.p /*unused*/, 0, nullptr, nullptr)) return 1;
-    std::vector<int> cnts(items);
-    EDLIB_AMD_HIP(hipMemcpyAsync(cnts.data(), d_sc.p, items * sizeof(int), hipMemcpyDeviceToHost, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    std::vector<long long> offs(items);
+    std::vector<int> cnts;
+    if (nr) {
+        // (a handful of slots is a handful of waves per segment: the pass takes what ONE wave takes for its segment, so the
+        // segments go down to four warm-ups -- 18 slots of a 16,384-read batch: 2 x 0.83 ms at 4,112 columns)
+        plan_segments((int)nr, T, mode, g.warm, 16384, S2, segLen2, warm2, nr <= 256 ? 1024 : 4096);
+        const size_t items = nr * (size_t)S2;
+        EDLIB_AMD_HIP(d_map.alloc(nr)); EDLIB_AMD_HIP(d_sb.alloc(items)); EDLIB_AMD_HIP(d_sc.alloc(items));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_map.p, rescan.data(), nr * sizeof(int), hipMemcpyHostToDevice, stream_));
+        // (a) count; threshold = the exact best (d_best), so the band is as narrow as it gets
+        if (scanGroup(g, mode, d_map.p, (int)nr, kNoCap, g.d_best.p, S2, segLen2, warm2,
+                      d_sb.p, d_sc.p, d_sb.p /*unused*/, 0, nullptr, nullptr)) return 1;
+        cnts.resize(items);
+        EDLIB_AMD_HIP(hipMemcpyAsync(cnts.data(), d_sc.p, items * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    }
+    // the lists in slot order: a gathered slot takes the merge's total, a rescanned one what its segments counted
+    std::vector<long long> offs(nr * (size_t)S2);
+    std::vector<int> gIdx[2], gLim[2]; std::vector<long long> gOff[2];
     long long acc = 0;
     g.ovfOff.assign(no + 1, 0);
     for (size_t i = 0; i < no; ++i) {
-        for (int sg = 0; sg < S2; ++sg) { offs[i * S2 + sg] = acc; acc += cnts[i * S2 + sg]; }
+        if (src[i]) {
+            const int w = src[i] - 1, n = std::max(0, recs[3 * i + 2]);
+            gIdx[w].push_back(at[i]); gOff[w].push_back(acc); gLim[w].push_back(n);
+            acc += n;
+        } else {
+            const size_t r = (size_t)at[i];
+            for (int sg = 0; sg < S2; ++sg) { offs[r * S2 + sg] = acc; acc += cnts[r * S2 + sg]; }
+        }
         g.ovfOff[i + 1] = acc;
     }
-    EDLIB_AMD_HIP(d_caps.alloc(items)); EDLIB_AMD_HIP(d_off.alloc(items)); EDLIB_AMD_HIP(g.d_ovfPool.ensure((size_t)acc));
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_caps.p, cnts.data(), items * sizeof(int), hipMemcpyHostToDevice, stream_));
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_off.p, offs.data(), items * sizeof(long long), hipMemcpyHostToDevice, stream_));
-    // (b) write
-    if (scanGroup(g, mode, d_map.p, (int)no, kNoCap, g.d_best.p, S2, segLen2, warm2,
-                  d_sb.p, d_sc.p, g.d_ovfPool.p, 0, d_off.p, d_caps.p)) return 1;
+    EDLIB_AMD_HIP(g.d_ovfPool.ensure((size_t)std::max<long long>(acc, 1)));
+    DevBuf<int> d_gi[2], d_gl[2]; DevBuf<long long> d_go[2];
+    for (int w = 0; w < 2; ++w) {
+        const size_t n = gIdx[w].size();
+        if (!n) continue;
+        EDLIB_AMD_HIP(d_gi[w].alloc(n)); EDLIB_AMD_HIP(d_gl[w].alloc(n)); EDLIB_AMD_HIP(d_go[w].alloc(n));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_gi[w].p, gIdx[w].data(), n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_gl[w].p, gLim[w].data(), n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_go[w].p, gOff[w].data(), n * sizeof(long long), hipMemcpyHostToDevice, stream_));
+        if (w == 0)
+            EDLIB_AMD_HIP(launch_gather_segments(g.d_lvBest.p, g.d_lvCnt.p, g.d_lvPos.p, g.lvS, g.lvCap, (int)n,
+                                                 d_gi[w].p, d_go[w].p, d_gl[w].p, g.d_ovfPool.p, stream_));
+        else
+            EDLIB_AMD_HIP(launch_gather_segments(g.d_segBest.p, g.d_segCnt.p, g.d_segPos.p, g.numSegments, 8, (int)n,
+                                                 d_gi[w].p, d_go[w].p, d_gl[w].p, g.d_ovfPool.p, stream_));
+    }
+    if (nr) {
+        const size_t items = nr * (size_t)S2;
+        EDLIB_AMD_HIP(d_caps.alloc(items)); EDLIB_AMD_HIP(d_off.alloc(items));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_caps.p, cnts.data(), items * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_off.p, offs.data(), items * sizeof(long long), hipMemcpyHostToDevice, stream_));
+        // (b) write
+        if (scanGroup(g, mode, d_map.p, (int)nr, kNoCap, g.d_best.p, S2, segLen2, warm2,
+                      d_sb.p, d_sc.p, g.d_ovfPool.p, 0, d_off.p, d_caps.p)) return 1;
+    }
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));                    // temporaries die here
+    static const bool dbg = getenv("EDLIB_AMD_DEBUG") != nullptr;
+    if (dbg) fprintf(stderr, "[edlib_amd] exact pass nwords=%d: %zu gathered, %zu rescanned\n", g.nwords, no - nr, nr);
     stats.overflow_units += (int)no;
     return 0;
 }

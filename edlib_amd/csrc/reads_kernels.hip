@@ -440,15 +440,20 @@ hipError_t launch_collect_candidates(const int* segCnt, const int* segPos, int n
 
 // Joins the per-segment records of a slot: global best, number of columns
 // attaining it, and the first capFinal positions in ascending order
-// (reference semantics of positions_, edlib.cpp:662-671).  flags bit0 = the
-// list is incomplete (a segment or the final list overflowed): the host runs
-// the exact second pass for that slot.
+// (reference semantics of positions_, edlib.cpp:662-671).  flags != 0: the
+// list is incomplete and the host runs the exact second pass for that slot.
+// 1: a contributing segment holds more hits than its cap (the slot is scanned
+// again); gatherFlag: every contributing segment fits and only the final list
+// overflowed -- the complete ascending list is in these records, and
+// gather_segments_kernel copies it out without a scan (gatherFlag = 1: the
+// records will not live that long).  total[] is exact either way: segCnt
+// counts the hits past the cap too.
 __global__ void __launch_bounds__(256)
 merge_segments_kernel(const int* __restrict__ segBest, const int* __restrict__ segCnt,
                       const int* __restrict__ segPos, int S, int cap, int nlanes,
                       const int* __restrict__ slotmap, int capFinal,
                       int* __restrict__ best, int* __restrict__ total, int* __restrict__ pos,
-                      int* __restrict__ flags)
+                      int* __restrict__ flags, int gatherFlag)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;      // lane index of the scan launch
     if (idx >= nlanes) return;
@@ -468,7 +473,7 @@ merge_segments_kernel(const int* __restrict__ segBest, const int* __restrict__ s
                 if (n + i < capFinal) pos[(size_t)slot * capFinal + n + i] = segPos[(base + s) * cap + i];
             n += c;
         }
-        if (n > capFinal) ovf = 1;
+        if (!ovf && n > capFinal) ovf = gatherFlag;
     }
     best[slot] = (b == 0x7fffffff) ? -1 : b;
     total[slot] = n;
@@ -483,7 +488,7 @@ merge_segments_wave_kernel(const int* __restrict__ segBest, const int* __restric
                            const int* __restrict__ segPos, int S, int cap, int nlanes,
                            const int* __restrict__ slotmap, int capFinal,
                            int* __restrict__ best, int* __restrict__ total, int* __restrict__ pos,
-                           int* __restrict__ flags)
+                           int* __restrict__ flags, int gatherFlag)
 {
     const int idx = blockIdx.x, lane = threadIdx.x;
     const int slot = slotmap ? slotmap[idx] : idx;
@@ -507,7 +512,7 @@ merge_segments_wave_kernel(const int* __restrict__ segBest, const int* __restric
             n += __shfl(incl, 63);
         }
         ovf = __any(ovf) ? 1 : 0;
-        if (n > capFinal) ovf = 1;
+        if (!ovf && n > capFinal) ovf = gatherFlag;
     }
     if (lane == 0) {
         best[slot] = (b == 0x7fffffff) ? -1 : b;
@@ -518,16 +523,55 @@ merge_segments_wave_kernel(const int* __restrict__ segBest, const int* __restric
 
 hipError_t launch_merge_segments(const int* segBest, const int* segCnt, const int* segPos, int S,
                                  int cap, int nlanes, const int* slotmap, int capFinal, int* best,
-                                 int* total, int* pos, int* flags, hipStream_t stream)
+                                 int* total, int* pos, int* flags, hipStream_t stream, int gatherFlag)
 {
     if (nlanes == 0) return hipSuccess;
     if (S >= 64) {
         hipLaunchKernelGGL(merge_segments_wave_kernel, dim3(nlanes), dim3(64), 0, stream,
-                           segBest, segCnt, segPos, S, cap, nlanes, slotmap, capFinal, best, total, pos, flags);
+                           segBest, segCnt, segPos, S, cap, nlanes, slotmap, capFinal, best, total, pos, flags, gatherFlag);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(merge_segments_kernel, dim3((nlanes + 255) / 256), dim3(256), 0, stream,
-                       segBest, segCnt, segPos, S, cap, nlanes, slotmap, capFinal, best, total, pos, flags);
+                       segBest, segCnt, segPos, S, cap, nlanes, slotmap, capFinal, best, total, pos, flags, gatherFlag);
+    return hipGetLastError();
+}
+
+// The exact pass of a slot whose segments all fit their cap: merge_segments_wave_kernel's prefix sums with the slot's own
+// total as the capacity.  A wave per entry; idx = lane of the scan launch that left the records, off / lim = where the list
+// goes in `out` and how long it is (the merge's total[]).
+__global__ void __launch_bounds__(64)
+gather_segments_kernel(const int* __restrict__ segBest, const int* __restrict__ segCnt,
+                       const int* __restrict__ segPos, int S, int cap, const int* __restrict__ idx,
+                       const long long* __restrict__ off, const int* __restrict__ lim, int* __restrict__ out)
+{
+    const int lane = threadIdx.x;
+    const size_t base = (size_t)idx[blockIdx.x] * S;
+    int* dst = out + off[blockIdx.x];
+    const int capOut = lim[blockIdx.x];
+    int b = 0x7fffffff;
+    for (int s = lane; s < S; s += 64)
+        if (segCnt[base + s] > 0 && segBest[base + s] < b) b = segBest[base + s];
+    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(b, o); b = t < b ? t : b; }
+    if (b == 0x7fffffff) return;
+    int n = 0;
+    for (int s0 = 0; s0 < S; s0 += 64) {
+        const int s = s0 + lane;
+        int c = s < S ? segCnt[base + s] : 0;
+        if (c <= 0 || segBest[base + s] != b) c = 0;
+        int incl = c;
+        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+        const int at = n + incl - c, take = c < cap ? c : cap;
+        for (int i = 0; i < take; ++i)
+            if (at + i < capOut) dst[at + i] = segPos[(base + s) * cap + i];
+        n += __shfl(incl, 63);
+    }
+}
+
+hipError_t launch_gather_segments(const int* segBest, const int* segCnt, const int* segPos, int S, int cap, int n,
+                                  const int* idx, const long long* off, const int* lim, int* out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(gather_segments_kernel, dim3(n), dim3(64), 0, stream, segBest, segCnt, segPos, S, cap, idx, off, lim, out);
     return hipGetLastError();
 }
 

@@ -112,6 +112,23 @@ hipError_t launch_seed_verify(int nwords, const SeedArgs& a, hipStream_t stream)
 
 hipError_t launch_merge_segments(const int* segBest, const int* segCnt, const int* segPos,
                                  int numSegments, int cap, int nlanes, const int* slotmap, int capFinal,
-                                 int* best, int* total, int* pos, int* flags, hipStream_t stream);
+                                 int* best, int* total, int* pos, int* flags, hipStream_t stream, int gatherFlag = 1);
+// flags[] of the merge: the slot's list is scanned again / is complete in the records of the last level / of the group's pass 1
+constexpr int kOvfRescan = 1, kOvfGatherLevel = 2, kOvfGatherGroup = 4;
+// exact pass without a scan for n slots whose contributing segments all fit `cap`: the complete ascending list of entry e
+// (records of scan lane idx[e]) goes to out + off[e], at most lim[e] positions
+hipError_t launch_gather_segments(const int* segBest, const int* segCnt, const int* segPos, int numSegments, int cap, int n,
+                                  const int* idx, const long long* off, const int* lim, int* out, hipStream_t stream);
+
+// Ascending lists of a group's slots, compacted on the device (rocPRIM select; tmp: select_slots_scratch_bytes(nslots)).
+// Open slots: real (perm >= 0), nothing found (total <= 0) and a threshold min(qlen, k; kcfg < 0: qlen) above kDone.
+// Flagged slots: real and flags != 0.  *count (device) = length of the list.
+hipError_t select_slots_scratch_bytes(int nslots, size_t* bytes);
+hipError_t launch_select_open_slots(const int* perm, const int* total, const int* qlen, int kcfg, int kDone, int nslots,
+                                    int* out, int* count, void* tmp, size_t tmpBytes, hipStream_t stream);
+hipError_t launch_select_flagged_slots(const int* perm, const int* flags, int nslots, int* out, int* count,
+                                       void* tmp, size_t tmpBytes, hipStream_t stream);
+// out[3 i ..] = {slots[i], flags[slots[i]], total[slots[i]]}
+hipError_t launch_pick_slot_records(const int* slots, int n, const int* flags, const int* total, int* out, hipStream_t stream);
 
 }  // namespace edlib_amd

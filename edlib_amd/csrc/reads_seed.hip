@@ -23,6 +23,8 @@
 #include "reads_scan.hpp"
 
 #include <rocprim/device/device_scan.hpp>
+#include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace edlib_amd {
 
@@ -251,6 +253,69 @@ hipError_t launch_seed_verify(int nwords, const SeedArgs& a, hipStream_t stream)
 #undef CASE
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------ slot lists
+
+namespace {
+struct OpenSlot {
+    const int *perm, *total, *qlen; int kcfg, kDone;
+    __device__ bool operator()(int s) const
+    {
+        if (perm[s] < 0 || total[s] > 0) return false;
+        const int m = qlen[s];
+        return (kcfg < 0 ? m : min(m, kcfg)) > kDone;
+    }
+};
+struct FlaggedSlot {
+    const int *perm, *flags;
+    __device__ bool operator()(int s) const { return flags[s] != 0 && perm[s] >= 0; }
+};
+}  // namespace
+
+hipError_t select_slots_scratch_bytes(int nslots, size_t* bytes)
+{
+    size_t a = 0, b = 0;
+    hipError_t e = rocprim::select(nullptr, a, rocprim::counting_iterator<int>(0), (int*)nullptr, (int*)nullptr, (size_t)nslots,
+                                   OpenSlot{});
+    if (e != hipSuccess) return e;
+    e = rocprim::select(nullptr, b, rocprim::counting_iterator<int>(0), (int*)nullptr, (int*)nullptr, (size_t)nslots,
+                        FlaggedSlot{});
+    *bytes = a > b ? a : b;
+    return e;
+}
+
+hipError_t launch_select_open_slots(const int* perm, const int* total, const int* qlen, int kcfg, int kDone, int nslots,
+                                    int* out, int* count, void* tmp, size_t tmpBytes, hipStream_t stream)
+{
+    size_t bytes = tmpBytes;
+    return rocprim::select(tmp, bytes, rocprim::counting_iterator<int>(0), out, count, (size_t)nslots,
+                           OpenSlot{perm, total, qlen, kcfg, kDone}, stream);
+}
+
+hipError_t launch_select_flagged_slots(const int* perm, const int* flags, int nslots, int* out, int* count,
+                                       void* tmp, size_t tmpBytes, hipStream_t stream)
+{
+    size_t bytes = tmpBytes;
+    return rocprim::select(tmp, bytes, rocprim::counting_iterator<int>(0), out, count, (size_t)nslots,
+                           FlaggedSlot{perm, flags}, stream);
+}
+
+__global__ void __launch_bounds__(256)
+pick_slot_records_kernel(const int* __restrict__ slots, int n, const int* __restrict__ flags, const int* __restrict__ total,
+                         int* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int s = slots[i];
+    out[3 * i] = s; out[3 * i + 1] = flags[s]; out[3 * i + 2] = total[s];
+}
+
+hipError_t launch_pick_slot_records(const int* slots, int n, const int* flags, const int* total, int* out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(pick_slot_records_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, slots, n, flags, total, out);
     return hipGetLastError();
 }
 
