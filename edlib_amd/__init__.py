@@ -4,8 +4,8 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 ``getNiceAlignment()`` have the same arguments, defaults, result dictionary and
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
-``align_batch()`` / ``align_pairs()`` / ``align_cross()`` and the resident ``SharedBatch`` /
-``PairBatch`` / ``CrossBatch`` sessions over include/edlib_amd.h.
+``align_batch()`` / ``align_pairs()`` / ``align_cross()``, ``reverse_complement()`` and the resident
+``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` sessions over include/edlib_amd.h.
 
 There is no CPU path in here: everything calls ``libedlib.so`` (built by
 ``__graft_entry__.build()`` / ``make``), and a missing library or a missing GPU
@@ -71,6 +71,10 @@ class CrossHits(C.Structure):            # edlib_amd.h EdlibAmdCrossHits
         (f, C.POINTER(C.c_int)) for f in ("query", "editDistance", "numLocations", "endLocation")]
 
 
+class StrandView(C.Structure):           # edlib_amd.h EdlibAmdStrandView
+    _fields_ = [("numUnits", C.c_int), ("strand", C.POINTER(C.c_ubyte)), ("bothStrands", C.POINTER(C.c_ubyte))]
+
+
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
 CROSS_BEST = 2                            # EDLIB_AMD_CROSS_BEST
 
@@ -99,6 +103,11 @@ def lib():
         L.edlibAmdBatchCreateShared.restype = C.c_void_p
         L.edlibAmdBatchCreateShared.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                 AlignConfig, C.c_int]
+        L.edlibAmdBatchCreateSharedBothStrands.restype = C.c_void_p
+        L.edlibAmdBatchCreateSharedBothStrands.argtypes = L.edlibAmdBatchCreateShared.argtypes
+        L.edlibAmdBatchStrandView.argtypes = [C.c_void_p, C.POINTER(StrandView)]
+        L.edlibAmdReverseComplement.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.edlibAmdReverseComplement.restype = None
         L.edlibAmdBatchCreatePairs.restype = C.c_void_p
         L.edlibAmdBatchCreatePairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                AlignConfig, C.c_int]
@@ -261,6 +270,17 @@ def align(query, target, mode="NW", task="distance", k=-1, additionalEqualities=
     if raw["status"] == 1:
         raise Exception("There was an error.")
     return _nice_result(raw)
+
+
+def reverse_complement(seq):
+    """edlibAmdReverseComplement: the reverse complement of a nucleotide sequence (bytes in, bytes out; a uint8 array gives
+    a uint8 array).  A<->T, C<->G, U->A, the IUPAC codes by their meaning, both cases; every other byte stays."""
+    as_array = isinstance(seq, np.ndarray)
+    src = np.ascontiguousarray(seq, dtype=np.uint8) if as_array else np.frombuffer(bytes(seq), dtype=np.uint8)
+    out = np.empty(len(src) + 1, dtype=np.uint8)
+    if len(src):
+        lib().edlibAmdReverseComplement(src.ctypes.data, len(src), out.ctypes.data)
+    return out[:len(src)].copy() if as_array else out[:len(src)].tobytes()
 
 
 # how each extended-CIGAR op fills the three display rows: (takes a query symbol, takes a target symbol, marker)
@@ -435,6 +455,34 @@ class SharedBatch(_Batch):
         super().__init__(h, len(qo) - 1, keep)
 
 
+class BothStrandsBatch(_Batch):
+    """Many reads against one target, each as itself and as its reverse complement (edlibAmdBatchCreateSharedBothStrands):
+    unit i reports the better strand's result, ties to the forward strand; strands() says which."""
+
+    def __init__(self, queries, target, mode="HW", task="distance", k=-1, additionalEqualities=None, device=0):
+        qd, qo = _pack(queries)
+        t = np.frombuffer(target, dtype=np.uint8) if isinstance(target, (bytes, bytearray)) else np.asarray(target, dtype=np.uint8)
+        t = np.ascontiguousarray(t) if len(t) else np.zeros(1, dtype=np.uint8)
+        tlen = len(target)
+        cfg, keep = _make_config(mode, task, k, additionalEqualities)
+        h = lib().edlibAmdBatchCreateSharedBothStrands(qd.ctypes.data, qo.ctypes.data, len(qo) - 1,
+                                                       t.ctypes.data, tlen, cfg, device)
+        super().__init__(h, len(qo) - 1, keep)
+
+    def strands(self, copy=True):
+        """(strand, bothStrands) of the last run: uint8 arrays [n]; strand 0 forward, 1 reverse complement; bothStrands 1
+        where the other strand reaches the same distance.  copy=False: views of the batch's pinned memory, valid until
+        its next run() / close()."""
+        v = StrandView()
+        if lib().edlibAmdBatchStrandView(self._h, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: strand view failed: " + last_error())
+        if self.n == 0:
+            return np.zeros(0, dtype=np.uint8), np.zeros(0, dtype=np.uint8)
+        a = np.ctypeslib.as_array(v.strand, shape=(self.n,))
+        b = np.ctypeslib.as_array(v.bothStrands, shape=(self.n,))
+        return (a.copy(), b.copy()) if copy else (a, b)
+
+
 class PairBatch(_Batch):
     """Independent (query, target) pairs."""
 
@@ -533,12 +581,22 @@ def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hi
         b.close()
 
 
-def align_batch(queries, target, mode="HW", task="distance", k=-1, additionalEqualities=None, raw=False):
-    """[align(q, target, ...) for q in queries] in one device batch."""
-    b = SharedBatch(queries, target, mode, task, k, additionalEqualities)
+def align_batch(queries, target, mode="HW", task="distance", k=-1, additionalEqualities=None, raw=False, strands="forward"):
+    """[align(q, target, ...) for q in queries] in one device batch.  strands="both": every query is also searched as its
+    reverse complement and the better strand is reported (ties: forward); the results gain the entries ``strand``
+    (0 forward, 1 reverse complement) and ``bothStrands`` (1: the other strand reaches the same distance)."""
+    if strands not in ("forward", "both"):
+        raise ValueError("strands must be 'forward' or 'both'")
+    both = strands == "both"
+    b = (BothStrandsBatch if both else SharedBatch)(queries, target, mode, task, k, additionalEqualities)
     try:
         b.run()
-        return b.results(raw=raw)
+        out = b.results(raw=raw)
+        if both:
+            st, bs = b.strands()
+            for i, r in enumerate(out):
+                r["strand"], r["bothStrands"] = int(st[i]), int(bs[i])
+        return out
     finally:
         b.close()
 

@@ -150,6 +150,33 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreatePairs(const char* queries, const lon
     return b;
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedBothStrands(const char* queries, const long long* queryOffsets,
+                                                              int numQueries, const char* target, int targetLength,
+                                                              EdlibAlignConfig config, int device) {
+    const char* where = "edlibAmdBatchCreateSharedBothStrands";
+    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
+    if (!b) return nullptr;
+    const long long toff[2] = {0, targetLength};
+    const int rc = targetLength < 0 ? 1 : guarded(where, 1, [&] {
+        return b->impl.init(queries, queryOffsets, numQueries, target, toff, 1, config, device, /*bothStrands=*/true); });
+    if (targetLength < 0) set_error("negative target length");
+    if (rc) {
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+EDLIB_API int edlibAmdBatchStrandView(EdlibAmdBatch* b, EdlibAmdStrandView* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_cross(b, "edlibAmdBatchStrandView")) return EDLIB_STATUS_ERROR;
+    return guarded("edlibAmdBatchStrandView", 1, [&] { return b->impl.strandView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+EDLIB_API void edlibAmdReverseComplement(const char* in, int n, char* out) {
+    for (int j = 0; j < n; ++j) out[j] = (char)complement_byte((uint8_t)in[n - 1 - j]);
+}
+
 static EdlibAmdBatch* create_cross(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
                                    const char* targets, const long long* targetOffsets, int numTargets,
                                    EdlibAlignConfig config, int device, bool hits) {

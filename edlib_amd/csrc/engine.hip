@@ -212,9 +212,10 @@ Batch::~Batch() {
 int roundup(int x, int q) { return (x + q - 1) / q * q; }
 
 int Batch::init(const char* queries, const long long* qoff, int n, const char* targets,
-                const long long* toff, int numTargets, EdlibAlignConfig cfg, int device)
+                const long long* toff, int numTargets, EdlibAlignConfig cfg, int device, bool bothStrands)
 {
     if (n < 0 || (numTargets != 1 && numTargets != n)) { set_error("bad batch shape"); return 1; }
+    if (bothStrands && (numTargets != 1 || n > 0x3fffffff)) { set_error("bad both-strand batch shape"); return 1; }
     const int ndev = device_count();
     if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
@@ -224,13 +225,22 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
     cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
     cfg_.additionalEqualitiesLength = (int)eqs_.size();
     device_ = device;
-    n_ = n;
+    strands_ = bothStrands;
     shared_ = (numTargets == 1);
-    qoff_.assign(qoff, qoff + n + 1);
     toff_.assign(toff, toff + numTargets + 1);
     for (int u = 0; u < n; ++u) {
-        if (qoff_[u + 1] < qoff_[u] || qoff_[u + 1] - qoff_[u] > 0x7fffffffLL) { set_error("bad query offsets"); return 1; }
+        if (qoff[u + 1] < qoff[u] || qoff[u + 1] - qoff[u] > 0x7fffffffLL) { set_error("bad query offsets"); return 1; }
     }
+    const int numReads = n;
+    const long long qb = qoff[0];
+    if (strands_) {
+        // units 2i / 2i + 1: read i and its reverse complement, back to back in a pool of twice the bytes (already rebased)
+        n = 2 * numReads;
+        qoff_.resize((size_t)n + 1);
+        for (int i = 0; i < numReads; ++i) { qoff_[2 * i] = 2 * (qoff[i] - qb); qoff_[2 * i + 1] = 2 * (qoff[i] - qb) + (qoff[i + 1] - qoff[i]); }
+        qoff_[n] = 2 * (qoff[numReads] - qb);
+    } else qoff_.assign(qoff, qoff + n + 1);
+    n_ = n;
     for (int u = 0; u < numTargets; ++u) {
         if (toff_[u + 1] < toff_[u] || toff_[u + 1] - toff_[u] > 0x7fffffffLL) { set_error("bad target offsets"); return 1; }
     }
@@ -248,16 +258,17 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
     // the sequences themselves -- go up as ONE block through pinned staging with one asynchronous copy: a call
     // of edlibAlign() is a batch of one, and nine blocking hipMemcpy calls from pageable memory were most of
     // what it cost.  Large pools are copied straight from the caller's memory.
-    const long long qb = qoff_[0], tb = toff_[0];
-    for (auto& v : qoff_) v -= qb;
+    const long long tb = toff_[0];
+    if (!strands_) for (auto& v : qoff_) v -= qb;
     for (auto& v : toff_) v -= tb;
     {
-        const bool inlinePools = qbytes + tbytes <= (1 << 20);
+        // (the pool of a both-strand batch is written by a kernel: it is a block of its own)
+        const bool inlineT = qbytes + tbytes <= (1 << 20), inlineQ = inlineT && !strands_;
         size_t at = 0;
         auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
         const size_t oQoff = take(qoff_.size() * sizeof(long long)), oToff = take(toff_.size() * sizeof(long long));
         const size_t oTlut = take(256), oId = take(256), oEq4 = take(512), oPres = take(32);
-        const size_t oQ = inlinePools ? take((size_t)qbytes + 16) : 0, oT = inlinePools ? take((size_t)tbytes + 16) : 0;
+        const size_t oQ = inlineQ ? take((size_t)qbytes + 16) : 0, oT = inlineT ? take((size_t)tbytes + 16) : 0;
         EDLIB_AMD_HIP(d_in_.alloc(at));
         EDLIB_AMD_HIP(h_in_.alloc(at));
         uint8_t* h = h_in_.p;
@@ -268,18 +279,35 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
         d_qoff_.alias(d_in_.p + oQoff, qoff_.size()); d_toff_.alias(d_in_.p + oToff, toff_.size());
         d_tlut_.alias(d_in_.p + oTlut, 256); d_idToByte_.alias(d_in_.p + oId, 256);
         d_eqtbl_.alias(d_in_.p + oEq4, 256); d_presence_.alias(d_in_.p + oPres, 8);
-        if (inlinePools) {
+        if (inlineQ) {
             if (qbytes) memcpy(h + oQ, queries + qb, (size_t)qbytes);
-            if (tbytes) memcpy(h + oT, targets + tb, (size_t)tbytes);
-            memset(h + oQ + qbytes, 0, 16); memset(h + oT + tbytes, 0, 16);
-            d_qpool_.alias(d_in_.p + oQ, (size_t)qbytes + 16); d_tpool_.alias(d_in_.p + oT, (size_t)tbytes + 16);
+            memset(h + oQ + qbytes, 0, 16);
+            d_qpool_.alias(d_in_.p + oQ, (size_t)qbytes + 16);
         } else {
             EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16));
+            if (qbytes && !strands_) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
+        }
+        if (inlineT) {
+            if (tbytes) memcpy(h + oT, targets + tb, (size_t)tbytes);
+            memset(h + oT + tbytes, 0, 16);
+            d_tpool_.alias(d_in_.p + oT, (size_t)tbytes + 16);
+        } else {
             EDLIB_AMD_HIP(d_tpool_.alloc((size_t)tbytes + 16));
-            if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
             if (tbytes) EDLIB_AMD_HIP(hipMemcpy(d_tpool_.p, targets + tb, (size_t)tbytes, hipMemcpyHostToDevice));
         }
         EDLIB_AMD_HIP(hipMemcpyAsync(d_in_.p, h, at, hipMemcpyHostToDevice, stream_));
+    }
+    if (strands_) {
+        // the caller's pool goes up as it is; both strands of every read are written from it on the device
+        const size_t inBytes = (size_t)(qbytes / 2);
+        DevBuf<uint8_t> d_raw;
+        EDLIB_AMD_HIP(d_raw.alloc(inBytes + 16));
+        if (inBytes) EDLIB_AMD_HIP(hipMemcpy(d_raw.p, queries + qb, inBytes, hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p, 0, (size_t)qbytes + 16, stream_));
+        EDLIB_AMD_HIP(launch_strand_pool(d_raw.p, d_qoff_.p, numReads, d_qpool_.p, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));               // d_raw dies here
+        EDLIB_AMD_HIP(h_strand_.alloc(2 * (size_t)numReads));
+        memset(h_strand_.p, 0, 2 * (size_t)numReads);
     }
 
     // classification of the units for phase 1
@@ -333,6 +361,13 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
         if (byWords[w].empty()) continue;
         std::unique_ptr<ReadGroup> g;
         if (makeGroup(byWords[w], w, g)) return 1;
+        if (strands_) {
+            // mates have one length, hence one class and one word count, and a group lists its units in unit order
+            for (int sl = 0; sl < g->nslots; sl += 2)
+                if (g->perm[sl] >= 0 && ((g->perm[sl] & 1) || g->perm[sl + 1] != g->perm[sl] + 1)) { set_error("both strands: mates are not in adjacent slots"); return 1; }
+            g->mates = true;
+            EDLIB_AMD_HIP(g->d_win.alloc((size_t)g->nslots / 2));
+        }
         groups_.push_back(std::move(g));
     }
     if (initFlatPairs()) return 1;
@@ -563,6 +598,7 @@ int Batch::runImpl()
     stats = EdlibAmdBatchStats{};
     stats.cells = cells;
     scanEventsUsed_ = 0;
+    hostStrandCounts_[0] = hostStrandCounts_[1] = hostStrandCounts_[2] = hostStrandCounts_[3] = 0;
     haveResults_ = false;
     opsKeep_.clear();            // (the previous run's views die with the reset of their records below)
     knownSplits_.clear();
@@ -772,6 +808,8 @@ int Batch::runImpl()
     lap("run: finalize pairs");
     if (!flatDone && alphabetLengthsEnd(res)) return 1;      // alphabetLength for everything the reads path did not cover (flat pairs: at collection)
     lap("run: phase 1 (distance)");
+    // both strands: the distance phase decides the strand; the later phases see the reported record only
+    if (strands_ && !res.empty() && resolveStrandsOnHost(res)) return 1;
     std::vector<int>& live = live_;            // non-empty units with a solution (only the later phases want them)
     live.clear();
     // (a flat batch has done its phases 2 and 3 on the device: its records do not exist yet)
@@ -877,6 +915,60 @@ int Batch::runImpl()
     results_.swap(res);
     haveResults_ = true;
     lap("run: stats");
+    if (strands_ && lap.on) {
+        // (tests/test_gpu_strands.py reads this line)
+        int c[4];
+        if (strandCounts(c)) return 1;
+        fprintf(stderr, "[edlib_amd] strands: %d reads, forward %d, reverse %d, both %d, none %d, located %zu\n", outN(), c[0], c[1],
+                c[2], c[3], laterPhases ? live.size() : (size_t)0);
+    }
+    return 0;
+}
+
+// Both strands: the mate pairs that are not in a read group (empty units, long reads, pair units) ran both strands in full;
+// their records say which one is reported (the table of edlib_amd.h), and the other record is blanked.
+int Batch::resolveStrandsOnHost(std::vector<UnitResult>& res)
+{
+    hostStrandCounts_[0] = hostStrandCounts_[1] = hostStrandCounts_[2] = hostStrandCounts_[3] = 0;
+    for (const std::vector<int>* list : {&emptyUnits_, &longUnits_, &pairUnits_})
+        for (int u : *list) {
+            if (u & 1) continue;
+            const int w = resolve_strands(res[u].editDistance, res[u + 1].editDistance);
+            setStrand(u >> 1, w);
+            blank_record(res[(w & kStrandReverse) ? u : u + 1]);
+            ++hostStrandCounts_[(w & kStrandNone) ? 3 : (w & kStrandReverse)];
+            if (w & kStrandBoth) ++hostStrandCounts_[2];
+        }
+    return 0;
+}
+
+// forward, reverse, both, none over the reads of the last run (EDLIB_AMD_DEBUG only: the groups' codes come down for it)
+int Batch::strandCounts(int c[4])
+{
+    for (int i = 0; i < 4; ++i) c[i] = hostStrandCounts_[i];
+    for (auto& gp : groups_) {
+        if (!gp->mates) continue;
+        std::vector<int> win((size_t)gp->nslots / 2);
+        EDLIB_AMD_HIP(hipMemcpyAsync(win.data(), gp->d_win.p, win.size() * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        for (size_t p2 = 0; p2 < win.size(); ++p2) {
+            if (gp->perm[2 * p2] < 0) continue;
+            const int w = win[p2];
+            ++c[(w & kStrandNone) ? 3 : (w & kStrandReverse)];
+            if (w & kStrandBoth) ++c[2];
+        }
+    }
+    return 0;
+}
+
+// strand / bothStrands of the last run, in pinned memory of the batch
+int Batch::strandView(EdlibAmdStrandView* out)
+{
+    if (!strands_) { set_error("edlibAmdBatchStrandView: not a both-strand batch"); return 1; }
+    if (!haveResults_) { set_error("results before a successful run()"); return 1; }
+    // (the groups' codes reach the host with the view of a DISTANCE run over read groups, else with the records)
+    if (readsViewOnDevice() ? resultsView(nullptr) : ensureCollected()) return 1;
+    out->numUnits = outN(); out->strand = h_strand_.p; out->bothStrands = h_strand_.p + outN();
     return 0;
 }
 
@@ -908,6 +1000,7 @@ static int* malloc_ints(const LocList& v) {
 int Batch::results(EdlibAlignResult* out)
 {
     // the failure contract of edlib_amd.h: on ANY failure every entry is blank with status ERROR (nothing to free)
+    const int n_ = outN();                        // (shadows the member: the units the caller sees)
     for (int u = 0; u < n_; ++u) {
         EdlibAlignResult& o = out[u];
         o.status = EDLIB_STATUS_ERROR; o.editDistance = -1; o.endLocations = nullptr; o.startLocations = nullptr;
@@ -933,7 +1026,7 @@ int Batch::results(EdlibAlignResult* out)
             o.numLocations = nl;
         }
         for (int u = lo; !fromView && u < hi; ++u) {
-            const UnitResult& r = results_[u];
+            const UnitResult& r = results_[unitOf(u)];
             EdlibAlignResult& o = out[u];
             o.status = r.status;
             o.editDistance = r.editDistance;
@@ -994,11 +1087,12 @@ int Batch::buildHostView()
 {
     if (viewReady_) return 0;
     if (ensureCollected()) return 1;
-    const size_t n = (size_t)n_;
+    const size_t n = (size_t)outN();
+    const int n_ = outN();                        // (shadows the member: the units the caller sees)
     long long nloc = 0, naln = 0;
     bool anyStarts = false;
     for (size_t u = 0; u < n; ++u) {
-        const UnitResult& r = results_[u];
+        const UnitResult& r = results_[unitOf((int)u)];
         nloc += r.hasEnds ? (long long)r.ends.size() : 0;
         naln += r.hasAlignment ? (long long)r.opsViewLen : 0;
         anyStarts = anyStarts || r.hasStarts;
@@ -1008,7 +1102,7 @@ int Batch::buildHostView()
     long long* lo = viewOffs_.data(); long long* ao = lo + n + 1;
     long long li = 0, ai = 0;
     for (size_t u = 0; u < n; ++u) {
-        const UnitResult& r = results_[u];
+        const UnitResult& r = results_[unitOf((int)u)];
         st[u] = r.status; ed[u] = r.editDistance; al[u] = r.alphabetLength;
         const size_t c = r.hasEnds ? r.ends.size() : 0;
         nl[u] = (int)c; lo[u] = li; ao[u] = ai;
@@ -1047,7 +1141,7 @@ int Batch::resultsFlat(int* status, int* editDistance, int* numLocations, int* a
     if (alignment) *alignment = nullptr;
     EdlibAmdResultsView v;
     if (resultsView(&v)) return 1;
-    const size_t n = (size_t)n_;
+    const size_t n = (size_t)outN();
     if (status) memcpy(status, v.status, n * sizeof(int));
     if (editDistance) memcpy(editDistance, v.editDistance, n * sizeof(int));
     if (numLocations) memcpy(numLocations, v.numLocations, n * sizeof(int));
@@ -1079,7 +1173,7 @@ int Batch::cigarView(int format, const char** chars, const long long** offsets)
     EdlibAmdResultsView v;
     if (resultsView(&v)) return 1;
     CigarOut& c = cigar_[format == EDLIB_CIGAR_STANDARD ? 1 : 0];
-    const size_t n = (size_t)n_;
+    const size_t n = (size_t)outN();
     cigarSticky_ = true;
     if (!c.ready) {
         DeviceGuard guard(device_);

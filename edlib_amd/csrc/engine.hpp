@@ -8,6 +8,7 @@
 #include "lanepair.hpp"
 #include "reads_kernels.hpp"
 #include "cross_kernels.hpp"
+#include "strands.hpp"
 
 #include <chrono>
 #include <deque>
@@ -119,7 +120,7 @@ public:
     // sequences are copied to the device here; nothing of the caller's memory is retained
     int init(const char* queries, const long long* qoff, int n,
              const char* targets, const long long* toff, int numTargets,   // numTargets == 1: shared
-             EdlibAlignConfig cfg, int device);
+             EdlibAlignConfig cfg, int device, bool bothStrands = false);   // bothStrands (shared only): n reads, 2n units
     int run();
     int runImpl();
     int results(EdlibAlignResult* out);
@@ -127,6 +128,7 @@ public:
                     int** endLocations, int** startLocations, long long* alnOffsets, unsigned char** alignment);
     int resultsView(EdlibAmdResultsView* out);
     int cigarView(int format, const char** chars, const long long** offsets);
+    int strandView(EdlibAmdStrandView* out);
     EdlibAmdBatchStats stats{};
     void finishStats();          // fills the fields of `stats` that cost a walk over the records (algo_bytes)
 
@@ -138,6 +140,16 @@ private:
     bool shared_ = false;
     int n_ = 0;
     std::vector<long long> qoff_, toff_;
+    // ---- both strands: unit 2i is read i, unit 2i + 1 its reverse complement (made on the device at init);
+    // the caller sees n_ / 2 units, each the record of unit 2i + strand[i]
+    bool strands_ = false;
+    PinBuf h_strand_;                            // [outN()] strand, then [outN()] bothStrands, of the last run
+    int outN() const { return strands_ ? n_ / 2 : n_; }
+    int unitOf(int u) const { return strands_ ? 2 * u + h_strand_.p[u] : u; }
+    void setStrand(int read, int code) { h_strand_.p[read] = (uint8_t)(code & kStrandReverse); h_strand_.p[outN() + read] = (code & kStrandBoth) ? 1 : 0; }
+    int resolveStrandsOnHost(std::vector<UnitResult>& res);      // the mate pairs outside the read groups, from their records
+    int hostStrandCounts_[4] = {0, 0, 0, 0};                     // of the pairs resolveStrandsOnHost decided in the last run
+    int strandCounts(int counts[4]);                             // forward, reverse, both, none of the last run (debug line)
     Tables tab_;
     hipStream_t stream_ = nullptr;
     Event evRun0_, evRun1_, evA_, evB_;           // evB_: the side stream's alphabet kernel is done
@@ -171,6 +183,9 @@ private:
         DevBuf<int> d_lvMap, d_lvBest, d_lvCnt, d_lvPos; std::vector<int> lvMap; int lvS = 0, lvCap = 0; bool lvValid = false;
         DevBuf<int> d_list;                    // [nslots + 1] a slot list compacted on the device, then its length
         int nreal = -1;                        // slots that hold a unit (counted when first needed)
+        // both strands: the slots s and s ^ 1 hold a read and its reverse complement (the groups made at init only);
+        // d_win[p]: what the pair in the slots 2p, 2p + 1 reports (strands.hpp), decided after the levels of a run
+        bool mates = false; DevBuf<int> d_win;
     };
     static constexpr int kLastLevelCap = 16;   // positions per (lane, segment) of the last level = the slot's own 16
     int listOpenSlots(ReadGroup& g, int kDone, std::vector<int>& out);

@@ -145,6 +145,7 @@ int Batch::initFlatPairs()
     flatStarts_ = flatPaths_ = flatNwStore_ = flatRing32_ = false;
     flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0);
     if (!emptyUnits_.empty() || !groups_.empty() || !longUnits_.empty()) return 0;
+    if (strands_) return 0;                                         // both strands resolve from the general path's records
     if ((int)pairUnits_.size() != n_ || n_ < 1024) return 0;       // (a handful of units: the zero-copy path of solveChunk)
     const int mode = (int)cfg_.mode;
     if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) return 0;
@@ -680,9 +681,10 @@ int Batch::buildReadsView()
 {
     if (viewReady_) return 0;
     const int mode = (int)cfg_.mode;
-    const size_t n = (size_t)n_;
+    // (both strands: the units of the view are the reads, each the reported one of its two slots -- n of them cross the link)
+    const size_t n = (size_t)outN();
     const size_t nblocks = (n + 255) / 256;
-    const bool inPlace = groups_.size() == 1;          // slot == unit (makeGroup lists a group's units in unit order)
+    const bool inPlace = groups_.size() == 1 && !strands_;   // slot == unit (makeGroup lists a group's units in unit order)
     size_t novf = 0; long long ovfTotal = 0;
     for (auto& gp : groups_) { novf += gp->ovfSlots.size(); ovfTotal += gp->ovfOff.empty() ? 0 : gp->ovfOff.back(); }
     const int posCap = mode == EDLIB_MODE_NW ? 0 : kFlatPosCap;
@@ -698,6 +700,7 @@ int Batch::buildReadsView()
     const size_t oOvfPool = take(inPlace ? 4 : (size_t)ovfTotal * 4 + 4);
     const size_t oUScore = take(inPlace ? 4 : n * 4), oUCount = take(inPlace ? 4 : n * 4), oUQlen = take(inPlace ? 4 : n * 4), oUAlpha = take(inPlace ? 4 : n * 4);
     const size_t oUPos = take(inPlace ? 4 : n * (size_t)posCap * 4 + 4);
+    const size_t oUStrand = take(strands_ ? 2 * n : 4);
     const size_t hostHead = headBytes + ((n * 4 + 63) & ~(size_t)63);
     const size_t oEnds = take((size_t)capLoc * 4), oAln = take(64);
     EDLIB_AMD_HIP(d_view_.ensure(at));
@@ -705,7 +708,7 @@ int Batch::buildReadsView()
     uint8_t* const dv = d_view_.p; uint8_t* const hv = h_view_.p;
     FlatResultArgs a{};
     a.descs = nullptr; a.sharedT = tlen(0); a.alphaBase = tab_.sigmaT;
-    a.n = n_; a.mode = mode; a.k = cfg_.k; a.wantPath = 0; a.posCap = kFlatPosCap;
+    a.n = (int)n; a.mode = mode; a.k = cfg_.k; a.wantPath = 0; a.posCap = kFlatPosCap;
     // ---- the per-unit inputs: in place, or gathered from the groups
     std::vector<int> ovfUnits; std::vector<long long> ovfOffAll;
     if (inPlace) {
@@ -721,12 +724,17 @@ int Batch::buildReadsView()
         long long poolAt = 0;
         for (auto& gp : groups_) {
             ReadGroup& g = *gp;
+            if (strands_)
+                EDLIB_AMD_HIP(launch_gather_group_strands(g.d_perm.p, g.nslots, g.d_win.p, g.d_best.p, g.d_total.p, g.d_qlen.p,
+                                                          g.d_alphaExtra.p, g.d_pos.p, posCap, uScore, uCount, uQlen, uAlpha, uPos,
+                                                          dv + oUStrand, dv + oUStrand + n, stream_));
+            else
             hipLaunchKernelGGL(gather_group_kernel, dim3((unsigned)((g.nslots + 255) / 256)), dim3(256), 0, stream_,
                                g.d_perm.p, g.nslots, g.d_best.p, g.d_total.p, g.d_qlen.p, g.d_alphaExtra.p, g.d_pos.p, posCap,
                                uScore, uCount, uQlen, uAlpha, uPos);
             EDLIB_AMD_HIP(hipGetLastError());
             for (size_t i = 0; i < g.ovfSlots.size(); ++i) {
-                ovfUnits.push_back(g.perm[g.ovfSlots[i]]);
+                ovfUnits.push_back(strands_ ? g.perm[g.ovfSlots[i]] >> 1 : g.perm[g.ovfSlots[i]]);
                 ovfOffAll.push_back(poolAt + g.ovfOff[i + 1]);
             }
             const long long mine = g.ovfOff.empty() ? 0 : g.ovfOff.back();
@@ -753,6 +761,7 @@ int Batch::buildReadsView()
     a.ends = reinterpret_cast<int*>(dv + oEnds); a.starts = nullptr; a.aln = dv + oAln;
     EDLIB_AMD_HIP(launch_flat_results(a, reinterpret_cast<long long*>(dv + oTotals), stream_));
     EDLIB_AMD_HIP(hipMemcpyAsync(hv, dv, headBytes, hipMemcpyDeviceToHost, stream_));
+    if (strands_ && n) EDLIB_AMD_HIP(hipMemcpyAsync(h_strand_.p, dv + oUStrand, 2 * n, hipMemcpyDeviceToHost, stream_));
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     const long long nloc = reinterpret_cast<const long long*>(hv + oTotals)[0];
     if (nloc < 0 || nloc > capLoc) { set_error("reads view: totals out of range"); return 1; }
@@ -762,7 +771,7 @@ int Batch::buildReadsView()
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     memset(hv + headBytes, 0, n * 4);                    // status: every unit of a reads group is EDLIB_STATUS_OK
     view_ = EdlibAmdResultsView{};
-    view_.numUnits = n_;
+    view_.numUnits = (int)n;
     view_.status = reinterpret_cast<const int*>(hv + headBytes); view_.editDistance = reinterpret_cast<const int*>(hv + oEd);
     view_.numLocations = reinterpret_cast<const int*>(hv + oNloc); view_.alphabetLength = reinterpret_cast<const int*>(hv + oAlpha);
     view_.locOffsets = reinterpret_cast<const long long*>(hv + oLocOff); view_.alnOffsets = reinterpret_cast<const long long*>(hv + oAlnOff);
@@ -770,7 +779,7 @@ int Batch::buildReadsView()
     view_.startLocations = nullptr; view_.alignment = nullptr;
     viewAlnDev_ = nullptr; viewAlnOffDev_ = nullptr;
     viewReady_ = true;
-    if (getenv("EDLIB_AMD_DEBUG")) fprintf(stderr, "[edlib_amd] reads view made on the device: %d units in %zu group(s), %lld locations, %zu lists of the exact pass\n", n_, groups_.size(), nloc, novf);
+    if (getenv("EDLIB_AMD_DEBUG")) fprintf(stderr, "[edlib_amd] reads view made on the device: %d units in %zu group(s), %lld locations, %zu lists of the exact pass\n", (int)n, groups_.size(), nloc, novf);
     return 0;
 }
 

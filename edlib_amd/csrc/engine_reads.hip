@@ -99,6 +99,11 @@ int Batch::runReads()
     for (auto& gp : groups_) seed = seed || seedThreshold(*gp, false) >= 0;
     if (seed && buildSeedIndex()) return 1;
     for (auto& gp : groups_) if (runGroupScans(*gp, false)) return 1;
+    // both strands: what every mate pair reports, before the exact pass (it serves the reported slots only)
+    const int mode = (cfg_.mode == EDLIB_MODE_HW || cfg_.mode == EDLIB_MODE_SHW) ? (int)cfg_.mode : (int)EDLIB_MODE_NW;
+    for (auto& gp : groups_)
+        if (gp->mates) EDLIB_AMD_HIP(launch_resolve_strands(gp->d_perm.p, gp->d_best.p, gp->d_total.p, gp->nslots, mode, cfg_.k,
+                                                            gp->d_win.p, stream_));
     for (auto& gp : groups_) if (runGroupExact(*gp)) return 1;
     return 0;
 }
@@ -345,7 +350,9 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
     return 0;
 }
 
-// The group's slots that are still open above kDone (launch_select_open_slots), ascending, on the host
+// The group's slots that are still open above kDone (launch_select_open_slots), ascending, on the host.
+// Both strands: a slot is open only while its mate holds no result either.  Mates are scanned at the same
+// thresholds while both are open, so a mate that resolved at d <= kDone beats a slot with nothing <= kDone.
 int Batch::listOpenSlots(ReadGroup& g, int kDone, std::vector<int>& out)
 {
     size_t tmp = 0;
@@ -354,7 +361,7 @@ int Batch::listOpenSlots(ReadGroup& g, int kDone, std::vector<int>& out)
     EDLIB_AMD_HIP(g.d_list.ensure((size_t)g.nslots + 1));
     int* count = g.d_list.p + g.nslots;
     EDLIB_AMD_HIP(launch_select_open_slots(g.d_perm.p, g.d_total.p, g.d_qlen.p, cfg_.k, kDone, g.nslots, g.d_list.p, count,
-                                           d_selTmp_.p, d_selTmp_.bytes(), stream_));
+                                           d_selTmp_.p, d_selTmp_.bytes(), stream_, g.mates));
     int n = 0;
     EDLIB_AMD_HIP(hipMemcpyAsync(&n, count, sizeof(int), hipMemcpyDeviceToHost, stream_));
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
@@ -462,7 +469,7 @@ int Batch::runGroupExact(ReadGroup& g)
     if (mode == EDLIB_MODE_NW) return 0;
     // the flagged slots, ascending, with their flag and their number of end locations
     std::vector<int> recs;                                    // {slot, flag, total} each
-    if (g.zeroCopy) {
+    if (g.zeroCopy && !g.mates) {
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
         for (size_t s = 0; s < ns; ++s)
             if (g.d_flags.p[s] && g.perm[s] >= 0) { recs.push_back((int)s); recs.push_back(g.d_flags.p[s]); recs.push_back(g.d_total.p[s]); }
@@ -473,7 +480,7 @@ int Batch::runGroupExact(ReadGroup& g)
         EDLIB_AMD_HIP(g.d_list.ensure(ns + 1));
         int* count = g.d_list.p + ns;
         EDLIB_AMD_HIP(launch_select_flagged_slots(g.d_perm.p, g.d_flags.p, g.nslots, g.d_list.p, count,
-                                                  d_selTmp_.p, d_selTmp_.bytes(), stream_));
+                                                  d_selTmp_.p, d_selTmp_.bytes(), stream_, g.mates ? g.d_win.p : nullptr));
         int novf = 0;
         EDLIB_AMD_HIP(hipMemcpyAsync(&novf, count, sizeof(int), hipMemcpyDeviceToHost, stream_));
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
@@ -610,6 +617,13 @@ int Batch::collectGroup(ReadGroup& g, std::vector<UnitResult>& res)
     }
     if (!ovfPos.empty())
         EDLIB_AMD_HIP(hipMemcpyAsync(ovfPos.data(), g.d_ovfPool.p, ovfPos.size() * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    PinBuf winStage;
+    const int* win = nullptr;                  // both strands: what every mate pair reports
+    if (g.mates) {
+        EDLIB_AMD_HIP(winStage.alloc(ns / 2 * sizeof(int)));
+        EDLIB_AMD_HIP(hipMemcpyAsync(winStage.p, g.d_win.p, ns / 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+        win = reinterpret_cast<const int*>(winStage.p);
+    }
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     size_t oi = 0;
     for (size_t s = 0; s < ns; ++s) {
@@ -617,6 +631,12 @@ int Batch::collectGroup(ReadGroup& g, std::vector<UnitResult>& res)
         if (u < 0) continue;
         UnitResult& r = res[u];
         if (deferReadsReset_) blank_record(r);
+        if (win) {
+            const int w = win[s >> 1];
+            if (!(s & 1)) setStrand(u >> 1, w);
+            // the mate is reported: this record stays blank (its slot may be pruned, its list above 16 was never made)
+            if ((w & kStrandReverse) != (int)(s & 1)) { blank_record(r); continue; }
+        }
         r.alphabetLength = tab_.sigmaT + extra[s];
         const int m = qlen(u);
         if (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) {

@@ -123,11 +123,13 @@ hipError_t launch_gather_segments(const int* segBest, const int* segCnt, const i
 // Ascending lists of a group's slots, compacted on the device (rocPRIM select; tmp: select_slots_scratch_bytes(nslots)).
 // Open slots: real (perm >= 0), nothing found (total <= 0) and a threshold min(qlen, k; kcfg < 0: qlen) above kDone.
 // Flagged slots: real and flags != 0.  *count (device) = length of the list.
+// Both-strand groups (strands.hpp, mates in the slots s and s ^ 1): `mates` closes a slot whose mate has found something,
+// `win` (the pairs' codes) drops the flagged slots whose mate is the one reported.
 hipError_t select_slots_scratch_bytes(int nslots, size_t* bytes);
 hipError_t launch_select_open_slots(const int* perm, const int* total, const int* qlen, int kcfg, int kDone, int nslots,
-                                    int* out, int* count, void* tmp, size_t tmpBytes, hipStream_t stream);
+                                    int* out, int* count, void* tmp, size_t tmpBytes, hipStream_t stream, bool mates = false);
 hipError_t launch_select_flagged_slots(const int* perm, const int* flags, int nslots, int* out, int* count,
-                                       void* tmp, size_t tmpBytes, hipStream_t stream);
+                                       void* tmp, size_t tmpBytes, hipStream_t stream, const int* win = nullptr);
 // out[3 i ..] = {slots[i], flags[slots[i]], total[slots[i]]}
 hipError_t launch_pick_slot_records(const int* slots, int n, const int* flags, const int* total, int* out, hipStream_t stream);
 

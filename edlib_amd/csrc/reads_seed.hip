@@ -260,17 +260,22 @@ hipError_t launch_seed_verify(int nwords, const SeedArgs& a, hipStream_t stream)
 
 namespace {
 struct OpenSlot {
-    const int *perm, *total, *qlen; int kcfg, kDone;
+    const int *perm, *total, *qlen; int kcfg, kDone, mates;
     __device__ bool operator()(int s) const
     {
         if (perm[s] < 0 || total[s] > 0) return false;
+        if (mates && total[s ^ 1] > 0) return false;      // both strands: the mate resolved at a threshold this slot missed
         const int m = qlen[s];
         return (kcfg < 0 ? m : min(m, kcfg)) > kDone;
     }
 };
 struct FlaggedSlot {
-    const int *perm, *flags;
-    __device__ bool operator()(int s) const { return flags[s] != 0 && perm[s] >= 0; }
+    const int *perm, *flags, *win;                        // win (both strands): strands.hpp's code of the pair s >> 1
+    __device__ bool operator()(int s) const
+    {
+        if (flags[s] == 0 || perm[s] < 0) return false;
+        return !win || (win[s >> 1] & 1) == (s & 1);      // a slot whose mate is reported never shows its list
+    }
 };
 }  // namespace
 
@@ -287,19 +292,19 @@ hipError_t select_slots_scratch_bytes(int nslots, size_t* bytes)
 }
 
 hipError_t launch_select_open_slots(const int* perm, const int* total, const int* qlen, int kcfg, int kDone, int nslots,
-                                    int* out, int* count, void* tmp, size_t tmpBytes, hipStream_t stream)
+                                    int* out, int* count, void* tmp, size_t tmpBytes, hipStream_t stream, bool mates)
 {
     size_t bytes = tmpBytes;
     return rocprim::select(tmp, bytes, rocprim::counting_iterator<int>(0), out, count, (size_t)nslots,
-                           OpenSlot{perm, total, qlen, kcfg, kDone}, stream);
+                           OpenSlot{perm, total, qlen, kcfg, kDone, mates ? 1 : 0}, stream);
 }
 
 hipError_t launch_select_flagged_slots(const int* perm, const int* flags, int nslots, int* out, int* count,
-                                       void* tmp, size_t tmpBytes, hipStream_t stream)
+                                       void* tmp, size_t tmpBytes, hipStream_t stream, const int* win)
 {
     size_t bytes = tmpBytes;
     return rocprim::select(tmp, bytes, rocprim::counting_iterator<int>(0), out, count, (size_t)nslots,
-                           FlaggedSlot{perm, flags}, stream);
+                           FlaggedSlot{perm, flags, win}, stream);
 }
 
 __global__ void __launch_bounds__(256)

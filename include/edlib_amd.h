@@ -87,6 +87,37 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(
     const char* targets, const long long* targetOffsets, int numTargets,
     EdlibAlignConfig config, int device);
 
+/* out[j] = C[in[n-1-j]]: the reverse complement of a nucleotide sequence.  C swaps A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H,
+ * sends U to A, and leaves S, W, N and every other byte as they are; lower case likewise (u -> a).  in and out must not
+ * overlap.  Host only, needs no device. */
+EDLIB_API void edlibAmdReverseComplement(const char* in, int n, char* out);
+
+/* As edlibAmdBatchCreateShared, but every query is searched on both strands: as itself and as its reverse complement
+ * (edlibAmdReverseComplement), which the library makes on the device.  With d+ / d- the two edit distances (-1: nothing
+ * within k), unit i reports
+ *   d+ >= 0 and (d- < 0 or d+ <= d-):  the forward result, every field; strand 0; bothStrands 1 iff d- == d+
+ *   otherwise, d- >= 0:                the result of the reverse complement, every field; strand 1; bothStrands 0
+ *   d+ == d- == -1:                    the forward result (distance -1, no locations); strand 0; bothStrands 0
+ * Ties go to the forward strand.  For strand 1 the locations are target coordinates of the alignment of the reverse
+ * complement, and the alignment's query is the reverse complement.  All modes and tasks, any k, additionalEqualities.
+ * Run / Results / ResultsFlat / ResultsView / CigarView / Stats / Destroy work as for a shared batch and report numQueries
+ * units; Stats.cells counts both strands.  Reads of up to 256 bases in HW mode (the read groups) stop climbing the
+ * threshold levels as soon as one strand has resolved: a batch whose reads each match on one strand costs about two
+ * single-strand steps, not the full-height scan of every wrong strand. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedBothStrands(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* target, int targetLength,
+    EdlibAlignConfig config, int device);
+
+/* Which strand every unit of the last Run of a both-strand batch reports.  Pinned memory the batch owns, valid until the
+ * next Run / Destroy; fails on any other kind of batch. */
+typedef struct {
+    int numUnits;
+    const unsigned char* strand;        /* [numUnits] 0 forward, 1 reverse complement                  */
+    const unsigned char* bothStrands;   /* [numUnits] 1: the other strand reaches the same distance    */
+} EdlibAmdStrandView;
+EDLIB_API int edlibAmdBatchStrandView(EdlibAmdBatch* batch, EdlibAmdStrandView* out);
+
 /* One pass of the device path over the resident batch (encode target, build
  * the query profiles, scan, merge; for LOC/PATH also start locations and
  * traceback), then wait for it.  Results stay on the device. */
