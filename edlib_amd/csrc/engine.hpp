@@ -48,6 +48,39 @@ struct SolveOut {
     std::vector<const uint8_t*> opsPtr;
     std::vector<int> opsLen;
     std::vector<std::shared_ptr<PinBuf>> opsBufs;
+    void reset(size_t n) {                // n units without an answer
+        score.assign(n, -1); count.assign(n, 0); last.assign(n, -1);
+        posStart.assign(n + 1, 0); posFlat.clear();
+        opsPtr.assign(n, nullptr); opsLen.assign(n, 0); opsBufs.clear();
+    }
+};
+
+// Units answered by several solves, put back in unit order: unit i takes entry q of `from` (score, count, last, its slice
+// of posFlat; no op strings), a unit nothing was taken for has no answer.  The SolveOuts outlive write().
+struct Assembler {
+    struct Pick { const SolveOut* from = nullptr; size_t q = 0; };
+    std::vector<Pick> pick;
+    explicit Assembler(size_t n) : pick(n) {}
+    void take(size_t i, const SolveOut& from, size_t q) { pick[i].from = &from; pick[i].q = q; }
+    void write(SolveOut& out) const {
+        out.reset(pick.size());
+        for (size_t i = 0; i < pick.size(); ++i) {
+            if (const SolveOut* p = pick[i].from) {
+                const size_t q = pick[i].q;
+                out.score[i] = p->score[q]; out.count[i] = p->count[q]; out.last[i] = p->last[q];
+                out.posFlat.insert(out.posFlat.end(), p->posFlat.begin() + p->posStart[q], p->posFlat.begin() + p->posStart[q + 1]);
+            }
+            out.posStart[i + 1] = (long long)out.posFlat.size();
+        }
+    }
+};
+
+// What the threshold ladder of banded semi-global units (Batch::solveBanded) leaves to the mode
+struct BandLadder {
+    int mode;
+    bool (*enter)(const UnitSpec& u, long long& K);                          // does the unit climb at all, and from which K
+    UnitSpec (*level)(const UnitSpec& u, long long K);                       // the unit as level K <= u.kinit scans it
+    bool (*final)(const UnitSpec& u, const UnitSpec& level, int score);      // is that level's answer the unit's
 };
 
 // Op string of one job: a view into a staging block, or an owned concatenation (Hirschberg pieces).
@@ -269,15 +302,12 @@ private:
     // k-doubling, edlib.cpp:197-217, with thresholds chosen for the hardware)
     // paths != null (TASK_PATH, every unit below the 1 MiB rule): the levels run with the column store and the traceback, so
     // that a unit's first successful level is also its path (one scan instead of the distance scan + the storing scan)
-    bool hwBandSplit_ = false;                   // solveSemiGlobal: the units its HW band does not take are on their way through it again
     int solveGlobalDistances(const std::vector<UnitSpec>& units, std::vector<int>& score, std::vector<OpsOut>* paths = nullptr);
     // SHW / HW units: short queries packed on 4- and 16-lane rings, the rest on the strips
     int solveSemiGlobal(int mode, bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out);
     int solveSemiGlobalUnits(int mode, bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out);
-    // SHW inside Ukkonen's band (edlib.cpp:562, 602-630): threshold levels like the NW distances, target cut at m + K
-    int solveShwBanded(bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out);
-    // HW inside the static band of a threshold: diagonals [-K, (T - m) + 2 K] (queries in windows not much longer than themselves)
-    int solveHwBanded(bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out);
+    // SHW / HW inside the band of a threshold: levels K, 4 K, 16 K ... like the NW distances, by the mode's BandLadder
+    int solveBanded(const BandLadder& ladder, bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out);
     // alphabetLength of the empty / pair units: launched on a side stream before phase 1, collected after it
     int alphabetLengthsBegin(hipEvent_t after = nullptr);      // after: the side stream also waits for this event
     bool alphaDeferred_ = false;
@@ -487,6 +517,7 @@ struct Lap {
 };
 
 // helpers shared by the translation units of the host side
+static inline bool switched_off(const char* v) { return v && v[0] == '0'; }      // an environment switch set to "0..."
 const int kMaxDevices = 16;                       // devices the process-wide caches and gates are kept for
 const int kPosCap = 16;                           // end positions kept beside a pair unit's results (longer lists: exact second pass)
 int peq_row_stride(long long nb);                 // row length of the LDS-resident Peq of the ring kernels

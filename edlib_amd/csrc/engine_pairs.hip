@@ -10,14 +10,13 @@
 #include <cmath>
 #include <condition_variable>
 #include <cstring>
+#include <deque>
 #include <mutex>
 #include <thread>
 
 namespace edlib_amd {
 
 // ------------------------------------------------------ block-per-lane path
-
-
 
 // Row length of the LDS-resident Peq of the ring kernels: the next power of two up to 32 blocks, a
 // multiple of 32 above (bank-conflict-free lookups, scan_pairs_ring_kernel)
@@ -60,9 +59,7 @@ int Batch::solve(int mode, bool wantPositions, bool wantPath, const std::vector<
                  int ring, int ringH)
 {
     const size_t n = units.size();
-    out.score.assign(n, -1); out.count.assign(n, 0); out.last.assign(n, -1);
-    out.posStart.assign(n + 1, 0); out.posFlat.clear();
-    out.opsPtr.assign(n, nullptr); out.opsLen.assign(n, 0); out.opsBufs.clear();
+    out.reset(n);
     if (n == 0) return 0;
     if (ring == kWide && wantPath) { set_error("the wide kernel keeps no column store"); return 1; }
     stats.path |= 2;
@@ -195,7 +192,7 @@ int Batch::solveChunk(int mode, bool wantPositions, bool wantPath, const std::ve
     a.tlut = d_tlut_.p; a.sigmaT = tab_.sigmaT; a.peq = d_peq64_.p; a.aux = d_aux_.p;
     a.peqRowStride = peq_row_stride(nbMax);
     a.peqFullStride = (int)std::min<long long>((long long)a.peqRowStride * tab_.sigmaT, 1 << 20);
-    if (getenv("EDLIB_AMD_PEQFULL") && getenv("EDLIB_AMD_PEQFULL")[0] == '0') a.peqFullStride = 0;
+    if (switched_off(getenv("EDLIB_AMD_PEQFULL"))) a.peqFullStride = 0;
     a.store = d_store_.p;
     a.outScore = d_outScore_.p; a.outCount = d_outCount_.p; a.outLast = d_outLast_.p; a.posPool = d_posPool_.p;
     a.colP = nullptr; a.colM = nullptr; a.colS = nullptr;
@@ -428,50 +425,81 @@ int Batch::checkWide()
 
 // ------------------------------------------------- semi-global units on rings
 
-// SHW / HW units of at most 4 (16) blocks share a wave 16 (4) at a time on the lane rings; longer ones take
-// the strips.  Same outputs as solve().
-// HW is shift-invariant (a scan that starts 2m-1 columns early from the fresh state reproduces the
-// exact bottom-row scores of its own columns), and a unit of kernel W is one wave's serial walk over its target: a
-// 1 kb query against a 5 Mb chromosome is 5M dependent steps (0.3 s) while 1023 SIMDs idle.  When a batch of HW units
-// does not fill the chip, every unit with a long target is cut into target segments (each a unit of its own with a
-// warm-up that records nothing: UnitSpec::skip) and the segments' answers are merged: minimum score, the end
-// locations of the segments that attain it in order, the last of them.  Results never depend on the cut.
+// SHW with a threshold: D[i][j] >= |i - j|, so a scan with threshold K only needs the diagonals [-K, K] and the first
+// m + K columns (the reference's band for SHW, edlib.cpp:562, 602-630, written for a fixed k).  A unit with a real
+// threshold (the reverse scans of HW start locations run with k = the distance, :253-257; calls with k >= 0) is scanned
+// inside that band once; an open unit (k = -1: threshold m) climbs levels K = 256, 1024, 4096 ... like the reference
+// doubles k (:197-217), exact as soon as some column scores <= K.  What it buys: the smallest ring that holds the BAND
+// instead of the query (a 10 kb reverse scan with k = 100: a 16-lane ring, four units per wave, instead of five 2048-row
+// strips), and m + K columns instead of 2 m.
+// HW with a threshold, as a STATIC band (the reference narrows HW with its first..lastBlock bookkeeping, block 0 kept
+// alive): an alignment of the whole query with cost <= K starts at a column j0 in [0, T - m + K] and stays within K
+// diagonals of j0, so only the diagonals [-K, (T - m) + 2 K] are needed -- (T - m) + 3 K + 1 rows per column instead of m.
+// That pays for a query in a window not much longer than itself (the verification step of a mapper: 1 kb in 1.2 kb at
+// k = 20 is 261 rows: an 8-lane ring, eight units per wave, instead of 16 lanes and four).  Levels K = 64, 256, 1024 ...;
+// one whose band is no narrower than the query is the plain scan at the unit's own threshold, which ends the climb.
+long long hw_band_rows(const UnitSpec& u, long long K) { return std::max(0, u.tlen - u.qlen) + 3 * K + 1; }
+// a level K pays while its band is at least a block narrower than the query
+static bool hw_band_narrow(const UnitSpec& u, long long K) { return hw_band_rows(u, K) + 64 <= 64LL * ((u.qlen + 63) / 64 - 1); }
+// a level K can only find a column when row m - 1 is inside its band somewhere: T >= m - K (else the last block never starts)
+static bool band_reaches(const UnitSpec& u, long long K) { return (long long)u.tlen >= (long long)u.qlen - K; }
+
+static const BandLadder kShwLadder = {
+    EDLIB_MODE_SHW,
+    [](const UnitSpec& u, long long& K) {      // a unit whose own threshold cannot reach row m - 1 has no answer (-1); levels that cannot are skipped
+        if (!band_reaches(u, std::min(u.kinit, u.qlen))) return false;
+        K = u.kinit < u.qlen ? u.kinit : 256;
+        while (K < u.kinit && !band_reaches(u, K)) K *= 4;
+        return true;
+    },
+    [](const UnitSpec& u, long long K) {
+        UnitSpec v = u;
+        v.kinit = (int)K; v.band = K < u.qlen ? 1 : 0; v.tlen = (int)std::min<long long>(u.tlen, (long long)u.qlen + K);
+        return v;
+    },
+    [](const UnitSpec& u, const UnitSpec& level, int score) { return score >= 0 || level.kinit >= u.kinit; },      // exact / the caller's own threshold found nothing
+};
+
+static const BandLadder kHwLadder = {
+    EDLIB_MODE_HW,
+    [](const UnitSpec& u, long long& K) { K = u.kinit < u.qlen ? u.kinit : 64; return true; },      // the caller's threshold, or the first level of an open unit
+    [](const UnitSpec& u, long long K) {
+        UnitSpec v = u;                        // (not banded: the plain scan at the unit's own threshold)
+        v.band = (K < u.kinit || u.kinit < u.qlen) && hw_band_narrow(u, K) && band_reaches(u, K) ? 1 : 0;
+        if (v.band) v.kinit = (int)K;
+        return v;
+    },
+    [](const UnitSpec& u, const UnitSpec& level, int score) { return !level.band || score >= 0 || level.kinit >= u.kinit; },      // plain / exact / the caller's own threshold found nothing
+};
+
+// Which SHW / HW unit goes where (nb = blocks of its query):
+//   1. SHW, some query of the batch above 4 blocks (up to 4 sit whole on the smallest ring whatever their threshold): every
+//      unit climbs kShwLadder                                                                (not with EDLIB_AMD_SHWBAND=0)
+//   2. HW, hw_band_narrow(u, min(kinit, 64)): the unit climbs kHwLadder -- the whole batch, or, of a mixed batch, the units
+//      that qualify; the others go on below, where long targets still get their segments    (not with EDLIB_AMD_HWBAND=0)
+//   3. HW, fewer than 4096 units: a target of at least 2 max(4096, 8 m) columns is cut into up to 8192 / n segments (each
+//      a unit with a warm-up of 2 m - 1 columns that records nothing: HW is shift-invariant), merged by
+//      minimum score; a 1 kb query against a 5 Mb target is otherwise one wave's 5M dependent steps while 1023 SIMDs idle
+//   4. every unit, ladder level or segment (solveSemiGlobalUnits): nb <= 4 / 8 / 16 on rings of 4 / 8 / 16 lanes, nb <= 32 /
+//      64 on 16 lanes of 2 / 4 blocks, more on the wide kernel; a banded unit on the smallest of those rings that holds the
+//      rows of its band (SHW 2 K + 1, HW hw_band_rows), else by nb; with EDLIB_AMD_NWBAND=0 the strips for nb <= 64
+// Same outputs as solve().  Results never depend on the route.
 int Batch::solveSemiGlobal(int mode, bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out)
 {
     const size_t n = units.size();
-    if (mode == EDLIB_MODE_SHW && n > 0 && !(getenv("EDLIB_AMD_SHWBAND") && getenv("EDLIB_AMD_SHWBAND")[0] == '0')) {
-        // (queries of up to four blocks sit whole on the smallest ring whatever their threshold: nothing to band)
-        bool any = false;
-        for (size_t i = 0; i < n && !any; ++i) any = units[i].qlen > 256;
-        if (any) return solveShwBanded(wantPositions, units, out);
-    }
-    if (mode == EDLIB_MODE_HW && n > 0 && !(getenv("EDLIB_AMD_HWBAND") && getenv("EDLIB_AMD_HWBAND")[0] == '0')) {
-        // a query in a window not much longer than itself, with a threshold well below its length: the band of solveHwBanded
-        // (only the units that qualify: the others keep the path below, which cuts long targets into segments when the batch
-        // alone does not fill the chip -- a narrow-window unit next to a few long-target ones used to pull those past it)
-        std::vector<char> qual(n);
-        size_t nq = 0;
-        for (size_t i = 0; i < n; ++i) { qual[i] = hw_band_rows(units[i], std::min(units[i].kinit, 64)) + 64 <= 64LL * ((units[i].qlen + 63) / 64 - 1); nq += qual[i]; }
-        if (nq == n) return solveHwBanded(wantPositions, units, out);
-        if (nq > 0 && !hwBandSplit_) {
-            std::vector<UnitSpec> part[2]; std::vector<size_t> where(n);
-            for (size_t i = 0; i < n; ++i) { where[i] = part[qual[i]].size(); part[qual[i]].push_back(units[i]); }
-            SolveOut so[2];
-            if (solveHwBanded(wantPositions, part[1], so[1])) return 1;
-            hwBandSplit_ = true;                                    // (the rest: this function again, without the band)
-            const int rc = solveSemiGlobal(mode, wantPositions, part[0], so[0]);
-            hwBandSplit_ = false;
-            if (rc) return 1;
-            out.score.resize(n); out.count.resize(n); out.last.resize(n);
-            out.posStart.assign(n + 1, 0); out.posFlat.clear();
-            out.opsPtr.assign(n, nullptr); out.opsLen.assign(n, 0); out.opsBufs.clear();
-            for (size_t i = 0; i < n; ++i) {
-                const SolveOut& p = so[qual[i]];
-                const size_t q = where[i];
-                out.score[i] = p.score[q]; out.count[i] = p.count[q]; out.last[i] = p.last[q];
-                out.posFlat.insert(out.posFlat.end(), p.posFlat.begin() + p.posStart[q], p.posFlat.begin() + p.posStart[q + 1]);
-                out.posStart[i + 1] = (long long)out.posFlat.size();
-            }
+    if (mode == EDLIB_MODE_SHW && !switched_off(getenv("EDLIB_AMD_SHWBAND")) &&
+        std::any_of(units.begin(), units.end(), [](const UnitSpec& u) { return u.qlen > 256; }))
+        return solveBanded(kShwLadder, wantPositions, units, out);
+    if (mode == EDLIB_MODE_HW && n > 0 && !switched_off(getenv("EDLIB_AMD_HWBAND"))) {
+        std::vector<unsigned char> qual(n); size_t nq = 0;
+        for (size_t i = 0; i < n; ++i) nq += qual[i] = hw_band_narrow(units[i], std::min(units[i].kinit, 64));
+        if (nq == n) return solveBanded(kHwLadder, wantPositions, units, out);
+        if (nq > 0) {
+            std::vector<UnitSpec> part[2]; SolveOut so[2]; Assembler all(n);
+            for (size_t i = 0; i < n; ++i) { all.take(i, so[qual[i]], part[qual[i]].size()); part[qual[i]].push_back(units[i]); }
+            // (the rest: this function again -- none of them qualifies, so on to the segments)
+            if (solveBanded(kHwLadder, wantPositions, part[1], so[1]) || solveSemiGlobal(mode, wantPositions, part[0], so[0])) return 1;
+            all.write(out);
             return 0;
         }
     }
@@ -498,9 +526,8 @@ int Batch::solveSemiGlobal(int mode, bool wantPositions, const std::vector<UnitS
     if (!any) return solveSemiGlobalUnits(mode, wantPositions, units, out);
     SolveOut so;
     if (solveSemiGlobalUnits(mode, wantPositions, sub, so)) return 1;
-    out.score.assign(n, -1); out.count.assign(n, 0); out.last.assign(n, -1);
-    out.posStart.assign(n + 1, 0); out.posFlat.clear();
-    out.opsPtr.assign(n, nullptr); out.opsLen.assign(n, 0); out.opsBufs.clear();
+    // minimum score over a unit's segments, the end locations of the segments that attain it in order, the last of them
+    out.reset(n);
     for (size_t i = 0; i < n; ++i) {
         int best = -1;
         for (int q = firstSeg[i]; q < firstSeg[i + 1]; ++q)
@@ -518,134 +545,36 @@ int Batch::solveSemiGlobal(int mode, bool wantPositions, const std::vector<UnitS
     return 0;
 }
 
-// SHW with a threshold: D[i][j] >= |i - j|, so a scan with threshold K only needs the diagonals [-K, K] and the first
-// m + K columns (the reference's band for SHW, edlib.cpp:562, 602-630, written for a fixed k).  A unit with a real
-// threshold (the reverse scans of HW start locations run with k = the distance, :253-257; calls with k >= 0) is scanned
-// inside that band once; an open unit (k = -1: threshold m) climbs levels K = 256, 1024, 4096 ... like the reference
-// doubles k (:197-217), the answer being exact as soon as some column scores <= K.  What it buys: the smallest ring that
-// holds the BAND instead of the whole query (a 10 kb reverse scan with k = 100 on an 8-lane... here 16-lane ring, four
-// units per wave, instead of five 2048-row strips), and m + K columns instead of 2 m.
-int Batch::solveShwBanded(bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out)
+// The levels of a ladder: every unit that enters is scanned at its K; one whose level is not final goes on to 4 K.
+int Batch::solveBanded(const BandLadder& ladder, bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out)
 {
     const size_t n = units.size();
-    out.score.assign(n, -1); out.count.assign(n, 0); out.last.assign(n, -1);
-    out.posStart.assign(n + 1, 0); out.posFlat.clear();
-    out.opsPtr.assign(n, nullptr); out.opsLen.assign(n, 0); out.opsBufs.clear();
-    std::vector<long long> kcur(n);
-    std::vector<std::vector<int>> posOf(wantPositions ? n : 0);
-    std::vector<size_t> rest;
-    // a level K can only find a column when row m-1 is inside its band somewhere: T >= m - K (else the kernels would never
-    // start the last block); levels that cannot are skipped, a unit whose own threshold cannot has no answer (-1)
-    auto reachable = [&](const UnitSpec& u, long long K) { return (long long)u.tlen >= (long long)u.qlen - K; };
-    for (size_t i = 0; i < n; ++i) {
-        const UnitSpec& u = units[i];
-        if (!reachable(u, std::min(u.kinit, u.qlen))) continue;
-        kcur[i] = u.kinit < u.qlen ? u.kinit : 256;
-        while (kcur[i] < u.kinit && !reachable(u, kcur[i])) kcur[i] *= 4;
-        rest.push_back(i);
-    }
+    std::vector<long long> kcur(n); std::vector<size_t> rest;
+    for (size_t i = 0; i < n; ++i) if (ladder.enter(units[i], kcur[i])) rest.push_back(i);
+    std::deque<SolveOut> levels; Assembler all(n);          // (a level's answers stay where they are until write())
     while (!rest.empty()) {
         std::vector<UnitSpec> sel; sel.reserve(rest.size());
-        for (size_t i : rest) {
-            UnitSpec u = units[i];
-            const long long K = std::min<long long>(kcur[i], u.kinit);
-            u.kinit = (int)K;
-            u.band = K < u.qlen ? 1 : 0;
-            u.tlen = (int)std::min<long long>(u.tlen, (long long)u.qlen + K);
-            sel.push_back(u);
-        }
-        SolveOut so;
-        if (solveSemiGlobalUnits(EDLIB_MODE_SHW, wantPositions, sel, so)) return 1;
+        for (size_t i : rest) sel.push_back(ladder.level(units[i], std::min<long long>(kcur[i], units[i].kinit)));
+        levels.emplace_back(); SolveOut& so = levels.back();
+        if (solveSemiGlobalUnits(ladder.mode, wantPositions, sel, so)) return 1;
         std::vector<size_t> again;
         for (size_t q = 0; q < sel.size(); ++q) {
             const size_t i = rest[q];
-            if (so.score[q] >= 0 || sel[q].kinit >= units[i].kinit) {          // exact / the caller's own threshold found nothing
-                out.score[i] = so.score[q]; out.count[i] = so.count[q]; out.last[i] = so.last[q];
-                if (wantPositions) posOf[i].assign(so.posFlat.begin() + so.posStart[q], so.posFlat.begin() + so.posStart[q + 1]);
-                continue;
-            }
-            kcur[i] = 4LL * sel[q].kinit;
-            again.push_back(i);
+            if (ladder.final(units[i], sel[q], so.score[q])) { all.take(i, so, q); continue; }
+            kcur[i] = 4LL * sel[q].kinit; again.push_back(i);
         }
         rest.swap(again);
     }
-    if (wantPositions)
-        for (size_t i = 0; i < n; ++i) {
-            out.posFlat.insert(out.posFlat.end(), posOf[i].begin(), posOf[i].end());
-            out.posStart[i + 1] = (long long)out.posFlat.size();
-        }
-    return 0;
-}
-
-// HW with a threshold, as a STATIC band (the reference narrows HW with its first..lastBlock bookkeeping, edlib.cpp:562,
-// 602-630, block 0 kept alive): an alignment of the whole query with cost <= K starts at a column j0 in [0, T - m + K] and
-// stays within K diagonals of j0, so only the diagonals [-K, (T - m) + 2 K] are needed -- (T - m) + 3 K + 1 rows per column
-// instead of m.  That pays for a query in a window not much longer than itself (the verification step of a mapper: 1 kb in
-// 1.2 kb at k = 20 is 261 rows: an 8-lane ring, eight units per wave, instead of 16 lanes and four).  A unit with a real
-// threshold is scanned inside it once; an open unit (k = -1: threshold m) climbs K = 64, 256, 1024 ... like the reference
-// doubles k (:197-217), exact as soon as some column scores <= K; a level whose band is no narrower than the query is
-// the plain scan, which ends the climb.  Units with long targets keep the plain path (target segments, the piece filter).
-long long hw_band_rows(const UnitSpec& u, long long K) { return std::max(0, u.tlen - u.qlen) + 3 * K + 1; }
-
-int Batch::solveHwBanded(bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out)
-{
-    const size_t n = units.size();
-    out.score.assign(n, -1); out.count.assign(n, 0); out.last.assign(n, -1);
-    out.posStart.assign(n + 1, 0); out.posFlat.clear();
-    out.opsPtr.assign(n, nullptr); out.opsLen.assign(n, 0); out.opsBufs.clear();
-    std::vector<long long> kcur(n);
-    std::vector<std::vector<int>> posOf(wantPositions ? n : 0);
-    std::vector<size_t> rest;
-    // a level K pays while its band is at least a block narrower than the query
-    auto narrow = [&](const UnitSpec& u, long long K) { return hw_band_rows(u, K) + 64 <= 64LL * ((u.qlen + 63) / 64 - 1); };
-    for (size_t i = 0; i < n; ++i) {
-        const UnitSpec& u = units[i];
-        kcur[i] = u.kinit < u.qlen ? u.kinit : 64;                    // the caller's threshold, or the first level of an open unit
-        rest.push_back(i);
-    }
-    while (!rest.empty()) {
-        std::vector<UnitSpec> sel; sel.reserve(rest.size());
-        for (size_t i : rest) {
-            UnitSpec u = units[i];
-            const long long K = std::min<long long>(kcur[i], u.kinit);
-            // (T < m - K: no alignment of cost <= K exists; the band would never reach row m - 1 -- the plain scan answers)
-            const bool banded = K < u.kinit || u.kinit < u.qlen ? (narrow(u, K) && (long long)u.tlen >= (long long)u.qlen - K) : false;
-            u.kinit = banded ? (int)K : units[i].kinit;
-            u.band = banded ? 1 : 0;
-            sel.push_back(u);
-        }
-        SolveOut so;
-        if (solveSemiGlobalUnits(EDLIB_MODE_HW, wantPositions, sel, so)) return 1;
-        std::vector<size_t> again;
-        for (size_t q = 0; q < sel.size(); ++q) {
-            const size_t i = rest[q];
-            if (!sel[q].band || so.score[q] >= 0 || sel[q].kinit >= units[i].kinit) {   // plain / exact / the caller's own threshold found nothing
-                out.score[i] = so.score[q]; out.count[i] = so.count[q]; out.last[i] = so.last[q];
-                if (wantPositions) posOf[i].assign(so.posFlat.begin() + so.posStart[q], so.posFlat.begin() + so.posStart[q + 1]);
-                continue;
-            }
-            kcur[i] = 4LL * sel[q].kinit;
-            again.push_back(i);
-        }
-        rest.swap(again);
-    }
-    if (wantPositions)
-        for (size_t i = 0; i < n; ++i) {
-            out.posFlat.insert(out.posFlat.end(), posOf[i].begin(), posOf[i].end());
-            out.posStart[i + 1] = (long long)out.posFlat.size();
-        }
+    all.write(out);
     return 0;
 }
 
 int Batch::solveSemiGlobalUnits(int mode, bool wantPositions, const std::vector<UnitSpec>& units, SolveOut& out)
 {
     const size_t n = units.size();
-    const bool ringsOff = getenv("EDLIB_AMD_NWBAND") && getenv("EDLIB_AMD_NWBAND")[0] == '0';
-    // units of up to 4 / 16 blocks on 4- / 16-lane rings, up to 32 / 64 blocks on 16-lane rings whose lanes hold 2 / 4
-    // blocks (four units per wave, every lane busy: a 1025-base query on the strips uses 17 of a wave's 64 lanes), the
-    // rest on the strips
-    // more than 64 blocks: the strips as a pipeline over many waves (wide_kernels.hip) instead of one wave walking them
-    // one after the other
+    const bool ringsOff = switched_off(getenv("EDLIB_AMD_NWBAND"));
+    // classes 0..4: rings (16 lanes of 2 / 4 blocks keep every lane busy: a 1025-base query on the strips uses 17 of a wave's
+    // 64 lanes); 5: the strips; 6: the strips as a pipeline over many waves instead of one wave walking them in turn
     static const int rings[7] = {4, 8, 16, 16, 16, 0, kWide}, ringH[7] = {1, 1, 1, 2, 4, 1, 1};
     const int NG = 7;
     std::vector<int> grp(n, 5);
@@ -669,24 +598,14 @@ int Batch::solveSemiGlobalUnits(int mode, bool wantPositions, const std::vector<
     }
     for (int g = 0; g < NG; ++g)
         if (cnt[g] == n) return solve(mode, wantPositions, false, units, out, rings[g], ringH[g]);   // the usual case: one kind
-    SolveOut part[NG];
-    std::vector<size_t> where(n);
+    SolveOut part[NG]; Assembler all(n);
     for (int g = 0; g < NG; ++g) {
         if (!cnt[g]) continue;
         std::vector<UnitSpec> sel; sel.reserve(cnt[g]);
-        for (size_t i = 0; i < n; ++i) if (grp[i] == g) { where[i] = sel.size(); sel.push_back(units[i]); }
+        for (size_t i = 0; i < n; ++i) if (grp[i] == g) { all.take(i, part[g], sel.size()); sel.push_back(units[i]); }
         if (solve(mode, wantPositions, false, sel, part[g], rings[g], ringH[g])) return 1;
     }
-    out.score.resize(n); out.count.resize(n); out.last.resize(n);
-    out.posStart.assign(n + 1, 0); out.posFlat.clear();
-    out.opsPtr.assign(n, nullptr); out.opsLen.assign(n, 0); out.opsBufs.clear();
-    for (size_t i = 0; i < n; ++i) {
-        const SolveOut& p = part[grp[i]];
-        const size_t q = where[i];
-        out.score[i] = p.score[q]; out.count[i] = p.count[q]; out.last[i] = p.last[q];
-        out.posFlat.insert(out.posFlat.end(), p.posFlat.begin() + p.posStart[q], p.posFlat.begin() + p.posStart[q + 1]);
-        out.posStart[i + 1] = (long long)out.posFlat.size();
-    }
+    all.write(out);
     return 0;
 }
 
@@ -758,7 +677,7 @@ int Batch::runLevelAll(const std::vector<UnitSpec>& units, int ring, int ringH, 
     a.tlut = d_tlut_.p; a.sigmaT = tab_.sigmaT; a.peq = d_peqAll_.p; a.aux = d_aux_.p;
     a.peqRowStride = peq_row_stride(nbMax);
     a.peqFullStride = (int)std::min<long long>((long long)a.peqRowStride * tab_.sigmaT, 1 << 20);
-    if (getenv("EDLIB_AMD_PEQFULL") && getenv("EDLIB_AMD_PEQFULL")[0] == '0') a.peqFullStride = 0;      // (as solveChunk)
+    if (switched_off(getenv("EDLIB_AMD_PEQFULL"))) a.peqFullStride = 0;      // (as solveChunk)
     a.outScore = d_outScore_.p; a.outCount = d_outCount_.p; a.outLast = d_outLast_.p; a.posPool = d_posPool_.p;
     a.wordSteps = ringStepsCounter();
     scanTimerStart();
@@ -875,7 +794,7 @@ int Batch::solveGlobalDistances(const std::vector<UnitSpec>& units, std::vector<
     score.assign(n, -1);
     if (paths) { paths->clear(); paths->resize(n); }
     if (n == 0) return 0;
-    const bool bandOff = getenv("EDLIB_AMD_NWBAND") && getenv("EDLIB_AMD_NWBAND")[0] == '0';
+    const bool bandOff = switched_off(getenv("EDLIB_AMD_NWBAND"));
     // ring levels (lanes, blocks per lane); level nl = unbanded strips.  Rings whose lanes hold 2 / 4 blocks (16 x 2: four
     // units per wave, DPP carry) were measured here in round 3 and lost: a ring computes ALL its rows every step, and
     // 16 x 2 = 2048 rows for a band that needs ~1300 is 52 % more block updates than the 21-lane ring's 1344, which the
@@ -914,7 +833,7 @@ int Batch::solveGlobalDistances(const std::vector<UnitSpec>& units, std::vector<
         // (only for units of like lengths: a level takes every unit when the batch's extremes land on the same ring)
         const bool bigAlike = paths == nullptr && n >= 8192 && &units == &pairSpecs_ && 4LL * shape.minLenHi <= 5LL * shape.minLenLo;
         // four target symbols at most: the lane-per-pair level (a lane owns a unit; prepareLaneLevel); else the rings
-        const bool laneOff = getenv("EDLIB_AMD_LANEPAIR") && getenv("EDLIB_AMD_LANEPAIR")[0] == '0';
+        const bool laneOff = switched_off(getenv("EDLIB_AMD_LANEPAIR"));
         if (bigAlike && !laneOff && prepareLaneLevel(units)) return 1;
         if (bigAlike && !laneReady_ && prepareLevelAll(units)) return 1;
         // 64 strided units, the first 512 bases of the query against the first 512 + 128 of the target in PREFIX mode

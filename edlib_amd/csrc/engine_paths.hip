@@ -34,7 +34,7 @@ int Batch::hirschbergLevel(const std::vector<PathPiece>& big, std::vector<int>& 
     // (packing only pays with enough pieces to fill the chip: a handful of long pieces runs faster one per wave)
     const bool packed = np >= 256;
     auto ring_of = [&](const PathPiece& pc) {
-        const bool off = getenv("EDLIB_AMD_NWBAND") && getenv("EDLIB_AMD_NWBAND")[0] == '0';
+        const bool off = switched_off(getenv("EDLIB_AMD_NWBAND"));
         if (off) return kNumRings;
         // (a few long pieces are bound by dependent steps: 0.074 us on the wide kernel's waves against 0.12 on a ring's)
         if (!packed) return (pc.m > 64 * 64 && pc.score <= kMaxBandK && pc.T < 4096) ? kNumRings - 1 : kNumRings;
@@ -293,7 +293,7 @@ int Batch::solvePaths(const std::vector<PathPiece>& jobs, std::vector<OpsOut>& o
     // smallest ring that holds the band (or all blocks) of each leaf; strips when none does
     std::vector<const uint8_t*> leafPtr(units.size(), nullptr); std::vector<int> leafLen(units.size(), 0);
     {
-        const bool bandOff = getenv("EDLIB_AMD_NWBAND") && getenv("EDLIB_AMD_NWBAND")[0] == '0';
+        const bool bandOff = switched_off(getenv("EDLIB_AMD_NWBAND"));
         static const int rings[kNumRings + 1] = {4, 8, 16, 21, 32, 64, 0};
         std::vector<int> ringOfUnit(units.size(), 0);
         for (size_t u = 0; u < units.size(); ++u) {

@@ -486,7 +486,7 @@ struct OneCtx {
 // 0 = answered in *out, 1 = error (last_error set), 2 = not handled here (the caller takes the general path)
 int align_one_fused(const char* q, int m, const char* t, int T, EdlibAlignConfig cfg, EdlibAlignResult* out)
 {
-    static const bool enabled = !(getenv("EDLIB_AMD_ONEPAIR") && getenv("EDLIB_AMD_ONEPAIR")[0] == '0');
+    static const bool enabled = !switched_off(getenv("EDLIB_AMD_ONEPAIR"));
     if (!enabled || m < 1 || T < 1 || m > kOneMaxQ || T > kOneMaxT) return 2;
     if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0) return 2;
     const int mode = (int)cfg.mode, task = (int)cfg.task;

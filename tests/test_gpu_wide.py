@@ -266,7 +266,7 @@ def test_wide_rerun_with_one_slot_after_a_launch_that_is_not_resident(engine, ch
 
 def test_hw_inside_the_band_of_a_threshold(engine, checker):
     """HW pair units whose window is not much longer than the query, inside the static band [-K, (T - m) + 2 K]
-    (Batch::solveHwBanded): fixed k below / at / above the distance, open units (levels 64, 256, ...), queries from
+    (Batch::solveBanded with kHwLadder): fixed k below / at / above the distance, open units (levels 64, 256, ...), queries from
     5 blocks (an 8-lane ring holds them whole) to beyond 64 blocks (the wide kernel inside the band), equal hits at
     both ends of the window, targets shorter than m - k, unrelated pairs; the same answers with EDLIB_AMD_HWBAND=0;
     and the band is what runs: fewer word-steps than the whole matrix."""
@@ -327,3 +327,28 @@ def test_banded_units_with_overflowing_end_location_lists(engine, checker):
         for mode in ("HW", "SHW"):
             for k in (-1, 5):
                 _check(engine, checker, [q, q[:3000]], [t, t], mode, "locations", k, "periodic target m=%d" % m)
+
+
+def test_results_assembled_from_several_solves_keep_unit_order(engine, checker):
+    """seven units whose answers come from different solves and are put back in unit order (Assembler): one query in each
+    ring class (up to 4, 8, 16, 32, 64 blocks, beyond 64), interleaved, against a periodic target, so that the slices of
+    the end-location list differ in length, with an unrelated query in the middle whose slice is empty at a small k.
+    Band switches at their defaults: the threshold ladders and, for HW, the split of a mixed batch; switched off: the
+    class partition directly; rings off: strips and the wide kernel."""
+    period = (synth.random_dna(43, 331).tobytes()) * 20
+    t = period[:6000]
+    qs = [period[a:a + m] for m, a in ((3500, 2), (200, 0), (4200, 100))]
+    qs.append(synth.random_dna(44, 900).tobytes())                                     # unrelated
+    qs += [period[a:a + m] for m, a in ((400, 3), (1800, 40), (900, 0))]
+    ts = [t] * len(qs)
+    open_hw = [checker.align(q, t, "HW", "locations", -1) for q in qs]
+    assert sum(w["numLocations"] > 1 for w in open_hw) >= 3, [w["numLocations"] for w in open_hw]
+    assert all(checker.align(qs[3], t, mode, "locations", 5)["editDistance"] == -1 for mode in ("HW", "SHW"))
+    for off in (None, "0"):
+        with _env(EDLIB_AMD_HWBAND=off, EDLIB_AMD_SHWBAND=off):
+            for mode in ("HW", "SHW"):
+                for k in (-1, 5):
+                    _check(engine, checker, qs, ts, mode, "locations", k, "assembled, band switches %s" % off)
+    with _env(EDLIB_AMD_NWBAND="0"):
+        for mode in ("HW", "SHW"):
+            _check(engine, checker, qs, ts, mode, "locations", -1, "assembled, rings off")

@@ -138,7 +138,7 @@ def test_lane_by_lane_ring_with_bands_of_a_few_diagonals():
 
 @pytest.mark.parametrize("G", [4, 8])
 def test_lane_by_lane_ring_inside_a_static_prefix_band(oracle, G):
-    """SHW with a fixed k runs inside the static band [-K, K] (2 K + 1 diagonals: Batch::solveShwBanded); K = ring_max_k(G) / 2
+    """SHW with a fixed k runs inside the static band [-K, K] (2 K + 1 diagonals: Batch::solveBanded with kShwLadder); K = ring_max_k(G) / 2
     fills the ring.  The cheapest prefix alignment skips K target symbols and stays on the band's upper edge: the best
     bottom-row score the lanes see is the reference's SHW distance when that is <= K, and nothing <= K otherwise."""
     rng = random.Random(950 + G)

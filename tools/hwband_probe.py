@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""HW pair units inside the static band (Batch::solveHwBanded): one case per subprocess, so that a device fault names its case.
+"""HW pair units inside the static band (Batch::solveBanded with kHwLadder): one case per subprocess, so that a device fault names its case.
 usage: hwband_probe.py            (the list below)
        hwband_probe.py m T k seed (one case; prints OK / MISMATCH)"""
 import os, subprocess, sys
