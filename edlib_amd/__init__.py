@@ -4,7 +4,7 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 ``getNiceAlignment()`` have the same arguments, defaults, result dictionary and
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
-``align_batch()`` / ``align_pairs()`` / ``align_cross()``, ``reverse_complement()`` and the resident
+``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``find_all()``, ``reverse_complement()`` and the resident
 ``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` sessions over include/edlib_amd.h.
 
 There is no CPU path in here: everything calls ``libedlib.so`` (built by
@@ -71,6 +71,11 @@ class CrossHits(C.Structure):            # edlib_amd.h EdlibAmdCrossHits
         (f, C.POINTER(C.c_int)) for f in ("query", "editDistance", "numLocations", "endLocation")]
 
 
+class ReadHits(C.Structure):             # edlib_amd.h EdlibAmdReadHits
+    _fields_ = [("numUnits", C.c_int), ("numHits", C.c_longlong), ("unitOffsets", C.POINTER(C.c_longlong))] + [
+        (f, C.POINTER(C.c_int)) for f in ("firstEnd", "lastEnd", "editDistance", "endLocation", "numLocations")]
+
+
 class StrandView(C.Structure):           # edlib_amd.h EdlibAmdStrandView
     _fields_ = [("numUnits", C.c_int), ("strand", C.POINTER(C.c_ubyte)), ("bothStrands", C.POINTER(C.c_ubyte))]
 
@@ -106,6 +111,9 @@ def lib():
         L.edlibAmdBatchCreateSharedBothStrands.restype = C.c_void_p
         L.edlibAmdBatchCreateSharedBothStrands.argtypes = L.edlibAmdBatchCreateShared.argtypes
         L.edlibAmdBatchStrandView.argtypes = [C.c_void_p, C.POINTER(StrandView)]
+        L.edlibAmdBatchCreateSharedHits.restype = C.c_void_p
+        L.edlibAmdBatchCreateSharedHits.argtypes = L.edlibAmdBatchCreateShared.argtypes
+        L.edlibAmdBatchSharedHits.argtypes = [C.c_void_p, C.POINTER(ReadHits)]
         L.edlibAmdReverseComplement.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.edlibAmdReverseComplement.restype = None
         L.edlibAmdBatchCreatePairs.restype = C.c_void_p
@@ -442,17 +450,52 @@ class _Batch:
 
 
 class SharedBatch(_Batch):
-    """Many queries against one target (the loop of apps/aligner/aligner.cpp:162-225)."""
+    """Many queries against one target (the loop of apps/aligner/aligner.cpp:162-225).
+    hits=True (edlibAmdBatchCreateSharedHits; HW, distance, k >= 0, reads up to 256 bases): hits() lists, per read, every
+    maximal run of target columns that end an occurrence within k; results() is not available."""
 
-    def __init__(self, queries, target, mode="HW", task="distance", k=-1, additionalEqualities=None, device=0):
+    is_hits = False
+
+    def __init__(self, queries, target, mode="HW", task="distance", k=-1, additionalEqualities=None, device=0, hits=False):
         qd, qo = _pack(queries)
         t = np.frombuffer(target, dtype=np.uint8) if isinstance(target, (bytes, bytearray)) else np.asarray(target, dtype=np.uint8)
         t = np.ascontiguousarray(t) if len(t) else np.zeros(1, dtype=np.uint8)
         tlen = len(target)
         cfg, keep = _make_config(mode, task, k, additionalEqualities)
-        h = lib().edlibAmdBatchCreateShared(qd.ctypes.data, qo.ctypes.data, len(qo) - 1,
-                                            t.ctypes.data, tlen, cfg, device)
+        self.is_hits = bool(hits)
+        create = lib().edlibAmdBatchCreateSharedHits if hits else lib().edlibAmdBatchCreateShared
+        h = create(qd.ctypes.data, qo.ctypes.data, len(qo) - 1, t.ctypes.data, tlen, cfg, device)
         super().__init__(h, len(qo) - 1, keep)
+
+    def hits(self, copy=True):
+        """The hits of a hits=True batch, grouped by read in the caller's order (CSR), ascending firstEnd inside a read:
+        unitOffsets int64 [n + 1] (read i: [unitOffsets[i], unitOffsets[i + 1])) and firstEnd / lastEnd / editDistance /
+        endLocation / numLocations int32 [numHits], plus numHits.  copy=False: views of the batch's pinned memory, valid
+        until its next run() / close()."""
+        if not self.is_hits:
+            raise RuntimeError("edlib_amd: not a hit-list batch: create it with hits=True (a plain batch has results())")
+        v = ReadHits()
+        if lib().edlibAmdBatchSharedHits(self._h, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: read hits failed: " + last_error())
+        n = int(v.numHits)
+        off = np.ctypeslib.as_array(v.unitOffsets, shape=(self.n + 1,))
+        out = {"numHits": n, "unitOffsets": off.copy() if copy else off}
+        for f in ("firstEnd", "lastEnd", "editDistance", "endLocation", "numLocations"):
+            a = np.ctypeslib.as_array(getattr(v, f), shape=(n,)) if n else np.zeros(0, dtype=np.int32)
+            out[f] = a.copy() if copy and n else a
+        return out
+
+    def _no_results(self, *a, **kw):
+        raise RuntimeError("edlib_amd: a hit-list batch has no per-read results: use hits()")
+
+    def results(self, raw=True):
+        return self._no_results() if self.is_hits else super().results(raw)
+
+    def results_flat(self, copy=True):
+        return self._no_results() if self.is_hits else super().results_flat(copy)
+
+    def cigars(self, extended=True, copy=True):
+        return self._no_results() if self.is_hits else super().cigars(extended, copy)
 
 
 class BothStrandsBatch(_Batch):
@@ -577,6 +620,18 @@ def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hi
         out = b.hits() if hits else b.matrix()
         out.update(b.best())
         return out
+    finally:
+        b.close()
+
+
+def find_all(queries, target, k, additionalEqualities=None):
+    """Every occurrence of every query within k edits along the target, in one device batch: the hits() arrays of
+    SharedBatch(..., hits=True) -- the loop ``for q in queries: every window of target within k of q`` that adapter /
+    primer trimming and multi-mapping searches run."""
+    b = SharedBatch(queries, target, "HW", "distance", k, additionalEqualities, hits=True)
+    try:
+        b.run()
+        return b.hits()
     finally:
         b.close()
 

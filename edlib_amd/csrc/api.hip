@@ -24,6 +24,12 @@ static int not_on_cross(EdlibAmdBatch* b, const char* what) {
     return 1;
 }
 
+static int not_on_hits(EdlibAmdBatch* b, const char* what) {
+    if (b->cross || !b->impl.isHits()) return 0;
+    set_error("%s: not available on a hit-list read batch (edlibAmdBatchSharedHits has its results)", what);
+    return 1;
+}
+
 static void fail_loudly(const char* where) {
     fprintf(stderr, "edlib (MI355X engine): %s failed: %s\n", where, last_error().c_str());
 }
@@ -167,9 +173,33 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedBothStrands(const char* querie
     return b;
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedHits(const char* queries, const long long* queryOffsets, int numQueries,
+                                                       const char* target, int targetLength, EdlibAlignConfig config,
+                                                       int device) {
+    const char* where = "edlibAmdBatchCreateSharedHits";
+    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
+    if (!b) return nullptr;
+    const long long toff[2] = {0, targetLength};
+    const int rc = targetLength < 0 ? 1 : guarded(where, 1, [&] {
+        return b->impl.init(queries, queryOffsets, numQueries, target, toff, 1, config, device, /*bothStrands=*/false,
+                            /*hits=*/true); });
+    if (targetLength < 0) set_error("negative target length");
+    if (rc) {
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* b, EdlibAmdReadHits* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (b->cross) { set_error("edlibAmdBatchSharedHits: not a hit-list read batch (a cross batch has edlibAmdBatchCrossHits)"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchSharedHits", 1, [&] { return b->impl.hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchStrandView(EdlibAmdBatch* b, EdlibAmdStrandView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_cross(b, "edlibAmdBatchStrandView")) return EDLIB_STATUS_ERROR;
+    if (not_on_cross(b, "edlibAmdBatchStrandView") || not_on_hits(b, "edlibAmdBatchStrandView")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchStrandView", 1, [&] { return b->impl.strandView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
@@ -228,7 +258,7 @@ EDLIB_API int edlibAmdBatchRun(EdlibAmdBatch* b) {
 
 EDLIB_API int edlibAmdBatchResults(EdlibAmdBatch* b, EdlibAlignResult* results) {
     if (!b || !results) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_cross(b, "edlibAmdBatchResults")) return EDLIB_STATUS_ERROR;
+    if (not_on_cross(b, "edlibAmdBatchResults") || not_on_hits(b, "edlibAmdBatchResults")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchResults", 1, [&] { return b->impl.results(results); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
@@ -236,7 +266,7 @@ EDLIB_API int edlibAmdBatchResultsFlat(EdlibAmdBatch* b, int* status, int* editD
                                        int* alphabetLength, long long* locOffsets, int** endLocations,
                                        int** startLocations, long long* alnOffsets, unsigned char** alignment) {
     if (!b) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_cross(b, "edlibAmdBatchResultsFlat")) return EDLIB_STATUS_ERROR;
+    if (not_on_cross(b, "edlibAmdBatchResultsFlat") || not_on_hits(b, "edlibAmdBatchResultsFlat")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchResultsFlat", 1, [&] {
                return b->impl.resultsFlat(status, editDistance, numLocations, alphabetLength, locOffsets, endLocations,
                                           startLocations, alnOffsets, alignment); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
@@ -244,13 +274,13 @@ EDLIB_API int edlibAmdBatchResultsFlat(EdlibAmdBatch* b, int* status, int* editD
 
 EDLIB_API int edlibAmdBatchResultsView(EdlibAmdBatch* b, EdlibAmdResultsView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_cross(b, "edlibAmdBatchResultsView")) return EDLIB_STATUS_ERROR;
+    if (not_on_cross(b, "edlibAmdBatchResultsView") || not_on_hits(b, "edlibAmdBatchResultsView")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchResultsView", 1, [&] { return b->impl.resultsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchCigarView(EdlibAmdBatch* b, EdlibCigarFormat cigarFormat, const char** chars, const long long** offsets) {
     if (!b) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_cross(b, "edlibAmdBatchCigarView")) return EDLIB_STATUS_ERROR;
+    if (not_on_cross(b, "edlibAmdBatchCigarView") || not_on_hits(b, "edlibAmdBatchCigarView")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchCigarView", 1, [&] { return b->impl.cigarView((int)cigarFormat, chars, offsets); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 

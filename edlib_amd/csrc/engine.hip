@@ -212,9 +212,29 @@ Batch::~Batch() {
 int roundup(int x, int q) { return (x + q - 1) / q * q; }
 
 int Batch::init(const char* queries, const long long* qoff, int n, const char* targets,
-                const long long* toff, int numTargets, EdlibAlignConfig cfg, int device, bool bothStrands)
+                const long long* toff, int numTargets, EdlibAlignConfig cfg, int device, bool bothStrands, bool hits)
 {
     if (n < 0 || (numTargets != 1 && numTargets != n)) { set_error("bad batch shape"); return 1; }
+    if (hits) {
+        // what a hit-list read batch takes (edlib_amd.h): everything else is refused with the limit named
+        if (numTargets != 1 || bothStrands) { set_error("hit-list read batch: one shared target, one strand"); return 1; }
+        if (cfg.mode != EDLIB_MODE_HW) { set_error("hit-list read batch: config.mode must be EDLIB_MODE_HW (SHW and NW have no hit list)"); return 1; }
+        if (cfg.task != EDLIB_TASK_DISTANCE) {
+            set_error("hit-list read batch: config.task must be EDLIB_TASK_DISTANCE (start locations and paths: align the chosen windows with a pair batch)");
+            return 1;
+        }
+        if (cfg.k < 0) { set_error("hit-list read batch: config.k must be >= 0 (got %d)", cfg.k); return 1; }
+        for (int u = 0; u < n; ++u)
+            if (qoff[u + 1] - qoff[u] > 32LL * kMaxReadWords) {
+                set_error("hit-list read batch: read %d has %lld bases, the limit is %d", u, qoff[u + 1] - qoff[u], 32 * kMaxReadWords);
+                return 1;
+            }
+        bool seen[256] = {false};
+        int sigma = 0;
+        for (long long j = toff[0]; j < toff[1]; ++j) if (!seen[(uint8_t)targets[j]]) { seen[(uint8_t)targets[j]] = true; ++sigma; }
+        if (sigma > 16) { set_error("hit-list read batch: the target has %d distinct symbols, the limit is 16", sigma); return 1; }
+    }
+    hits_ = hits;
     if (bothStrands && (numTargets != 1 || n > 0x3fffffff)) { set_error("bad both-strand batch shape"); return 1; }
     const int ndev = device_count();
     if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
@@ -598,6 +618,7 @@ int Batch::runImpl()
     stats = EdlibAmdBatchStats{};
     stats.cells = cells;
     scanEventsUsed_ = 0;
+    if (hits_) return runReadHits();
     hostStrandCounts_[0] = hostStrandCounts_[1] = hostStrandCounts_[2] = hostStrandCounts_[3] = 0;
     haveResults_ = false;
     opsKeep_.clear();            // (the previous run's views die with the reset of their records below)

@@ -153,7 +153,8 @@ public:
     // sequences are copied to the device here; nothing of the caller's memory is retained
     int init(const char* queries, const long long* qoff, int n,
              const char* targets, const long long* toff, int numTargets,   // numTargets == 1: shared
-             EdlibAlignConfig cfg, int device, bool bothStrands = false);   // bothStrands (shared only): n reads, 2n units
+             EdlibAlignConfig cfg, int device, bool bothStrands = false,    // bothStrands (shared only): n reads, 2n units
+             bool hits = false);                                            // hits (shared only): a hit-list read batch
     int run();
     int runImpl();
     int results(EdlibAlignResult* out);
@@ -162,6 +163,8 @@ public:
     int resultsView(EdlibAmdResultsView* out);
     int cigarView(int format, const char** chars, const long long** offsets);
     int strandView(EdlibAmdStrandView* out);
+    int hitsView(EdlibAmdReadHits* out);
+    bool isHits() const { return hits_; }
     EdlibAmdBatchStats stats{};
     void finishStats();          // fills the fields of `stats` that cost a walk over the records (algo_bytes)
 
@@ -243,6 +246,25 @@ private:
     int runSeedPass(ReadGroup& g, int k);                         // pass 1 at threshold k, hand-backs through the banded kernel
     DevBuf<uint32_t> d_seedCnt_, d_seedOff_, d_seedPos_;          // [4^12 + 1] counts, [4^12 + 1] bucket offsets, [T] positions
     DevBuf<uint8_t> d_seedTmp_;                                   // rocPRIM scan scratch
+    // ---- hit-list read batches (reads_hits.hip): every maximal run of columns scoring <= k, HW / DISTANCE,
+    // reads up to 256 bases.  A Run is Peq rows, the HITS scans of every group (seeded where seedThreshold() allows k), and the
+    // finish on the device; nothing else of runImpl() runs.  The list starts at max(2^20, n_) runs and grows to the count of
+    // a Run that overflowed it (that Run scans again).
+    bool hits_ = false, hitsHaveRun_ = false, hitsFetched_ = false;
+    long long hitCap_ = 0, numHits_ = 0;
+    int hitSlots_ = 0;                                            // slots of all groups, then one per empty unit
+    DevBuf<int> d_hitSlotUnit_;                                   // [hitSlots_] slot -> unit, -1 = padding
+    DevBuf<unsigned long long> d_hitCount_, d_hitKey_, d_hitSkey_;
+    DevBuf<int> d_hitVal_, d_hitUnit_;
+    DevBuf<uint32_t> d_hitIdx_, d_hitSidx_, d_hitHead_, d_hitAt_;
+    DevBuf<long long> d_hitTotal_;
+    DevBuf<uint8_t> d_hitTmp_, d_hitOut_;
+    PinBuf h_hitCount_, h_hits_;
+    std::vector<unsigned long long> hostHitKey_; std::vector<int> hostHitVal_;   // the empty reads' hits, answered on the host
+    int growHitList(long long cap);
+    int runReadHits();                                            // the whole Run of such a batch
+    int scanGroupHits(ReadGroup& g, int slotBase);                // one group's runs appended to the list
+    int hitsScanBanded(ReadGroup& g, int slotBase, const int* d_slotmap, int nlanes, int numSegments, int segLen, int warm);
     // ---- long HW queries: piece filter on the reads-per-lane kernel + window verification on kernel W (long_reads.hip)
     struct Piece { long long off; int len; int thr; };           // rows [off, off + len) of the query pool, threshold of its scan
     int scanPieces(const std::vector<Piece>& pieces, bool filter, std::vector<std::pair<int, int>>* cand,

@@ -364,7 +364,31 @@ static_assert(band_height_up<10>(8) == 10 && band_height_down<10>(10) <= 10 - 2 
 struct HwTrack {            // per-lane tracking state of the banded kernel
     int best, cnt, cap;
     int* pos;
+    // HITS instantiation only: the lane's slot, the list, and the open run of columns scoring <= best (rLast < 0: none) --
+    // its first and last column, its least score, the first column holding that score and how many columns hold it
+    int slot, rFirst, rLast, rMin, rPos, rCnt;
+    HitList hl;
 };
+
+// Appends the run of every lane with `emit` to the hit list: one atomic per wave (ballot / mbcnt, as the seed kernel's hand-back
+// list), among the lanes that are active at the call.  Entries past the capacity are counted, not written.
+__device__ __forceinline__ void hit_append(const HitList& h, const bool emit, const int slot, const int first, const int last,
+                                           const int ed, const int pos, const int cnt)
+{
+    typedef unsigned long long u64;
+    const u64 bal = __builtin_amdgcn_ballot_w64(emit);
+    if (!bal) return;
+    const int lead = __builtin_ctzll(bal);
+    const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+    u64 base = 0;
+    if (emit && rank == 0) base = atomicAdd(h.count, (u64)__popcll(bal));
+    base = ((u64)(u32)__builtin_amdgcn_readlane((int)(base >> 32), lead) << 32) | (u32)__builtin_amdgcn_readlane((int)base, lead);
+    const u64 at = base + rank;
+    if (emit && at < (u64)h.cap) {
+        h.key[at] = ((u64)(u32)(h.slotBase + slot) << 32) | (u32)first;
+        h.val[at] = last; h.val[h.cap + at] = ed; h.val[2 * h.cap + at] = pos; h.val[3 * h.cap + at] = cnt;
+    }
+}
 
 // Rows carried from quad to quad by the one-word band (the next quad's rows, already in registers); local to a run
 // of that band height (nothing of it is live at any other height).
@@ -384,7 +408,10 @@ typedef u32 QuadRows[4];
 // like the reference's new block (edlib.cpp:605-608).
 // FILTER (the piece filter of long reads, long_reads.hip; its own instantiation, so that the scans of whole reads carry none of
 // it): the threshold stays where it is and the lane lists the 16-column blocks that hold a column scoring <= best, each once.
-template <int NA, int NWD, int Q, int S, bool CHECK = true, bool CHAIN = false, bool FILTER = false>
+// HITS (hit-list read batches, reads_hits.hip): the threshold stays where it is as well, and the lane follows the maximal runs
+// of consecutive columns scoring <= best: a column next to the open run extends it, any other closes it (hit_append) and
+// opens a new one; the kernel closes the last run at the end of the lane's segment.
+template <int NA, int NWD, int Q, int S, bool CHECK = true, bool CHAIN = false, bool FILTER = false, bool HITS = false>
 __device__ __forceinline__ int band_quad(const u32 lo, const u32 hi, const u32 nlo, const u32 nhi, QuadRows& qr,
                                          const int colBase, const int colEnd, const bool track, u32 (&Pv)[NWD],
                                          u32 (&Mv)[NWD], int& e, int& flag, HwTrack& tr, const u32 sh, const int lastRows,
@@ -426,7 +453,23 @@ __device__ __forceinline__ int band_quad(const u32 lo, const u32 hi, const u32 n
             if (fresh && tr.cnt < tr.cap) tr.pos[tr.cnt] = blk;
             tr.cnt += fresh ? 1 : 0;
             flag = 0;                                                   // e stays relative to the fixed threshold
-        } else if (!FILTER && track && __builtin_amdgcn_ballot_w64(flag < 0) != 0ull) {   // wave-uniform
+        } else if (HITS && track && __builtin_amdgcn_ballot_w64(flag < 0) != 0ull) {      // wave-uniform
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int col = colBase + j;
+                const int sc = eh[j] + tr.best + 1;
+                const bool hit = eh[j] < 0 && col < colEnd && tr.cap > 0;   // (cap 0: a lane past nlanes owns no slot)
+                const bool ext = hit && col == tr.rLast + 1, fresh = hit && !ext;
+                hit_append(tr.hl, fresh && tr.rLast >= 0, tr.slot, tr.rFirst, tr.rLast, tr.rMin, tr.rPos, tr.rCnt);
+                const bool better = fresh || (ext && sc < tr.rMin);
+                tr.rFirst = fresh ? col : tr.rFirst;
+                tr.rLast = hit ? col : tr.rLast;
+                tr.rCnt = better ? 1 : tr.rCnt + ((ext && sc == tr.rMin) ? 1 : 0);
+                tr.rPos = better ? col : tr.rPos;
+                tr.rMin = better ? sc : tr.rMin;
+            }
+            flag = 0;                                                   // e stays relative to the fixed threshold
+        } else if (!FILTER && !HITS && track && __builtin_amdgcn_ballot_w64(flag < 0) != 0ull) {   // wave-uniform
             const int bestIn = tr.best;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -516,7 +559,7 @@ typedef u32 u32x8 __attribute__((ext_vector_type(8)));
 
 // S: Peq rows per word = target symbols rounded up to 4, 8 or 16 (a genome with N, soft-masked lower case, IUPAC
 // codes).  LDS per wave = NWD * S * 256 bytes: 8 waves per SIMD at S = 4 and up to 5 words, 4 at S = 8, 2 at S = 16.
-template <int NWD, int S, bool FILTER = false>
+template <int NWD, int S, bool FILTER = false, bool HITS = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((S == 4 && NWD <= 5) ? 8 : 1, 8)))
 scan_reads_banded_kernel(const ReadScanArgs a)
 {
@@ -557,6 +600,7 @@ scan_reads_banded_kernel(const ReadScanArgs a)
         tr.cap = live ? (a.posCap ? a.posCap[item] : a.cap) : 0;
         tr.pos = a.segPos + (!live ? 0 : (a.posOff ? a.posOff[item] : item * a.cap));
     }
+    if constexpr (HITS) { tr.slot = slot; tr.rFirst = 0; tr.rLast = -2; tr.rMin = 0; tr.rPos = 0; tr.rCnt = 0; tr.hl = a.hits; }
     int e = m - tr.best - 1;                                          // score at column -1 is m
     int flag = 0;
 
@@ -583,7 +627,7 @@ scan_reads_banded_kernel(const ReadScanArgs a)
     while (b < bend) {
         switch (nw) {
 #define QUAD(NA, Q)                                                                                             \
-            nw = band_quad<(NA <= NWD ? NA : NWD), NWD, Q, S, true, false, FILTER>(cur[2 * Q], cur[2 * Q + 1],     \
+            nw = band_quad<(NA <= NWD ? NA : NWD), NWD, Q, S, true, false, FILTER, HITS>(cur[2 * Q], cur[2 * Q + 1], \
                      Q < 3 ? cur[(2 * Q + 2) & 7] : nxt[0], Q < 3 ? cur[(2 * Q + 3) & 7] : nxt[1], qr,          \
                      b * 16 + Q * 4, c1, b >= bmain /* warm-up columns record nothing */, Pv, Mv, e, flag, tr,  \
                      sh, lastRows, noChain, noChain);
@@ -618,7 +662,9 @@ scan_reads_banded_kernel(const ReadScanArgs a)
 #undef QUAD
         }
     }
-    if (live) {
+    if constexpr (HITS) {
+        hit_append(tr.hl, tr.rLast >= 0, tr.slot, tr.rFirst, tr.rLast, tr.rMin, tr.rPos, tr.rCnt);   // the segment's last run
+    } else if (live) {
         const long long it = (long long)(blockIdx.x * 64 + threadIdx.x) * a.numSegments + blockIdx.y;
         a.segBest[it] = tr.best;
         a.segCnt[it] = tr.cnt;

@@ -212,6 +212,42 @@ typedef struct {
 } EdlibAmdCrossHits;
 EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* batch, EdlibAmdCrossHits* out);
 
+/* A shared-target batch whose results are, per read, EVERY occurrence within k along the target -- the search question of
+ * adapter / primer trimming, concatemer splitting, repeat finding and multi-mapping reads, which no choice of k makes
+ * edlibAlign() answer (it keeps the columns of the single best score only).
+ * With m = the read's length, T = targetLength and D[j] (j = 0 .. T-1) the HW bottom-row score -- the least edit distance
+ * between the read and any substring of the target that ends at column j (the empty one counts: D[j] <= m; there is no
+ * column -1 here) -- a HIT is a maximal run [firstEnd, lastEnd] of consecutive columns with D[j] <= k.  Its editDistance is
+ * the least D of the run, endLocation the lowest column of the run holding it, numLocations the number of columns of the
+ * run holding it.  The least editDistance over a read's hits equals edlibAlign(read, target, HW, k).editDistance, no hit
+ * means -1 there, and every non-negative end location of that call lies in a hit of that distance.
+ * Accepted: config.mode == EDLIB_MODE_HW, config.task == EDLIB_TASK_DISTANCE, config.k >= 0, every read at most 256 bases,
+ * at most 16 distinct target symbols; additionalEqualities allowed.  Anything else (SHW / NW, start locations and paths,
+ * longer reads, more symbols) returns NULL with the limit named in edlibAmdLastError().  For both strands pass the reverse
+ * complements as reads of their own; for start locations or paths align the chosen windows with a pair batch.
+ * An empty read hits once: [0, T-1], distance 0, endLocation 0, numLocations T; an empty target gives no hit.
+ * Run, Stats (path bit 0) and Destroy work as for a shared batch; Results, ResultsFlat, ResultsView, CigarView, StrandView,
+ * CrossView and CrossHits fail.  The device list starts at max(2^20, numQueries) runs; a Run that counts more grows it to
+ * its count and scans once more (later Runs of the batch fit); a list that does not fit in device memory fails the Run with
+ * the count in the message. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedHits(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* target, int targetLength, EdlibAlignConfig config, int device);
+
+/* The hits of the last Run of such a batch (it fails on every other kind), made on the device and copied as one block:
+ * pointers into pinned memory the batch owns, valid until the next Run / Destroy.  Hits are grouped by read in the caller's
+ * order (CSR) and ascend by firstEnd inside a read. */
+typedef struct {
+    int numUnits; long long numHits;
+    const long long* unitOffsets;   /* [numUnits + 1]: hits of read i are [unitOffsets[i], unitOffsets[i+1]) */
+    const int* firstEnd;            /* [numHits] */
+    const int* lastEnd;             /* [numHits] */
+    const int* editDistance;        /* [numHits] */
+    const int* endLocation;         /* [numHits] */
+    const int* numLocations;        /* [numHits] */
+} EdlibAmdReadHits;
+EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* batch, EdlibAmdReadHits* out);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
