@@ -28,7 +28,7 @@ seed_thresholds_kernel(int* __restrict__ kinit, const int* __restrict__ best, co
 int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, int kcap, const int* d_kinit,
                      int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                      const long long* posOff, const int* posCap, bool unbanded, unsigned long long* wordSteps,
-                     const uint32_t* peqDense, const int* qlenDense)
+                     const uint32_t* peqDense, const int* qlenDense, bool peqBottom)
 {
     ReadScanArgs a{};
     // peqDense / qlenDense (+ d_kinit): rows rebuilt for exactly the lanes of this launch, in lane order (pass 2)
@@ -42,6 +42,7 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     a.posOff = posOff; a.posCap = posCap;
     a.kcap = kcap; a.wordSteps = wordSteps ? wordSteps : d_wordSteps_.p;
     a.filter = filterScan_ ? 1 : 0;
+    a.bottomAligned = peqBottom ? 1 : 0;              // (only scan_reads_kernel reads such rows: launch_scan_reads below)
     a.chainIn = chain_.in; a.chainOut = chain_.out; a.chainSrc = chain_.src; a.chainInLanes = chain_.inLanes;
     a.chainBlocks = chain_.blocks; a.rowBase = chain_.rowBase;
     const bool chained = chain_.in != nullptr || chain_.out != nullptr;
@@ -60,10 +61,12 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     // columns a lane walks: the segments' own columns (a launch may cover a prefix of the target only) and their warm-ups
     const long long colsScanned = std::min<long long>(a.targetLength, (long long)numSegments * segLen) + (long long)(numSegments - 1) * warm;
     const bool fullHeight = banded_ && mode == EDLIB_MODE_HW && unbanded && (chained || syms_ > 4 || longGroup);
+    const bool bandedKernel = !fullHeight && banded_ && mode == EDLIB_MODE_HW && (!unbanded || syms_ > 4 || longGroup);
+    if (peqBottom && (fullHeight || bandedKernel)) EDLIB_AMD_HIP(hipErrorInvalidValue);   // rows only scan_reads_kernel reads
     if (fullHeight) {
         EDLIB_AMD_HIP(launch_scan_reads_full(g.nwords, syms_, a, stream_));
         stats.word_steps += (long long)((nlanes + 63) / 64 * 64) * g.nwords * colsScanned;
-    } else if (banded_ && mode == EDLIB_MODE_HW && (!unbanded || syms_ > 4 || longGroup)) EDLIB_AMD_HIP(launch_scan_reads_banded(g.nwords, syms_, a, stream_));
+    } else if (bandedKernel) EDLIB_AMD_HIP(launch_scan_reads_banded(g.nwords, syms_, a, stream_));
     else {
         EDLIB_AMD_HIP(launch_scan_reads(g.nwords, mode, a, stream_));
         stats.word_steps += (long long)((nlanes + 63) / 64 * 64) * g.nwords * colsScanned;
@@ -310,6 +313,11 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             // The leftovers are scattered over the batch: through the slot map every lane of a wave would pull its
             // rows from a different 256-byte line (16x the bytes, once per segment: 3 GB of fetch per 1M-read step
             // in round 1).  Their rows are rebuilt in lane order instead -- the builder reads each query once.
+            // When the pass goes to the plain kernel (scanGroup: HW, four symbols, up to kMaxReadWords words, no chain), the
+            // rebuilt rows are bottom-aligned: row m-1 at bit 31 of the last word, where the column reads the score's
+            // delta with two full-rate shifts.  The pre-scan below shares them, on the same kernel.
+            const bool bottom = plain && mode == EDLIB_MODE_HW && syms_ == 4 && g.nwords <= kMaxReadWords &&
+                                chain_.in == nullptr && chain_.out == nullptr;
             const size_t no64 = (no + 63) / 64 * 64;
             std::vector<int> perm2(no64, -1);
             for (size_t i = 0; i < no; ++i) perm2[i] = g.perm[todo[i]];
@@ -319,7 +327,7 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             EDLIB_AMD_HIP(hipMemcpyAsync(d_perm2.p, perm2.data(), no64 * sizeof(int), hipMemcpyHostToDevice, stream_));
             EDLIB_AMD_HIP(launch_build_peq_reads(g.nwords, syms_, d_qpool_.p, d_qoff_.p, d_perm2.p, (int)no64,
                                                  d_eqtbl_.p, d_presence_.p, cfg_.k, d_peq2.p, d_qlen2.p,
-                                                 d_kinit2.p, d_extra2.p, stream_));
+                                                 d_kinit2.p, d_extra2.p, stream_, bottom));
             // Every segment starts from its lane's threshold, and a lane records a position whenever its best improves: from
             // min(k, m) an unrelated read walks down ~100 improvements per segment, each a scattered 4-byte store (1.2 GB of
             // write traffic per 1M-read step in round 2).  The first columns of the target give every lane a score that
@@ -330,13 +338,13 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             if (mode == EDLIB_MODE_HW && last && no >= 4096 && S2 > 1 && T >= 16 * seedCols) {
                 EDLIB_AMD_HIP(d_b0.alloc(no)); EDLIB_AMD_HIP(d_c0.alloc(no)); EDLIB_AMD_HIP(d_p0.alloc(no * 8));
                 if (scanGroup(g, mode, nullptr, (int)no, kcapL, d_kinit2.p, 1, seedCols, 0,
-                              d_b0.p, d_c0.p, d_p0.p, 8, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p)) return 1;
+                              d_b0.p, d_c0.p, d_p0.p, 8, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p, bottom)) return 1;
                 hipLaunchKernelGGL(seed_thresholds_kernel, dim3((unsigned)((no + 255) / 256)), dim3(256), 0, stream_,
                                    d_kinit2.p, d_b0.p, d_c0.p, (int)no);
                 EDLIB_AMD_HIP(hipGetLastError());
             }
             if (scanGroup(g, mode, nullptr, (int)no, kcapL, d_kinit2.p, S2, segLen2, warm2,
-                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p)) return 1;
+                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p, bottom)) return 1;
             EDLIB_AMD_HIP(launch_merge_segments(d_sb, d_sc, d_sp, S2, capL, (int)no, d_map, 16,
                                                 g.d_best.p, g.d_total.p, g.d_pos.p, g.d_flags.p, stream_,
                                                 last ? kOvfGatherLevel : kOvfRescan));

@@ -7,6 +7,16 @@
 // and 8-byte (VOP3) encodings, so the phase flips every few instructions: 158 SIMD cycles per 5-word column where its 35 full-
 // rate + 18 half-rate instructions add up to 133 (rounds 1-5).  Here every instruction is a VOP3 encoding behind an alignment
 // fence.  (The macro chains are unrolled by hand-run Python, see tools/gen_lanepair_asm.py for the pattern.)
+//
+// Half-rate instructions the column does without:
+//   * HW, word 0: a zero comes in from row -1, so x << 1 is x + x -- two full-rate v_add_u32 where two v_alignbit_b32 stood
+//     (RC_W_SH_HW: scan_reads_kernel, the banded kernel's multi-word columns and the seed verifier share it).
+//   * rows built bottom-aligned (RC_SCORE_B, scan_reads_kernel<NWD, 2, true>: the dense last level of HW): the followed row is
+//     bit 31 of the last word in every lane, so its delta is v_lshrrev_b32 / v_ashrrev_i32 by 31 and two v_add_u32, all full
+//     rate, where the per-lane bit `sh` takes two v_bfe and a v_add3_u32.
+// The five-word bottom-aligned column is 54 instructions: 41 full-rate, 13 half-rate (the 5 adds of the carry chain, the 8
+// v_alignbit_b32 of words 1..4), then the compare of the tracking test; the other word counts and layouts keep their chains
+// the same way.  Shifts on register pairs (v_lshl_add_u64 on two words at once): see DESIGN.md 3, the dropped table.
 #pragma once
 
 #define RC_HEAD ".p2align 3\n\ts_nop 0\n\t"
@@ -17,12 +27,15 @@
                          "v_bitop3_b32 %[ph" #c "], %[m" #i "], %[xh], %[p" #i "] bitop3:0xf1\n\t" \
                          "v_and_b32_e64 %[mh" #c "], %[p" #i "], %[xh]\n\t"
 #define RC_W_SH(c, p)    "v_alignbit_b32 %[phs], %[ph" #c "], %[ph" #p "], 31\n\t" "v_alignbit_b32 %[mhs], %[mh" #c "], %[mh" #p "], 31\n\t"
-#define RC_W_SH_HW(c)    "v_alignbit_b32 %[phs], %[ph" #c "], 0, 31\n\t" "v_alignbit_b32 %[mhs], %[mh" #c "], 0, 31\n\t"      /* row -1 of HW: hin = 0 */
+#define RC_W_SH_HW(c)    "v_add_u32_e64 %[phs], %[ph" #c "], %[ph" #c "]\n\t" "v_add_u32_e64 %[mhs], %[mh" #c "], %[mh" #c "]\n\t"  /* row -1 of HW: hin = 0, so x << 1 = x + x (full rate) */
 #define RC_W_SH_NW(c)    "v_alignbit_b32 %[phs], %[ph" #c "], -1, 31\n\t" "v_alignbit_b32 %[mhs], %[mh" #c "], 0, 31\n\t"     /* SHW / NW: hin = +1 (edlib.cpp:584,779) */
 #define RC_W_C(i)        "v_or_b32_e64 %[xv], %[e" #i "], %[m" #i "]\n\t" \
                          "v_bitop3_b32 %[pn" #i "], %[mhs], %[xv], %[phs] bitop3:0xf1\n\t" \
                          "v_and_b32_e64 %[mn" #i "], %[phs], %[xv]\n\t"
 #define RC_SCORE(c)      "v_bfe_u32 %[t], %[ph" #c "], %[sh], 1\n\t" "v_bfe_i32 %[s], %[mh" #c "], %[sh], 1\n\t" "v_add3_u32 %[scoreN], %[score], %[t], %[s]\n\t"
+// bottom-aligned rows (scan_reads_kernel<NWD, 2, true>): the followed row is bit 31 of the last word in every lane
+#define RC_SCORE_B(c)    "v_lshrrev_b32_e64 %[t], 31, %[ph" #c "]\n\t" "v_ashrrev_i32_e64 %[s], 31, %[mh" #c "]\n\t" \
+                         "v_add_u32_e64 %[scoreN], %[score], %[t]\n\t" "v_add_u32_e64 %[scoreN], %[scoreN], %[s]\n\t"
 #define RC_WORD0_HW      RC_W_A(0) RC_W_ADD0(0) RC_W_B(0, 0) RC_W_SH_HW(0) RC_W_C(0)
 #define RC_WORD0_NW      RC_W_A(0) RC_W_ADD0(0) RC_W_B(0, 0) RC_W_SH_NW(0) RC_W_C(0)
 #define RC_WORD(i, c, p) RC_W_A(i) RC_W_ADDC(i) RC_W_B(i, c) RC_W_SH(c, p) RC_W_C(i)
@@ -64,13 +77,19 @@
 #define RC_LAST_8 1
 #define RC_TEMPS [t] "=&v"(t_), [s] "=&v"(s_), [xh] "=&v"(xh_), [ph0] "=&v"(ph0_), [ph1] "=&v"(ph1_), [mh0] "=&v"(mh0_), [mh1] "=&v"(mh1_), [phs] "=&v"(phs_), [mhs] "=&v"(mhs_), [xv] "=&v"(xv_), [cy] "=&s"(cy_)
 #define RC_SCORE_X(c) RC_SCORE(c)
+#define RC_SCORE_BX(c) RC_SCORE_B(c)
 #define RC_COLUMN_ASM(N, WORD0) asm(RC_HEAD WORD0 RC_REST_##N RC_SCORE_X(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score), [sh] "v"(sh))
+#define RC_COLUMN_ASM_B(N, WORD0) asm(RC_HEAD WORD0 RC_REST_##N RC_SCORE_BX(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score))
 // the same column without a followed row (the band of scan_reads_banded_kernel below its full height)
 #define RC_COLUMN_ASM_NS(N, WORD0) asm(RC_HEAD WORD0 RC_REST_##N : RC_OUTS_##N, RC_TEMPS : RC_INS_##N)
 #define RC_COLUMN_DISPATCH_NS(NA, WORD0) \
     if constexpr (NA == 1) RC_COLUMN_ASM_NS(1, WORD0); if constexpr (NA == 2) RC_COLUMN_ASM_NS(2, WORD0); if constexpr (NA == 3) RC_COLUMN_ASM_NS(3, WORD0); \
     if constexpr (NA == 4) RC_COLUMN_ASM_NS(4, WORD0); if constexpr (NA == 5) RC_COLUMN_ASM_NS(5, WORD0); if constexpr (NA == 6) RC_COLUMN_ASM_NS(6, WORD0); \
     if constexpr (NA == 7) RC_COLUMN_ASM_NS(7, WORD0); if constexpr (NA == 8) RC_COLUMN_ASM_NS(8, WORD0);
+#define RC_COLUMN_DISPATCH_B(NWD, WORD0) \
+    if constexpr (NWD == 1) RC_COLUMN_ASM_B(1, WORD0); if constexpr (NWD == 2) RC_COLUMN_ASM_B(2, WORD0); if constexpr (NWD == 3) RC_COLUMN_ASM_B(3, WORD0); \
+    if constexpr (NWD == 4) RC_COLUMN_ASM_B(4, WORD0); if constexpr (NWD == 5) RC_COLUMN_ASM_B(5, WORD0); if constexpr (NWD == 6) RC_COLUMN_ASM_B(6, WORD0); \
+    if constexpr (NWD == 7) RC_COLUMN_ASM_B(7, WORD0); if constexpr (NWD == 8) RC_COLUMN_ASM_B(8, WORD0);
 #define RC_COLUMN_DISPATCH(NWD, WORD0) \
     if constexpr (NWD == 1) RC_COLUMN_ASM(1, WORD0); if constexpr (NWD == 2) RC_COLUMN_ASM(2, WORD0); if constexpr (NWD == 3) RC_COLUMN_ASM(3, WORD0); \
     if constexpr (NWD == 4) RC_COLUMN_ASM(4, WORD0); if constexpr (NWD == 5) RC_COLUMN_ASM(5, WORD0); if constexpr (NWD == 6) RC_COLUMN_ASM(6, WORD0); \

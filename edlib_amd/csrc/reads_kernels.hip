@@ -22,13 +22,16 @@
 //   * the score of the bottom query row is followed directly at bit (m-1) of
 //     the last word, so no wildcard padding (the reference's W) is needed and
 //     end positions are produced un-shifted.
+//     (The dense last level of HW builds its rows bottom-aligned instead: pad rows that
+//     match every symbol sit ABOVE the query, where HW keeps them at zero, and the followed
+//     row is bit 31 of the last word in every lane -- scan_reads_kernel<NWD, 2, true>.)
 //   * HW is shift-invariant: a segment that starts 2m-1 columns early from the
 //     fresh state reproduces the exact bottom-row scores of its own columns,
 //     so the target is cut into segments for load balance and for small
 //     batches; merge_segments() joins them.
 //
 // Two scan kernels:
-//   scan_reads_kernel<NWD, MODE>        every row of every column (SHW, NW; HW for the leftovers of the
+//   scan_reads_kernel<NWD, MODE, BOTTOM> every row of every column (SHW, NW; HW for the leftovers of the
 //                                       k-doubling whose band is the whole query, and with EDLIB_AMD_BAND=0).
 //                                       All outputs are functions of the full DP matrix, so no band is
 //                                       needed for correctness and the kernel never branches on data.
@@ -114,13 +117,17 @@ hipError_t launch_pack_target_2bit(const uint8_t* raw, const uint8_t* lut, int T
 // rows, which lane j keeps.  (Round 1 gave every lane its own read and walked it byte
 // by byte: 64 different lines per load instruction, 8.9 GB of fetch per 1M reads against 150 MB of queries.)
 // Symbols are done four at a time (4 x NWD row registers); the query bytes are re-read per group from L1 / L2.
+// bottomAlign (the rows scan_reads_kernel<NWD, 2, true> reads): query row i goes to bit pad + i, pad = 32 NWD - m, so that
+// row m-1 is bit 31 of the last word, and the pad bits below are set in the row of every symbol.  pad is below 32 for the
+// reads of a group (read_group_words: they reach into the last word); the padding slots of a list (m = 1) and any shorter
+// read get whole words of pad the same way, nothing here or in the scan's initial state assumes pad < 32.
 template <int NWD>
 __global__ void __launch_bounds__(256)
 build_peq_reads_kernel(const uint8_t* __restrict__ reads, const long long* __restrict__ qoff,
                        const int* __restrict__ perm, int nslots, int S,
                        const uint16_t* __restrict__ eqtbl, const u32* __restrict__ tpres, int kcfg,
                        u32* __restrict__ peq, int* __restrict__ qlen, int* __restrict__ kinit,
-                       int* __restrict__ alphaExtra)
+                       int* __restrict__ alphaExtra, int bottomAlign)
 {
     __shared__ uint16_t s_eq[256];
     s_eq[threadIdx.x] = eqtbl[threadIdx.x];
@@ -150,12 +157,13 @@ build_peq_reads_kernel(const uint8_t* __restrict__ reads, const long long* __res
             unsigned long long seen0 = 0, seen1 = 0, seen2 = 0, seen3 = 0;
             int extraJ = 0;
             const bool mine = lane == j;                               // the lane that keeps read j's rows
+            const int padj = bottomAlign ? 32 * NWD - mj : 0;          // wave-uniform
 #pragma unroll
             for (int c = 0; c < (NWD + 1) / 2; ++c) {                  // 64 rows = two words per trip
-                const int i = 64 * c + lane;
-                const bool in = i < mj;
+                const int i = 64 * c + lane - padj;                    // query row of bit 64 c + lane
+                const bool in = i >= 0 && i < mj;
                 const u32 by = in ? reads[offj + i] : 0u;
-                const u32 mask = in ? ((u32)s_eq[by] >> g0) : 0u;
+                const u32 mask = in ? ((u32)s_eq[by] >> g0) : (i < 0 ? 0xfu : 0u);   // pad rows match every symbol
                 const unsigned long long b0 = __builtin_amdgcn_ballot_w64((mask & 1u) != 0), b1 = __builtin_amdgcn_ballot_w64((mask & 2u) != 0);
                 const unsigned long long b2 = __builtin_amdgcn_ballot_w64((mask & 4u) != 0), b3 = __builtin_amdgcn_ballot_w64((mask & 8u) != 0);
                 constexpr int w0 = 0;
@@ -200,22 +208,22 @@ template <int NWD>
 static hipError_t launch_build_peq_t(const uint8_t* reads, const long long* qoff, const int* perm,
                                      int nslots, int S, const uint16_t* eqtbl, const u32* tpres, int kcfg,
                                      u32* peq, int* qlen, int* kinit, int* alphaExtra,
-                                     hipStream_t stream)
+                                     hipStream_t stream, bool bottomAlign)
 {
     hipLaunchKernelGGL(build_peq_reads_kernel<NWD>, dim3((nslots + 255) / 256), dim3(256), 0, stream,
-                       reads, qoff, perm, nslots, S, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra);
+                       reads, qoff, perm, nslots, S, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, bottomAlign ? 1 : 0);
     return hipGetLastError();
 }
 
 hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, const long long* qoff,
                                   const int* perm, int nslots, const uint16_t* eqtbl,
                                   const u32* tpres, int kcfg, u32* peq, int* qlen, int* kinit,
-                                  int* alphaExtra, hipStream_t stream)
+                                  int* alphaExtra, hipStream_t stream, bool bottomAlign)
 {
     if (nslots == 0) return hipSuccess;
     if (syms != 4 && syms != 8 && syms != 16) return hipErrorInvalidValue;
     switch (nwords) {
-#define CASE(N) case N: return launch_build_peq_t<N>(reads, qoff, perm, nslots, syms, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, stream);
+#define CASE(N) case N: return launch_build_peq_t<N>(reads, qoff, perm, nslots, syms, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, stream, bottomAlign);
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(10) CASE(12) CASE(14) CASE(16) CASE(24) CASE(32)
 #undef CASE
     }
@@ -228,10 +236,10 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 // into one body fed by v_mov/v_cndmask of the Peq row.
 #define EDLIB_AMD_DISPATCH_COLUMN(sym)                                                     \
     switch (sym) {                                                                         \
-        case 0:  column_step<NWD, MODE>(E0, Pv, Mv, score, sh); asm volatile("; sym0"); break; \
-        case 1:  column_step<NWD, MODE>(E1, Pv, Mv, score, sh); asm volatile("; sym1"); break; \
-        case 2:  column_step<NWD, MODE>(E2, Pv, Mv, score, sh); asm volatile("; sym2"); break; \
-        default: column_step<NWD, MODE>(E3, Pv, Mv, score, sh); asm volatile("; sym3"); break; \
+        case 0:  column_step<NWD, MODE, BOTTOM>(E0, Pv, Mv, score, sh); asm volatile("; sym0"); break; \
+        case 1:  column_step<NWD, MODE, BOTTOM>(E1, Pv, Mv, score, sh); asm volatile("; sym1"); break; \
+        case 2:  column_step<NWD, MODE, BOTTOM>(E2, Pv, Mv, score, sh); asm volatile("; sym2"); break; \
+        default: column_step<NWD, MODE, BOTTOM>(E3, Pv, Mv, score, sh); asm volatile("; sym3"); break; \
     }
 
 // Record column `col` if it ties or improves the best bottom-row score
@@ -243,7 +251,10 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
         ++cnt;                                                 \
     }
 
-template <int NWD, int MODE>
+// BOTTOM (HW): the Peq rows were built bottom-aligned (build_peq_reads_kernel), query row r at bit 32 NWD - m + r.  The
+// pad rows below bit 32 NWD - m match every symbol; with HW's zero row -1 they stay at D = 0 in every column, so the real
+// rows see the boundary they always saw, and the followed row m-1 is bit 31 of the last word in every lane.
+template <int NWD, int MODE, bool BOTTOM = false>
 __global__ void __launch_bounds__(256)
 scan_reads_kernel(const ReadScanArgs a)
 {
@@ -269,6 +280,17 @@ scan_reads_kernel(const ReadScanArgs a)
         }
     }
     const int m = a.qlen[slot];
+    if constexpr (BOTTOM) {
+        // column -1 of the pad rows is 0: Pv is clear on the 32 NWD - m low bits.  Reads of a group fill their last word
+        // (read_group_words), so the pad is below 32 there; the padding slots of the rebuilt rows (m = 1) and anything
+        // shorter still get whole words of pad.
+        const int pad = 32 * NWD - m;
+#pragma unroll
+        for (int d = 0; d < NWD; ++d) {
+            const int lo = pad - 32 * d;
+            Pv[d] = lo <= 0 ? ~0u : (lo >= 32 ? 0u : ~0u << lo);
+        }
+    }
     const u32 sh = (u32)(m - 1) & 31u;
     int score = m;
     int best = a.kinit[slot];
@@ -330,7 +352,9 @@ static hipError_t launch_scan_mode(int mode, const ReadScanArgs& a, hipStream_t 
     switch (mode) {
         case 0: hipLaunchKernelGGL((scan_reads_kernel<NWD, 0>), grid, block, 0, stream, a); break;
         case 1: hipLaunchKernelGGL((scan_reads_kernel<NWD, 1>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((scan_reads_kernel<NWD, 2>), grid, block, 0, stream, a); break;
+        case 2: if (a.bottomAligned) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true>), grid, block, 0, stream, a);
+                else hipLaunchKernelGGL((scan_reads_kernel<NWD, 2>), grid, block, 0, stream, a);
+                break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -339,6 +363,7 @@ static hipError_t launch_scan_mode(int mode, const ReadScanArgs& a, hipStream_t 
 hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStream_t stream)
 {
     if (a.nlanes == 0) return hipSuccess;
+    if (a.bottomAligned && mode != 2) return hipErrorInvalidValue;      // only HW keeps the pad rows at zero
     switch (nwords) {
 #define CASE(N) case N: return launch_scan_mode<N>(mode, a, stream);
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)

@@ -59,6 +59,7 @@ struct ReadScanArgs {
     int filter;               // banded HW kernel: 1 = fixed threshold, segPos lists the 16-column BLOCKS that hold a column
                               // scoring <= kinit (each once), segCnt their number (piece filter of long reads)
     HitList hits;             // HITS instantiation of the banded kernel only (launch_scan_reads_hits)
+    int bottomAligned;        // scan_reads_kernel, HW only: peq was built with bottomAlign (row m-1 at bit 31 of the last word)
 };
 
 // mode: 0 NW, 1 SHW, 2 HW (values of EdlibAlignMode).  Returns hipSuccess or the launch error.
@@ -80,11 +81,12 @@ hipError_t launch_pack_target_rows(const uint8_t* raw, const uint8_t* lut, int t
 // Builds Peq for every slot (reference buildPeq, edlib.cpp:358-384, for the <= syms target symbols; eqtbl[byte] =
 // 16-bit set of the target symbols a query byte equals),
 // the per-slot query length and the number of query byte values absent from the target.
+// bottomAlign: query row i at bit 32 nwords - m + i and the bits below set in every row (ReadScanArgs::bottomAligned).
 hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, const long long* qoff,
                                   const int* perm, int nslots, const uint16_t* eqtbl,
                                   const uint32_t* targetPresence /*8 dwords*/, int kcfg,
                                   uint32_t* peq, int* qlen, int* kinit, int* alphaExtra,
-                                  hipStream_t stream);
+                                  hipStream_t stream, bool bottomAlign = false);
 
 // Piece filter: gathers the (lane, block) candidates of a filter scan into one list.  out[2i] = lane, out[2i+1] = block;
 // *counter = number of candidates (may exceed maxOut: the caller retries with a larger list); overflow[lane] = 1 when a

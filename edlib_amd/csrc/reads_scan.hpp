@@ -18,11 +18,23 @@ typedef uint32_t u32;
 // boundary: 0 for HW, +1 for SHW/NW -- hin is never negative at row -1, so the
 // "Eq |= hinIsNeg" term vanishes).  Also advances the bottom-row score by the
 // horizontal delta of row m-1 (bit `sh` of the last word).
-template <int NWD, int MODE>
+// BOTTOM (HW, scan_reads_kernel over rows built bottom-aligned): row m-1 is bit 31 of the last word in every lane, `sh` is
+// not read, and the delta comes out of two full-rate shifts instead of two v_bfe.
+template <int NWD, int MODE, bool BOTTOM = false>
 __device__ __forceinline__ void column_step(const u32 (&Eq)[NWD], u32 (&Pv)[NWD], u32 (&Mv)[NWD],
                                             int& score, const u32 sh)
 {
-    if constexpr (NWD <= 8) {
+    static_assert(!BOTTOM || (MODE == 2 && NWD <= 8), "bottom-aligned rows: HW, up to 8 words");
+    if constexpr (BOTTOM) {
+        u32 t_, s_, xh_, ph0_, ph1_, mh0_, mh1_, phs_, mhs_, xv_, Pn[NWD], Mn[NWD];
+        int scoreN;
+        unsigned long long cy_;
+        RC_COLUMN_DISPATCH_B(NWD, RC_WORD0_HW)
+#pragma unroll
+        for (int i = 0; i < NWD; ++i) { Pv[i] = Pn[i]; Mv[i] = Mn[i]; }
+        score = scoreN;
+        return;
+    } else if constexpr (NWD <= 8) {
         // one asm statement: VOP3 encodings behind an alignment fence (reads_column_asm.hpp: why)
         u32 t_, s_, xh_, ph0_, ph1_, mh0_, mh1_, phs_, mhs_, xv_, Pn[NWD], Mn[NWD];
         int scoreN;

@@ -97,6 +97,49 @@ __global__ void __launch_bounds__(256) k_addc(u32* out, int iters, u32 seed)
     out[blockIdx.x * blockDim.x + threadIdx.x] = s;
 }
 
+// The << 1 of the column's two five-word vectors (Ph, Mh), in place, both ways; fixed registers, since inline asm cannot name
+// the halves of a 64-bit operand (pairs even-aligned: v[32:33] v[34:35] v36 = Ph, v[38:39] v[40:41] v42 = Mh, v[44:45] = the
+// carry into a pair with a zero high half).  Every encoding is 8 bytes behind the alignment fence of reads_column_asm.hpp.
+//   PAIRS = 0: 4 x v_alignbit_b32 + v_add_u32 (word 0, a zero comes in) per vector: 8 half-rate + 2 full-rate instructions
+//   PAIRS = 1: v_alignbit_b32 (word 4), v_lshrrev_b32 (the carry out of word 1, taken before its pair moves), v_lshl_add_u64
+//              (words 2-3 + carry), v_lshl_add_u64 (words 0-1 + 0) per vector, and one v_mov of the zero half per column
+#define SH5_ALIGN(p0, p1, p2, p3, p4)                                                                    \
+    "v_alignbit_b32 v" #p4 ", v" #p4 ", v" #p3 ", 31\n\tv_alignbit_b32 v" #p3 ", v" #p3 ", v" #p2 ", 31\n\t" \
+    "v_alignbit_b32 v" #p2 ", v" #p2 ", v" #p1 ", 31\n\tv_alignbit_b32 v" #p1 ", v" #p1 ", v" #p0 ", 31\n\t" \
+    "v_add_u32_e64 v" #p0 ", v" #p0 ", v" #p0 "\n\t"
+#define SH5_PAIRS(p0, p1, p2, p3, p4)                                                                    \
+    "v_alignbit_b32 v" #p4 ", v" #p4 ", v" #p3 ", 31\n\tv_lshrrev_b32_e64 v44, 31, v" #p1 "\n\t"           \
+    "v_lshl_add_u64 v[" #p2 ":" #p3 "], v[" #p2 ":" #p3 "], 1, v[44:45]\n\t"                                \
+    "v_lshl_add_u64 v[" #p0 ":" #p1 "], v[" #p0 ":" #p1 "], 1, 0\n\t"
+#define SH5_COL_ALIGN SH5_ALIGN(32, 33, 34, 35, 36) SH5_ALIGN(38, 39, 40, 41, 42)
+#define SH5_COL_PAIRS "v_mov_b32_e64 v45, 0\n\t" SH5_PAIRS(32, 33, 34, 35, 36) SH5_PAIRS(38, 39, 40, 41, 42)
+#define SH5_X16(C) C C C C C C C C C C C C C C C C
+template <int PAIRS>
+__global__ void __launch_bounds__(256) k_shift5(u32* out, int iters, u32 seed)
+{
+    u32 r[10];
+    for (int i = 0; i < 10; ++i) r[i] = seed * (threadIdx.x + 1) + i * 77;
+    for (int it = 0; it < iters; ++it) {
+#define SH5_BODY(COL)                                                                                                          \
+        asm volatile(".p2align 3\n\ts_nop 0\n\t"                                                                               \
+                     "v_mov_b32_e64 v32, %0\n\tv_mov_b32_e64 v33, %1\n\tv_mov_b32_e64 v34, %2\n\tv_mov_b32_e64 v35, %3\n\t"        \
+                     "v_mov_b32_e64 v36, %4\n\tv_mov_b32_e64 v38, %5\n\tv_mov_b32_e64 v39, %6\n\tv_mov_b32_e64 v40, %7\n\t"        \
+                     "v_mov_b32_e64 v41, %8\n\tv_mov_b32_e64 v42, %9\n\t"                                                      \
+                     SH5_X16(COL) SH5_X16(COL) SH5_X16(COL) SH5_X16(COL)                                                       \
+                     "v_mov_b32_e64 %0, v32\n\tv_mov_b32_e64 %1, v33\n\tv_mov_b32_e64 %2, v34\n\tv_mov_b32_e64 %3, v35\n\t"        \
+                     "v_mov_b32_e64 %4, v36\n\tv_mov_b32_e64 %5, v38\n\tv_mov_b32_e64 %6, v39\n\tv_mov_b32_e64 %7, v40\n\t"        \
+                     "v_mov_b32_e64 %8, v41\n\tv_mov_b32_e64 %9, v42\n\t"                                                      \
+                     : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]) \
+                     : : "v32", "v33", "v34", "v35", "v36", "v38", "v39", "v40", "v41", "v42", "v44", "v45")
+        if (PAIRS) SH5_BODY(SH5_COL_PAIRS); else SH5_BODY(SH5_COL_ALIGN);
+#undef SH5_BODY
+        r[0] |= 0x10001u; r[5] |= 0x101u;               // keep the vectors from running empty
+    }
+    u32 s = 0;
+    for (int i = 0; i < 10; ++i) s ^= r[i];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = s;
+}
+
 // the Myers column body on NWD words with a fixed Eq row (no dispatch): ops/column as in the scan kernel
 template <int NWD>
 __device__ __forceinline__ void column_step(const u32 (&Eq)[NWD], u32 (&Pv)[NWD], u32 (&Mv)[NWD], int& score, u32 sh)
@@ -190,6 +233,15 @@ int main()
         { const double lo = (double)blocks * 256 * iters * 8 * 5;
           float ms = time_ms([&] { hipLaunchKernelGGL(k_addc, dim3(blocks), dim3(256), 0, 0, out, iters, 7u); });
           printf("waves/SIMD %d  %-16s %8.3f ms  %7.2f T lane-ops/s  %6.1f lane-ops/clk/CU@2.4GHz\n", wps, "add_co+4addc", ms, lo / ms / 1e9, lo / (ms * 1e-3) / 2.4e9 / 256); }
+        // 64 columns per trip (+ 20 v_mov in and out of the fixed registers, the same for both forms); five repeats each, alternating
+        for (int r5 = 0; r5 < 5; ++r5) {
+            const int it5 = 2000;
+            const double cols5 = (double)it5 * 64;
+            float a = time_ms([&] { hipLaunchKernelGGL(k_shift5<0>, dim3(blocks), dim3(256), 0, 0, out, it5, 7u); });
+            float p = time_ms([&] { hipLaunchKernelGGL(k_shift5<1>, dim3(blocks), dim3(256), 0, 0, out, it5, 7u); });
+            printf("waves/SIMD %d  5-word Ph+Mh shift, repeat %d: alignbit chain %.3f ms (%.2f ns/col/wave-slot)  register pairs %.3f ms (%.2f)  ratio %.4f\n",
+                   wps, r5, a, a * 1e6 / cols5 / wps, p, p * 1e6 / cols5 / wps, p / a);
+        }
         { const double cols = (double)nwords * 16; const double waves = (double)blocks * 4;
           float m0 = time_ms([&] { hipLaunchKernelGGL(k_body<0>, dim3(blocks), dim3(256), 0, 0, out, tpk, nwords, 7u); });
           float m1 = time_ms([&] { hipLaunchKernelGGL(k_body<1>, dim3(blocks), dim3(256), 0, 0, out, tpk, nwords, 7u); });
