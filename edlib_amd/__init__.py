@@ -4,8 +4,9 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 ``getNiceAlignment()`` have the same arguments, defaults, result dictionary and
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
-``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``find_all()``, ``reverse_complement()`` and the resident
-``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` sessions over include/edlib_amd.h.
+``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``align_windows()`` / ``find_all()``,
+``reverse_complement()`` and the resident ``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` /
+``WindowBatch`` sessions over include/edlib_amd.h.
 
 There is no CPU path in here: everything calls ``libedlib.so`` (built by
 ``__graft_entry__.build()`` / ``make``), and a missing library or a missing GPU
@@ -80,8 +81,16 @@ class StrandView(C.Structure):           # edlib_amd.h EdlibAmdStrandView
     _fields_ = [("numUnits", C.c_int), ("strand", C.POINTER(C.c_ubyte)), ("bothStrands", C.POINTER(C.c_ubyte))]
 
 
+class WindowView(C.Structure):           # edlib_amd.h EdlibAmdWindowView
+    _fields_ = [("numUnits", C.c_int), ("numQueries", C.c_int)] + [
+        (f, C.POINTER(C.c_int)) for f in ("editDistance", "numLocations", "endLocation",
+                                          "bestUnit", "bestDistance", "secondDistance")]
+
+
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
 CROSS_BEST = 2                            # EDLIB_AMD_CROSS_BEST
+WINDOW_UNITS = 1                          # EDLIB_AMD_WINDOW_UNITS
+WINDOW_BEST = 2                           # EDLIB_AMD_WINDOW_BEST
 
 _lib = None
 
@@ -126,6 +135,10 @@ def lib():
         L.edlibAmdBatchCreateCrossHits.restype = C.c_void_p
         L.edlibAmdBatchCreateCrossHits.argtypes = L.edlibAmdBatchCreateCross.argtypes
         L.edlibAmdBatchCrossHits.argtypes = [C.c_void_p, C.POINTER(CrossHits)]
+        L.edlibAmdBatchCreateWindows.restype = C.c_void_p
+        L.edlibAmdBatchCreateWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
+        L.edlibAmdBatchWindowView.argtypes = [C.c_void_p, C.c_int, C.POINTER(WindowView)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -622,6 +635,89 @@ def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hi
         return out
     finally:
         b.close()
+
+
+class WindowBatch(_Batch):
+    """Units over one resident target, distances only (edlibAmdBatchCreateWindows): unit u is query unit_query[u]
+    against target[unit_start[u] : unit_start[u] + unit_length[u]] -- the loop
+    ``for read, (s, e) in candidates: edlib.align(read, ref[s:e], mode)`` as one resident batch that holds the target
+    and every query once.  units() has the three fields of every unit, best() the best unit per query."""
+
+    def __init__(self, queries, target, unit_query, unit_start, unit_length, mode="HW", k=-1,
+                 additionalEqualities=None, device=0):
+        qd, qo = _pack(queries)
+        t = np.frombuffer(target, dtype=np.uint8) if isinstance(target, (bytes, bytearray)) else np.asarray(target, dtype=np.uint8)
+        tlen = len(t)
+        t = np.ascontiguousarray(t) if tlen else np.zeros(1, dtype=np.uint8)
+        uq, us, ul = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (unit_query, unit_start, unit_length))
+        if not (len(uq) == len(us) == len(ul)):
+            raise ValueError("unit_query, unit_start and unit_length differ in length")
+        cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
+        self.numQueries, self.numUnits = len(qo) - 1, len(uq)
+        pad = [a if len(a) else np.zeros(1, dtype=np.int32) for a in (uq, us, ul)]
+        h = lib().edlibAmdBatchCreateWindows(qd.ctypes.data, qo.ctypes.data, self.numQueries, t.ctypes.data, tlen,
+                                             pad[0].ctypes.data, pad[1].ctypes.data, pad[2].ctypes.data, self.numUnits,
+                                             cfg, device)
+        super().__init__(h, self.numUnits, keep)
+
+    def _view(self, what):
+        v = WindowView()
+        if lib().edlibAmdBatchWindowView(self._h, what, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: window view failed: " + last_error())
+        return v
+
+    def units(self, copy=True):
+        """{editDistance, numLocations, endLocation}: int32 arrays [numUnits]; endLocation is the first end location of
+        the unit's call, relative to its window (-1: none).  copy=False: views of the batch's pinned memory, valid
+        until its next run() / close()."""
+        v = self._view(WINDOW_UNITS)
+        return {f: CrossBatch._arr(getattr(v, f), (self.numUnits,), copy)
+                for f in ("editDistance", "numLocations", "endLocation")}
+
+    def best(self, copy=True):
+        """{bestUnit, bestDistance, secondDistance}: int32 arrays [numQueries] over the units that name each query; ties
+        go to the lowest unit index, -1 where the query has no unit within k."""
+        v = self._view(WINDOW_BEST)
+        return {f: CrossBatch._arr(getattr(v, f), (self.numQueries,), copy)
+                for f in ("bestUnit", "bestDistance", "secondDistance")}
+
+    def results(self, raw=True):
+        raise RuntimeError("edlib_amd: a window batch has no per-unit result records: use units() / best()")
+
+
+def align_windows(queries, target, unit_query, unit_start, unit_length, mode="HW", k=-1, additionalEqualities=None):
+    """[align(queries[q], target[s:s + n], mode) for q, s, n in zip(unit_query, unit_start, unit_length)] in one device
+    batch: the units() and best() arrays of WindowBatch in one dictionary."""
+    b = WindowBatch(queries, target, unit_query, unit_start, unit_length, mode, k, additionalEqualities)
+    try:
+        b.run()
+        out = b.units()
+        out.update(b.best())
+        return out
+    finally:
+        b.close()
+
+
+def window_best_model(unit_query, ed, numQueries):
+    """The best-unit rules of a window batch stated in numpy (what WindowBatch.best() must equal): per query, over the
+    units that name it and are within k (ed != -1), the smallest key (distance << 32) | unit index is the best; the
+    second distance is the smallest distance over the query's other units; -1 where there is none."""
+    uq = np.asarray(unit_query, dtype=np.int64).reshape(-1)
+    ed = np.asarray(ed, dtype=np.int64).reshape(-1)
+    out = {f: np.full(numQueries, -1, dtype=np.int32) for f in ("bestUnit", "bestDistance", "secondDistance")}
+    hit = np.nonzero(ed >= 0)[0]
+    key = (ed[hit] << 32) | hit
+    order = np.lexsort((key, uq[hit]))                  # by query, then by key
+    q, key = uq[hit][order], key[order]
+    first = np.ones(len(q), dtype=bool)
+    first[1:] = q[1:] != q[:-1]
+    lead = np.nonzero(first)[0]
+    out["bestUnit"][q[lead]] = key[lead] & 0xffffffff
+    out["bestDistance"][q[lead]] = key[lead] >> 32
+    has2 = lead + 1 < len(q)
+    has2[has2] = q[lead[has2] + 1] == q[lead[has2]]
+    out["secondDistance"][q[lead[has2]]] = key[lead[has2] + 1] >> 32
+    return out
 
 
 def find_all(queries, target, k, additionalEqualities=None):

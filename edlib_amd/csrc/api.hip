@@ -16,16 +16,24 @@
 
 using namespace edlib_amd;
 
-struct EdlibAmdBatch { Batch impl; std::unique_ptr<CrossBatch> cross; };      // cross: a cross batch (impl unused)
+// cross: a cross batch, windows: a window batch (impl unused by both)
+struct EdlibAmdBatch { Batch impl; std::unique_ptr<CrossBatch> cross; std::unique_ptr<WindowBatch> windows; };
+
+static int not_on_windows(EdlibAmdBatch* b, const char* what) {
+    if (!b->windows) return 0;
+    set_error("%s: not available on a window batch (edlibAmdBatchWindowView has its results)", what);
+    return 1;
+}
 
 static int not_on_cross(EdlibAmdBatch* b, const char* what) {
+    if (not_on_windows(b, what)) return 1;
     if (!b->cross) return 0;
     set_error("%s: not available on a cross batch (edlibAmdBatchCrossView has its results)", what);
     return 1;
 }
 
 static int not_on_hits(EdlibAmdBatch* b, const char* what) {
-    if (b->cross || !b->impl.isHits()) return 0;
+    if (b->cross || b->windows || !b->impl.isHits()) return 0;
     set_error("%s: not available on a hit-list read batch (edlibAmdBatchSharedHits has its results)", what);
     return 1;
 }
@@ -193,6 +201,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedHits(const char* queries, cons
 
 EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* b, EdlibAmdReadHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_windows(b, "edlibAmdBatchSharedHits")) return EDLIB_STATUS_ERROR;
     if (b->cross) { set_error("edlibAmdBatchSharedHits: not a hit-list read batch (a cross batch has edlibAmdBatchCrossHits)"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSharedHits", 1, [&] { return b->impl.hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
@@ -241,19 +250,48 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHits(const char* queries, const
 
 EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* b, int what, EdlibAmdCrossView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_windows(b, "edlibAmdBatchCrossView")) return EDLIB_STATUS_ERROR;
     if (!b->cross) { set_error("edlibAmdBatchCrossView: not a cross batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchCrossView", 1, [&] { return b->cross->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_windows(b, "edlibAmdBatchCrossHits")) return EDLIB_STATUS_ERROR;
     if (!b->cross) { set_error("edlibAmdBatchCrossHits: not a cross batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchCrossHits", 1, [&] { return b->cross->hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(const char* queries, const long long* queryOffsets, int numQueries,
+                                                    const char* target, int targetLength, const int* unitQuery,
+                                                    const int* unitStart, const int* unitLength, int numUnits,
+                                                    EdlibAlignConfig config, int device) {
+    const char* where = "edlibAmdBatchCreateWindows";
+    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
+        EdlibAmdBatch* x = new EdlibAmdBatch;
+        x->windows.reset(new WindowBatch);
+        return x;
+    });
+    if (!b) return nullptr;
+    if (guarded(where, 1, [&] {
+            return b->windows->init(queries, queryOffsets, numQueries, target, targetLength, unitQuery, unitStart,
+                                    unitLength, numUnits, config, device); })) {
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* b, int what, EdlibAmdWindowView* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->windows) { set_error("edlibAmdBatchWindowView: not a window batch"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchWindowView", 1, [&] { return b->windows->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchRun(EdlibAmdBatch* b) {
     if (!b) { set_error("null batch"); return EDLIB_STATUS_ERROR; }
-    return guarded("edlibAmdBatchRun", 1, [&] { return b->cross ? b->cross->run() : b->impl.run(); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+    return guarded("edlibAmdBatchRun", 1, [&] {
+               return b->windows ? b->windows->run() : b->cross ? b->cross->run() : b->impl.run(); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchResults(EdlibAmdBatch* b, EdlibAlignResult* results) {
@@ -296,6 +334,7 @@ EDLIB_API void edlibAmdTrim(void) { (void)guarded("edlibAmdTrim", 0, [] { pool_t
 
 EDLIB_API int edlibAmdBatchStats(EdlibAmdBatch* b, EdlibAmdBatchStats* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (b->windows) { *out = b->windows->stats; return EDLIB_STATUS_OK; }
     if (b->cross) { *out = b->cross->stats; return EDLIB_STATUS_OK; }
     (void)guarded("edlibAmdBatchStats", 0, [&] { b->impl.finishStats(); return 0; });
     *out = b->impl.stats;

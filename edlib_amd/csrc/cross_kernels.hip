@@ -3,6 +3,7 @@
 // over its target; a wave is a tile of qt queries x 64 / qt targets, holds the Peq rows of its queries in LDS and strides
 // over the target tiles.
 #include "cross_kernels.hpp"
+#include "cross_column.hpp"
 
 namespace edlib_amd {
 
@@ -48,32 +49,7 @@ hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, 
 
 // ------------------------------------------------------------------- scan
 
-// One column of Myers' bit-vector recurrence over the NWD words of a lane (reference calculateBlock, edlib.cpp:422-460, on
-// 32-row words, the horizontal delta carried from word to word).  The top row's delta is 0 for HW, +1 for NW / SHW.
-// Returns nothing; `score` follows the bottom row m - 1 (bit sh of the last word).
-template <int NWD, int MODE>
-__device__ __forceinline__ void cross_column(const u32* __restrict__ rows, int stride, u32 (&Pv)[NWD], u32 (&Mv)[NWD],
-                                             const int sh, int& score)
-{
-    u32 hinPos = MODE == 2 ? 0u : 1u, hinNeg = 0u;
-#pragma unroll
-    for (int d = 0; d < NWD; ++d) {
-        u32 eq = rows[d * stride];
-        const u32 xv = eq | Mv[d];
-        eq |= hinNeg;
-        const u32 pv = Pv[d];
-        const u32 xh = (((eq & pv) + pv) ^ pv) | eq;
-        u32 ph = Mv[d] | ~(xh | pv);
-        u32 mh = pv & xh;
-        if (d == NWD - 1) score += (int)((ph >> sh) & 1u) - (int)((mh >> sh) & 1u);
-        const u32 hop = ph >> 31, hom = mh >> 31;
-        ph = (ph << 1) | hinPos;
-        mh = (mh << 1) | hinNeg;
-        Pv[d] = mh | ~(xv | ph);
-        Mv[d] = ph & xv;
-        hinPos = hop; hinNeg = hom;
-    }
-}
+// The column is cross_column<NWD, MODE> (cross_column.hpp, shared with the window kernel).
 
 // HITS: the epilogue appends the cells within k to the hit list (one 64-bit atomicAdd per target-tile step of a wave that
 // has any) instead of writing the matrix.  Every lane reaches it with a flag: padding slots and target slots past the end

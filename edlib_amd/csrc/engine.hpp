@@ -8,6 +8,7 @@
 #include "lanepair.hpp"
 #include "reads_kernels.hpp"
 #include "cross_kernels.hpp"
+#include "window_kernels.hpp"
 #include "strands.hpp"
 
 #include <chrono>
@@ -519,6 +520,54 @@ private:
     int scanGroups();
     int growHits(long long cap);
     int finishHits();
+};
+
+// Units over one resident target (engine_windows.hip, DESIGN.md "Window batches"): unit u is query unitQuery[u] against
+// the window [unitStart[u], unitStart[u] + unitLength[u]) of the target, DISTANCE only, a cross batch's cell contract per
+// unit and the best unit per query, both made on the device.  The target is packed once and every query's Peq is built
+// once per Run whatever the number of units that name them; units outside the window kernel's envelope (query above 256
+// bases, window above 65,536 columns, more than 16 target symbols) run through one internal pair Batch over slices
+// materialised at Create and are scattered into the unit arrays.
+class WindowBatch {
+public:
+    ~WindowBatch();
+    int init(const char* queries, const long long* qoff, int nq, const char* target, int targetLength,
+             const int* unitQuery, const int* unitStart, const int* unitLength, int numUnits,
+             EdlibAlignConfig cfg, int device);
+    int run();
+    int view(int what, EdlibAmdWindowView* out);
+    EdlibAmdBatchStats stats{};
+
+private:
+    struct Group {
+        int words = 0, slots = 0, numSorted = 0;
+        long long wordSteps = 0;                  // word-steps of its scanned units (not the empty or the NW-skipped ones)
+        DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;          // per query slot
+        DevBuf<uint32_t> d_peq;
+        DevBuf<int> d_uslot, d_ustart, d_ulen, d_uperm;        // per unit, sorted by window length
+    };
+    EdlibAlignConfig cfg_{};
+    std::vector<EdlibEqualityPair> eqs_;
+    int device_ = 0, nq_ = 0, nu_ = 0, targetLength_ = 0, syms_ = 4;
+    hipStream_t stream_ = nullptr;
+    Tables tab_;
+    std::vector<std::unique_ptr<Group>> groups_;
+    DevBuf<uint8_t> d_qpool_;
+    DevBuf<long long> d_qoff_;
+    DevBuf<uint16_t> d_eqtbl_;
+    DevBuf<uint32_t> d_presence_, d_tpk_;
+    DevBuf<int> d_uq_;                            // [nu] query of every unit (the best reduction)
+    DevBuf<int> d_units_;                         // [3][nu]: editDistance, numLocations, endLocation
+    DevBuf<int> d_best_;                          // [3][nq]
+    DevBuf<unsigned long long> d_bkey_;           // [2][nq]
+    // units outside the kernel's envelope: one pair Batch over their materialised slices
+    std::unique_ptr<Batch> pairs_;
+    std::vector<long long> pairUnits_;
+    DevBuf<long long> d_cells_; DevBuf<int> d_vals_; PinBuf h_vals_;
+    Event evScan0_, evScan1_;
+    PinBuf h_units_, h_best_;
+    long long cellsSum_ = 0;
+    bool haveRun_ = false, unitsFetched_ = false, bestFetched_ = false;
 };
 
 // single-pair convenience used by edlibAlign()

@@ -248,6 +248,50 @@ typedef struct {
 } EdlibAmdReadHits;
 EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* batch, EdlibAmdReadHits* out);
 
+/* numUnits units over ONE resident target (a window batch): unit u is query unitQuery[u] against the window
+ * target[unitStart[u] .. unitStart[u] + unitLength[u]).  Replaces
+ *   for u: r[u] = edlibAlign(query(unitQuery[u]), .., target + unitStart[u], unitLength[u], config)
+ * (the verification step of a seed-and-extend mapper: a read against a few candidate loci of one reference) without
+ * replicating a byte of the target or of a query: the target is uploaded and packed once, every query once, and the
+ * units are three ints each.  config.task must be EDLIB_TASK_DISTANCE (for locations or paths align the chosen units
+ * with a pair batch, as for cross batches); NW, SHW and HW, any k, additionalEqualities.
+ * Create returns NULL, with the limit named in edlibAmdLastError(), for another task, numUnits < 0, and for a unit with
+ * unitQuery outside [0, numQueries), unitStart < 0, unitLength < 0 or unitStart + unitLength > targetLength (the message
+ * names the first such unit); these are checked before the device is.  numUnits == 0 is a valid batch.
+ * Units of queries up to 256 bases against windows up to 65,536 columns of a target with at most 16 distinct symbols
+ * run on the window kernel.  Every other unit runs through one internal pair batch over slices copied at Create: that
+ * route DOES replicate bytes -- right for a handful of long reads, and for a protein target the cost of a pair batch.
+ * Run, Stats and Destroy work as for the other batches (Stats.path bit 4: the window kernel, bit 1: the internal pair
+ * batch ran; Stats.cells the sum of queryLength * unitLength); Results, ResultsFlat, ResultsView, CigarView, StrandView,
+ * CrossView, CrossHits and SharedHits fail. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* target, int targetLength,
+    const int* unitQuery, const int* unitStart, const int* unitLength, int numUnits,
+    EdlibAlignConfig config, int device);
+
+/* Results of the last Run of a window batch (it fails on every other kind, and before the first Run), as pointers into
+ * pinned host memory the batch owns (valid until the next Run / Destroy).  Only the parts asked for in `what`
+ * (EDLIB_AMD_WINDOW_UNITS | EDLIB_AMD_WINDOW_BEST) cross the link; the others are NULL.
+ * Unit u equals its edlibAlign() call above in editDistance (-1: above k), numLocations and the first end location (-1
+ * when there is none) -- the contract of a cross batch's cell.  End locations are WINDOW-relative, as that call returns
+ * them: add unitStart[u] to a non-negative one for the target coordinate.
+ * Best per query, over the units that name it: the smallest (distance << 32) | unit index wins, so ties go to the lowest
+ * unit index; secondDistance is the smallest distance over the query's other units (equal to the best on a tie); a query
+ * with no unit within k, or no unit at all, has -1 in all three. */
+typedef struct {
+    int numUnits, numQueries;
+    const int* editDistance;     /* [numUnits] -1: above k                                   */
+    const int* numLocations;     /* [numUnits]                                               */
+    const int* endLocation;      /* [numUnits] endLocations[0] of that call, WINDOW-relative */
+    const int* bestUnit;         /* [numQueries] */
+    const int* bestDistance;     /* [numQueries] */
+    const int* secondDistance;   /* [numQueries] */
+} EdlibAmdWindowView;
+#define EDLIB_AMD_WINDOW_UNITS 1
+#define EDLIB_AMD_WINDOW_BEST  2
+EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* batch, int what, EdlibAmdWindowView* out);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
@@ -264,7 +308,7 @@ typedef struct {
     long long cells;        /* sum over units of queryLength * targetLength (GCUPS numerator)*/
     long long word_steps;   /* 32-row word-column updates the scan kernels executed          */
     long long algo_bytes;   /* algorithmic bytes: target+query+Peq+results    */
-    int path;               /* bit 0 reads-per-lane kernel, bit 1 block-per-lane kernel, bit 2 piece filter (long HW reads), bit 3 cross kernel */
+    int path;               /* bit 0 reads-per-lane kernel, bit 1 block-per-lane kernel, bit 2 piece filter (long HW reads), bit 3 cross kernel, bit 4 (value 16) window kernel */
     int overflow_units;     /* units whose end-location list needed the exact second pass    */
     int wide_retries;       /* launches of the many-wave kernel that gave up (not resident together / stalled) and were run again with one slot per unit */
 } EdlibAmdBatchStats;
