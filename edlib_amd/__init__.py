@@ -5,7 +5,7 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
 ``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``align_windows()`` / ``find_all()``,
-``reverse_complement()`` and the resident ``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` /
+``reverse_complement()``, ``cross_strands_model()`` and the resident ``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` /
 ``WindowBatch`` sessions over include/edlib_amd.h.
 
 There is no CPU path in here: everything calls ``libedlib.so`` (built by
@@ -72,6 +72,11 @@ class CrossHits(C.Structure):            # edlib_amd.h EdlibAmdCrossHits
         (f, C.POINTER(C.c_int)) for f in ("query", "editDistance", "numLocations", "endLocation")]
 
 
+class CrossStrands(C.Structure):         # edlib_amd.h EdlibAmdCrossStrands
+    _fields_ = [("numQueries", C.c_int), ("numTargets", C.c_int), ("numHits", C.c_longlong)] + [
+        (f, C.POINTER(C.c_ubyte)) for f in ("cellStrand", "hitStrand", "bestQueryStrand", "bestTargetStrand")]
+
+
 class ReadHits(C.Structure):             # edlib_amd.h EdlibAmdReadHits
     _fields_ = [("numUnits", C.c_int), ("numHits", C.c_longlong), ("unitOffsets", C.POINTER(C.c_longlong))] + [
         (f, C.POINTER(C.c_int)) for f in ("firstEnd", "lastEnd", "editDistance", "endLocation", "numLocations")]
@@ -135,9 +140,22 @@ def lib():
         L.edlibAmdBatchCreateCrossHits.restype = C.c_void_p
         L.edlibAmdBatchCreateCrossHits.argtypes = L.edlibAmdBatchCreateCross.argtypes
         L.edlibAmdBatchCrossHits.argtypes = [C.c_void_p, C.POINTER(CrossHits)]
+        # the both-strand entry points are bound where the library has them: an older build named by EDLIB_AMD_LIB
+        # serves every other call, and these raise AttributeError where they are asked for
+        if hasattr(L, "edlibAmdBatchCrossStrands"):
+            L.edlibAmdBatchCreateCrossBothStrands.restype = C.c_void_p
+            L.edlibAmdBatchCreateCrossBothStrands.argtypes = L.edlibAmdBatchCreateCross.argtypes
+            L.edlibAmdBatchCreateCrossHitsBothStrands.restype = C.c_void_p
+            L.edlibAmdBatchCreateCrossHitsBothStrands.argtypes = L.edlibAmdBatchCreateCross.argtypes
+            L.edlibAmdBatchCrossStrands.argtypes = [C.c_void_p, C.c_int, C.POINTER(CrossStrands)]
         L.edlibAmdBatchCreateWindows.restype = C.c_void_p
         L.edlibAmdBatchCreateWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
+        if hasattr(L, "edlibAmdBatchCreateWindowsStranded"):
+            L.edlibAmdBatchCreateWindowsStranded.restype = C.c_void_p
+            L.edlibAmdBatchCreateWindowsStranded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                             AlignConfig, C.c_int]
         L.edlibAmdBatchWindowView.argtypes = [C.c_void_p, C.c_int, C.POINTER(WindowView)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
@@ -557,15 +575,27 @@ class CrossBatch(_Batch):
     """Every query against every target, distances only (edlibAmdBatchCreateCross): the loop
     ``for t in targets: for q in queries: edlib.align(q, t, mode)`` as one resident batch.  Results come as a
     matrix of shape (numTargets, numQueries) and as best hits per target and per query.
-    hits=True (edlibAmdBatchCreateCrossHits, k >= 0): no matrix; hits() lists the cells within k per target."""
+    hits=True (edlibAmdBatchCreateCrossHits, k >= 0): no matrix; hits() lists the cells within k per target.
+    strands="both" (edlibAmdBatchCreateCrossBothStrands / ...HitsBothStrands): every cell is the better of the query and
+    its reverse complement against the target (ties: forward); matrix(), hits() and best() describe these combined
+    cells, and strands() says which strand each reports."""
 
-    def __init__(self, queries, targets, mode="HW", k=-1, additionalEqualities=None, device=0, hits=False):
+    both_strands = False
+
+    def __init__(self, queries, targets, mode="HW", k=-1, additionalEqualities=None, device=0, hits=False,
+                 strands="forward"):
+        if strands not in ("forward", "both"):
+            raise ValueError("strands must be 'forward' or 'both'")
         qd, qo = _pack(queries)
         td, to = _pack(targets)
         cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
         self.numQueries, self.numTargets = len(qo) - 1, len(to) - 1
         self.is_hits = bool(hits)
-        create = lib().edlibAmdBatchCreateCrossHits if hits else lib().edlibAmdBatchCreateCross
+        self.both_strands = strands == "both"
+        if self.both_strands:
+            create = lib().edlibAmdBatchCreateCrossHitsBothStrands if hits else lib().edlibAmdBatchCreateCrossBothStrands
+        else:
+            create = lib().edlibAmdBatchCreateCrossHits if hits else lib().edlibAmdBatchCreateCross
         h = create(qd.ctypes.data, qo.ctypes.data, self.numQueries, td.ctypes.data, to.ctypes.data, self.numTargets,
                    cfg, device)
         super().__init__(h, self.numQueries * self.numTargets, keep)
@@ -620,18 +650,47 @@ class CrossBatch(_Batch):
             out[f] = self._arr(getattr(v, f), (n,), copy) if n else np.zeros(0, dtype=np.int32)
         return out
 
+    def strands(self, copy=True, cells=True):
+        """The strand bytes of a strands="both" batch (edlibAmdBatchCrossStrands), uint8: cellStrand of shape
+        (numTargets, numQueries) -- or hitStrand [numHits], in the order of hits(), for a hits=True batch -- and
+        bestQueryStrand [numTargets] / bestTargetStrand [numQueries] for the best() hits.  Bit 0: the cell reports the
+        reverse complement; bit 1: the other strand reaches the same distance; 0 where the cell or the best is -1.
+        cells=False: only the two best arrays cross the link."""
+        if not self.both_strands:
+            raise RuntimeError("edlib_amd: not a both-strand cross batch: create it with strands='both'")
+        v = CrossStrands()
+        if lib().edlibAmdBatchCrossStrands(self._h, (CROSS_MATRIX if cells else 0) | CROSS_BEST, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: cross strands failed: " + last_error())
+
+        def arr(ptr, shape):
+            if not ptr or int(np.prod(shape)) == 0:
+                return np.zeros(shape, dtype=np.uint8)
+            a = np.ctypeslib.as_array(ptr, shape=shape)
+            return a.copy() if copy else a
+        out = {}
+        if cells and self.is_hits:
+            out["hitStrand"] = arr(v.hitStrand, (int(v.numHits),))
+        elif cells:
+            out["cellStrand"] = arr(v.cellStrand, (self.numTargets, self.numQueries))
+        out["bestQueryStrand"] = arr(v.bestQueryStrand, (self.numTargets,))
+        out["bestTargetStrand"] = arr(v.bestTargetStrand, (self.numQueries,))
+        return out
+
     def results(self, raw=True):
         raise RuntimeError("edlib_amd: a cross batch has no per-unit results: use matrix() / best()")
 
 
-def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hits=False):
+def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hits=False, strands="forward"):
     """Every query against every target in one device batch: the matrix() arrays (shape (numTargets, numQueries))
-    and the best() arrays of CrossBatch in one dictionary; hits=True (k >= 0): the hits() arrays instead of the matrix."""
-    b = CrossBatch(queries, targets, mode, k, additionalEqualities, hits=hits)
+    and the best() arrays of CrossBatch in one dictionary; hits=True (k >= 0): the hits() arrays instead of the matrix;
+    strands="both": the cells combine both strands of every query and the strands() arrays are merged in."""
+    b = CrossBatch(queries, targets, mode, k, additionalEqualities, hits=hits, strands=strands)
     try:
         b.run()
         out = b.hits() if hits else b.matrix()
         out.update(b.best())
+        if b.both_strands:
+            out.update(b.strands())
         return out
     finally:
         b.close()
@@ -641,10 +700,12 @@ class WindowBatch(_Batch):
     """Units over one resident target, distances only (edlibAmdBatchCreateWindows): unit u is query unit_query[u]
     against target[unit_start[u] : unit_start[u] + unit_length[u]] -- the loop
     ``for read, (s, e) in candidates: edlib.align(read, ref[s:e], mode)`` as one resident batch that holds the target
-    and every query once.  units() has the three fields of every unit, best() the best unit per query."""
+    and every query once.  units() has the three fields of every unit, best() the best unit per query.
+    unit_strand (edlibAmdBatchCreateWindowsStranded): 0 / 1 per unit, 1 = the unit is the reverse complement of its query
+    against the window; best() runs over all units of a query whatever their strand."""
 
     def __init__(self, queries, target, unit_query, unit_start, unit_length, mode="HW", k=-1,
-                 additionalEqualities=None, device=0):
+                 additionalEqualities=None, device=0, unit_strand=None):
         qd, qo = _pack(queries)
         t = np.frombuffer(target, dtype=np.uint8) if isinstance(target, (bytes, bytearray)) else np.asarray(target, dtype=np.uint8)
         tlen = len(t)
@@ -655,9 +716,18 @@ class WindowBatch(_Batch):
         cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
         self.numQueries, self.numUnits = len(qo) - 1, len(uq)
         pad = [a if len(a) else np.zeros(1, dtype=np.int32) for a in (uq, us, ul)]
-        h = lib().edlibAmdBatchCreateWindows(qd.ctypes.data, qo.ctypes.data, self.numQueries, t.ctypes.data, tlen,
-                                             pad[0].ctypes.data, pad[1].ctypes.data, pad[2].ctypes.data, self.numUnits,
-                                             cfg, device)
+        if unit_strand is None:
+            h = lib().edlibAmdBatchCreateWindows(qd.ctypes.data, qo.ctypes.data, self.numQueries, t.ctypes.data, tlen,
+                                                 pad[0].ctypes.data, pad[1].ctypes.data, pad[2].ctypes.data,
+                                                 self.numUnits, cfg, device)
+        else:
+            st = np.ascontiguousarray(unit_strand, dtype=np.uint8).reshape(-1)
+            if len(st) != len(uq):
+                raise ValueError("unit_strand and unit_query differ in length")
+            st = st if len(st) else np.zeros(1, dtype=np.uint8)
+            h = lib().edlibAmdBatchCreateWindowsStranded(qd.ctypes.data, qo.ctypes.data, self.numQueries, t.ctypes.data,
+                                                         tlen, pad[0].ctypes.data, pad[1].ctypes.data,
+                                                         pad[2].ctypes.data, st.ctypes.data, self.numUnits, cfg, device)
         super().__init__(h, self.numUnits, keep)
 
     def _view(self, what):
@@ -685,10 +755,13 @@ class WindowBatch(_Batch):
         raise RuntimeError("edlib_amd: a window batch has no per-unit result records: use units() / best()")
 
 
-def align_windows(queries, target, unit_query, unit_start, unit_length, mode="HW", k=-1, additionalEqualities=None):
+def align_windows(queries, target, unit_query, unit_start, unit_length, mode="HW", k=-1, additionalEqualities=None,
+                  unit_strand=None):
     """[align(queries[q], target[s:s + n], mode) for q, s, n in zip(unit_query, unit_start, unit_length)] in one device
-    batch: the units() and best() arrays of WindowBatch in one dictionary."""
-    b = WindowBatch(queries, target, unit_query, unit_start, unit_length, mode, k, additionalEqualities)
+    batch: the units() and best() arrays of WindowBatch in one dictionary.  unit_strand: 1 where the unit is
+    reverse_complement(queries[q]) against its window."""
+    b = WindowBatch(queries, target, unit_query, unit_start, unit_length, mode, k, additionalEqualities,
+                    unit_strand=unit_strand)
     try:
         b.run()
         out = b.units()
@@ -718,6 +791,20 @@ def window_best_model(unit_query, ed, numQueries):
     has2[has2] = q[lead[has2] + 1] == q[lead[has2]]
     out["secondDistance"][q[lead[has2]]] = key[lead[has2] + 1] >> 32
     return out
+
+
+def cross_strands_model(fwd, rev):
+    """The strand rule of a both-strand cross batch stated in numpy (what its cells must equal): fwd / rev are dictionaries
+    of editDistance / numLocations / endLocation arrays of one shape, the cells of the queries and of their reverse
+    complements.  The forward cell is reported where it is within k and not worse than the reverse one (ties go
+    forward) and where neither is within k; the reverse cell elsewhere.  Returns (cells, strand): the three combined
+    arrays, and uint8 strand bytes -- bit 0 the reverse complement is reported, bit 1 both strands reach the distance."""
+    df, dr = (np.asarray(x["editDistance"]) for x in (fwd, rev))
+    take_rev = (dr >= 0) & ((df < 0) | (dr < df))
+    cells = {f: np.where(take_rev, np.asarray(rev[f]), np.asarray(fwd[f])).astype(np.int32)
+             for f in ("editDistance", "numLocations", "endLocation")}
+    strand = take_rev.astype(np.uint8) | (((df >= 0) & (df == dr)).astype(np.uint8) << 1)
+    return cells, strand
 
 
 def find_all(queries, target, k, additionalEqualities=None):

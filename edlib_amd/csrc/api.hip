@@ -208,6 +208,11 @@ EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* b, EdlibAmdReadHits* out) {
 
 EDLIB_API int edlibAmdBatchStrandView(EdlibAmdBatch* b, EdlibAmdStrandView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (b->cross && b->cross->bothStrands()) {
+        set_error("edlibAmdBatchStrandView: not available on a cross batch (edlibAmdBatchCrossStrands has the strands of a "
+                  "both-strand cross batch)");
+        return EDLIB_STATUS_ERROR;
+    }
     if (not_on_cross(b, "edlibAmdBatchStrandView") || not_on_hits(b, "edlibAmdBatchStrandView")) return EDLIB_STATUS_ERROR;
     return guarded("edlibAmdBatchStrandView", 1, [&] { return b->impl.strandView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
@@ -218,7 +223,7 @@ EDLIB_API void edlibAmdReverseComplement(const char* in, int n, char* out) {
 
 static EdlibAmdBatch* create_cross(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
                                    const char* targets, const long long* targetOffsets, int numTargets,
-                                   EdlibAlignConfig config, int device, bool hits) {
+                                   EdlibAlignConfig config, int device, bool hits, bool strands = false) {
     EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
         EdlibAmdBatch* x = new EdlibAmdBatch;
         x->cross.reset(new CrossBatch);
@@ -227,7 +232,7 @@ static EdlibAmdBatch* create_cross(const char* where, const char* queries, const
     if (!b) return nullptr;
     if (guarded(where, 1, [&] {
             return b->cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device,
-                                  hits); })) {
+                                  hits, strands); })) {
         delete b;
         return nullptr;
     }
@@ -248,6 +253,32 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHits(const char* queries, const
                         numTargets, config, device, true);
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossBothStrands(const char* queries, const long long* queryOffsets,
+                                                             int numQueries, const char* targets,
+                                                             const long long* targetOffsets, int numTargets,
+                                                             EdlibAlignConfig config, int device) {
+    return create_cross("edlibAmdBatchCreateCrossBothStrands", queries, queryOffsets, numQueries, targets, targetOffsets,
+                        numTargets, config, device, false, true);
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHitsBothStrands(const char* queries, const long long* queryOffsets,
+                                                                 int numQueries, const char* targets,
+                                                                 const long long* targetOffsets, int numTargets,
+                                                                 EdlibAlignConfig config, int device) {
+    return create_cross("edlibAmdBatchCreateCrossHitsBothStrands", queries, queryOffsets, numQueries, targets,
+                        targetOffsets, numTargets, config, device, true, true);
+}
+
+EDLIB_API int edlibAmdBatchCrossStrands(EdlibAmdBatch* b, int what, EdlibAmdCrossStrands* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_windows(b, "edlibAmdBatchCrossStrands")) return EDLIB_STATUS_ERROR;
+    if (!b->cross) {
+        set_error("edlibAmdBatchCrossStrands: not a both-strand cross batch (a both-strand read batch has edlibAmdBatchStrandView)");
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchCrossStrands", 1, [&] { return b->cross->strandsView(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* b, int what, EdlibAmdCrossView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
     if (not_on_windows(b, "edlibAmdBatchCrossView")) return EDLIB_STATUS_ERROR;
@@ -262,11 +293,10 @@ EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
     return guarded("edlibAmdBatchCrossHits", 1, [&] { return b->cross->hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
-EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(const char* queries, const long long* queryOffsets, int numQueries,
-                                                    const char* target, int targetLength, const int* unitQuery,
-                                                    const int* unitStart, const int* unitLength, int numUnits,
-                                                    EdlibAlignConfig config, int device) {
-    const char* where = "edlibAmdBatchCreateWindows";
+static EdlibAmdBatch* create_windows(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
+                                     const char* target, int targetLength, const int* unitQuery, const int* unitStart,
+                                     const int* unitLength, const unsigned char* unitStrand, int numUnits,
+                                     EdlibAlignConfig config, int device) {
     EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
         EdlibAmdBatch* x = new EdlibAmdBatch;
         x->windows.reset(new WindowBatch);
@@ -275,11 +305,28 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(const char* queries, const l
     if (!b) return nullptr;
     if (guarded(where, 1, [&] {
             return b->windows->init(queries, queryOffsets, numQueries, target, targetLength, unitQuery, unitStart,
-                                    unitLength, numUnits, config, device); })) {
+                                    unitLength, unitStrand, numUnits, config, device); })) {
         delete b;
         return nullptr;
     }
     return b;
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(const char* queries, const long long* queryOffsets, int numQueries,
+                                                    const char* target, int targetLength, const int* unitQuery,
+                                                    const int* unitStart, const int* unitLength, int numUnits,
+                                                    EdlibAlignConfig config, int device) {
+    return create_windows("edlibAmdBatchCreateWindows", queries, queryOffsets, numQueries, target, targetLength, unitQuery,
+                          unitStart, unitLength, nullptr, numUnits, config, device);
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindowsStranded(const char* queries, const long long* queryOffsets,
+                                                            int numQueries, const char* target, int targetLength,
+                                                            const int* unitQuery, const int* unitStart,
+                                                            const int* unitLength, const unsigned char* unitStrand,
+                                                            int numUnits, EdlibAlignConfig config, int device) {
+    return create_windows("edlibAmdBatchCreateWindowsStranded", queries, queryOffsets, numQueries, target, targetLength,
+                          unitQuery, unitStart, unitLength, unitStrand, numUnits, config, device);
 }
 
 EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* b, int what, EdlibAmdWindowView* out) {

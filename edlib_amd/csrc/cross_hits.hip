@@ -43,7 +43,8 @@ hipError_t launch_cross_hits_iota(u32* idx, long long n, hipStream_t stream)
 // out [4][n]: query, editDistance, numLocations, endLocation of sorted hit i
 __global__ void __launch_bounds__(256)
 cross_hits_gather_kernel(const u64* __restrict__ skey, const u32* __restrict__ sidx, const int* __restrict__ val,
-                         long long cap, long long n, int* __restrict__ out)
+                         long long cap, long long n, int* __restrict__ out, const uint8_t* __restrict__ strand,
+                         uint8_t* __restrict__ strandOut)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -52,6 +53,7 @@ cross_hits_gather_kernel(const u64* __restrict__ skey, const u32* __restrict__ s
     out[n + i] = val[j];
     out[2 * n + i] = val[cap + j];
     out[3 * n + i] = val[2 * cap + j];
+    if (strand) strandOut[i] = strand[j];
 }
 
 // targetOffsets[t] = first sorted hit of target t or later (t = numTargets: n)
@@ -93,6 +95,20 @@ cross_hits_best_kernel(const u64* __restrict__ key, const int* __restrict__ ed, 
     }
 }
 
+// both strands: the byte of the hit whose key is the best of its target / of its query (keys differ, so one hit each)
+__global__ void __launch_bounds__(256)
+cross_hits_best_strands_kernel(const u64* __restrict__ key, const int* __restrict__ ed, const uint8_t* __restrict__ strand,
+                               long long n, int numTargets, int numQueries, const u64* __restrict__ bkey,
+                               uint8_t* __restrict__ bestStrand)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = key[i];
+    const int t = (int)(k >> 32), q = (int)(u32)k;
+    if (cross_key(ed[i], q) == bkey[t]) bestStrand[t] = strand[i];
+    if (cross_key(ed[i], t) == bkey[numTargets + q]) bestStrand[numTargets + q] = strand[i];
+}
+
 __global__ void __launch_bounds__(256)
 cross_hits_best_store_kernel(const u64* __restrict__ bkey, int numTargets, int numQueries, int* __restrict__ best)
 {
@@ -109,7 +125,8 @@ cross_hits_best_store_kernel(const u64* __restrict__ bkey, int numTargets, int n
 
 hipError_t launch_cross_hits_finish(const u64* key, const int* val, long long cap, long long n, int numQueries,
                                     int numTargets, const u32* idx, u64* skey, u32* sidx, void* tmp, size_t tmpBytes,
-                                    long long* targetOffsets, int* out, u64* bkey, int* best, hipStream_t stream)
+                                    long long* targetOffsets, int* out, u64* bkey, int* best, const uint8_t* strand,
+                                    uint8_t* strandOut, uint8_t* bestStrand, hipStream_t stream)
 {
     hipError_t e;
     const unsigned nb = (unsigned)((n + 255) / 256);
@@ -117,7 +134,8 @@ hipError_t launch_cross_hits_finish(const u64* key, const int* val, long long ca
         size_t bytes = tmpBytes;
         e = rocprim::radix_sort_pairs(tmp, bytes, key, skey, idx, sidx, (size_t)n, 0u, key_end_bit(numTargets), stream);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(cross_hits_gather_kernel, dim3(nb), dim3(256), 0, stream, skey, sidx, val, cap, n, out);
+        hipLaunchKernelGGL(cross_hits_gather_kernel, dim3(nb), dim3(256), 0, stream, skey, sidx, val, cap, n, out,
+                           strand, strandOut);
     }
     hipLaunchKernelGGL(cross_hits_offsets_kernel, dim3((unsigned)((numTargets + 1 + 255) / 256)), dim3(256), 0, stream,
                        skey, n, numTargets, targetOffsets);
@@ -125,9 +143,16 @@ hipError_t launch_cross_hits_finish(const u64* key, const int* val, long long ca
     if (all == 0) return hipGetLastError();
     e = hipMemsetAsync(bkey, 0xff, 2 * (size_t)all * sizeof(u64), stream);
     if (e != hipSuccess) return e;
+    if (strand) {
+        e = hipMemsetAsync(bestStrand, 0, (size_t)all, stream);
+        if (e != hipSuccess) return e;
+    }
     if (n > 0) {
         hipLaunchKernelGGL(cross_hits_best_kernel<1>, dim3(nb), dim3(256), 0, stream, key, val, n, numTargets, numQueries, bkey);
         hipLaunchKernelGGL(cross_hits_best_kernel<2>, dim3(nb), dim3(256), 0, stream, key, val, n, numTargets, numQueries, bkey);
+        if (strand)
+            hipLaunchKernelGGL(cross_hits_best_strands_kernel, dim3(nb), dim3(256), 0, stream, key, val, strand, n, numTargets,
+                               numQueries, bkey, bestStrand);
     }
     hipLaunchKernelGGL(cross_hits_best_store_kernel, dim3((unsigned)((all + 255) / 256)), dim3(256), 0, stream,
                        bkey, numTargets, numQueries, best);

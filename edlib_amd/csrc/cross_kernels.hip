@@ -2,13 +2,9 @@
 // batches").  A lane owns one (query, target) cell and scans the whole height of its query (at most 8 words of 32 rows)
 // over its target; a wave is a tile of qt queries x 64 / qt targets, holds the Peq rows of its queries in LDS and strides
 // over the target tiles.
-#include "cross_kernels.hpp"
-#include "cross_column.hpp"
+#include "cross_scan.hpp"
 
 namespace edlib_amd {
-
-typedef uint32_t u32;
-typedef unsigned long long u64;
 
 // ------------------------------------------------------------- target pack
 
@@ -49,136 +45,15 @@ hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, 
 
 // ------------------------------------------------------------------- scan
 
-// The column is cross_column<NWD, MODE> (cross_column.hpp, shared with the window kernel).
-
-// HITS: the epilogue appends the cells within k to the hit list (one 64-bit atomicAdd per target-tile step of a wave that
-// has any) instead of writing the matrix.  Every lane reaches it with a flag: padding slots and target slots past the end
-// take part as non-hits.
-template <int NWD, int S, int MODE, bool HITS>
-__global__ void __launch_bounds__(64)
-scan_cross_kernel(CrossScanArgs a)
-{
-    __shared__ u32 s_peq[S * NWD * 64];                 // [symbol][word][query of the tile]
-    const int lane = threadIdx.x;
-    const int qt = a.qt;
-    const int slot0 = blockIdx.x * qt;
-    {
-        // staged once: the wave keeps this query tile for all its target tiles
-        const u32* src = a.peq + (size_t)(slot0 >> 6) * (S * NWD * 64) + (slot0 & 63);
-        for (int i = lane; i < S * NWD * qt; i += 64) {
-            const int r = i / qt;
-            s_peq[i] = src[r * 64 + (i - r * qt)];
-        }
-    }
-    __syncthreads();
-    const int qi = lane & (qt - 1);
-    const int ti = lane / qt;
-    const int tpt = 64 / qt;
-    const int slot = slot0 + qi;
-    const int q = a.qperm[slot];
-    const int m = a.qlen[slot];
-    const int sh = (m - 1) & 31;
-    if (!HITS && q < 0) return;                         // (no barrier or ballot below)
-    const int numTT = (a.numSorted + tpt - 1) / tpt;
-    for (int tt = blockIdx.y; tt < numTT; tt += gridDim.y) {   // wave-uniform trip count
-        const int ts = tt * tpt + ti;
-        const bool live = q >= 0 && ts < a.numSorted;
-        int ed = -1, nloc = 0, end = -1;
-        if (live) {
-            const int n = a.tlen[ts];
-            int score = m, best = 0x7fffffff, cnt = 0, first = -1;
-            if (!cross_nw_outside(MODE, a.kcfg, m, n)) {
-                const u32* __restrict__ tp = a.tpk + a.tdw[ts];
-                u32 Pv[NWD], Mv[NWD];
-#pragma unroll
-                for (int d = 0; d < NWD; ++d) { Pv[d] = ~0u; Mv[d] = 0u; }
-                auto step = [&](u32 c, int j) {
-                    cross_column<NWD, MODE>(s_peq + c * (NWD * qt) + qi, qt, Pv, Mv, sh, score);
-                    if (MODE != 0) {
-                        if (score < best) { best = score; cnt = 1; first = j; }
-                        else if (score == best) ++cnt;
-                    }
-                };
-                int j = 0;
-                for (; j + 8 <= n; j += 8) {
-                    u32 w = tp[j >> 3];
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) { step(w & 15u, j + c); w >>= 4; }
-                }
-                if (j < n) {
-                    u32 w = tp[j >> 3];
-                    for (; j < n; ++j) { step(w & 15u, j); w >>= 4; }
-                }
-            }
-            cross_cell_result(MODE, a.kcfg, m, n, MODE == 0 ? score : best, cnt, first, ed, nloc, end);
-        }
-        if (!HITS) {
-            if (live) {
-                const size_t at = (size_t)a.tperm[ts] * (size_t)a.numQueries + (size_t)q;
-                a.ed[at] = ed; a.nloc[at] = nloc; a.end[at] = end;
-            }
-            continue;
-        }
-        const bool hit = live && ed != -1;
-        const u64 mask = __ballot(hit);
-        if (mask == 0) continue;                        // a sparse batch issues almost no atomics
-        const int leader = __ffsll((long long)mask) - 1;    // a lane with a hit: active
-        u64 base = 0;
-        if (lane == leader) base = atomicAdd(a.hitCount, (u64)__popcll(mask));
-        base = __shfl(base, leader, 64);
-        if (hit) {
-            const u64 at = base + __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
-            if (at < a.hitCap) {
-                a.hitKey[at] = ((u64)(u32)a.tperm[ts] << 32) | (u32)q;
-                a.hitVal[at] = ed; a.hitVal[a.hitCap + at] = nloc; a.hitVal[2 * a.hitCap + at] = end;
-            }
-        }
-    }
-}
-
-template <int NWD, int S, bool HITS>
-static hipError_t launch_scan_cross_ws(int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
-{
-    const dim3 grid((unsigned)a.numQueryTiles, (unsigned)ysplit);
-    if (mode == 0) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 0, HITS>), grid, dim3(64), 0, stream, a);
-    else if (mode == 1) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 1, HITS>), grid, dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 2, HITS>), grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <int NWD, bool HITS>
-static hipError_t launch_scan_cross_w(int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
-{
-    if (syms == 4) return launch_scan_cross_ws<NWD, 4, HITS>(mode, a, ysplit, stream);
-    if (syms == 8) return launch_scan_cross_ws<NWD, 8, HITS>(mode, a, ysplit, stream);
-    return launch_scan_cross_ws<NWD, 16, HITS>(mode, a, ysplit, stream);
-}
-
-template <bool HITS>
-static hipError_t launch_scan_cross_h(int nwords, int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
-{
-    switch (nwords) {
-    case 1: return launch_scan_cross_w<1, HITS>(syms, mode, a, ysplit, stream);
-    case 2: return launch_scan_cross_w<2, HITS>(syms, mode, a, ysplit, stream);
-    case 3: return launch_scan_cross_w<3, HITS>(syms, mode, a, ysplit, stream);
-    case 4: return launch_scan_cross_w<4, HITS>(syms, mode, a, ysplit, stream);
-    case 5: return launch_scan_cross_w<5, HITS>(syms, mode, a, ysplit, stream);
-    case 6: return launch_scan_cross_w<6, HITS>(syms, mode, a, ysplit, stream);
-    case 7: return launch_scan_cross_w<7, HITS>(syms, mode, a, ysplit, stream);
-    case 8: return launch_scan_cross_w<8, HITS>(syms, mode, a, ysplit, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
+// The kernel is scan_cross_kernel (cross_scan.hpp); its both-strand instantiations are in cross_kernels_strands.hip.
 
 hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
                              hipStream_t stream)
 {
-    if (a.numQueryTiles == 0 || a.numSorted == 0) return hipSuccess;
-    if ((syms != 4 && syms != 8 && syms != 16) || mode < 0 || mode > 2 || a.qt < 1 || a.qt > 64 || (64 % a.qt) != 0)
-        return hipErrorInvalidValue;
-    if (hits && (!a.hitCount || !a.hitKey || !a.hitVal)) return hipErrorInvalidValue;
-    return hits ? launch_scan_cross_h<true>(nwords, syms, mode, a, ysplit, stream)
-                : launch_scan_cross_h<false>(nwords, syms, mode, a, ysplit, stream);
+    const int st = cross_scan_args_state(syms, mode, hits, a);
+    if (st) return st > 0 ? hipSuccess : hipErrorInvalidValue;
+    return hits ? launch_scan_cross_h<true, false>(nwords, syms, mode, a, ysplit, stream)
+                : launch_scan_cross_h<false, false>(nwords, syms, mode, a, ysplit, stream);
 }
 
 // -------------------------------------------------------------- best hits
@@ -258,6 +133,34 @@ hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,
     return hipGetLastError();
 }
 
+// the strand bytes of the best cells (both-strand batches): a gather of the strand matrix at the best indices
+__global__ void __launch_bounds__(256)
+cross_best_strands_kernel(const uint8_t* __restrict__ cellStrand, int numQueries, int numTargets,
+                          const int* __restrict__ bestQ, const int* __restrict__ bestT, uint8_t* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= numTargets + numQueries) return;
+    uint8_t v = 0;
+    if (i < numTargets) {
+        const int q = bestQ[i];
+        if (q >= 0) v = cellStrand[(size_t)i * (size_t)numQueries + (size_t)q];
+    } else {
+        const int q = i - numTargets, t = bestT[q];
+        if (t >= 0) v = cellStrand[(size_t)t * (size_t)numQueries + (size_t)q];
+    }
+    out[i] = v;
+}
+
+hipError_t launch_cross_best_strands(const uint8_t* cellStrand, int numQueries, int numTargets, const int* bestQ,
+                                     const int* bestT, uint8_t* out, hipStream_t stream)
+{
+    const int all = numTargets + numQueries;
+    if (all == 0) return hipSuccess;
+    hipLaunchKernelGGL(cross_best_strands_kernel, dim3((unsigned)((all + 255) / 256)), dim3(256), 0, stream,
+                       cellStrand, numQueries, numTargets, bestQ, bestT, out);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- scatter
 
 __global__ void __launch_bounds__(256)
@@ -276,6 +179,22 @@ hipError_t launch_cross_scatter(const long long* cell, const int* vals, long lon
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(cross_scatter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                        cell, vals, n, ed, nloc, end);
+    return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256)
+cross_scatter_bytes_kernel(const long long* __restrict__ cell, const uint8_t* __restrict__ vals, long long n, uint8_t* out)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[cell[i]] = vals[i];
+}
+
+hipError_t launch_cross_scatter_bytes(const long long* cell, const uint8_t* vals, long long n, uint8_t* out,
+                                      hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(cross_scatter_bytes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       cell, vals, n, out);
     return hipGetLastError();
 }
 

@@ -89,6 +89,10 @@ struct CrossScanArgs {
     unsigned long long hitCap;
     unsigned long long* hitKey;  // [hitCap]
     int* hitVal;                // [3][hitCap]: editDistance, numLocations, endLocation
+    // both-strand batches (launch_scan_cross_strands): qperm = 2 * query + strand with mates in the slots s and s ^ 1, qt
+    // even, numQueries the number of queries (not of slots); one strand byte (bit 0 reverse complement, bit 1 the other
+    // strand reaches the same distance) per stored cell [numTargets][numQueries], per appended hit [hitCap] in a hit list
+    uint8_t* strand;
 };
 
 hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, const int* tperm, const long long* tdw,
@@ -97,14 +101,22 @@ hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, 
 // hits: append the cells within k to the hit list instead of writing the matrix
 hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
                              hipStream_t stream);
+// the same scan over both strands of every query (cross_kernels_strands.hip): the combined cell per mate pair
+hipError_t launch_scan_cross_strands(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
+                                     hipStream_t stream);
 // per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are
 // best index / best distance / second distance
 hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,
                              int* bestQ, int* bestQD, int* secondQD, int* bestT, int* bestTD, int* secondTD,
                              CrossBest2* partial, int targetChunk, hipStream_t stream);
+// out [numTargets] then [numQueries]: the strand byte of every best cell (0 where there is none)
+hipError_t launch_cross_best_strands(const uint8_t* cellStrand, int numQueries, int numTargets, const int* bestQ,
+                                     const int* bestT, uint8_t* out, hipStream_t stream);
 // cells computed by other engines: ed / nloc / end of cell[i] (index into the matrix)
 hipError_t launch_cross_scatter(const long long* cell, const int* vals, long long n, int* ed, int* nloc, int* end,
                                 hipStream_t stream);
+hipError_t launch_cross_scatter_bytes(const long long* cell, const uint8_t* vals, long long n, uint8_t* out,
+                                      hipStream_t stream);
 
 // ---- hit lists (cross_hits.hip)
 // temporary bytes of the sort of up to n hits
@@ -114,10 +126,12 @@ hipError_t launch_cross_hits_iota(uint32_t* idx, long long n, hipStream_t stream
 // The n hits (key, val [3][cap]) into CSR order: sorted by key (target-major, ascending query inside a target) into
 // skey / sidx, gathered into out [4][n] (query, editDistance, numLocations, endLocation), targetOffsets [nt + 1] from the
 // boundaries of the sorted keys; best hits per target and per query from the list into best ([3][nt] then [3][nq], the
-// layout of launch_cross_best) through bkey ([2][nt + nq]).
+// layout of launch_cross_best) through bkey ([2][nt + nq]).  Both-strand batches (strand != NULL, [cap] as appended):
+// the strand byte travels with its hit into strandOut [n], and bestStrand ([nt] then [nq]) is the byte of every best hit.
 hipError_t launch_cross_hits_finish(const unsigned long long* key, const int* val, long long cap, long long n,
                                     int numQueries, int numTargets, const uint32_t* idx, unsigned long long* skey,
                                     uint32_t* sidx, void* tmp, size_t tmpBytes, long long* targetOffsets, int* out,
-                                    unsigned long long* bkey, int* best, hipStream_t stream);
+                                    unsigned long long* bkey, int* best, const uint8_t* strand, uint8_t* strandOut,
+                                    uint8_t* bestStrand, hipStream_t stream);
 
 }  // namespace edlib_amd

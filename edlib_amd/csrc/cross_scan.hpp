@@ -1,0 +1,164 @@
+// cross_scan.hpp -- the lane-per-cell scan of cross batches (DESIGN.md "Cross batches"): the kernel template and its
+// launch ladder, included by the two translation units that instantiate it -- cross_kernels.hip (one strand) and
+// cross_kernels_strands.hip (both strands), each half of the instantiations.
+#pragma once
+#include "cross_kernels.hpp"
+#include "cross_column.hpp"
+#include "strands.hpp"
+
+namespace edlib_amd {
+
+typedef uint32_t u32;
+typedef unsigned long long u64;
+
+// ------------------------------------------------------------------- scan
+
+// The column is cross_column<NWD, MODE> (cross_column.hpp, shared with the window kernel).
+
+// HITS: the epilogue appends the cells within k to the hit list (one 64-bit atomicAdd per target-tile step of a wave that
+// has any) instead of writing the matrix.  Every lane reaches it with a flag: padding slots and target slots past the end
+// take part as non-hits.
+// STRANDS: the slots s and s ^ 1 of a query tile hold a query and its reverse complement (qperm = 2 query + strand, qt is
+// even), so mates are the lanes l and l ^ 1 of the wave: the same target, `live`, n, query length, NW length window and
+// trip count.  Peq staging and the column loop are as for one strand; behind cross_cell_result() the mates exchange their
+// records, the even (forward) lane decides by resolve_strands() and is the only one that stores or appends.
+template <int NWD, int S, int MODE, bool HITS, bool STRANDS>
+__global__ void __launch_bounds__(64)
+scan_cross_kernel(CrossScanArgs a)
+{
+    __shared__ u32 s_peq[S * NWD * 64];                 // [symbol][word][query of the tile]
+    const int lane = threadIdx.x;
+    const int qt = a.qt;
+    const int slot0 = blockIdx.x * qt;
+    {
+        // staged once: the wave keeps this query tile for all its target tiles
+        const u32* src = a.peq + (size_t)(slot0 >> 6) * (S * NWD * 64) + (slot0 & 63);
+        for (int i = lane; i < S * NWD * qt; i += 64) {
+            const int r = i / qt;
+            s_peq[i] = src[r * 64 + (i - r * qt)];
+        }
+    }
+    __syncthreads();
+    const int qi = lane & (qt - 1);
+    const int ti = lane / qt;
+    const int tpt = 64 / qt;
+    const int slot = slot0 + qi;
+    const int q = a.qperm[slot];
+    const int m = a.qlen[slot];
+    const int sh = (m - 1) & 31;
+    if (!HITS && q < 0) return;                         // (no barrier or ballot below)
+    const int numTT = (a.numSorted + tpt - 1) / tpt;
+    for (int tt = blockIdx.y; tt < numTT; tt += gridDim.y) {   // wave-uniform trip count
+        const int ts = tt * tpt + ti;
+        const bool live = q >= 0 && ts < a.numSorted;
+        int ed = -1, nloc = 0, end = -1;
+        if (live) {
+            const int n = a.tlen[ts];
+            int score = m, best = 0x7fffffff, cnt = 0, first = -1;
+            if (!cross_nw_outside(MODE, a.kcfg, m, n)) {
+                const u32* __restrict__ tp = a.tpk + a.tdw[ts];
+                u32 Pv[NWD], Mv[NWD];
+#pragma unroll
+                for (int d = 0; d < NWD; ++d) { Pv[d] = ~0u; Mv[d] = 0u; }
+                auto step = [&](u32 c, int j) {
+                    cross_column<NWD, MODE>(s_peq + c * (NWD * qt) + qi, qt, Pv, Mv, sh, score);
+                    if (MODE != 0) {
+                        if (score < best) { best = score; cnt = 1; first = j; }
+                        else if (score == best) ++cnt;
+                    }
+                };
+                int j = 0;
+                for (; j + 8 <= n; j += 8) {
+                    u32 w = tp[j >> 3];
+#pragma unroll
+                    for (int c = 0; c < 8; ++c) { step(w & 15u, j + c); w >>= 4; }
+                }
+                if (j < n) {
+                    u32 w = tp[j >> 3];
+                    for (; j < n; ++j) { step(w & 15u, j); w >>= 4; }
+                }
+            }
+            cross_cell_result(MODE, a.kcfg, m, n, MODE == 0 ? score : best, cnt, first, ed, nloc, end);
+        }
+        int sbyte = 0;
+        if (STRANDS) {
+            // every lane that is still here has its mate here: padding slots come in mate pairs (the early return above
+            // takes both lanes or neither), and the lanes of a pair left the branch on `live` together
+            const int oed = __shfl_xor(ed, 1, 64), onloc = __shfl_xor(nloc, 1, 64), oend = __shfl_xor(end, 1, 64);
+            const int w = resolve_strands(ed, oed);
+            if (w & kStrandReverse) { ed = oed; nloc = onloc; end = oend; }
+            sbyte = w & (kStrandReverse | kStrandBoth);
+        }
+        const bool mine = !STRANDS || !(q & 1);         // the forward lane reports the pair
+        const int qout = STRANDS ? q >> 1 : q;
+        if (!HITS) {
+            if (live && mine) {
+                const size_t at = (size_t)a.tperm[ts] * (size_t)a.numQueries + (size_t)qout;
+                a.ed[at] = ed; a.nloc[at] = nloc; a.end[at] = end;
+                if (STRANDS) a.strand[at] = (uint8_t)sbyte;
+            }
+            continue;
+        }
+        const bool hit = live && mine && ed != -1;
+        const u64 mask = __ballot(hit);
+        if (mask == 0) continue;                        // a sparse batch issues almost no atomics
+        const int leader = __ffsll((long long)mask) - 1;    // a lane with a hit: active
+        u64 base = 0;
+        if (lane == leader) base = atomicAdd(a.hitCount, (u64)__popcll(mask));
+        base = __shfl(base, leader, 64);
+        if (hit) {
+            const u64 at = base + __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
+            if (at < a.hitCap) {
+                a.hitKey[at] = ((u64)(u32)a.tperm[ts] << 32) | (u32)qout;
+                a.hitVal[at] = ed; a.hitVal[a.hitCap + at] = nloc; a.hitVal[2 * a.hitCap + at] = end;
+                if (STRANDS) a.strand[at] = (uint8_t)sbyte;
+            }
+        }
+    }
+}
+
+template <int NWD, int S, bool HITS, bool STRANDS>
+static hipError_t launch_scan_cross_ws(int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
+{
+    const dim3 grid((unsigned)a.numQueryTiles, (unsigned)ysplit);
+    if (mode == 0) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 0, HITS, STRANDS>), grid, dim3(64), 0, stream, a);
+    else if (mode == 1) hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 1, HITS, STRANDS>), grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((scan_cross_kernel<NWD, S, 2, HITS, STRANDS>), grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <int NWD, bool HITS, bool STRANDS>
+static hipError_t launch_scan_cross_w(int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
+{
+    if (syms == 4) return launch_scan_cross_ws<NWD, 4, HITS, STRANDS>(mode, a, ysplit, stream);
+    if (syms == 8) return launch_scan_cross_ws<NWD, 8, HITS, STRANDS>(mode, a, ysplit, stream);
+    return launch_scan_cross_ws<NWD, 16, HITS, STRANDS>(mode, a, ysplit, stream);
+}
+
+template <bool HITS, bool STRANDS>
+static hipError_t launch_scan_cross_h(int nwords, int syms, int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
+{
+    switch (nwords) {
+    case 1: return launch_scan_cross_w<1, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 2: return launch_scan_cross_w<2, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 3: return launch_scan_cross_w<3, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 4: return launch_scan_cross_w<4, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 5: return launch_scan_cross_w<5, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 6: return launch_scan_cross_w<6, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 7: return launch_scan_cross_w<7, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    case 8: return launch_scan_cross_w<8, HITS, STRANDS>(syms, mode, a, ysplit, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the checks both launchers make before the ladder; 1: nothing to launch, -1: bad arguments
+static inline int cross_scan_args_state(int syms, int mode, bool hits, const CrossScanArgs& a)
+{
+    if (a.numQueryTiles == 0 || a.numSorted == 0) return 1;
+    if ((syms != 4 && syms != 8 && syms != 16) || mode < 0 || mode > 2 || a.qt < 1 || a.qt > 64 || (64 % a.qt) != 0)
+        return -1;
+    if (hits && (!a.hitCount || !a.hitKey || !a.hitVal)) return -1;
+    return 0;
+}
+
+}  // namespace edlib_amd

@@ -458,14 +458,19 @@ private:
 // A hit-list batch (hits: k >= 0) keeps no matrix: the scan appends the cells within k to a list, the internal sessions'
 // cells within k are appended behind them, and the list is sorted on the device into CSR order (per target, ascending
 // query) and reduced to the same best hits.
+// A both-strand batch (strands) scans every query and its reverse complement (made on the device at init)
+// as the mates of neighbouring slots; a cell is the better strand's record (resolve_strands) and a strand byte beside it.
+// Its internal shared-target sessions are both-strand batches, its pair session holds both strands of every long query.
 class CrossBatch {
 public:
     ~CrossBatch();
     int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
-             EdlibAlignConfig cfg, int device, bool hits = false);
+             EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false);
     int run();
     int view(int what, EdlibAmdCrossView* out);
     int hitsView(EdlibAmdCrossHits* out);
+    int strandsView(int what, EdlibAmdCrossStrands* out);
+    bool bothStrands() const { return strands_; }
     EdlibAmdBatchStats stats{};
 
 private:
@@ -516,7 +521,13 @@ private:
     std::vector<long long> otherCellIdx_;         // cells of the internal sessions (t * nq + q), host side
     std::vector<unsigned long long> xKey_;        // their cells within k of the last Run
     std::vector<int> xVal_;
-    int gather(Batch& b, size_t n, int* vals);
+    // both strands: a strand byte (bit 0 reverse complement, bit 1 the other strand reaches the same distance) per cell
+    // [nt][nq] or per hit, and per best hit [nt] then [nq]
+    bool strands_ = false, cellStrandFetched_ = false, bestStrandFetched_ = false;
+    DevBuf<uint8_t> d_smat_, d_sbest_, d_hstrand_, d_hsout_, d_svals_;
+    PinBuf h_smat_, h_sbest_, h_svals_;
+    std::vector<uint8_t> xStrand_;                // strand bytes of xKey_
+    int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
     int scanGroups();
     int growHits(long long cap);
     int finishHits();
@@ -531,9 +542,11 @@ private:
 class WindowBatch {
 public:
     ~WindowBatch();
+    // unitStrand (NULL: all forward): 1 = the unit is the reverse complement of its query; the query pool then holds both
+    // strands of every query (made on the device) and a Peq slot goes to each (query, strand) a kernel unit names
     int init(const char* queries, const long long* qoff, int nq, const char* target, int targetLength,
-             const int* unitQuery, const int* unitStart, const int* unitLength, int numUnits,
-             EdlibAlignConfig cfg, int device);
+             const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
+             int numUnits, EdlibAlignConfig cfg, int device);
     int run();
     int view(int what, EdlibAmdWindowView* out);
     EdlibAmdBatchStats stats{};

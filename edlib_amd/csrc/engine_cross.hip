@@ -6,6 +6,8 @@
 // it to the best hits.  Results stay in HBM until view() asks for a part of them.  A hit-list batch appends the cells
 // within k instead (the scan, then the internal sessions' cells behind them) and finishes the list on the device
 // (cross_hits.hip): sorted into CSR order, target offsets, best hits from the list.
+// A both-strand batch makes the pool of every query and its reverse complement on the device, gives mates
+// the slots s and s ^ 1 of their word group, and keeps a strand byte beside every cell, hit and best hit.
 #include "engine.hpp"
 
 #include <algorithm>
@@ -21,10 +23,11 @@ CrossBatch::~CrossBatch()
 }
 
 // lanes a tile shape leaves idle decide it; on a tie the wider query tile (fewer Peq stagings)
-static int choose_qt(long long nq, long long nt)
+// (minQt = 2 for both strands: nq counts slots, mates are neighbouring lanes)
+static int choose_qt(long long nq, long long nt, int minQt = 1)
 {
     int bestQt = 64; long long bestLanes = -1;
-    for (int qt = 64; qt >= 1; qt >>= 1) {
+    for (int qt = 64; qt >= minQt; qt >>= 1) {
         const long long tpt = 64 / qt;
         const long long lanes = ((nq + qt - 1) / qt) * qt * ((nt + tpt - 1) / tpt) * tpt;
         if (bestLanes < 0 || lanes < bestLanes) { bestLanes = lanes; bestQt = qt; }
@@ -33,7 +36,7 @@ static int choose_qt(long long nq, long long nt)
 }
 
 int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const char* targets,
-                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device, bool hits)
+                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device, bool hits, bool strands)
 {
     if (cfg.task != EDLIB_TASK_DISTANCE) {
         set_error("cross batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
@@ -47,6 +50,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     }
     if (cfg.mode != EDLIB_MODE_NW && cfg.mode != EDLIB_MODE_SHW && cfg.mode != EDLIB_MODE_HW) { set_error("unknown mode"); return 1; }
     if (nq < 0 || nt < 0 || (nq > 0 && !qoffIn) || (nt > 0 && !toffIn)) { set_error("bad batch shape"); return 1; }
+    if (strands && nq > 0x3fffffff) { set_error("bad both-strand batch shape"); return 1; }
     const int ndev = device_count();
     if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
@@ -55,7 +59,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
     cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
     cfg_.additionalEqualitiesLength = (int)eqs_.size();
-    device_ = device; nq_ = nq; nt_ = nt; hits_ = hits;
+    device_ = device; nq_ = nq; nt_ = nt; hits_ = hits; strands_ = strands;
     std::vector<long long> qoff(nq + 1, 0), toff(nt + 1, 0);
     if (nq > 0) qoff.assign(qoffIn, qoffIn + nq + 1);
     if (nt > 0) toff.assign(toffIn, toffIn + nt + 1);
@@ -69,7 +73,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     auto tlen = [&](int t) { return (int)(toff[t + 1] - toff[t]); };
     cells_ = (size_t)nq * (size_t)nt;
     stats = EdlibAmdBatchStats{};
-    stats.cells = qbytes * tbytes;
+    stats.cells = qbytes * tbytes * (strands ? 2 : 1);
 
     // the union alphabet of all targets decides the Peq rows (and whether the kernel can take any cell)
     build_tables(tab_, reinterpret_cast<const uint8_t*>(targets) + tb, tbytes, eqs_.data(), (int)eqs_.size());
@@ -89,6 +93,10 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     EDLIB_AMD_HIP(pool_stream(&stream_));
     EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
     EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
+    if (strands_) {
+        EDLIB_AMD_HIP(d_sbest_.alloc(std::max<size_t>((size_t)nt + (size_t)nq, 1)));
+        if (!hits_) EDLIB_AMD_HIP(d_smat_.alloc(std::max<size_t>(cells_, 1)));
+    }
     if (!hits_) {
         EDLIB_AMD_HIP(d_mat_.alloc(3 * std::max<size_t>(cells_, 1)));
         targetChunk_ = std::max(1024, (nt + 32767) / 32768);
@@ -142,9 +150,15 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         // queries (rebased), their tables
         std::vector<long long> qoffR(qoff);
         for (auto& v : qoffR) v -= qb;
-        EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
-        if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        if (!strands_) {
+            EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
+            if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        } else {
+            // the caller's pool goes up as it is; query i and its reverse complement are written from it on the device as
+            // the entries 2i and 2i + 1 of a pool twice its size
+            if (make_strand_pool(queries + qb, qoffR.data(), nq, d_qpool_, d_qoff_, stream_)) return 1;
+        }
         EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
         EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
         EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
@@ -161,16 +175,26 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
             std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return qlen(a) < qlen(b); });
             std::unique_ptr<Group> g(new Group);
             g->words = w;
-            g->qt = choose_qt((long long)qs.size(), numSorted_);
-            g->tiles = ((int)qs.size() + g->qt - 1) / g->qt;
+            // both strands: each query of the sorted list becomes two slots, itself and its reverse complement
+            const long long need = (long long)qs.size() * (strands_ ? 2 : 1);
+            g->qt = choose_qt(need, numSorted_, strands_ ? 2 : 1);
+            g->tiles = (int)((need + g->qt - 1) / g->qt);
             g->slots = g->tiles * g->qt;
-            for (int q : qs) g->wordSteps += (long long)w * scannedCols(qlen(q));
+            for (int q : qs) g->wordSteps += (long long)w * scannedCols(qlen(q)) * (strands_ ? 2 : 1);
             const int tpt = 64 / g->qt;
             const long long targetTiles = (numSorted_ + tpt - 1) / tpt;
             // about 8,192 waves per launch (256 CUs), each persistent over a strided range of target tiles
             g->ysplit = (int)std::min<long long>({targetTiles, std::max(1LL, (8192LL + g->tiles - 1) / g->tiles), 65535LL});
             std::vector<int> perm(g->slots, -1);
-            std::copy(qs.begin(), qs.end(), perm.begin());
+            if (!strands_) std::copy(qs.begin(), qs.end(), perm.begin());
+            else {
+                for (size_t i = 0; i < qs.size(); ++i) { perm[2 * i] = 2 * qs[i]; perm[2 * i + 1] = 2 * qs[i] + 1; }
+                // what the kernel's lane exchange rests on: mates in the slots s and s ^ 1, padding in pairs, an even tile
+                bool ok = !(g->qt & 1) && !(g->slots & 1);
+                for (int sl = 0; ok && sl < g->slots; sl += 2)
+                    ok = perm[sl] < 0 ? perm[sl + 1] < 0 : (!(perm[sl] & 1) && perm[sl + 1] == perm[sl] + 1);
+                if (!ok) { set_error("both strands: mates are not in adjacent slots"); return 1; }
+            }
             const size_t blocks = (size_t)(g->slots + 63) / 64;
             EDLIB_AMD_HIP(g->d_perm.alloc(g->slots)); EDLIB_AMD_HIP(g->d_qlen.alloc(g->slots));
             EDLIB_AMD_HIP(g->d_kinit.alloc(g->slots)); EDLIB_AMD_HIP(g->d_alpha.alloc(g->slots));
@@ -185,7 +209,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         for (int t : outTargets_) {
             std::unique_ptr<Batch> b(new Batch);
             const long long to[2] = {toff[t], toff[t + 1]};
-            if (b->init(queries, qoffIn, nq, targets, to, 1, cfg_, device)) return 1;
+            if (b->init(queries, qoffIn, nq, targets, to, 1, cfg_, device, strands_)) return 1;
             outShared_.push_back(std::move(b));
             otherCells_ += nq;
         }
@@ -193,16 +217,24 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
             // every long query against every target the kernel takes, as pairs (their bytes replicated per cell)
             std::vector<char> qp, tp;
             std::vector<long long> qo(1, 0), to(1, 0);
+            // (both strands: the pairs 2c and 2c + 1 of cell c, the second with the reverse complement made here)
             for (int t : inT)
                 for (int q : longQ) {
-                    qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
-                    tp.insert(tp.end(), targets + toff[t], targets + toff[t + 1]);
-                    qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
+                    for (int st = 0; st < (strands_ ? 2 : 1); ++st) {
+                        if (!st) qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
+                        else
+                            for (long long j = qoff[q + 1] - 1; j >= qoff[q]; --j)
+                                qp.push_back((char)complement_byte((uint8_t)queries[j]));
+                        tp.insert(tp.end(), targets + toff[t], targets + toff[t + 1]);
+                        qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
+                    }
                     longCells_.push_back((long long)t * nq + q);
                 }
+            const long long np = (long long)longCells_.size() * (strands_ ? 2 : 1);
+            if (np > 0x7fffffffLL) { set_error("cross batch: too many cells of long queries (%lld pairs)", np); return 1; }
+            if (tp.empty()) tp.push_back(0);
             longPairs_.reset(new Batch);
-            if (longPairs_->init(qp.data(), qo.data(), (int)longCells_.size(), tp.data(), to.data(), (int)longCells_.size(),
-                                 cfg_, device)) return 1;
+            if (longPairs_->init(qp.data(), qo.data(), (int)np, tp.data(), to.data(), (int)np, cfg_, device)) return 1;
             otherCells_ += (long long)longCells_.size();
         }
         if (otherCells_ > 0) {
@@ -212,6 +244,10 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
                 for (int q = 0; q < nq; ++q) cellIdx.push_back((long long)t * nq + q);
             cellIdx.insert(cellIdx.end(), longCells_.begin(), longCells_.end());
             EDLIB_AMD_HIP(h_vals_.alloc(3 * (size_t)otherCells_ * sizeof(int)));
+            if (strands_) {
+                EDLIB_AMD_HIP(h_svals_.alloc((size_t)otherCells_));
+                if (!hits_) EDLIB_AMD_HIP(d_svals_.alloc((size_t)otherCells_));
+            }
             if (hits_) otherCellIdx_.swap(cellIdx);            // their hits are appended from the host
             else {
                 EDLIB_AMD_HIP(d_cells_.alloc((size_t)otherCells_)); EDLIB_AMD_HIP(d_vals_.alloc(3 * (size_t)otherCells_));
@@ -222,11 +258,18 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     return 0;
 }
 
-// editDistance / numLocations / first end location of the n units of an internal session's last run
-int CrossBatch::gather(Batch& b, size_t n, int* vals)
+// editDistance / numLocations / first end location of the n units of an internal session's last run; sbytes (a both-strand
+// session): their strand bytes
+int CrossBatch::gather(Batch& b, size_t n, int* vals, uint8_t* sbytes)
 {
     EdlibAmdResultsView v{};
     if (b.resultsView(&v)) return 1;
+    if (sbytes) {
+        EdlibAmdStrandView sv{};
+        if (b.strandView(&sv)) return 1;
+        for (size_t i = 0; i < n; ++i)
+            sbytes[i] = v.editDistance[i] < 0 ? 0 : (uint8_t)((sv.strand[i] ? kStrandReverse : 0) | (sv.bothStrands[i] ? kStrandBoth : 0));
+    }
     for (size_t i = 0; i < n; ++i) {
         if (v.status[i] != EDLIB_STATUS_OK) { set_error("cross batch: an internal alignment failed"); return 1; }
         vals[3 * i] = v.editDistance[i];
@@ -250,7 +293,9 @@ int CrossBatch::scanGroups()
         } else {
             a.ed = d_mat_.p; a.nloc = d_mat_.p + cells_; a.end = d_mat_.p + 2 * cells_;
         }
-        EDLIB_AMD_HIP(launch_scan_cross(g->words, syms_, (int)cfg_.mode, hits_, a, g->ysplit, stream_));
+        a.strand = !strands_ ? nullptr : (hits_ ? d_hstrand_.p : d_smat_.p);
+        EDLIB_AMD_HIP((strands_ ? launch_scan_cross_strands : launch_scan_cross)(g->words, syms_, (int)cfg_.mode, hits_, a,
+                                                                                 g->ysplit, stream_));
         ++stats.scan_launches;
         stats.word_steps += g->wordSteps;
     }
@@ -268,6 +313,8 @@ int CrossBatch::growHits(long long cap)
     if (e == hipSuccess) e = d_skey_.alloc((size_t)cap);
     if (e == hipSuccess) e = d_sidx_.alloc((size_t)cap);
     if (e == hipSuccess) e = d_hout_.alloc(4 * (size_t)cap);
+    if (e == hipSuccess && strands_) e = d_hstrand_.alloc((size_t)cap);
+    if (e == hipSuccess && strands_) e = d_hsout_.alloc((size_t)cap);
     if (e == hipSuccess) e = cross_hits_sort_bytes(cap, nt_, &tmp);
     if (e == hipSuccess) e = d_sortTmp_.alloc(tmp);
     if (e == hipSuccess) e = launch_cross_hits_iota(d_hidx_.p, cap, stream_);
@@ -303,12 +350,15 @@ int CrossBatch::finishHits()
         for (int f = 0; f < 3; ++f)
             EDLIB_AMD_HIP(hipMemcpyAsync(d_hval_.p + f * cap + kernelHits, xVal_.data() + f * (size_t)extra,
                                          (size_t)extra * sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (strands_)
+            EDLIB_AMD_HIP(hipMemcpyAsync(d_hstrand_.p + kernelHits, xStrand_.data(), (size_t)extra, hipMemcpyHostToDevice, stream_));
     }
     size_t tmp = 0;
     EDLIB_AMD_HIP(cross_hits_sort_bytes(total, nt_, &tmp));
     if (tmp > d_sortTmp_.n) EDLIB_AMD_HIP(d_sortTmp_.alloc(tmp));
     EDLIB_AMD_HIP(launch_cross_hits_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nq_, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
-                                           d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, d_bkey_.p, d_best_.p, stream_));
+                                           d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, d_bkey_.p, d_best_.p,
+                                           strands_ ? d_hstrand_.p : nullptr, d_hsout_.p, d_sbest_.p, stream_));
     numHits_ = total;
     return 0;
 }
@@ -319,7 +369,7 @@ int CrossBatch::run()
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    haveRun_ = matFetched_ = bestFetched_ = hitsFetched_ = false;
+    haveRun_ = matFetched_ = bestFetched_ = hitsFetched_ = cellStrandFetched_ = bestStrandFetched_ = false;
     const long long cells = stats.cells;
     stats = EdlibAmdBatchStats{};
     stats.cells = cells;
@@ -338,13 +388,14 @@ int CrossBatch::run()
         stats.path |= 8;
     }
     // the other engines run on their own streams meanwhile
-    xKey_.clear(); xVal_.clear();
+    xKey_.clear(); xVal_.clear(); xStrand_.clear();
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
+        uint8_t* svals = strands_ ? h_svals_.p : nullptr;
         size_t at = 0;
         for (auto& b : outShared_) {
             if (b->run()) return 1;
-            if (gather(*b, (size_t)nq_, vals + 3 * at)) return 1;
+            if (gather(*b, (size_t)nq_, vals + 3 * at, strands_ ? svals + at : nullptr)) return 1;
             at += (size_t)nq_;
             b->finishStats();
             stats.word_steps += b->stats.word_steps; stats.scan_launches += b->stats.scan_launches;
@@ -352,7 +403,20 @@ int CrossBatch::run()
         }
         if (longPairs_) {
             if (longPairs_->run()) return 1;
-            if (gather(*longPairs_, longCells_.size(), vals + 3 * at)) return 1;
+            if (!strands_) {
+                if (gather(*longPairs_, longCells_.size(), vals + 3 * at, nullptr)) return 1;
+            } else {
+                // the pairs 2c (forward) and 2c + 1 (reverse complement) of every cell, decided here
+                const size_t nc = longCells_.size();
+                std::vector<int> both(6 * nc);
+                if (gather(*longPairs_, 2 * nc, both.data(), nullptr)) return 1;
+                for (size_t c = 0; c < nc; ++c) {
+                    const int w = resolve_strands(both[6 * c], both[6 * c + 3]);
+                    const int* rec = both.data() + 6 * c + ((w & kStrandReverse) ? 3 : 0);
+                    for (int f = 0; f < 3; ++f) vals[3 * (at + c) + f] = rec[f];
+                    svals[at + c] = (uint8_t)(w & (kStrandReverse | kStrandBoth));
+                }
+            }
             longPairs_->finishStats();
             const EdlibAmdBatchStats& s = longPairs_->stats;
             stats.word_steps += s.word_steps; stats.scan_launches += s.scan_launches;
@@ -361,6 +425,10 @@ int CrossBatch::run()
         if (!hits_) {
             EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, 3 * (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
             EDLIB_AMD_HIP(launch_cross_scatter(d_cells_.p, d_vals_.p, otherCells_, ed, nloc, end, stream_));
+            if (strands_) {
+                EDLIB_AMD_HIP(hipMemcpyAsync(d_svals_.p, svals, (size_t)otherCells_, hipMemcpyHostToDevice, stream_));
+                EDLIB_AMD_HIP(launch_cross_scatter_bytes(d_cells_.p, d_svals_.p, otherCells_, d_smat_.p, stream_));
+            }
         } else {
             // their cells within k, as [key], [ed][nloc][end]
             std::vector<int> e3[3];
@@ -369,6 +437,7 @@ int CrossBatch::run()
                 const long long c = otherCellIdx_[(size_t)i];
                 xKey_.push_back(((unsigned long long)(c / nq_) << 32) | (unsigned long long)(c % nq_));
                 for (int f = 0; f < 3; ++f) e3[f].push_back(vals[3 * i + f]);
+                if (strands_) xStrand_.push_back(svals[i]);
             }
             for (int f = 0; f < 3; ++f) xVal_.insert(xVal_.end(), e3[f].begin(), e3[f].end());
         }
@@ -379,6 +448,7 @@ int CrossBatch::run()
         int* bq = d_best_.p; int* bt = d_best_.p + 3 * (size_t)nt_;
         EDLIB_AMD_HIP(launch_cross_best(ed, nq_, nt_, bq, bq + nt_, bq + 2 * (size_t)nt_, bt, bt + nq_, bt + 2 * (size_t)nq_,
                                         d_partial_.p, targetChunk_, stream_));
+        if (strands_) EDLIB_AMD_HIP(launch_cross_best_strands(d_smat_.p, nq_, nt_, bq, bt, d_sbest_.p, stream_));
     }
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     if (!groups_.empty()) {
@@ -457,6 +527,38 @@ int CrossBatch::hitsView(EdlibAmdCrossHits* out)
     const int* l = reinterpret_cast<const int*>(h_hits_.p + offBytes);
     const size_t n = (size_t)numHits_;
     out->query = l; out->editDistance = l + n; out->numLocations = l + 2 * n; out->endLocation = l + 3 * n;
+    return 0;
+}
+
+int CrossBatch::strandsView(int what, EdlibAmdCrossStrands* out)
+{
+    if (!strands_) {
+        set_error("edlibAmdBatchCrossStrands: not a both-strand cross batch (create it with "
+                  "edlibAmdBatchCreateCrossBothStrands or edlibAmdBatchCreateCrossHitsBothStrands)");
+        return 1;
+    }
+    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    if (what & ~(EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST)) { set_error("cross strands: unknown parts %d", what); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    const size_t cellBytes = hits_ ? (size_t)numHits_ : cells_, bestBytes = (size_t)nt_ + (size_t)nq_;
+    if ((what & EDLIB_AMD_CROSS_MATRIX) && !cellStrandFetched_) {
+        if (h_smat_.n < cellBytes || !h_smat_.p) EDLIB_AMD_HIP(h_smat_.alloc(std::max<size_t>(cellBytes, 1)));
+        if (cellBytes)
+            EDLIB_AMD_HIP(hipMemcpyAsync(h_smat_.p, hits_ ? d_hsout_.p : d_smat_.p, cellBytes, hipMemcpyDeviceToHost, stream_));
+    }
+    if ((what & EDLIB_AMD_CROSS_BEST) && !bestStrandFetched_) {
+        if (h_sbest_.n < bestBytes || !h_sbest_.p) EDLIB_AMD_HIP(h_sbest_.alloc(std::max<size_t>(bestBytes, 1)));
+        if (bestBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_sbest_.p, d_sbest_.p, bestBytes, hipMemcpyDeviceToHost, stream_));
+    }
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (what & EDLIB_AMD_CROSS_MATRIX) cellStrandFetched_ = true;
+    if (what & EDLIB_AMD_CROSS_BEST) bestStrandFetched_ = true;
+    memset(out, 0, sizeof *out);
+    out->numQueries = nq_; out->numTargets = nt_; out->numHits = hits_ ? numHits_ : 0;
+    if (what & EDLIB_AMD_CROSS_MATRIX) (hits_ ? out->hitStrand : out->cellStrand) = h_smat_.p;
+    if (what & EDLIB_AMD_CROSS_BEST) { out->bestQueryStrand = h_sbest_.p; out->bestTargetStrand = h_sbest_.p + nt_; }
     return 0;
 }
 

@@ -5,6 +5,9 @@
 // sized by bytes of windows.  A Run builds the Peq rows of every query, scans every group on the window kernel, lets the
 // internal pair session of the units outside the kernel's envelope run meanwhile, scatters its results into the unit
 // arrays and reduces them to the best unit per query.  Results stay in HBM until view() asks for a part of them.
+// Units with a strand: where a unit names the reverse complement of its query the query pool holds both
+// strands of every query, made on the device (entry 2 q + strand), and a Peq slot goes to each (query, strand) a kernel
+// unit names; the scan and the best reduction do not know about strands.
 #include "engine.hpp"
 
 #include <algorithm>
@@ -19,8 +22,8 @@ WindowBatch::~WindowBatch()
 }
 
 int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, const char* target, int targetLength,
-                      const int* unitQuery, const int* unitStart, const int* unitLength, int nu,
-                      EdlibAlignConfig cfg, int device)
+                      const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
+                      int nu, EdlibAlignConfig cfg, int device)
 {
     // ---- refusals, before the device is looked at
     if (cfg.task != EDLIB_TASK_DISTANCE) {
@@ -51,7 +54,15 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
                       unitStart[u], unitLength[u], targetLength);
             return 1;
         }
+        if (unitStrand && unitStrand[u] > 1) {
+            set_error("window batch: unit %d has unitStrand %d (0: the query, 1: its reverse complement)", u, (int)unitStrand[u]);
+            return 1;
+        }
     }
+    bool stranded = false;                                                // a unit names a reverse complement
+    for (int u = 0; u < nu && unitStrand && !stranded; ++u) stranded = unitStrand[u] != 0;
+    if (stranded && nq > 0x3fffffff) { set_error("bad batch shape"); return 1; }
+    auto strandOf = [&](int u) { return stranded ? (int)unitStrand[u] : 0; };
     const int ndev = device_count();
     if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
@@ -114,13 +125,20 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
         // queries (rebased), their tables
         std::vector<long long> qoffR(qoff);
         for (auto& v : qoffR) v -= qb;
-        EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
-        if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        if (!stranded) {
+            EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
+            if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        } else {
+            // the caller's pool goes up as it is; query i and its reverse complement are written from it on the device as
+            // the entries 2i and 2i + 1 of a pool twice its size
+            if (make_strand_pool(queries + qb, qoffR.data(), nq, d_qpool_, d_qoff_, stream_)) return 1;
+        }
         EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
         EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
         EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
-        std::vector<int> slotOf(nq, -1);                                  // a query's slot in its group
+        // a pool entry's slot in its group; the entry of a unit is its query, or 2 * query + strand in a stranded batch
+        std::vector<int> slotOf((size_t)nq * (stranded ? 2 : 1), -1);
         for (int w = 1; w <= kCrossMaxQueryWords; ++w) {
             auto& us = byWords[w];
             if (us.empty()) continue;
@@ -131,8 +149,9 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
             std::vector<int> perm, uslot(us.size()), ustart(us.size()), ulen(us.size());
             for (size_t i = 0; i < us.size(); ++i) {
                 const int u = us[i], q = unitQuery[u], m = qlen(q), n = unitLength[u];
-                if (slotOf[q] < 0) { slotOf[q] = (int)perm.size(); perm.push_back(q); }    // queries that a unit names
-                uslot[i] = slotOf[q]; ustart[i] = unitStart[u]; ulen[i] = n;
+                const int e = stranded ? 2 * q + strandOf(u) : q;
+                if (slotOf[e] < 0) { slotOf[e] = (int)perm.size(); perm.push_back(e); }    // entries that a unit names
+                uslot[i] = slotOf[e]; ustart[i] = unitStart[u]; ulen[i] = n;
                 if (m > 0 && n > 0 && !cross_nw_outside((int)cfg.mode, cfg.k, m, n)) g->wordSteps += (long long)w * n;
             }
             g->slots = (int)perm.size();
@@ -157,7 +176,9 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
         std::vector<long long> qo(1, 0), to(1, 0);
         for (long long u : pairUnits_) {
             const int q = unitQuery[u];
-            qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
+            if (!strandOf((int)u)) qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
+            else
+                for (long long j = qoff[q + 1] - 1; j >= qoff[q]; --j) qp.push_back((char)complement_byte((uint8_t)queries[j]));
             tp.insert(tp.end(), target + unitStart[u], target + unitStart[u] + unitLength[u]);
             qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
         }

@@ -2,6 +2,8 @@
 // query pool, the decision per mate pair, and the gather of the winners into read order.
 #include "strands.hpp"
 
+#include <vector>
+
 namespace edlib_amd {
 
 // A wave per read: lane j copies byte j and writes the complement of byte m - 1 - j (both loads hit the lines the wave
@@ -26,6 +28,23 @@ hipError_t launch_strand_pool(const uint8_t* in, const long long* off2, int numR
     if (numReads <= 0) return hipSuccess;
     hipLaunchKernelGGL(strand_pool_kernel, dim3((unsigned)((numReads + 3) / 4)), dim3(256), 0, stream, in, off2, numReads, out);
     return hipGetLastError();
+}
+
+int make_strand_pool(const char* queries, const long long* off, int nq, DevBuf<uint8_t>& d_pool, DevBuf<long long>& d_off,
+                     hipStream_t stream)
+{
+    const long long bytes = off[nq];
+    std::vector<long long> off2(2 * (size_t)nq + 1);
+    for (int i = 0; i < nq; ++i) { off2[2 * i] = 2 * off[i]; off2[2 * i + 1] = off[i] + off[i + 1]; }
+    off2[2 * (size_t)nq] = 2 * bytes;
+    DevBuf<uint8_t> d_raw;
+    EDLIB_AMD_HIP(d_raw.alloc((size_t)bytes + 16));
+    EDLIB_AMD_HIP(d_pool.alloc(2 * (size_t)bytes + 16)); EDLIB_AMD_HIP(d_off.alloc(2 * (size_t)nq + 1));
+    if (bytes) EDLIB_AMD_HIP(hipMemcpy(d_raw.p, queries, (size_t)bytes, hipMemcpyHostToDevice));
+    EDLIB_AMD_HIP(hipMemcpy(d_off.p, off2.data(), off2.size() * sizeof(long long), hipMemcpyHostToDevice));
+    EDLIB_AMD_HIP(launch_strand_pool(d_raw.p, d_off.p, nq, d_pool.p, stream));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream));                // d_raw dies here
+    return 0;
 }
 
 __device__ __forceinline__ int slot_distance(int best, int total, int mode, int k)

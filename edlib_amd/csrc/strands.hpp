@@ -36,6 +36,12 @@ __host__ __device__ inline int resolve_strands(int dFwd, int dRev)
 // offset in `in`.  A wave per read.
 hipError_t launch_strand_pool(const uint8_t* in, const long long* off2, int numReads, uint8_t* out, hipStream_t stream);
 
+// The same for a batch that holds the caller's offsets: `queries` are the nq queries back to back, off[0 .. nq] their
+// offsets from 0.  The bytes go up as they are, d_off gets the 2 nq + 1 offsets described above, d_pool the pool made by
+// launch_strand_pool, and the stream is waited for.  0, or 1 with the error set.
+int make_strand_pool(const char* queries, const long long* off, int nq, DevBuf<uint8_t>& d_pool, DevBuf<long long>& d_off,
+                     hipStream_t stream);
+
 // win[p] of the mate pair in the slots 2 p, 2 p + 1 of a read group, from the merged per-slot records (best, total).
 // mode 0: NW (the score is the distance unless it exceeds k), else SHW / HW (a slot has an alignment iff total > 0).
 hipError_t launch_resolve_strands(const int* perm, const int* best, const int* total, int nslots, int mode, int k, int* win,

@@ -212,6 +212,44 @@ typedef struct {
 } EdlibAmdCrossHits;
 EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* batch, EdlibAmdCrossHits* out);
 
+/* Cross batches on both strands: as edlibAmdBatchCreateCross / edlibAmdBatchCreateCrossHits (the same arguments, routing
+ * and refusals, checked before the device is looked for: task other than EDLIB_TASK_DISTANCE, unknown mode, k < 0 for the
+ * hit-list form), but cell (q, t) is the better of edlibAlign(query q, target t, config) and
+ * edlibAlign(revcomp(query q), target t, config), chosen by the table above edlibAmdBatchCreateSharedBothStrands: the
+ * forward strand wins a tie, the winner's editDistance, numLocations and first end location are reported, and a cell
+ * that is -1 on both strands is the forward record with -1.  revcomp is edlibAmdReverseComplement, made on the device from
+ * the uploaded pool.  (A barcode or adapter sits on either strand of a read: with the reverse complements passed as
+ * queries of their own, a query's other strand competes with it as the runner-up of every best hit.)
+ * edlibAmdBatchCrossView (MATRIX, BEST) and edlibAmdBatchCrossHits work as on the plain batches and describe the COMBINED
+ * cells: numQueries wide, a hit is a combined cell that is not -1 (one per (q, t)), best and second best run over the
+ * combined cells with the same tie and index rules, so a query's other strand is never its own runner-up.
+ * edlibAmdBatchCrossStrands says which strand every cell reports; StrandView and the views of the other kinds fail.
+ * Stats.cells and Stats.word_steps count both strands; Stats.path bit 3 as for a plain cross batch.  On the cross kernel
+ * a query and its reverse complement are neighbouring lanes of a wave and the choice is one lane exchange per cell. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossBothStrands(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* targets, const long long* targetOffsets, int numTargets,
+    EdlibAlignConfig config, int device);
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHitsBothStrands(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* targets, const long long* targetOffsets, int numTargets,
+    EdlibAlignConfig config, int device);
+
+/* The strands of the last Run of such a batch (it fails on every other kind, and before the first Run): pointers into
+ * pinned memory the batch owns, valid until the next Run / Destroy.  A strand byte has bit 0 set when the cell reports
+ * the reverse complement and bit 1 set when the other strand reaches the same distance (then bit 0 is clear: ties go
+ * forward); it is 0 for a -1 cell and for a best that is -1.  `what`: EDLIB_AMD_CROSS_MATRIX asks for the byte of every
+ * cell -- cellStrand of a dense batch, hitStrand of a hit-list batch --, EDLIB_AMD_CROSS_BEST for the bytes of the best
+ * hits of edlibAmdBatchCrossView; the parts not asked for, and the part of the other form, are NULL. */
+typedef struct {
+    int numQueries, numTargets; long long numHits;
+    const unsigned char* cellStrand;        /* [numTargets * numQueries]  dense batches, asked with EDLIB_AMD_CROSS_MATRIX */
+    const unsigned char* hitStrand;         /* [numHits]                  hit-list batches, in the order of EdlibAmdCrossHits */
+    const unsigned char* bestQueryStrand;   /* [numTargets]               asked with EDLIB_AMD_CROSS_BEST */
+    const unsigned char* bestTargetStrand;  /* [numQueries] */
+} EdlibAmdCrossStrands;
+EDLIB_API int edlibAmdBatchCrossStrands(EdlibAmdBatch* batch, int what, EdlibAmdCrossStrands* out);
+
 /* A shared-target batch whose results are, per read, EVERY occurrence within k along the target -- the search question of
  * adapter / primer trimming, concatemer splitting, repeat finding and multi-mapping reads, which no choice of k makes
  * edlibAlign() answer (it keeps the columns of the single best score only).
@@ -224,7 +262,7 @@ EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* batch, EdlibAmdCrossHits* ou
  * Accepted: config.mode == EDLIB_MODE_HW, config.task == EDLIB_TASK_DISTANCE, config.k >= 0, every read at most 256 bases,
  * at most 16 distinct target symbols; additionalEqualities allowed.  Anything else (SHW / NW, start locations and paths,
  * longer reads, more symbols) returns NULL with the limit named in edlibAmdLastError().  For both strands pass the reverse
- * complements as reads of their own; for start locations or paths align the chosen windows with a pair batch.
+ * complements as reads of their own (this kind has no both-strand form); for start locations or paths align the chosen windows with a pair batch.
  * An empty read hits once: [0, T-1], distance 0, endLocation 0, numLocations T; an empty target gives no hit.
  * Run, Stats (path bit 0) and Destroy work as for a shared batch; Results, ResultsFlat, ResultsView, CigarView, StrandView,
  * CrossView and CrossHits fail.  The device list starts at max(2^20, numQueries) runs; a Run that counts more grows it to
@@ -268,6 +306,19 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(
     const char* queries, const long long* queryOffsets, int numQueries,
     const char* target, int targetLength,
     const int* unitQuery, const int* unitStart, const int* unitLength, int numUnits,
+    EdlibAlignConfig config, int device);
+
+/* As edlibAmdBatchCreateWindows with a strand per unit (a mapper's candidates are (read, locus, strand)): unit u is
+ * revcomp(query unitQuery[u]) against its window where unitStrand[u] == 1 and the query itself where it is 0; revcomp is
+ * edlibAmdReverseComplement, made on the device from the uploaded pool.  A NULL unitStrand is all forward and equals
+ * edlibAmdBatchCreateWindows.  Any other value is refused, naming the first such unit, with the other unit checks (before
+ * the device).  edlibAmdBatchWindowView is unchanged: units as defined here, and the best per query runs over ALL units
+ * that name the query, whatever their strand, by the same key rule -- the winner's strand is unitStrand[bestUnit].
+ * Stats as for a plain window batch. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindowsStranded(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* target, int targetLength,
+    const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand, int numUnits,
     EdlibAlignConfig config, int device);
 
 /* Results of the last Run of a window batch (it fails on every other kind, and before the first Run), as pointers into
