@@ -244,12 +244,13 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 
 // Record column `col` if it ties or improves the best bottom-row score
 // (reference edlib.cpp:658-673: "colScore <= k", "positions.clear()", "k = bestScore").
-#define EDLIB_AMD_TRACK(col)                                   \
-    if (score <= best) {                                       \
-        if (score < best) { best = score; cnt = 0; }           \
+#define EDLIB_AMD_TRACK_SCORE(sc, col)                         \
+    if ((sc) <= best) {                                        \
+        if ((sc) < best) { best = (sc); cnt = 0; }             \
         if (cnt < cap) pos[cnt] = (col);                       \
         ++cnt;                                                 \
     }
+#define EDLIB_AMD_TRACK(col) EDLIB_AMD_TRACK_SCORE(score, col)
 
 // BOTTOM (HW): the Peq rows were built bottom-aligned (build_peq_reads_kernel), query row r at bit 32 NWD - m + r.  The
 // pad rows below bit 32 NWD - m match every symbol; with HW's zero row -1 they stay at D = 0 in every column, so the real
@@ -258,6 +259,7 @@ template <int NWD, int MODE, bool BOTTOM = false>
 __global__ void __launch_bounds__(256)
 scan_reads_kernel(const ReadScanArgs a)
 {
+    constexpr int kHitGroup = 4;                                   // columns per hit test (divides 16)
     const int lane = threadIdx.x & 63;
     const int rblk = blockIdx.x * 4 + (threadIdx.x >> 6);          // 4 waves / workgroup
     const int seg = blockIdx.y;
@@ -317,15 +319,34 @@ scan_reads_kernel(const ReadScanArgs a)
     }
     // full words of the segment
     const int wend = c1 >> 4;
+    // The hit test runs once per group of kHitGroup columns: bottom-row scores of neighbouring columns differ by at most 1,
+    // so a last score above best + kHitGroup - 1 means that no column of the group is at or below best, and best only moves
+    // at a hit.  A group that may hold one goes through the per-column test, in order, with each column's own score: best,
+    // cnt and the stored positions are what the per-column test leaves.  (Unrelated reads sit ~14 above their best: a wave
+    // takes the slow path in about 0.5 % of its groups.)  The loop carries the limit, not best: one compare per group.
+    int lim = best + (kHitGroup - 1);
     for (int w = c0 >> 4; w < wend; ++w) {
         const u32 tw = a.tpk[w];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const u32 sym = (tw >> (2 * j)) & 3u;
-            EDLIB_AMD_DISPATCH_COLUMN(sym)
-            if (MODE != 0) { EDLIB_AMD_TRACK(w * 16 + j) }
+        for (int j = 0; j < 16; j += kHitGroup) {
+            int sc[kHitGroup];
+#pragma unroll
+            for (int q = 0; q < kHitGroup; ++q) {
+                const u32 sym = (tw >> (2 * (j + q))) & 3u;
+                EDLIB_AMD_DISPATCH_COLUMN(sym)
+                sc[q] = score;
+            }
+            if (MODE != 0) {
+                if (__builtin_expect(score <= lim, 0)) {
+                    best = lim - (kHitGroup - 1);
+#pragma unroll
+                    for (int q = 0; q < kHitGroup; ++q) { EDLIB_AMD_TRACK_SCORE(sc[q], w * 16 + j + q) }
+                    lim = best + (kHitGroup - 1);
+                }
+            }
         }
     }
+    best = lim - (kHitGroup - 1);
     // ragged tail of the target (last segment only)
     const int rem = c1 - (wend << 4);
     if (rem > 0) {
