@@ -4,9 +4,9 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 ``getNiceAlignment()`` have the same arguments, defaults, result dictionary and
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
-``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``align_windows()`` / ``find_all()``,
-``reverse_complement()``, ``cross_strands_model()`` and the resident ``SharedBatch`` / ``BothStrandsBatch`` / ``PairBatch`` / ``CrossBatch`` /
-``WindowBatch`` sessions over include/edlib_amd.h.
+``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``align_windows()`` / ``find_all()`` / ``pdist()`` /
+``pairs_within()``, ``reverse_complement()``, ``cross_strands_model()`` and the resident ``SharedBatch`` / ``BothStrandsBatch`` /
+``PairBatch`` / ``CrossBatch`` / ``WindowBatch`` / ``SelfBatch`` sessions over include/edlib_amd.h.
 
 There is no CPU path in here: everything calls ``libedlib.so`` (built by
 ``__graft_entry__.build()`` / ``make``), and a missing library or a missing GPU
@@ -92,6 +92,18 @@ class WindowView(C.Structure):           # edlib_amd.h EdlibAmdWindowView
                                           "bestUnit", "bestDistance", "secondDistance")]
 
 
+class SelfView(C.Structure):             # edlib_amd.h EdlibAmdSelfView
+    _fields_ = [("numSequences", C.c_int), ("numPairs", C.c_longlong)] + [
+        (f, C.POINTER(C.c_int)) for f in ("editDistance", "nearest", "nearestDistance", "secondDistance")]
+
+
+class SelfHits(C.Structure):             # edlib_amd.h EdlibAmdSelfHits
+    _fields_ = [("numSequences", C.c_int), ("numHits", C.c_longlong), ("rowOffsets", C.POINTER(C.c_longlong)),
+                ("partner", C.POINTER(C.c_int)), ("editDistance", C.POINTER(C.c_int))]
+
+
+SELF_DISTANCES = 1                        # EDLIB_AMD_SELF_DISTANCES
+SELF_NEAREST = 2                          # EDLIB_AMD_SELF_NEAREST
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
 CROSS_BEST = 2                            # EDLIB_AMD_CROSS_BEST
 WINDOW_UNITS = 1                          # EDLIB_AMD_WINDOW_UNITS
@@ -157,6 +169,13 @@ def lib():
                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                              AlignConfig, C.c_int]
         L.edlibAmdBatchWindowView.argtypes = [C.c_void_p, C.c_int, C.POINTER(WindowView)]
+        if hasattr(L, "edlibAmdBatchCreateSelf"):
+            L.edlibAmdBatchCreateSelf.restype = C.c_void_p
+            L.edlibAmdBatchCreateSelf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
+            L.edlibAmdBatchCreateSelfHits.restype = C.c_void_p
+            L.edlibAmdBatchCreateSelfHits.argtypes = L.edlibAmdBatchCreateSelf.argtypes
+            L.edlibAmdBatchSelfView.argtypes = [C.c_void_p, C.c_int, C.POINTER(SelfView)]
+            L.edlibAmdBatchSelfHits.argtypes = [C.c_void_p, C.POINTER(SelfHits)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -769,6 +788,116 @@ def align_windows(queries, target, unit_query, unit_start, unit_length, mode="HW
         return out
     finally:
         b.close()
+
+
+class SelfBatch(_Batch):
+    """One set against itself, NW distances only (edlibAmdBatchCreateSelf): the loop
+    ``for i: for j > i: edlib.align(seqs[i], seqs[j], "NW")`` as one resident batch that computes every unordered pair
+    once.  condensed() is the int32 vector of the n (n - 1) / 2 distances in scipy's pdist order (-1: above k),
+    nearest() the nearest other sequence of each.  hits=True (edlibAmdBatchCreateSelfHits, k >= 0): no vector; hits()
+    lists the pairs i < j within k."""
+
+    def __init__(self, seqs, k=-1, additionalEqualities=None, device=0, hits=False):
+        sd, so = _pack(seqs)
+        cfg, keep = _make_config("NW", "distance", k, additionalEqualities)
+        self.numSequences = len(so) - 1
+        self.numPairs = self.numSequences * (self.numSequences - 1) // 2
+        self.is_hits = bool(hits)
+        create = lib().edlibAmdBatchCreateSelfHits if hits else lib().edlibAmdBatchCreateSelf
+        h = create(sd.ctypes.data, so.ctypes.data, self.numSequences, cfg, device)
+        super().__init__(h, self.numPairs, keep)
+
+    def _view(self, what):
+        v = SelfView()
+        if lib().edlibAmdBatchSelfView(self._h, what, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: self view failed: " + last_error())
+        return v
+
+    def condensed(self, copy=True):
+        """The distances of the pairs i < j, int32 [n (n - 1) / 2], pair (i, j) at condensed_index(n, i, j).
+        copy=False: a view of the batch's pinned memory, valid until its next run() / close()."""
+        if self.is_hits:
+            raise RuntimeError("edlib_amd: a hit-list self batch keeps no condensed vector: use hits(), or create the "
+                               "batch without hits=True")
+        return CrossBatch._arr(self._view(SELF_DISTANCES).editDistance, (self.numPairs,), copy)
+
+    def nearest(self, copy=True):
+        """{nearest, nearestDistance, secondDistance}: int32 [n], over all other sequences; ties go to the lowest index,
+        -1 where no other sequence is within k."""
+        v = self._view(SELF_NEAREST)
+        return {f: CrossBatch._arr(getattr(v, f), (self.numSequences,), copy)
+                for f in ("nearest", "nearestDistance", "secondDistance")}
+
+    def hits(self, copy=True):
+        """The pairs within k of a hits=True batch, each once: rowOffsets int64 [n + 1] (partners of i:
+        [rowOffsets[i], rowOffsets[i + 1])) and partner (j > i, ascending inside a row) / editDistance int32 [numHits]."""
+        v = SelfHits()
+        if lib().edlibAmdBatchSelfHits(self._h, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: self hits failed: " + last_error())
+        n = int(v.numHits)
+        out = {"rowOffsets": CrossBatch._arr(v.rowOffsets, (self.numSequences + 1,), copy).astype(np.int64, copy=False)}
+        for f in ("partner", "editDistance"):
+            out[f] = CrossBatch._arr(getattr(v, f), (n,), copy) if n else np.zeros(0, dtype=np.int32)
+        return out
+
+    def results(self, raw=True):
+        raise RuntimeError("edlib_amd: a self batch has no per-unit results: use condensed() / hits() / nearest()")
+
+
+def pdist(seqs, k=-1, additionalEqualities=None):
+    """NW edit distances of every pair of seqs in one device batch: the int32 condensed vector of
+    scipy.spatial.distance.pdist's order (squareform() makes the matrix); -1 where a distance is above k >= 0."""
+    b = SelfBatch(seqs, k, additionalEqualities)
+    try:
+        b.run()
+        return b.condensed()
+    finally:
+        b.close()
+
+
+def pairs_within(seqs, k, additionalEqualities=None):
+    """Every pair i < j of seqs within k NW edits, each once, and the nearest other sequence of each, in one device batch:
+    the hits() and nearest() arrays of SelfBatch(..., hits=True) in one dictionary."""
+    b = SelfBatch(seqs, k, additionalEqualities, hits=True)
+    try:
+        b.run()
+        out = b.hits()
+        out.update(b.nearest())
+        return out
+    finally:
+        b.close()
+
+
+def condensed_index(n, i, j):
+    """Where pair (i, j), i != j, of n sequences sits in a condensed vector (scalars or integer arrays)."""
+    i, j = np.asarray(i, dtype=np.int64), np.asarray(j, dtype=np.int64)
+    lo, hi = np.minimum(i, j), np.maximum(i, j)
+    at = np.int64(n) * lo - lo * (lo + 1) // 2 + (hi - lo - 1)
+    return int(at) if at.ndim == 0 else at
+
+
+def self_nearest_model(n, first, second, ed):
+    """The nearest rules of a self batch stated in numpy (what SelfBatch.nearest() must equal): first / second / ed list
+    pairs of different sequences, each unordered pair at most once in either orientation, with their distances (-1:
+    not within k).  Per sequence, over its partners within k on either side, the smallest key (distance << 32) | partner
+    is the nearest; the second distance is the smallest distance over its other partners; -1 where there is none."""
+    a = np.asarray(first, dtype=np.int64).reshape(-1)
+    b = np.asarray(second, dtype=np.int64).reshape(-1)
+    d = np.asarray(ed, dtype=np.int64).reshape(-1)
+    keep = d >= 0
+    owner = np.concatenate([a[keep], b[keep]])
+    partner = np.concatenate([b[keep], a[keep]])
+    key = (np.concatenate([d[keep], d[keep]]) << 32) | partner
+    out = {f: np.full(n, -1, dtype=np.int32) for f in ("nearest", "nearestDistance", "secondDistance")}
+    order = np.lexsort((key, owner))                    # by sequence, then by key
+    o, key = owner[order], key[order]
+    lead = np.nonzero(np.concatenate([[True], o[1:] != o[:-1]]))[0] if len(o) else np.zeros(0, dtype=np.int64)
+    out["nearest"][o[lead]] = key[lead] & 0xffffffff
+    out["nearestDistance"][o[lead]] = key[lead] >> 32
+    has2 = lead + 1 < len(o)
+    has2[has2] = o[lead[has2] + 1] == o[lead[has2]]
+    out["secondDistance"][o[lead[has2]]] = key[lead[has2] + 1] >> 32
+    return out
 
 
 def window_best_model(unit_query, ed, numQueries):

@@ -16,7 +16,7 @@
 
 using namespace edlib_amd;
 
-// cross: a cross batch, windows: a window batch (impl unused by both)
+// cross: a cross batch or a self batch (cross->isSelf()), windows: a window batch (impl unused by both)
 struct EdlibAmdBatch { Batch impl; std::unique_ptr<CrossBatch> cross; std::unique_ptr<WindowBatch> windows; };
 
 static int not_on_windows(EdlibAmdBatch* b, const char* what) {
@@ -25,8 +25,14 @@ static int not_on_windows(EdlibAmdBatch* b, const char* what) {
     return 1;
 }
 
+static int not_on_self(EdlibAmdBatch* b, const char* what) {
+    if (!b->cross || !b->cross->isSelf()) return 0;
+    set_error("%s: not available on a self batch (edlibAmdBatchSelfView and edlibAmdBatchSelfHits have its results)", what);
+    return 1;
+}
+
 static int not_on_cross(EdlibAmdBatch* b, const char* what) {
-    if (not_on_windows(b, what)) return 1;
+    if (not_on_windows(b, what) || not_on_self(b, what)) return 1;
     if (!b->cross) return 0;
     set_error("%s: not available on a cross batch (edlibAmdBatchCrossView has its results)", what);
     return 1;
@@ -201,7 +207,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedHits(const char* queries, cons
 
 EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* b, EdlibAmdReadHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_windows(b, "edlibAmdBatchSharedHits")) return EDLIB_STATUS_ERROR;
+    if (not_on_windows(b, "edlibAmdBatchSharedHits") || not_on_self(b, "edlibAmdBatchSharedHits")) return EDLIB_STATUS_ERROR;
     if (b->cross) { set_error("edlibAmdBatchSharedHits: not a hit-list read batch (a cross batch has edlibAmdBatchCrossHits)"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSharedHits", 1, [&] { return b->impl.hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
@@ -271,7 +277,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossHitsBothStrands(const char* que
 
 EDLIB_API int edlibAmdBatchCrossStrands(EdlibAmdBatch* b, int what, EdlibAmdCrossStrands* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_windows(b, "edlibAmdBatchCrossStrands")) return EDLIB_STATUS_ERROR;
+    if (not_on_windows(b, "edlibAmdBatchCrossStrands") || not_on_self(b, "edlibAmdBatchCrossStrands")) return EDLIB_STATUS_ERROR;
     if (!b->cross) {
         set_error("edlibAmdBatchCrossStrands: not a both-strand cross batch (a both-strand read batch has edlibAmdBatchStrandView)");
         return EDLIB_STATUS_ERROR;
@@ -281,16 +287,53 @@ EDLIB_API int edlibAmdBatchCrossStrands(EdlibAmdBatch* b, int what, EdlibAmdCros
 
 EDLIB_API int edlibAmdBatchCrossView(EdlibAmdBatch* b, int what, EdlibAmdCrossView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_windows(b, "edlibAmdBatchCrossView")) return EDLIB_STATUS_ERROR;
+    if (not_on_windows(b, "edlibAmdBatchCrossView") || not_on_self(b, "edlibAmdBatchCrossView")) return EDLIB_STATUS_ERROR;
     if (!b->cross) { set_error("edlibAmdBatchCrossView: not a cross batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchCrossView", 1, [&] { return b->cross->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_windows(b, "edlibAmdBatchCrossHits")) return EDLIB_STATUS_ERROR;
+    if (not_on_windows(b, "edlibAmdBatchCrossHits") || not_on_self(b, "edlibAmdBatchCrossHits")) return EDLIB_STATUS_ERROR;
     if (!b->cross) { set_error("edlibAmdBatchCrossHits: not a cross batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchCrossHits", 1, [&] { return b->cross->hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+static EdlibAmdBatch* create_self(const char* where, const char* seqs, const long long* offsets, int numSequences,
+                                  EdlibAlignConfig config, int device, bool hits) {
+    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
+        EdlibAmdBatch* x = new EdlibAmdBatch;
+        x->cross.reset(new CrossBatch);
+        return x;
+    });
+    if (!b) return nullptr;
+    if (guarded(where, 1, [&] { return b->cross->initSelf(seqs, offsets, numSequences, config, device, hits); })) {
+        delete b;
+        return nullptr;
+    }
+    return b;
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelf(const char* seqs, const long long* offsets, int numSequences,
+                                                 EdlibAlignConfig config, int device) {
+    return create_self("edlibAmdBatchCreateSelf", seqs, offsets, numSequences, config, device, false);
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHits(const char* seqs, const long long* offsets, int numSequences,
+                                                     EdlibAlignConfig config, int device) {
+    return create_self("edlibAmdBatchCreateSelfHits", seqs, offsets, numSequences, config, device, true);
+}
+
+EDLIB_API int edlibAmdBatchSelfView(EdlibAmdBatch* b, int what, EdlibAmdSelfView* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfView: not a self batch"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchSelfView", 1, [&] { return b->cross->selfView(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+EDLIB_API int edlibAmdBatchSelfHits(EdlibAmdBatch* b, EdlibAmdSelfHits* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfHits: not a self batch"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchSelfHits", 1, [&] { return b->cross->selfHitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 static EdlibAmdBatch* create_windows(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
@@ -331,6 +374,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindowsStranded(const char* queries,
 
 EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* b, int what, EdlibAmdWindowView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_self(b, "edlibAmdBatchWindowView")) return EDLIB_STATUS_ERROR;
     if (!b->windows) { set_error("edlibAmdBatchWindowView: not a window batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchWindowView", 1, [&] { return b->windows->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }

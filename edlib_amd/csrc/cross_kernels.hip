@@ -58,17 +58,7 @@ hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const Cr
 
 // -------------------------------------------------------------- best hits
 
-__device__ __forceinline__ void best2_add(CrossBest2& r, const u64 key)
-{
-    if (key < r.b) { r.s = r.b; r.b = key; }
-    else if (key < r.s) r.s = key;
-}
-
-__device__ __forceinline__ void best2_merge(CrossBest2& r, const CrossBest2& o)
-{
-    if (o.b < r.b) { r.s = r.b < o.s ? r.b : o.s; r.b = o.b; }
-    else { r.s = r.s < o.b ? r.s : o.b; }
-}
+// best2_add / best2_merge: cross_kernels.hpp (shared with the self batches' nearest reduction)
 
 // per target over its queries: one wave per row of the matrix
 __global__ void __launch_bounds__(256)

@@ -60,6 +60,18 @@ __device__ __forceinline__ unsigned long long cross_key(int ed, int idx)
     return ed < 0 ? ~0ull : (((unsigned long long)(uint32_t)ed << 32) | (uint32_t)idx);
 }
 
+__device__ __forceinline__ void best2_add(CrossBest2& r, const unsigned long long key)
+{
+    if (key < r.b) { r.s = r.b; r.b = key; }
+    else if (key < r.s) r.s = key;
+}
+
+__device__ __forceinline__ void best2_merge(CrossBest2& r, const CrossBest2& o)
+{
+    if (o.b < r.b) { r.s = r.b < o.s ? r.b : o.s; r.b = o.b; }
+    else { r.s = r.s < o.b ? r.s : o.b; }
+}
+
 __device__ __forceinline__ void best2_store(const CrossBest2& r, int* best, int* bestD, int* secondD, int i)
 {
     best[i] = r.b == ~0ull ? -1 : (int)(uint32_t)r.b;
@@ -93,6 +105,14 @@ struct CrossScanArgs {
     // even, numQueries the number of queries (not of slots); one strand byte (bit 0 reverse complement, bit 1 the other
     // strand reaches the same distance) per stored cell [numTargets][numQueries], per appended hit [hitCap] in a hit list
     uint8_t* strand;
+    // self batches (launch_scan_cross_self; DESIGN.md §4h "Self batches"): queries and targets are one set, the targets
+    // in the order (length, index) -- a sequence's position there is its rank --, the query slots of a group in the same
+    // order.  A lane scans cell (slot, ts) only where ts > qrank[slot]; block b takes work item b, the query tile
+    // items[3b] against the target tiles [items[3b + 1], items[3b + 1] + items[3b + 2]).  ed is the condensed vector of
+    // numQueries sequences (pair (i, j), i < j, at numQueries i - i (i + 1) / 2 + j - i - 1), a hit's key (i << 32) | j.
+    const int* qrank;           // [slots] rank of the slot's sequence, -1 for a padding slot
+    const int* items;           // [3][numItems] as triples
+    int numItems;
 };
 
 hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, const int* tperm, const long long* tdw,
@@ -104,6 +124,16 @@ hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const Cr
 // the same scan over both strands of every query (cross_kernels_strands.hip): the combined cell per mate pair
 hipError_t launch_scan_cross_strands(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
                                      hipStream_t stream);
+// the self scan (cross_kernels_self.hip): NW only, one block per work item
+hipError_t launch_scan_cross_self(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
+// nearest other sequence of each of n sequences from the condensed vector: out [3][n] = nearest, nearestDistance,
+// secondDistance (the key rule of CrossBest2 over all partners on either side of the triangle)
+hipError_t launch_self_nearest_dense(const int* ed, int n, int* out, hipStream_t stream);
+// the same from the best hits of a finished hit list (launch_cross_hits_finish with numQueries = numTargets = n and keys
+// (i << 32) | j, i < j): best [3][n] over the partners above, then [3][n] over the partners below
+hipError_t launch_self_nearest_hits(const int* best, int n, int* out, hipStream_t stream);
+// distances computed by other engines into the condensed vector: ed[cell[i]] = vals[i]
+hipError_t launch_self_scatter(const long long* cell, const int* vals, long long n, int* ed, hipStream_t stream);
 // per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are
 // best index / best distance / second distance
 hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,

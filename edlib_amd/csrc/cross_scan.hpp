@@ -1,6 +1,7 @@
 // cross_scan.hpp -- the lane-per-cell scan of cross batches (DESIGN.md "Cross batches"): the kernel template and its
-// launch ladder, included by the two translation units that instantiate it -- cross_kernels.hip (one strand) and
-// cross_kernels_strands.hip (both strands), each half of the instantiations.
+// launch ladder, included by the translation units that instantiate it -- cross_kernels.hip (one strand) and
+// cross_kernels_strands.hip (both strands), each half of the cross instantiations, and cross_kernels_self.hip (self
+// batches, NW only).
 #pragma once
 #include "cross_kernels.hpp"
 #include "cross_column.hpp"
@@ -22,14 +23,19 @@ typedef unsigned long long u64;
 // even), so mates are the lanes l and l ^ 1 of the wave: the same target, `live`, n, query length, NW length window and
 // trip count.  Peq staging and the column loop are as for one strand; behind cross_cell_result() the mates exchange their
 // records, the even (forward) lane decides by resolve_strands() and is the only one that stores or appends.
-template <int NWD, int S, int MODE, bool HITS, bool STRANDS>
+// SELF (NW, one strand): one set against itself, every unordered pair once (CrossScanArgs::qrank / items).  Block b is
+// work item b: a query tile over a run of consecutive target tiles; a lane whose target's rank is not above its query's
+// is not live.  The rows are then the shorter sequence of the pair (ranks ascend with the length), a cell is stored at
+// the condensed index of its two sequence indices or appended with the key (lower << 32) | higher.
+template <int NWD, int S, int MODE, bool HITS, bool STRANDS, bool SELF = false>
 __global__ void __launch_bounds__(64)
 scan_cross_kernel(CrossScanArgs a)
 {
+    static_assert(!SELF || (MODE == 0 && !STRANDS), "self batches are NW on one strand");
     __shared__ u32 s_peq[S * NWD * 64];                 // [symbol][word][query of the tile]
     const int lane = threadIdx.x;
     const int qt = a.qt;
-    const int slot0 = blockIdx.x * qt;
+    const int slot0 = (SELF ? a.items[3 * blockIdx.x] : (int)blockIdx.x) * qt;
     {
         // staged once: the wave keeps this query tile for all its target tiles
         const u32* src = a.peq + (size_t)(slot0 >> 6) * (S * NWD * 64) + (slot0 & 63);
@@ -47,10 +53,13 @@ scan_cross_kernel(CrossScanArgs a)
     const int m = a.qlen[slot];
     const int sh = (m - 1) & 31;
     if (!HITS && q < 0) return;                         // (no barrier or ballot below)
-    const int numTT = (a.numSorted + tpt - 1) / tpt;
-    for (int tt = blockIdx.y; tt < numTT; tt += gridDim.y) {   // wave-uniform trip count
+    const int rank = SELF ? a.qrank[slot] : 0;
+    const int ttFirst = SELF ? a.items[3 * blockIdx.x + 1] : (int)blockIdx.y;
+    const int ttStep = SELF ? 1 : (int)gridDim.y;
+    const int numTT = SELF ? ttFirst + a.items[3 * blockIdx.x + 2] : (a.numSorted + tpt - 1) / tpt;
+    for (int tt = ttFirst; tt < numTT; tt += ttStep) {         // wave-uniform trip count
         const int ts = tt * tpt + ti;
-        const bool live = q >= 0 && ts < a.numSorted;
+        const bool live = q >= 0 && ts < a.numSorted && (!SELF || ts > rank);
         int ed = -1, nloc = 0, end = -1;
         if (live) {
             const int n = a.tlen[ts];
@@ -92,6 +101,15 @@ scan_cross_kernel(CrossScanArgs a)
         const bool mine = !STRANDS || !(q & 1);         // the forward lane reports the pair
         const int qout = STRANDS ? q >> 1 : q;
         if (!HITS) {
+            if (SELF) {
+                if (live) {
+                    // the pair's two sequence indices, lower first
+                    const u32 other = (u32)a.tperm[ts];
+                    const size_t slo = (u32)q < other ? (u32)q : other, shi = (u32)q < other ? other : (u32)q;
+                    a.ed[(size_t)a.numQueries * slo - (slo * (slo + 1)) / 2 + (shi - slo - 1)] = ed;
+                }
+                continue;
+            }
             if (live && mine) {
                 const size_t at = (size_t)a.tperm[ts] * (size_t)a.numQueries + (size_t)qout;
                 a.ed[at] = ed; a.nloc[at] = nloc; a.end[at] = end;
@@ -109,7 +127,10 @@ scan_cross_kernel(CrossScanArgs a)
         if (hit) {
             const u64 at = base + __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
             if (at < a.hitCap) {
-                a.hitKey[at] = ((u64)(u32)a.tperm[ts] << 32) | (u32)qout;
+                const u32 other = (u32)a.tperm[ts];
+                // self: the pair's two sequence indices, lower first
+                a.hitKey[at] = SELF ? ((u64)((u32)q < other ? (u32)q : other) << 32) | ((u32)q < other ? other : (u32)q)
+                                    : ((u64)other << 32) | (u32)qout;
                 a.hitVal[at] = ed; a.hitVal[a.hitCap + at] = nloc; a.hitVal[2 * a.hitCap + at] = end;
                 if (STRANDS) a.strand[at] = (uint8_t)sbyte;
             }

@@ -461,12 +461,19 @@ private:
 // A both-strand batch (strands) scans every query and its reverse complement (made on the device at init)
 // as the mates of neighbouring slots; a cell is the better strand's record (resolve_strands) and a strand byte beside it.
 // Its internal shared-target sessions are both-strand batches, its pair session holds both strands of every long query.
+// A self batch (initSelf; engine_self.hip, DESIGN.md §4h "Self batches") is one set against itself, NW only: every
+// unordered pair once, as a condensed vector or an i < j hit list, and the nearest other sequence of each.  nq_ = nt_ = n,
+// the packed targets, the Peq build, the hit list and its finish are the cross batch's own.
 class CrossBatch {
 public:
     ~CrossBatch();
     int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
              EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false);
+    int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits);
     int run();
+    int selfView(int what, EdlibAmdSelfView* out);
+    int selfHitsView(EdlibAmdSelfHits* out);
+    bool isSelf() const { return self_; }
     int view(int what, EdlibAmdCrossView* out);
     int hitsView(EdlibAmdCrossHits* out);
     int strandsView(int what, EdlibAmdCrossStrands* out);
@@ -479,6 +486,9 @@ private:
         long long wordSteps = 0;                  // word-steps of its scanned cells (NW, k >= 0: inside the length window)
         DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;
         DevBuf<uint32_t> d_peq;
+        // self batches: the rank of every slot, and the work items (query tile, first target tile, trips) of its launch
+        DevBuf<int> d_rank, d_items;
+        int numItems = 0;
     };
     EdlibAlignConfig cfg_{};
     std::vector<EdlibEqualityPair> eqs_;
@@ -527,11 +537,22 @@ private:
     DevBuf<uint8_t> d_smat_, d_sbest_, d_hstrand_, d_hsout_, d_svals_;
     PinBuf h_smat_, h_sbest_, h_svals_;
     std::vector<uint8_t> xStrand_;                // strand bytes of xKey_
+    // self batches: d_mat_ is the condensed vector [n (n - 1) / 2] (cells_), longPairs_ the i < j pairs outside the
+    // kernel's envelope; selfOther_ the keys (i << 32) | j of the pairs answered off the kernel -- first the selfEmpty_
+    // pairs with an empty sequence (distance: the other's length), then the pairs of longPairs_
+    bool self_ = false, nearFetched_ = false;
+    std::vector<unsigned long long> selfOther_;
+    std::vector<int> selfEmptyVal_;
+    DevBuf<int> d_near_;                          // [3][n]: nearest, nearestDistance, secondDistance
+    PinBuf h_near_;
+    int runSelf();
     int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
     int scanGroups();
     int growHits(long long cap);
     int finishHits();
 };
+// tile width of a word group: the lanes a tile shape leaves idle decide it (engine_cross.hip)
+int choose_qt(long long nq, long long nt, int minQt = 1);
 
 // Units over one resident target (engine_windows.hip, DESIGN.md "Window batches"): unit u is query unitQuery[u] against
 // the window [unitStart[u], unitStart[u] + unitLength[u]) of the target, DISTANCE only, a cross batch's cell contract per

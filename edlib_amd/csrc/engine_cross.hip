@@ -24,7 +24,7 @@ CrossBatch::~CrossBatch()
 
 // lanes a tile shape leaves idle decide it; on a tie the wider query tile (fewer Peq stagings)
 // (minQt = 2 for both strands: nq counts slots, mates are neighbouring lanes)
-static int choose_qt(long long nq, long long nt, int minQt = 1)
+int choose_qt(long long nq, long long nt, int minQt)
 {
     int bestQt = 64; long long bestLanes = -1;
     for (int qt = 64; qt >= minQt; qt >>= 1) {
@@ -294,6 +294,15 @@ int CrossBatch::scanGroups()
             a.ed = d_mat_.p; a.nloc = d_mat_.p + cells_; a.end = d_mat_.p + 2 * cells_;
         }
         a.strand = !strands_ ? nullptr : (hits_ ? d_hstrand_.p : d_smat_.p);
+        if (self_) {
+            // (the condensed vector is one plane: numLocations and endLocation are 1 and length - 1 for NW)
+            a.nloc = a.end = nullptr;
+            a.qrank = g->d_rank.p; a.items = g->d_items.p; a.numItems = g->numItems;
+            EDLIB_AMD_HIP(launch_scan_cross_self(g->words, syms_, hits_, a, stream_));
+            if (g->numItems > 0) ++stats.scan_launches;
+            stats.word_steps += g->wordSteps;
+            continue;
+        }
         EDLIB_AMD_HIP((strands_ ? launch_scan_cross_strands : launch_scan_cross)(g->words, syms_, (int)cfg_.mode, hits_, a,
                                                                                  g->ysplit, stream_));
         ++stats.scan_launches;
@@ -365,6 +374,7 @@ int CrossBatch::finishHits()
 
 int CrossBatch::run()
 {
+    if (self_) return runSelf();
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);

@@ -1,0 +1,367 @@
+// engine_self.hip -- the self mode of the cross engine (DESIGN.md §4h "Self batches"): one set against itself, NW
+// distances, every unordered pair once.  Create puts the sequences the kernel takes into the order (length, index) -- a
+// sequence's place there is its rank --, packs them once as the targets, makes the word groups (runs of that order) the
+// query slots, and cuts every query tile's range of wanted target tiles into work items of about equal trip counts.  A
+// Run builds the Peq rows, scans the items of every group, lets the internal pair batch take the pairs outside the
+// kernel's envelope, and reduces the nearest other sequence of each on the device.  The pack, the Peq build, the hit
+// list and its finish are the cross batch's own (engine_cross.hip, cross_hits.hip).
+#include "engine.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+namespace edlib_amd {
+
+typedef unsigned long long u64;
+
+int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibAlignConfig cfg, int device, bool hits)
+{
+    if (cfg.task != EDLIB_TASK_DISTANCE) {
+        set_error("self batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
+                  "for locations or paths");
+        return 1;
+    }
+    if (cfg.mode == EDLIB_MODE_HW || cfg.mode == EDLIB_MODE_SHW) {
+        set_error("self batches are global (EDLIB_MODE_NW): %s distances are not symmetric, pass the set as queries and "
+                  "as targets of a cross batch", cfg.mode == EDLIB_MODE_HW ? "HW" : "SHW");
+        return 1;
+    }
+    if (cfg.mode != EDLIB_MODE_NW) { set_error("unknown mode"); return 1; }
+    if (hits && cfg.k < 0) {
+        set_error("hit-list self batches need config.k >= 0 (every pair is a hit at k = %d: use edlibAmdBatchCreateSelf "
+                  "for the condensed distances)", cfg.k);
+        return 1;
+    }
+    if (n < 0 || (n > 0 && !offIn)) { set_error("bad batch shape"); return 1; }
+    std::vector<long long> off(n + 1, 0);
+    if (n > 0) off.assign(offIn, offIn + n + 1);
+    for (int i = 0; i < n; ++i)
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7fffffffLL) { set_error("bad sequence offsets"); return 1; }
+    const int ndev = device_count();
+    if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
+    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
+    cfg_ = cfg;
+    if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0)
+        eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
+    cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
+    cfg_.additionalEqualitiesLength = (int)eqs_.size();
+    device_ = device; nq_ = nt_ = n; hits_ = hits; strands_ = false; self_ = true;
+    const long long base = off[0], bytes = off[n] - base;
+    auto len = [&](int i) { return (int)(off[i + 1] - off[i]); };
+    const long long numPairs = (long long)n * (n - 1) / 2;
+    cells_ = (size_t)std::max(numPairs, 0LL);
+    stats = EdlibAmdBatchStats{};
+    {   // sum over i < j of m_i m_j = ((sum m)^2 - sum m^2) / 2
+        unsigned __int128 sq = 0;
+        for (int i = 0; i < n; ++i) sq += (unsigned __int128)len(i) * (unsigned __int128)len(i);
+        stats.cells = (long long)((((unsigned __int128)bytes * (unsigned __int128)bytes) - sq) / 2);
+    }
+    auto key = [](int i, int j) { return ((u64)(uint32_t)std::min(i, j) << 32) | (uint32_t)std::max(i, j); };
+    auto inWindow = [&](int a, int b) {
+        const long long d = (long long)len(a) - len(b);
+        return cfg.k < 0 || (d < 0 ? -d : d) <= cfg.k;
+    };
+
+    build_tables(tab_, reinterpret_cast<const uint8_t*>(seqs) + base, bytes, eqs_.data(), (int)eqs_.size());
+    const bool wide = tab_.sigmaT > kCrossMaxSyms;
+    syms_ = tab_.sigmaT <= 4 ? 4 : (tab_.sigmaT <= 8 ? 8 : 16);
+    // the kernel's sequences in the order (length, index); the empty ones are answered here, the others by the pair batch
+    std::vector<int> inK, empties, outK;
+    for (int i = 0; i < n; ++i) {
+        if (len(i) == 0) empties.push_back(i);
+        else if (!wide && len(i) <= 32 * kCrossMaxQueryWords) inK.push_back(i);
+        else outK.push_back(i);
+    }
+    std::stable_sort(inK.begin(), inK.end(), [&](int a, int b) { return len(a) < len(b); });
+
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    EDLIB_AMD_HIP(pool_stream(&stream_));
+    EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
+    EDLIB_AMD_HIP(d_near_.alloc(3 * (size_t)n));
+    if (!hits_) EDLIB_AMD_HIP(d_mat_.alloc(std::max<size_t>(cells_, 1)));
+    else {
+        EDLIB_AMD_HIP(d_best_.alloc(6 * (size_t)n));
+        EDLIB_AMD_HIP(d_hcount_.alloc(1)); EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
+        EDLIB_AMD_HIP(d_htoff_.alloc((size_t)n + 1));
+        EDLIB_AMD_HIP(d_bkey_.alloc(4 * (size_t)n));
+        if (growHits(std::max<long long>(1LL << 20, 2LL * n))) return 1;
+    }
+
+    // ---- the kernel's share
+    if (inK.size() >= 2) {
+        numSorted_ = (int)inK.size();
+        std::vector<long long> tdw(numSorted_), colsBelow(numSorted_ + 1, 0);
+        std::vector<int> tl(numSorted_);
+        long long dw = 0;
+        for (int r = 0; r < numSorted_; ++r) {
+            tdw[r] = dw; tl[r] = len(inK[r]);
+            dw += (tl[r] + 7) / 8;
+            sortedCols_ += tl[r];
+            colsBelow[r + 1] = sortedCols_;
+        }
+        // one past the last rank inside the length window of a row of length m (rows are the shorter sequence)
+        auto windowEnd = [&](int m) -> int {
+            if (cfg.k < 0) return numSorted_;
+            return (int)(std::upper_bound(tl.begin(), tl.end(), (long long)m + cfg.k) - tl.begin());
+        };
+        std::vector<long long> offR(off);
+        for (auto& v : offR) v -= base;
+        // the pool goes up once: the pack reads it as the targets, the Peq build as the queries
+        EDLIB_AMD_HIP(d_qpool_.alloc((size_t)bytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc((size_t)n + 1));
+        EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, seqs + base, (size_t)bytes, hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, offR.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(d_tpk_.alloc((size_t)std::max(dw, 1LL)));
+        EDLIB_AMD_HIP(d_tdw_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tperm_.alloc(numSorted_));
+        EDLIB_AMD_HIP(hipMemcpy(d_tdw_.p, tdw.data(), numSorted_ * sizeof(long long), hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, tl.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_tperm_.p, inK.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
+        {
+            DevBuf<uint8_t> d_tlut;
+            EDLIB_AMD_HIP(d_tlut.alloc(256));
+            EDLIB_AMD_HIP(hipMemcpy(d_tlut.p, tab_.tlut, 256, hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(launch_pack_cross_targets(d_qpool_.p, d_qoff_.p, d_tperm_.p, d_tdw_.p, numSorted_, d_tlut.p, d_tpk_.p, stream_));
+            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        }
+        EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
+        EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
+        // a word group is a run of ranks [r0, r1): its slot s holds rank r0 + s, so the rank rises with the slot
+        for (int r0 = 0; r0 < numSorted_;) {
+            const int w = (tl[r0] + 31) / 32;
+            int r1 = r0;
+            while (r1 < numSorted_ && (tl[r1] + 31) / 32 == w) ++r1;
+            const int cnt = r1 - r0;
+            std::unique_ptr<Group> g(new Group);
+            g->words = w;
+            g->qt = choose_qt(cnt, numSorted_);
+            g->tiles = (cnt + g->qt - 1) / g->qt;
+            g->slots = g->tiles * g->qt;
+            const int tpt = 64 / g->qt;
+            std::vector<int> perm(g->slots, -1), rank(g->slots, -1);
+            for (int s = 0; s < cnt; ++s) {
+                perm[s] = inK[r0 + s]; rank[s] = r0 + s;
+                g->wordSteps += (long long)w * (colsBelow[windowEnd(tl[r0 + s])] - colsBelow[r0 + s + 1]);
+            }
+            // per query tile the target tiles that hold a wanted cell inside the length window: from the tile of the rank
+            // behind the tile's lowest to the tile of the last rank within k of the tile's longest query
+            std::vector<int> first(g->tiles), trips(g->tiles);
+            long long allTrips = 0;
+            for (int t = 0; t < g->tiles; ++t) {
+                const int lo = r0 + t * g->qt + 1, hi = windowEnd(tl[r0 + std::min(cnt, (t + 1) * g->qt) - 1]);
+                first[t] = lo / tpt;
+                trips[t] = hi > lo ? (hi - 1) / tpt - first[t] + 1 : 0;
+                allTrips += trips[t];
+            }
+            // work items of about equal trip counts, about 8,192 of them per launch (256 CUs; the cross launch's aim): a
+            // range is cut into equal parts of at most `chunk` trips, never under 16 trips unless the range is shorter, so
+            // the Peq staging of an item stays amortised
+            const long long chunk = std::max(16LL, (allTrips + 8191) / 8192);
+            std::vector<int> items;
+            for (int t = 0; t < g->tiles; ++t) {
+                if (trips[t] == 0) continue;
+                const long long parts = std::max(1LL, std::min((trips[t] + chunk - 1) / chunk, (long long)trips[t] / 16));
+                for (long long p = 0; p < parts; ++p) {
+                    const long long a = trips[t] * p / parts, b = trips[t] * (p + 1) / parts;
+                    items.push_back(t); items.push_back(first[t] + (int)a); items.push_back((int)(b - a));
+                }
+            }
+            g->numItems = (int)(items.size() / 3);
+            const size_t blocks = (size_t)(g->slots + 63) / 64;
+            EDLIB_AMD_HIP(g->d_perm.alloc(g->slots)); EDLIB_AMD_HIP(g->d_qlen.alloc(g->slots));
+            EDLIB_AMD_HIP(g->d_kinit.alloc(g->slots)); EDLIB_AMD_HIP(g->d_alpha.alloc(g->slots));
+            EDLIB_AMD_HIP(g->d_rank.alloc(g->slots)); EDLIB_AMD_HIP(g->d_items.alloc(std::max<size_t>(items.size(), 3)));
+            EDLIB_AMD_HIP(g->d_peq.alloc(blocks * syms_ * w * 64));
+            EDLIB_AMD_HIP(hipMemcpy(g->d_perm.p, perm.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(g->d_rank.p, rank.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
+            if (!items.empty())
+                EDLIB_AMD_HIP(hipMemcpy(g->d_items.p, items.data(), items.size() * sizeof(int), hipMemcpyHostToDevice));
+            groups_.push_back(std::move(g));
+            r0 = r1;
+        }
+    }
+
+    // ---- the pairs answered off the kernel: those with an empty sequence here, the rest by one pair batch
+    for (int e : empties)
+        for (int x = 0; x < n; ++x) {
+            if (x == e || (len(x) == 0 && x < e)) continue;          // two empty sequences: once
+            selfOther_.push_back(key(e, x));
+            selfEmptyVal_.push_back(len(x));
+        }
+    {
+        std::vector<char> qp, tp;
+        std::vector<long long> qo(1, 0), to(1, 0);
+        long long np = 0;
+        auto add = [&](int i, int j) {                                // i < j, both with bases
+            if (!inWindow(i, j)) return;
+            if (++np > 0x7fffffffLL) return;
+            qp.insert(qp.end(), seqs + off[i], seqs + off[i + 1]);
+            tp.insert(tp.end(), seqs + off[j], seqs + off[j + 1]);
+            qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
+            selfOther_.push_back(key(i, j));
+        };
+        std::vector<char> isOut(n, 0);
+        for (int i : outK) isOut[i] = 1;
+        for (int i : outK)
+            for (int x = 0; x < n && np <= 0x7fffffffLL; ++x) {
+                if (x == i || len(x) == 0 || (isOut[x] && x < i)) continue;   // two such sequences: once
+                add(std::min(i, x), std::max(i, x));
+            }
+        if (np > 0x7fffffffLL) {
+            set_error("self batch: too many pairs outside the kernel's envelope (more than 2^31 - 1): sequences above %d "
+                      "bases or a set with more than %d symbols", 32 * kCrossMaxQueryWords, kCrossMaxSyms);
+            return 1;
+        }
+        if (np > 0) {
+            longPairs_.reset(new Batch);
+            if (longPairs_->init(qp.data(), qo.data(), (int)np, tp.data(), to.data(), (int)np, cfg_, device)) return 1;
+        }
+    }
+    otherCells_ = (long long)selfOther_.size();
+    if (otherCells_ > 0) {
+        EDLIB_AMD_HIP(h_vals_.alloc((size_t)otherCells_ * sizeof(int)));
+        std::copy(selfEmptyVal_.begin(), selfEmptyVal_.end(), reinterpret_cast<int*>(h_vals_.p));
+        if (!hits_) {
+            std::vector<long long> cellIdx((size_t)otherCells_);
+            for (size_t c = 0; c < cellIdx.size(); ++c) {
+                const long long i = (long long)(selfOther_[c] >> 32), j = (long long)(uint32_t)selfOther_[c];
+                cellIdx[c] = (long long)n * i - i * (i + 1) / 2 + (j - i - 1);
+            }
+            EDLIB_AMD_HIP(d_cells_.alloc((size_t)otherCells_)); EDLIB_AMD_HIP(d_vals_.alloc((size_t)otherCells_));
+            EDLIB_AMD_HIP(hipMemcpy(d_cells_.p, cellIdx.data(), (size_t)otherCells_ * sizeof(long long), hipMemcpyHostToDevice));
+        }
+    }
+    return 0;
+}
+
+int CrossBatch::runSelf()
+{
+    pool_quarantine(false);
+    const auto t0 = std::chrono::steady_clock::now();
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    haveRun_ = matFetched_ = nearFetched_ = hitsFetched_ = false;
+    const long long cells = stats.cells;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = cells;
+    if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
+    // the pairs outside the length window are visited by no work item and are in no pair batch: -1 from here
+    else if (cfg_.k >= 0 && cells_ > 0) EDLIB_AMD_HIP(hipMemsetAsync(d_mat_.p, 0xff, cells_ * sizeof(int), stream_));
+
+    if (!groups_.empty()) {
+        for (auto& g : groups_)
+            EDLIB_AMD_HIP(launch_build_peq_reads(g->words, syms_, d_qpool_.p, d_qoff_.p, g->d_perm.p, g->slots, d_eqtbl_.p,
+                                                 d_presence_.p, cfg_.k, g->d_peq.p, g->d_qlen.p, g->d_kinit.p, g->d_alpha.p,
+                                                 stream_));
+        EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
+        if (scanGroups()) return 1;
+        EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
+        stats.path |= 8;
+    }
+    xKey_.clear(); xVal_.clear();
+    if (otherCells_ > 0) {
+        int* vals = reinterpret_cast<int*>(h_vals_.p);
+        const size_t ne = selfEmptyVal_.size(), np = (size_t)otherCells_ - ne;
+        if (longPairs_) {
+            if (longPairs_->run()) return 1;
+            std::vector<int> rec(3 * np);
+            if (gather(*longPairs_, np, rec.data(), nullptr)) return 1;
+            for (size_t c = 0; c < np; ++c) vals[ne + c] = rec[3 * c];
+            longPairs_->finishStats();
+            const EdlibAmdBatchStats& s = longPairs_->stats;
+            stats.scan_launches += s.scan_launches;
+            stats.path |= s.path; stats.overflow_units += s.overflow_units; stats.wide_retries += s.wide_retries;
+        }
+        if (!hits_) {
+            EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
+            EDLIB_AMD_HIP(launch_self_scatter(d_cells_.p, d_vals_.p, otherCells_, d_mat_.p, stream_));
+        } else {
+            // their pairs within k behind the kernel's, as [key], [ed][nloc][end] (NW: one location, the last column)
+            std::vector<int> e3[3];
+            for (long long c = 0; c < otherCells_; ++c) {
+                if (vals[c] == -1) continue;
+                xKey_.push_back(selfOther_[(size_t)c]);
+                e3[0].push_back(vals[c]); e3[1].push_back(1); e3[2].push_back(-1);      // (only the distance is reported)
+            }
+            for (int f = 0; f < 3; ++f) xVal_.insert(xVal_.end(), e3[f].begin(), e3[f].end());
+        }
+    }
+    if (hits_) {
+        if (finishHits()) return 1;
+        EDLIB_AMD_HIP(launch_self_nearest_hits(d_best_.p, nq_, d_near_.p, stream_));
+    } else {
+        EDLIB_AMD_HIP(launch_self_nearest_dense(d_mat_.p, nq_, d_near_.p, stream_));
+    }
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (!groups_.empty()) {
+        float ms = 0.f;
+        EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evScan0_.e, evScan1_.e));
+        stats.scan_ms = ms;
+    }
+    stats.algo_bytes = 0;
+    stats.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    haveRun_ = true;
+    return 0;
+}
+
+int CrossBatch::selfView(int what, EdlibAmdSelfView* out)
+{
+    if (!haveRun_) { set_error("self batch: no results (Run it first)"); return 1; }
+    if (what & ~(EDLIB_AMD_SELF_DISTANCES | EDLIB_AMD_SELF_NEAREST)) { set_error("self view: unknown parts %d", what); return 1; }
+    if (hits_) what &= ~EDLIB_AMD_SELF_DISTANCES;               // a hit-list batch keeps no condensed vector
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    const size_t matBytes = cells_ * sizeof(int), nearBytes = 3 * (size_t)nq_ * sizeof(int);
+    if ((what & EDLIB_AMD_SELF_DISTANCES) && !matFetched_) {
+        if (h_mat_.n < matBytes || !h_mat_.p) EDLIB_AMD_HIP(h_mat_.alloc(matBytes));
+        if (matBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_mat_.p, d_mat_.p, matBytes, hipMemcpyDeviceToHost, stream_));
+    }
+    if ((what & EDLIB_AMD_SELF_NEAREST) && !nearFetched_) {
+        if (h_near_.n < nearBytes || !h_near_.p) EDLIB_AMD_HIP(h_near_.alloc(nearBytes));
+        if (nearBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_near_.p, d_near_.p, nearBytes, hipMemcpyDeviceToHost, stream_));
+    }
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (what & EDLIB_AMD_SELF_DISTANCES) matFetched_ = true;
+    if (what & EDLIB_AMD_SELF_NEAREST) nearFetched_ = true;
+    memset(out, 0, sizeof *out);
+    out->numSequences = nq_; out->numPairs = (long long)cells_;
+    if (what & EDLIB_AMD_SELF_DISTANCES) out->editDistance = reinterpret_cast<const int*>(h_mat_.p);
+    if (what & EDLIB_AMD_SELF_NEAREST) {
+        const int* b = reinterpret_cast<const int*>(h_near_.p);
+        out->nearest = b; out->nearestDistance = b + nq_; out->secondDistance = b + 2 * (size_t)nq_;
+    }
+    return 0;
+}
+
+int CrossBatch::selfHitsView(EdlibAmdSelfHits* out)
+{
+    if (!hits_) {
+        set_error("edlibAmdBatchSelfHits: not a hit-list batch (create it with edlibAmdBatchCreateSelfHits; a dense self "
+                  "batch has edlibAmdBatchSelfView)");
+        return 1;
+    }
+    if (!haveRun_) { set_error("self batch: no results (Run it first)"); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    // the finished list is [4][numHits] (partner, editDistance, numLocations, endLocation): the first two planes travel
+    const size_t offBytes = ((size_t)nq_ + 1) * sizeof(long long), listBytes = 2 * (size_t)numHits_ * sizeof(int);
+    if (!hitsFetched_) {
+        if (h_hits_.n < offBytes + listBytes || !h_hits_.p) EDLIB_AMD_HIP(h_hits_.alloc(offBytes + listBytes));
+        EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p, d_htoff_.p, offBytes, hipMemcpyDeviceToHost, stream_));
+        if (listBytes)
+            EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p + offBytes, d_hout_.p, listBytes, hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        hitsFetched_ = true;
+    }
+    memset(out, 0, sizeof *out);
+    out->numSequences = nq_; out->numHits = numHits_;
+    out->rowOffsets = reinterpret_cast<const long long*>(h_hits_.p);
+    const int* l = reinterpret_cast<const int*>(h_hits_.p + offBytes);
+    out->partner = l; out->editDistance = l + (size_t)numHits_;
+    return 0;
+}
+
+}  // namespace edlib_amd

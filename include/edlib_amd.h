@@ -250,6 +250,62 @@ typedef struct {
 } EdlibAmdCrossStrands;
 EDLIB_API int edlibAmdBatchCrossStrands(EdlibAmdBatch* batch, int what, EdlibAmdCrossStrands* out);
 
+/* One set of numSequences sequences against itself (a self batch): replaces
+ *   for i: for j > i: d(i, j) = edlibAlign(seq i, .., seq j, .., config).editDistance
+ * (UMI / barcode de-duplication, barcode-set design checks, amplicon and sequence clustering, distance matrices for trees)
+ * with every unordered pair computed once -- NW distance is symmetric, and so are additionalEqualities -- and the set
+ * uploaded, packed and profiled once; a cross batch given the same pool twice scans every pair twice.  d(i, j) is what a
+ * cross batch reports for query i against target j: -1 above k or where the lengths differ by more than k, and for an
+ * empty sequence the other's length whatever k.  numLocations and endLocation are not reported (NW: 1 and length - 1).
+ * Accepted: config.mode == EDLIB_MODE_NW, config.task == EDLIB_TASK_DISTANCE, any k (CreateSelfHits: k >= 0),
+ * additionalEqualities; anything else returns NULL with the reason in edlibAmdLastError(), as do numSequences < 0 and
+ * offsets that descend -- all checked before the device is.  numSequences 0 and 1 are valid batches without a pair.
+ * edlibAmdBatchCreateSelf keeps the distances as a condensed vector (n (n - 1) / 2 ints on the device);
+ * edlibAmdBatchCreateSelfHits keeps only the pairs within k, as a list that starts at max(2^20, 2 n) hits and grows as a
+ * hit-list cross batch's does.  Pairs of sequences up to 256 bases over at most 16 symbols run on the self instantiation
+ * of the cross kernel; pairs with a longer sequence, and every pair of a set with more symbols, run through one internal
+ * pair batch over the i < j pairs inside the length window (at most 2^31 - 1 of them).
+ * Run, Stats and Destroy work as for a cross batch (Stats.path bit 3: the kernel, bit 1: the pair batch; Stats.cells the
+ * sum of length i * length j over i < j; Stats.word_steps the sum of ceil(min / 32) * max of the two lengths over the
+ * pairs the kernel scans); every other view (Results.., CigarView, StrandView, CrossView, CrossHits, CrossStrands,
+ * SharedHits, WindowView) fails and names the self views. */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelf(
+    const char* seqs, const long long* offsets, int numSequences, EdlibAlignConfig config, int device);
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHits(
+    const char* seqs, const long long* offsets, int numSequences, EdlibAlignConfig config, int device);
+
+/* Results of the last Run of a self batch (it fails on every other kind, and before the first Run), as pointers into
+ * pinned host memory the batch owns (valid until the next Run / Destroy).  Only the parts asked for in `what`
+ * (EDLIB_AMD_SELF_DISTANCES | EDLIB_AMD_SELF_NEAREST) cross the link.
+ * editDistance is in condensed order (scipy's pdist / squareform): pair (i, j), i < j, is at
+ * numSequences * i - i * (i + 1) / 2 + (j - i - 1), computed in 64 bits; it is NULL when not asked for and in a hit-list
+ * batch.  Nearest, of both kinds of batch: over all OTHER sequences, on either side of the triangle, the smallest
+ * (distance << 32) | partner wins, so ties go to the lowest index; secondDistance is the smallest distance over the
+ * remaining partners (equal to the best on a tie); all three are -1 where no other sequence is within k. */
+typedef struct {
+    int numSequences;
+    long long numPairs;               /* numSequences * (numSequences - 1) / 2                       */
+    const int* editDistance;          /* [numPairs] condensed, -1: above k                           */
+    const int* nearest;               /* [numSequences]                                              */
+    const int* nearestDistance;       /* [numSequences]                                              */
+    const int* secondDistance;        /* [numSequences]                                              */
+} EdlibAmdSelfView;
+#define EDLIB_AMD_SELF_DISTANCES 1
+#define EDLIB_AMD_SELF_NEAREST   2
+EDLIB_API int edlibAmdBatchSelfView(EdlibAmdBatch* batch, int what, EdlibAmdSelfView* out);
+
+/* The hits of the last Run of a hit-list self batch: every pair i < j whose distance is not -1, exactly once, grouped by
+ * i (CSR) with the partners j > i ascending inside a row; no (i, i) entry.  Pinned memory the batch owns, valid until the
+ * next Run / Destroy. */
+typedef struct {
+    int numSequences;
+    long long numHits;
+    const long long* rowOffsets;      /* [numSequences + 1]: partners of i are [rowOffsets[i], rowOffsets[i+1]) */
+    const int* partner;               /* [numHits] j > i */
+    const int* editDistance;          /* [numHits] */
+} EdlibAmdSelfHits;
+EDLIB_API int edlibAmdBatchSelfHits(EdlibAmdBatch* batch, EdlibAmdSelfHits* out);
+
 /* A shared-target batch whose results are, per read, EVERY occurrence within k along the target -- the search question of
  * adapter / primer trimming, concatemer splitting, repeat finding and multi-mapping reads, which no choice of k makes
  * edlibAlign() answer (it keeps the columns of the single best score only).
