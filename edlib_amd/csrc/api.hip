@@ -2,7 +2,7 @@
 // batch surface of include/edlib_amd.h.  No C++ types cross this boundary.
 #define EDLIB_SHARED
 #define EDLIB_BUILD
-#include "engine.hpp"
+#include "engine_lanes.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -65,6 +65,18 @@ static EdlibAlignResult blank_result(int status) {
     r.endLocations = nullptr; r.startLocations = nullptr; r.numLocations = 0;
     r.alignment = nullptr; r.alignmentLength = 0; r.alphabetLength = 0;
     return r;
+}
+
+// A batch whose init (a callable on the new batch) succeeded, or NULL with the error set
+template <typename F>
+static EdlibAmdBatch* create_batch(const char* where, F&& init) {
+    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
+    if (!b) return nullptr;
+    if (guarded(where, 1, [&] { return init(*b); })) {
+        delete b;
+        return nullptr;
+    }
+    return b;
 }
 
 extern "C" {
@@ -140,69 +152,42 @@ EDLIB_API int edlibAmdDeviceCount(void) { return device_count(); }
 EDLIB_API const char* edlibAmdLastError(void) { return last_error().c_str(); }
 EDLIB_API const char* edlibAmdVersion(void) { return "edlib-mi355x 0.1 (API of edlib 1.2.6)"; }
 
+static EdlibAmdBatch* create_shared(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
+                                    const char* target, int targetLength, EdlibAlignConfig config, int device,
+                                    bool bothStrands, bool hits) {
+    if (targetLength < 0) { set_error("negative target length"); return nullptr; }
+    const long long toff[2] = {0, targetLength};
+    return create_batch(where, [&](EdlibAmdBatch& b) {
+        return b.impl.init(queries, queryOffsets, numQueries, target, toff, 1, config, device, bothStrands, hits); });
+}
+
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateShared(const char* queries, const long long* queryOffsets,
                                                    int numQueries, const char* target, int targetLength,
                                                    EdlibAlignConfig config, int device) {
-    EdlibAmdBatch* b = guarded("edlibAmdBatchCreateShared", static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
-    if (!b) return nullptr;
-    const long long toff[2] = {0, targetLength};
-    const int rc = targetLength < 0 ? 1 : guarded("edlibAmdBatchCreateShared", 1, [&] {
-        return b->impl.init(queries, queryOffsets, numQueries, target, toff, 1, config, device); });
-    if (targetLength < 0) set_error("negative target length");
-    if (rc) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_shared("edlibAmdBatchCreateShared", queries, queryOffsets, numQueries, target, targetLength, config, device,
+                         false, false);
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreatePairs(const char* queries, const long long* queryOffsets,
                                                   const char* targets, const long long* targetOffsets,
                                                   int numPairs, EdlibAlignConfig config, int device) {
-    EdlibAmdBatch* b = guarded("edlibAmdBatchCreatePairs", static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
-    if (!b) return nullptr;
     // a one-pair batch is also a shared-target batch
-    if (guarded("edlibAmdBatchCreatePairs", 1, [&] {
-            return b->impl.init(queries, queryOffsets, numPairs, targets, targetOffsets, numPairs, config, device); })) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_batch("edlibAmdBatchCreatePairs", [&](EdlibAmdBatch& b) {
+        return b.impl.init(queries, queryOffsets, numPairs, targets, targetOffsets, numPairs, config, device); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedBothStrands(const char* queries, const long long* queryOffsets,
                                                               int numQueries, const char* target, int targetLength,
                                                               EdlibAlignConfig config, int device) {
-    const char* where = "edlibAmdBatchCreateSharedBothStrands";
-    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
-    if (!b) return nullptr;
-    const long long toff[2] = {0, targetLength};
-    const int rc = targetLength < 0 ? 1 : guarded(where, 1, [&] {
-        return b->impl.init(queries, queryOffsets, numQueries, target, toff, 1, config, device, /*bothStrands=*/true); });
-    if (targetLength < 0) set_error("negative target length");
-    if (rc) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_shared("edlibAmdBatchCreateSharedBothStrands", queries, queryOffsets, numQueries, target, targetLength,
+                         config, device, /*bothStrands=*/true, false);
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedHits(const char* queries, const long long* queryOffsets, int numQueries,
                                                        const char* target, int targetLength, EdlibAlignConfig config,
                                                        int device) {
-    const char* where = "edlibAmdBatchCreateSharedHits";
-    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] { return new EdlibAmdBatch; });
-    if (!b) return nullptr;
-    const long long toff[2] = {0, targetLength};
-    const int rc = targetLength < 0 ? 1 : guarded(where, 1, [&] {
-        return b->impl.init(queries, queryOffsets, numQueries, target, toff, 1, config, device, /*bothStrands=*/false,
-                            /*hits=*/true); });
-    if (targetLength < 0) set_error("negative target length");
-    if (rc) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_shared("edlibAmdBatchCreateSharedHits", queries, queryOffsets, numQueries, target, targetLength, config,
+                         device, false, /*hits=*/true);
 }
 
 EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* b, EdlibAmdReadHits* out) {
@@ -230,19 +215,10 @@ EDLIB_API void edlibAmdReverseComplement(const char* in, int n, char* out) {
 static EdlibAmdBatch* create_cross(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
                                    const char* targets, const long long* targetOffsets, int numTargets,
                                    EdlibAlignConfig config, int device, bool hits, bool strands = false) {
-    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
-        EdlibAmdBatch* x = new EdlibAmdBatch;
-        x->cross.reset(new CrossBatch);
-        return x;
-    });
-    if (!b) return nullptr;
-    if (guarded(where, 1, [&] {
-            return b->cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device,
-                                  hits, strands); })) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_batch(where, [&](EdlibAmdBatch& b) {
+        b.cross.reset(new CrossBatch);
+        return b.cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device, hits,
+                             strands); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(const char* queries, const long long* queryOffsets, int numQueries,
@@ -301,17 +277,9 @@ EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
 
 static EdlibAmdBatch* create_self(const char* where, const char* seqs, const long long* offsets, int numSequences,
                                   EdlibAlignConfig config, int device, bool hits) {
-    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
-        EdlibAmdBatch* x = new EdlibAmdBatch;
-        x->cross.reset(new CrossBatch);
-        return x;
-    });
-    if (!b) return nullptr;
-    if (guarded(where, 1, [&] { return b->cross->initSelf(seqs, offsets, numSequences, config, device, hits); })) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_batch(where, [&](EdlibAmdBatch& b) {
+        b.cross.reset(new CrossBatch);
+        return b.cross->initSelf(seqs, offsets, numSequences, config, device, hits); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelf(const char* seqs, const long long* offsets, int numSequences,
@@ -340,19 +308,10 @@ static EdlibAmdBatch* create_windows(const char* where, const char* queries, con
                                      const char* target, int targetLength, const int* unitQuery, const int* unitStart,
                                      const int* unitLength, const unsigned char* unitStrand, int numUnits,
                                      EdlibAlignConfig config, int device) {
-    EdlibAmdBatch* b = guarded(where, static_cast<EdlibAmdBatch*>(nullptr), [] {
-        EdlibAmdBatch* x = new EdlibAmdBatch;
-        x->windows.reset(new WindowBatch);
-        return x;
-    });
-    if (!b) return nullptr;
-    if (guarded(where, 1, [&] {
-            return b->windows->init(queries, queryOffsets, numQueries, target, targetLength, unitQuery, unitStart,
-                                    unitLength, unitStrand, numUnits, config, device); })) {
-        delete b;
-        return nullptr;
-    }
-    return b;
+    return create_batch(where, [&](EdlibAmdBatch& b) {
+        b.windows.reset(new WindowBatch);
+        return b.windows->init(queries, queryOffsets, numQueries, target, targetLength, unitQuery, unitStart, unitLength,
+                               unitStrand, numUnits, config, device); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindows(const char* queries, const long long* queryOffsets, int numQueries,

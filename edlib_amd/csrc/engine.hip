@@ -236,21 +236,12 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
     }
     hits_ = hits;
     if (bothStrands && (numTargets != 1 || n > 0x3fffffff)) { set_error("bad both-strand batch shape"); return 1; }
-    const int ndev = device_count();
-    if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
-    cfg_ = cfg;
-    if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0)
-        eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
-    cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
-    cfg_.additionalEqualitiesLength = (int)eqs_.size();
+    if (check_device(device)) return 1;
+    keep_config(cfg, cfg_, eqs_);
     device_ = device;
     strands_ = bothStrands;
     shared_ = (numTargets == 1);
-    toff_.assign(toff, toff + numTargets + 1);
-    for (int u = 0; u < n; ++u) {
-        if (qoff[u + 1] < qoff[u] || qoff[u + 1] - qoff[u] > 0x7fffffffLL) { set_error("bad query offsets"); return 1; }
-    }
+    if (copy_offsets(qoff, n, "query", qoff_)) return 1;
     const int numReads = n;
     const long long qb = qoff[0];
     if (strands_) {
@@ -259,11 +250,9 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
         qoff_.resize((size_t)n + 1);
         for (int i = 0; i < numReads; ++i) { qoff_[2 * i] = 2 * (qoff[i] - qb); qoff_[2 * i + 1] = 2 * (qoff[i] - qb) + (qoff[i + 1] - qoff[i]); }
         qoff_[n] = 2 * (qoff[numReads] - qb);
-    } else qoff_.assign(qoff, qoff + n + 1);
-    n_ = n;
-    for (int u = 0; u < numTargets; ++u) {
-        if (toff_[u + 1] < toff_[u] || toff_[u + 1] - toff_[u] > 0x7fffffffLL) { set_error("bad target offsets"); return 1; }
     }
+    n_ = n;
+    if (copy_offsets(toff, numTargets, "target", toff_)) return 1;
     const long long qbytes = qoff_[n] - qoff_[0], tbytes = toff_[numTargets] - toff_[0];
     build_tables(tab_, reinterpret_cast<const uint8_t*>(targets) + toff_[0], tbytes,
                  eqs_.data(), (int)eqs_.size());
@@ -336,7 +325,7 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
     // (the banded kernel keeps 8 or 16 Peq rows per word in LDS: genomes with N, soft-masked lower case, IUPAC codes)
     const int modeIn = (int)cfg.mode;
     const bool readsOk = shared_ && tlen(0) > 0 && (tab_.sigmaT <= 4 || (tab_.sigmaT <= 16 && modeIn == EDLIB_MODE_HW));
-    syms_ = tab_.sigmaT <= 4 ? 4 : (tab_.sigmaT <= 8 ? 8 : 16);
+    syms_ = peq_syms(tab_.sigmaT);
     banded_ = mode == EDLIB_MODE_HW;
     // Long HW queries against the shared target: piece filter + window verification (long_reads.hip) from kFilterFromWords
     // words on; below that the banded groups of kernel A.  257..320 / 321..384 bases on the 10- / 12-word groups: 38 / 41 / 50 /

@@ -451,159 +451,6 @@ private:
     int ensureCollected();                       // results of the last run that are still on the device -> results_
 };
 
-// Every query against every target (engine_cross.hip, DESIGN.md "Cross batches"): DISTANCE only, results as a
-// target-major matrix and best hits, both made on the device.  Cells inside the cross kernel's envelope run on it; each
-// other target runs through an internal shared-target Batch over all queries, longer queries against the rest through
-// one internal pair Batch, and their results are scattered into the matrix.
-// A hit-list batch (hits: k >= 0) keeps no matrix: the scan appends the cells within k to a list, the internal sessions'
-// cells within k are appended behind them, and the list is sorted on the device into CSR order (per target, ascending
-// query) and reduced to the same best hits.
-// A both-strand batch (strands) scans every query and its reverse complement (made on the device at init)
-// as the mates of neighbouring slots; a cell is the better strand's record (resolve_strands) and a strand byte beside it.
-// Its internal shared-target sessions are both-strand batches, its pair session holds both strands of every long query.
-// A self batch (initSelf; engine_self.hip, DESIGN.md §4h "Self batches") is one set against itself, NW only: every
-// unordered pair once, as a condensed vector or an i < j hit list, and the nearest other sequence of each.  nq_ = nt_ = n,
-// the packed targets, the Peq build, the hit list and its finish are the cross batch's own.
-class CrossBatch {
-public:
-    ~CrossBatch();
-    int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
-             EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false);
-    int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits);
-    int run();
-    int selfView(int what, EdlibAmdSelfView* out);
-    int selfHitsView(EdlibAmdSelfHits* out);
-    bool isSelf() const { return self_; }
-    int view(int what, EdlibAmdCrossView* out);
-    int hitsView(EdlibAmdCrossHits* out);
-    int strandsView(int what, EdlibAmdCrossStrands* out);
-    bool bothStrands() const { return strands_; }
-    EdlibAmdBatchStats stats{};
-
-private:
-    struct Group {
-        int words = 0, qt = 64, tiles = 0, slots = 0, ysplit = 1;
-        long long wordSteps = 0;                  // word-steps of its scanned cells (NW, k >= 0: inside the length window)
-        DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;
-        DevBuf<uint32_t> d_peq;
-        // self batches: the rank of every slot, and the work items (query tile, first target tile, trips) of its launch
-        DevBuf<int> d_rank, d_items;
-        int numItems = 0;
-    };
-    EdlibAlignConfig cfg_{};
-    std::vector<EdlibEqualityPair> eqs_;
-    int device_ = 0, nq_ = 0, nt_ = 0, syms_ = 4;
-    size_t cells_ = 0;
-    hipStream_t stream_ = nullptr;
-    Tables tab_;
-    std::vector<std::unique_ptr<Group>> groups_;
-    int numSorted_ = 0;                           // targets on the cross kernel
-    long long sortedCols_ = 0;                    // their columns
-    DevBuf<uint8_t> d_qpool_;
-    DevBuf<long long> d_qoff_, d_tdw_;
-    DevBuf<uint16_t> d_eqtbl_;
-    DevBuf<uint32_t> d_presence_, d_tpk_;
-    DevBuf<int> d_tperm_, d_tlen_;
-    DevBuf<int> d_mat_;                           // [3][nt][nq]: editDistance, numLocations, endLocation
-    DevBuf<int> d_best_;                          // [3][nt] then [3][nq]
-    DevBuf<CrossBest2> d_partial_;
-    int targetChunk_ = 1024;
-    // cells of the other engines: each out-of-envelope target's column (shared Batch), the long queries' cells (pair Batch)
-    std::vector<std::unique_ptr<Batch>> outShared_;
-    std::vector<int> outTargets_;
-    std::unique_ptr<Batch> longPairs_;
-    std::vector<long long> longCells_;
-    long long otherCells_ = 0;
-    DevBuf<long long> d_cells_; DevBuf<int> d_vals_; PinBuf h_vals_;
-    Event evScan0_, evScan1_;
-    PinBuf h_mat_, h_best_;
-    bool haveRun_ = false, matFetched_ = false, bestFetched_ = false;
-    // hit-list batches: nothing here scales with numQueries x numTargets; the list starts at max(2^20, nq + nt) entries
-    // and grows to the count of a Run that overflowed it (that Run scans again)
-    bool hits_ = false, hitsFetched_ = false;
-    long long hitCap_ = 0, numHits_ = 0;
-    DevBuf<unsigned long long> d_hcount_, d_hkey_, d_skey_, d_bkey_;
-    DevBuf<int> d_hval_, d_hout_;                 // [3][hitCap_] as appended; [4][numHits_] in CSR order
-    DevBuf<uint32_t> d_hidx_, d_sidx_;
-    DevBuf<uint8_t> d_sortTmp_;
-    DevBuf<long long> d_htoff_;                   // [nt + 1]
-    PinBuf h_hcount_, h_hits_;
-    std::vector<long long> otherCellIdx_;         // cells of the internal sessions (t * nq + q), host side
-    std::vector<unsigned long long> xKey_;        // their cells within k of the last Run
-    std::vector<int> xVal_;
-    // both strands: a strand byte (bit 0 reverse complement, bit 1 the other strand reaches the same distance) per cell
-    // [nt][nq] or per hit, and per best hit [nt] then [nq]
-    bool strands_ = false, cellStrandFetched_ = false, bestStrandFetched_ = false;
-    DevBuf<uint8_t> d_smat_, d_sbest_, d_hstrand_, d_hsout_, d_svals_;
-    PinBuf h_smat_, h_sbest_, h_svals_;
-    std::vector<uint8_t> xStrand_;                // strand bytes of xKey_
-    // self batches: d_mat_ is the condensed vector [n (n - 1) / 2] (cells_), longPairs_ the i < j pairs outside the
-    // kernel's envelope; selfOther_ the keys (i << 32) | j of the pairs answered off the kernel -- first the selfEmpty_
-    // pairs with an empty sequence (distance: the other's length), then the pairs of longPairs_
-    bool self_ = false, nearFetched_ = false;
-    std::vector<unsigned long long> selfOther_;
-    std::vector<int> selfEmptyVal_;
-    DevBuf<int> d_near_;                          // [3][n]: nearest, nearestDistance, secondDistance
-    PinBuf h_near_;
-    int runSelf();
-    int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
-    int scanGroups();
-    int growHits(long long cap);
-    int finishHits();
-};
-// tile width of a word group: the lanes a tile shape leaves idle decide it (engine_cross.hip)
-int choose_qt(long long nq, long long nt, int minQt = 1);
-
-// Units over one resident target (engine_windows.hip, DESIGN.md "Window batches"): unit u is query unitQuery[u] against
-// the window [unitStart[u], unitStart[u] + unitLength[u]) of the target, DISTANCE only, a cross batch's cell contract per
-// unit and the best unit per query, both made on the device.  The target is packed once and every query's Peq is built
-// once per Run whatever the number of units that name them; units outside the window kernel's envelope (query above 256
-// bases, window above 65,536 columns, more than 16 target symbols) run through one internal pair Batch over slices
-// materialised at Create and are scattered into the unit arrays.
-class WindowBatch {
-public:
-    ~WindowBatch();
-    // unitStrand (NULL: all forward): 1 = the unit is the reverse complement of its query; the query pool then holds both
-    // strands of every query (made on the device) and a Peq slot goes to each (query, strand) a kernel unit names
-    int init(const char* queries, const long long* qoff, int nq, const char* target, int targetLength,
-             const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
-             int numUnits, EdlibAlignConfig cfg, int device);
-    int run();
-    int view(int what, EdlibAmdWindowView* out);
-    EdlibAmdBatchStats stats{};
-
-private:
-    struct Group {
-        int words = 0, slots = 0, numSorted = 0;
-        long long wordSteps = 0;                  // word-steps of its scanned units (not the empty or the NW-skipped ones)
-        DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;          // per query slot
-        DevBuf<uint32_t> d_peq;
-        DevBuf<int> d_uslot, d_ustart, d_ulen, d_uperm;        // per unit, sorted by window length
-    };
-    EdlibAlignConfig cfg_{};
-    std::vector<EdlibEqualityPair> eqs_;
-    int device_ = 0, nq_ = 0, nu_ = 0, targetLength_ = 0, syms_ = 4;
-    hipStream_t stream_ = nullptr;
-    Tables tab_;
-    std::vector<std::unique_ptr<Group>> groups_;
-    DevBuf<uint8_t> d_qpool_;
-    DevBuf<long long> d_qoff_;
-    DevBuf<uint16_t> d_eqtbl_;
-    DevBuf<uint32_t> d_presence_, d_tpk_;
-    DevBuf<int> d_uq_;                            // [nu] query of every unit (the best reduction)
-    DevBuf<int> d_units_;                         // [3][nu]: editDistance, numLocations, endLocation
-    DevBuf<int> d_best_;                          // [3][nq]
-    DevBuf<unsigned long long> d_bkey_;           // [2][nq]
-    // units outside the kernel's envelope: one pair Batch over their materialised slices
-    std::unique_ptr<Batch> pairs_;
-    std::vector<long long> pairUnits_;
-    DevBuf<long long> d_cells_; DevBuf<int> d_vals_; PinBuf h_vals_;
-    Event evScan0_, evScan1_;
-    PinBuf h_units_, h_best_;
-    long long cellsSum_ = 0;
-    bool haveRun_ = false, unitsFetched_ = false, bestFetched_ = false;
-};
-
 // single-pair convenience used by edlibAlign()
 int align_one(const char* q, int qn, const char* t, int tn, EdlibAlignConfig cfg, EdlibAlignResult* out);
 // one small pair in one kernel launch (one_pair.hip): 0 = answered, 1 = error, 2 = not handled here (take align_one)
@@ -639,6 +486,11 @@ inline long long tall_round_waves() { return 1024; }
 void finalize_semiglobal(UnitResult& r, int kcfg, int m, int best, const int* pos, long long npos);
 // target alphabet and equality tables of a batch (engine.hip)
 void build_tables(Tables& tab, const uint8_t* targets, long long totalTargetBytes, const EdlibEqualityPair* eqs, int neq);
+// what every batch's init does alike (engine_lanes.hip); each keeps its own order of refusals
+int check_device(int device);                     // 1 and the error text: no usable device, or `device` out of range
+void keep_config(const EdlibAlignConfig& cfg, EdlibAlignConfig& kept, std::vector<EdlibEqualityPair>& eqs);   // kept points into eqs
+int copy_offsets(const long long* in, int n, const char* what, std::vector<long long>& out);    // "bad <what> offsets"
+inline int peq_syms(int sigmaT) { return sigmaT <= 4 ? 4 : (sigmaT <= 8 ? 8 : 16); }   // Peq rows per word: 4, 8 or 16
 
 int device_count();
 int host_threads(int cap);

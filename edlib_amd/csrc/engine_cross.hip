@@ -8,19 +8,13 @@
 // (cross_hits.hip): sorted into CSR order, target offsets, best hits from the list.
 // A both-strand batch makes the pool of every query and its reverse complement on the device, gives mates
 // the slots s and s ^ 1 of their word group, and keeps a strand byte beside every cell, hit and best hit.
-#include "engine.hpp"
+#include "engine_lanes.hpp"
 
 #include <algorithm>
 #include <cstring>
 #include <numeric>
 
 namespace edlib_amd {
-
-CrossBatch::~CrossBatch()
-{
-    DeviceGuard guard(device_);
-    if (stream_) { (void)hipStreamSynchronize(stream_); pool_stream_release(stream_); }
-}
 
 // lanes a tile shape leaves idle decide it; on a tie the wider query tile (fewer Peq stagings)
 // (minQt = 2 for both strands: nq counts slots, mates are neighbouring lanes)
@@ -51,24 +45,13 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     if (cfg.mode != EDLIB_MODE_NW && cfg.mode != EDLIB_MODE_SHW && cfg.mode != EDLIB_MODE_HW) { set_error("unknown mode"); return 1; }
     if (nq < 0 || nt < 0 || (nq > 0 && !qoffIn) || (nt > 0 && !toffIn)) { set_error("bad batch shape"); return 1; }
     if (strands && nq > 0x3fffffff) { set_error("bad both-strand batch shape"); return 1; }
-    const int ndev = device_count();
-    if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
-    cfg_ = cfg;
-    if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0)
-        eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
-    cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
-    cfg_.additionalEqualitiesLength = (int)eqs_.size();
+    if (check_device(device)) return 1;
+    keep_config(cfg, cfg_, eqs_);
     device_ = device; nq_ = nq; nt_ = nt; hits_ = hits; strands_ = strands;
-    std::vector<long long> qoff(nq + 1, 0), toff(nt + 1, 0);
-    if (nq > 0) qoff.assign(qoffIn, qoffIn + nq + 1);
-    if (nt > 0) toff.assign(toffIn, toffIn + nt + 1);
-    for (int i = 0; i < nq; ++i)
-        if (qoff[i + 1] < qoff[i] || qoff[i + 1] - qoff[i] > 0x7fffffffLL) { set_error("bad query offsets"); return 1; }
-    for (int i = 0; i < nt; ++i)
-        if (toff[i + 1] < toff[i] || toff[i + 1] - toff[i] > 0x7fffffffLL) { set_error("bad target offsets"); return 1; }
-    const long long qb = qoff[0], tb = toff[0];
-    const long long qbytes = qoff[nq] - qb, tbytes = toff[nt] - tb;
+    std::vector<long long> qoff, toff;
+    if (copy_offsets(qoffIn, nq, "query", qoff) || copy_offsets(toffIn, nt, "target", toff)) return 1;
+    const long long tb = toff[0];
+    const long long qbytes = qoff[nq] - qoff[0], tbytes = toff[nt] - tb;
     auto qlen = [&](int q) { return (int)(qoff[q + 1] - qoff[q]); };
     auto tlen = [&](int t) { return (int)(toff[t + 1] - toff[t]); };
     cells_ = (size_t)nq * (size_t)nt;
@@ -78,7 +61,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     // the union alphabet of all targets decides the Peq rows (and whether the kernel can take any cell)
     build_tables(tab_, reinterpret_cast<const uint8_t*>(targets) + tb, tbytes, eqs_.data(), (int)eqs_.size());
     const bool wide = tab_.sigmaT > kCrossMaxSyms;
-    syms_ = tab_.sigmaT <= 4 ? 4 : (tab_.sigmaT <= 8 ? 8 : 16);
+    syms_ = peq_syms(tab_.sigmaT);
     std::vector<int> inT, longQ;
     for (int t = 0; t < nt; ++t) {
         if (!wide && tlen(t) <= kCrossMaxTarget) inT.push_back(t);
@@ -90,8 +73,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    EDLIB_AMD_HIP(pool_stream(&stream_));
-    EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
+    if (openStream()) return 1;
     EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
     if (strands_) {
         EDLIB_AMD_HIP(d_sbest_.alloc(std::max<size_t>((size_t)nt + (size_t)nq, 1)));
@@ -112,12 +94,10 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     if (!inT.empty() && (int)longQ.size() < nq) {
         std::stable_sort(inT.begin(), inT.end(), [&](int a, int b) { return tlen(a) < tlen(b); });
         numSorted_ = (int)inT.size();
-        std::vector<long long> tdw(numSorted_), colsBelow(numSorted_ + 1, 0);
+        std::vector<long long> colsBelow(numSorted_ + 1, 0);
         std::vector<int> tl(numSorted_);
-        long long dw = 0;
         for (int i = 0; i < numSorted_; ++i) {
-            tdw[i] = dw; tl[i] = tlen(inT[i]);
-            dw += (tl[i] + 7) / 8;
+            tl[i] = tlen(inT[i]);
             sortedCols_ += tl[i];
             colsBelow[i + 1] = sortedCols_;
         }
@@ -131,37 +111,10 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
             }
             return sortedCols_;
         };
-        EDLIB_AMD_HIP(d_tpk_.alloc((size_t)std::max(dw, 1LL)));
-        EDLIB_AMD_HIP(d_tdw_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tperm_.alloc(numSorted_));
-        EDLIB_AMD_HIP(hipMemcpy(d_tdw_.p, tdw.data(), numSorted_ * sizeof(long long), hipMemcpyHostToDevice));
+        if (packHostTargets(targets, toff, inT, tl)) return 1;
+        EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_));
         EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, tl.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_tperm_.p, inT.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
-        {   // the raw target pool is only needed by the pack
-            DevBuf<uint8_t> d_traw, d_tlut; DevBuf<long long> d_toff;
-            std::vector<long long> toffR(toff);
-            for (auto& v : toffR) v -= tb;
-            EDLIB_AMD_HIP(d_traw.alloc((size_t)tbytes + 16)); EDLIB_AMD_HIP(d_tlut.alloc(256)); EDLIB_AMD_HIP(d_toff.alloc(nt + 1));
-            if (tbytes) EDLIB_AMD_HIP(hipMemcpy(d_traw.p, targets + tb, (size_t)tbytes, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_tlut.p, tab_.tlut, 256, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_toff.p, toffR.data(), (nt + 1) * sizeof(long long), hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(launch_pack_cross_targets(d_traw.p, d_toff.p, d_tperm_.p, d_tdw_.p, numSorted_, d_tlut.p, d_tpk_.p, stream_));
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        }
-        // queries (rebased), their tables
-        std::vector<long long> qoffR(qoff);
-        for (auto& v : qoffR) v -= qb;
-        if (!strands_) {
-            EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
-            if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        } else {
-            // the caller's pool goes up as it is; query i and its reverse complement are written from it on the device as
-            // the entries 2i and 2i + 1 of a pool twice its size
-            if (make_strand_pool(queries + qb, qoffR.data(), nq, d_qpool_, d_qoff_, stream_)) return 1;
-        }
-        EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
-        EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
+        if (uploadQueries(queries, qoff, strands_)) return 1;
         // word groups, each sorted by length; empty queries ride in the one-word group
         std::vector<std::vector<int>> byWords(kCrossMaxQueryWords + 1);
         for (int q = 0; q < nq; ++q) {
@@ -179,27 +132,22 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
             const long long need = (long long)qs.size() * (strands_ ? 2 : 1);
             g->qt = choose_qt(need, numSorted_, strands_ ? 2 : 1);
             g->tiles = (int)((need + g->qt - 1) / g->qt);
-            g->slots = g->tiles * g->qt;
             for (int q : qs) g->wordSteps += (long long)w * scannedCols(qlen(q)) * (strands_ ? 2 : 1);
             const int tpt = 64 / g->qt;
             const long long targetTiles = (numSorted_ + tpt - 1) / tpt;
             // about 8,192 waves per launch (256 CUs), each persistent over a strided range of target tiles
             g->ysplit = (int)std::min<long long>({targetTiles, std::max(1LL, (8192LL + g->tiles - 1) / g->tiles), 65535LL});
-            std::vector<int> perm(g->slots, -1);
+            std::vector<int> perm((size_t)g->tiles * g->qt, -1);           // whole tiles
             if (!strands_) std::copy(qs.begin(), qs.end(), perm.begin());
             else {
                 for (size_t i = 0; i < qs.size(); ++i) { perm[2 * i] = 2 * qs[i]; perm[2 * i + 1] = 2 * qs[i] + 1; }
                 // what the kernel's lane exchange rests on: mates in the slots s and s ^ 1, padding in pairs, an even tile
-                bool ok = !(g->qt & 1) && !(g->slots & 1);
-                for (int sl = 0; ok && sl < g->slots; sl += 2)
+                bool ok = !(g->qt & 1) && !(perm.size() & 1);
+                for (size_t sl = 0; ok && sl < perm.size(); sl += 2)
                     ok = perm[sl] < 0 ? perm[sl + 1] < 0 : (!(perm[sl] & 1) && perm[sl + 1] == perm[sl] + 1);
                 if (!ok) { set_error("both strands: mates are not in adjacent slots"); return 1; }
             }
-            const size_t blocks = (size_t)(g->slots + 63) / 64;
-            EDLIB_AMD_HIP(g->d_perm.alloc(g->slots)); EDLIB_AMD_HIP(g->d_qlen.alloc(g->slots));
-            EDLIB_AMD_HIP(g->d_kinit.alloc(g->slots)); EDLIB_AMD_HIP(g->d_alpha.alloc(g->slots));
-            EDLIB_AMD_HIP(g->d_peq.alloc(blocks * syms_ * w * 64));
-            EDLIB_AMD_HIP(hipMemcpy(g->d_perm.p, perm.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
+            if (allocGroup(*g, perm)) return 1;
             groups_.push_back(std::move(g));
         }
     }
@@ -215,26 +163,20 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         }
         if (!longQ.empty() && !inT.empty()) {
             // every long query against every target the kernel takes, as pairs (their bytes replicated per cell)
-            std::vector<char> qp, tp;
-            std::vector<long long> qo(1, 0), to(1, 0);
+            PairPool pool;
             // (both strands: the pairs 2c and 2c + 1 of cell c, the second with the reverse complement made here)
             for (int t : inT)
                 for (int q : longQ) {
-                    for (int st = 0; st < (strands_ ? 2 : 1); ++st) {
-                        if (!st) qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
-                        else
-                            for (long long j = qoff[q + 1] - 1; j >= qoff[q]; --j)
-                                qp.push_back((char)complement_byte((uint8_t)queries[j]));
-                        tp.insert(tp.end(), targets + toff[t], targets + toff[t + 1]);
-                        qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
-                    }
+                    for (int st = 0; st < (strands_ ? 2 : 1); ++st)
+                        pool.add(queries + qoff[q], qlen(q), st != 0, targets + toff[t], tlen(t));
                     longCells_.push_back((long long)t * nq + q);
                 }
-            const long long np = (long long)longCells_.size() * (strands_ ? 2 : 1);
-            if (np > 0x7fffffffLL) { set_error("cross batch: too many cells of long queries (%lld pairs)", np); return 1; }
-            if (tp.empty()) tp.push_back(0);
+            if (pool.size() > 0x7fffffffLL) {
+                set_error("cross batch: too many cells of long queries (%lld pairs)", pool.size());
+                return 1;
+            }
             longPairs_.reset(new Batch);
-            if (longPairs_->init(qp.data(), qo.data(), (int)np, tp.data(), to.data(), (int)np, cfg_, device)) return 1;
+            if (pool.init(*longPairs_, cfg_, device)) return 1;
             otherCells_ += (long long)longCells_.size();
         }
         if (otherCells_ > 0) {
@@ -262,19 +204,12 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
 // session): their strand bytes
 int CrossBatch::gather(Batch& b, size_t n, int* vals, uint8_t* sbytes)
 {
-    EdlibAmdResultsView v{};
-    if (b.resultsView(&v)) return 1;
+    if (readCells(b, n, vals, "cross")) return 1;
     if (sbytes) {
         EdlibAmdStrandView sv{};
         if (b.strandView(&sv)) return 1;
         for (size_t i = 0; i < n; ++i)
-            sbytes[i] = v.editDistance[i] < 0 ? 0 : (uint8_t)((sv.strand[i] ? kStrandReverse : 0) | (sv.bothStrands[i] ? kStrandBoth : 0));
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (v.status[i] != EDLIB_STATUS_OK) { set_error("cross batch: an internal alignment failed"); return 1; }
-        vals[3 * i] = v.editDistance[i];
-        vals[3 * i + 1] = v.numLocations[i];
-        vals[3 * i + 2] = v.numLocations[i] > 0 ? v.endLocations[v.locOffsets[i]] : -1;
+            sbytes[i] = vals[3 * i] < 0 ? 0 : (uint8_t)((sv.strand[i] ? kStrandReverse : 0) | (sv.bothStrands[i] ? kStrandBoth : 0));
     }
     return 0;
 }
@@ -378,25 +313,12 @@ int CrossBatch::run()
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
-    EDLIB_AMD_HIP(guard.status);
-    haveRun_ = matFetched_ = bestFetched_ = hitsFetched_ = cellStrandFetched_ = bestStrandFetched_ = false;
-    const long long cells = stats.cells;
-    stats = EdlibAmdBatchStats{};
-    stats.cells = cells;
+    if (beginRun(guard.status, {&mat_, &best_, &hitList_, &cellStrand_, &bestStrand_})) return 1;
     int* ed = d_mat_.p; int* nloc = hits_ ? nullptr : ed + cells_; int* end = hits_ ? nullptr : ed + 2 * cells_;
     if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
 
     // the cross kernel: Peq of every query, then one scan per word group
-    if (!groups_.empty()) {
-        for (auto& g : groups_)
-            EDLIB_AMD_HIP(launch_build_peq_reads(g->words, syms_, d_qpool_.p, d_qoff_.p, g->d_perm.p, g->slots, d_eqtbl_.p,
-                                                 d_presence_.p, cfg_.k, g->d_peq.p, g->d_qlen.p, g->d_kinit.p, g->d_alpha.p,
-                                                 stream_));
-        EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
-        if (scanGroups()) return 1;
-        EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
-        stats.path |= 8;
-    }
+    if (scanRun(groups_, 8, [&] { return scanGroups(); })) return 1;
     // the other engines run on their own streams meanwhile
     xKey_.clear(); xVal_.clear(); xStrand_.clear();
     if (otherCells_ > 0) {
@@ -407,9 +329,7 @@ int CrossBatch::run()
             if (b->run()) return 1;
             if (gather(*b, (size_t)nq_, vals + 3 * at, strands_ ? svals + at : nullptr)) return 1;
             at += (size_t)nq_;
-            b->finishStats();
-            stats.word_steps += b->stats.word_steps; stats.scan_launches += b->stats.scan_launches;
-            stats.path |= b->stats.path; stats.overflow_units += b->stats.overflow_units; stats.wide_retries += b->stats.wide_retries;
+            addSessionStats(*b, true);
         }
         if (longPairs_) {
             if (longPairs_->run()) return 1;
@@ -427,10 +347,7 @@ int CrossBatch::run()
                     svals[at + c] = (uint8_t)(w & (kStrandReverse | kStrandBoth));
                 }
             }
-            longPairs_->finishStats();
-            const EdlibAmdBatchStats& s = longPairs_->stats;
-            stats.word_steps += s.word_steps; stats.scan_launches += s.scan_launches;
-            stats.path |= s.path; stats.overflow_units += s.overflow_units; stats.wide_retries += s.wide_retries;
+            addSessionStats(*longPairs_, true);
         }
         if (!hits_) {
             EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, 3 * (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -460,16 +377,7 @@ int CrossBatch::run()
                                         d_partial_.p, targetChunk_, stream_));
         if (strands_) EDLIB_AMD_HIP(launch_cross_best_strands(d_smat_.p, nq_, nt_, bq, bt, d_sbest_.p, stream_));
     }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (!groups_.empty()) {
-        float ms = 0.f;
-        EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evScan0_.e, evScan1_.e));
-        stats.scan_ms = ms;
-    }
-    stats.algo_bytes = 0;
-    stats.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    haveRun_ = true;
-    return 0;
+    return endRun(t0, !groups_.empty());
 }
 
 int CrossBatch::view(int what, EdlibAmdCrossView* out)
@@ -485,29 +393,32 @@ int CrossBatch::view(int what, EdlibAmdCrossView* out)
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     const size_t matBytes = 3 * cells_ * sizeof(int), bestBytes = (3 * (size_t)nt_ + 3 * (size_t)nq_) * sizeof(int);
-    if ((what & EDLIB_AMD_CROSS_MATRIX) && !matFetched_) {
-        if (h_mat_.n < matBytes || !h_mat_.p) EDLIB_AMD_HIP(h_mat_.alloc(matBytes));
-        if (matBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_mat_.p, d_mat_.p, matBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    if ((what & EDLIB_AMD_CROSS_BEST) && !bestFetched_) {
-        if (h_best_.n < bestBytes || !h_best_.p) EDLIB_AMD_HIP(h_best_.alloc(bestBytes));
-        if (bestBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_best_.p, d_best_.p, bestBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (what & EDLIB_AMD_CROSS_MATRIX) matFetched_ = true;
-    if (what & EDLIB_AMD_CROSS_BEST) bestFetched_ = true;
+    if (fetchParts({{what & EDLIB_AMD_CROSS_MATRIX, &mat_, d_mat_.p, matBytes},
+                    {what & EDLIB_AMD_CROSS_BEST, &best_, d_best_.p, bestBytes}})) return 1;
     memset(out, 0, sizeof *out);
     out->numQueries = nq_; out->numTargets = nt_;
     if (what & EDLIB_AMD_CROSS_MATRIX) {
-        const int* m = reinterpret_cast<const int*>(h_mat_.p);
+        const int* m = reinterpret_cast<const int*>(mat_.h.p);
         out->editDistance = m; out->numLocations = m + cells_; out->endLocation = m + 2 * cells_;
     }
     if (what & EDLIB_AMD_CROSS_BEST) {
-        const int* b = reinterpret_cast<const int*>(h_best_.p);
+        const int* b = reinterpret_cast<const int*>(best_.h.p);
         out->bestQuery = b; out->bestQueryDistance = b + nt_; out->secondQueryDistance = b + 2 * (size_t)nt_;
         b += 3 * (size_t)nt_;
         out->bestTarget = b; out->bestTargetDistance = b + nq_; out->secondTargetDistance = b + 2 * (size_t)nq_;
     }
+    return 0;
+}
+
+int CrossBatch::fetchHits(int planes, int rows, size_t* offBytes)
+{
+    *offBytes = ((size_t)rows + 1) * sizeof(long long);
+    const size_t listBytes = (size_t)planes * (size_t)numHits_ * sizeof(int);
+    if (hitList_.fetched) return 0;
+    EDLIB_AMD_HIP(hitList_.fetch(d_htoff_.p, *offBytes, stream_, 0, *offBytes + listBytes));
+    EDLIB_AMD_HIP(hitList_.fetch(d_hout_.p, listBytes, stream_, *offBytes));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    hitList_.fetched = true;
     return 0;
 }
 
@@ -522,19 +433,12 @@ int CrossBatch::hitsView(EdlibAmdCrossHits* out)
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    const size_t offBytes = ((size_t)nt_ + 1) * sizeof(long long), listBytes = 4 * (size_t)numHits_ * sizeof(int);
-    if (!hitsFetched_) {
-        if (h_hits_.n < offBytes + listBytes || !h_hits_.p) EDLIB_AMD_HIP(h_hits_.alloc(offBytes + listBytes));
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p, d_htoff_.p, offBytes, hipMemcpyDeviceToHost, stream_));
-        if (listBytes)
-            EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p + offBytes, d_hout_.p, listBytes, hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        hitsFetched_ = true;
-    }
+    size_t offBytes = 0;
+    if (fetchHits(4, nt_, &offBytes)) return 1;
     memset(out, 0, sizeof *out);
     out->numQueries = nq_; out->numTargets = nt_; out->numHits = numHits_;
-    out->targetOffsets = reinterpret_cast<const long long*>(h_hits_.p);
-    const int* l = reinterpret_cast<const int*>(h_hits_.p + offBytes);
+    out->targetOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
+    const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
     const size_t n = (size_t)numHits_;
     out->query = l; out->editDistance = l + n; out->numLocations = l + 2 * n; out->endLocation = l + 3 * n;
     return 0;
@@ -553,22 +457,12 @@ int CrossBatch::strandsView(int what, EdlibAmdCrossStrands* out)
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     const size_t cellBytes = hits_ ? (size_t)numHits_ : cells_, bestBytes = (size_t)nt_ + (size_t)nq_;
-    if ((what & EDLIB_AMD_CROSS_MATRIX) && !cellStrandFetched_) {
-        if (h_smat_.n < cellBytes || !h_smat_.p) EDLIB_AMD_HIP(h_smat_.alloc(std::max<size_t>(cellBytes, 1)));
-        if (cellBytes)
-            EDLIB_AMD_HIP(hipMemcpyAsync(h_smat_.p, hits_ ? d_hsout_.p : d_smat_.p, cellBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    if ((what & EDLIB_AMD_CROSS_BEST) && !bestStrandFetched_) {
-        if (h_sbest_.n < bestBytes || !h_sbest_.p) EDLIB_AMD_HIP(h_sbest_.alloc(std::max<size_t>(bestBytes, 1)));
-        if (bestBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_sbest_.p, d_sbest_.p, bestBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (what & EDLIB_AMD_CROSS_MATRIX) cellStrandFetched_ = true;
-    if (what & EDLIB_AMD_CROSS_BEST) bestStrandFetched_ = true;
+    if (fetchParts({{what & EDLIB_AMD_CROSS_MATRIX, &cellStrand_, hits_ ? d_hsout_.p : d_smat_.p, cellBytes},
+                    {what & EDLIB_AMD_CROSS_BEST, &bestStrand_, d_sbest_.p, bestBytes}})) return 1;
     memset(out, 0, sizeof *out);
     out->numQueries = nq_; out->numTargets = nt_; out->numHits = hits_ ? numHits_ : 0;
-    if (what & EDLIB_AMD_CROSS_MATRIX) (hits_ ? out->hitStrand : out->cellStrand) = h_smat_.p;
-    if (what & EDLIB_AMD_CROSS_BEST) { out->bestQueryStrand = h_sbest_.p; out->bestTargetStrand = h_sbest_.p + nt_; }
+    if (what & EDLIB_AMD_CROSS_MATRIX) (hits_ ? out->hitStrand : out->cellStrand) = cellStrand_.h.p;
+    if (what & EDLIB_AMD_CROSS_BEST) { out->bestQueryStrand = bestStrand_.h.p; out->bestTargetStrand = bestStrand_.h.p + nt_; }
     return 0;
 }
 

@@ -1,0 +1,217 @@
+// engine_lanes.hpp -- the engines that put one query per lane over a packed target: cross batches with their self mode
+// (engine_cross.hip, engine_self.hip) and window batches (engine_windows.hip).  LaneEngine (engine_lanes.hip) is what
+// they keep alike: the resident query pool and packed target, the Peq buffers of a word group, the frame of a Run, the
+// internal sessions of the units outside the kernels' envelope, and the pinned parts a view fetches.
+#pragma once
+#include "engine.hpp"
+
+#include <initializer_list>
+
+namespace edlib_amd {
+
+// A part of the results in pinned host memory, fetched from the device when a view first asks for it after a Run.
+struct PinnedPart {
+    PinBuf h;
+    bool fetched = false;
+    // enqueues the D2H of `bytes` to h + at unless the part is fetched already (room: the bytes the whole part needs, where
+    // it is fetched in pieces); the caller sets `fetched` once the stream's synchronise succeeded
+    hipError_t fetch(const void* dev, size_t bytes, hipStream_t stream, size_t at = 0, size_t room = 0);
+};
+struct WantedPart { int asked; PinnedPart* part; const void* dev; size_t bytes; };
+
+// The pairs of an internal pair Batch: the bytes of every pair replicated, query and target
+struct PairPool {
+    std::vector<char> qp, tp;
+    std::vector<long long> qo = std::vector<long long>(1, 0), to = std::vector<long long>(1, 0);
+    long long size() const { return (long long)qo.size() - 1; }
+    void add(const char* q, long long qn, bool reverse, const char* t, long long tn);   // reverse: q's reverse complement
+    int init(Batch& b, const EdlibAlignConfig& cfg, int device);
+};
+
+class LaneEngine {
+public:
+    EdlibAmdBatchStats stats{};
+
+protected:
+    // what every word group has: its query slots and their Peq rows (the engines' own groups extend it)
+    struct LaneGroup {
+        int words = 0, slots = 0;
+        long long wordSteps = 0;                  // word-steps of what its scan takes
+        DevBuf<int> d_perm, d_qlen, d_kinit, d_alpha;          // per query slot
+        DevBuf<uint32_t> d_peq;
+    };
+    EdlibAlignConfig cfg_{};
+    std::vector<EdlibEqualityPair> eqs_;
+    int device_ = 0, nq_ = 0, syms_ = 4;
+    hipStream_t stream_ = nullptr;
+    Tables tab_;
+    DevBuf<uint8_t> d_qpool_;
+    DevBuf<long long> d_qoff_, d_tdw_;
+    DevBuf<uint16_t> d_eqtbl_;
+    DevBuf<uint32_t> d_presence_, d_tpk_;
+    DevBuf<int> d_tperm_;
+    DevBuf<int> d_best_;
+    DevBuf<unsigned long long> d_bkey_;
+    // results of the internal sessions on their way into the engine's arrays
+    DevBuf<long long> d_cells_; DevBuf<int> d_vals_; PinBuf h_vals_;
+    Event evScan0_, evScan1_;
+    PinnedPart best_;
+    bool haveRun_ = false;
+
+    void closeStream();                           // the destructors': the members die behind the stream's work
+    int openStream();                             // the stream and the scan events (the device is current)
+    // the query pool (rebased) with its offsets, plain or as both strands of every query made on the device, and the tables
+    int uploadQueries(const char* queries, const std::vector<long long>& qoff, bool strands);
+    // the sequences order[i] (of lengths len[i]) of a device pool as 4-bit codes, back to back from dword 0
+    int packTargets(const uint8_t* d_pool, const long long* d_off, const std::vector<int>& order, const std::vector<int>& len);
+    // the same from the caller's memory: the raw pool is only needed by the pack
+    int packHostTargets(const char* pool, const std::vector<long long>& off, const std::vector<int>& order,
+                        const std::vector<int>& len);
+    int allocGroup(LaneGroup& g, const std::vector<int>& perm);      // slots = perm's; the Peq buffers, perm uploaded
+    int buildPeq(LaneGroup& g);
+    // a Run's share of the engine's kernel: the Peq rows of every group, then scan() between the two scan events
+    template <typename Groups, typename Scan>
+    int scanRun(Groups& groups, unsigned pathBit, Scan&& scan) {
+        if (groups.empty()) return 0;
+        for (auto& g : groups)
+            if (buildPeq(*g)) return 1;
+        EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
+        if (scan()) return 1;
+        EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
+        stats.path |= pathBit;
+        return 0;
+    }
+    int beginRun(hipError_t guardStatus, std::initializer_list<PinnedPart*> parts);
+    int endRun(std::chrono::steady_clock::time_point t0, bool scanned);
+    int fetchParts(std::initializer_list<WantedPart> wants);         // a view's: the parts asked for are in pinned memory
+    // (editDistance, numLocations, first end location) of the n units of an internal session's last run
+    int readCells(Batch& b, size_t n, int* vals, const char* engine);
+    // wordSteps = false: edlib_amd.h defines a self batch's word_steps as the kernel's pairs only
+    void addSessionStats(Batch& b, bool wordSteps);
+};
+
+// Every query against every target (engine_cross.hip, DESIGN.md "Cross batches"): DISTANCE only, results as a
+// target-major matrix and best hits, both made on the device.  Cells inside the cross kernel's envelope run on it; each
+// other target runs through an internal shared-target Batch over all queries, longer queries against the rest through
+// one internal pair Batch, and their results are scattered into the matrix.
+// A hit-list batch (hits: k >= 0) keeps no matrix: the scan appends the cells within k to a list, the internal sessions'
+// cells within k are appended behind them, and the list is sorted on the device into CSR order (per target, ascending
+// query) and reduced to the same best hits.
+// A both-strand batch (strands) scans every query and its reverse complement (made on the device at init)
+// as the mates of neighbouring slots; a cell is the better strand's record (resolve_strands) and a strand byte beside it.
+// Its internal shared-target sessions are both-strand batches, its pair session holds both strands of every long query.
+// A self batch (initSelf; engine_self.hip, DESIGN.md §4h "Self batches") is one set against itself, NW only: every
+// unordered pair once, as a condensed vector or an i < j hit list, and the nearest other sequence of each.  nq_ = nt_ = n,
+// the packed targets, the Peq build, the hit list and its finish are the cross batch's own.
+class CrossBatch : public LaneEngine {
+public:
+    ~CrossBatch() { closeStream(); }
+    int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
+             EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false);
+    int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits);
+    int run();
+    int selfView(int what, EdlibAmdSelfView* out);
+    int selfHitsView(EdlibAmdSelfHits* out);
+    bool isSelf() const { return self_; }
+    int view(int what, EdlibAmdCrossView* out);
+    int hitsView(EdlibAmdCrossHits* out);
+    int strandsView(int what, EdlibAmdCrossStrands* out);
+    bool bothStrands() const { return strands_; }
+
+private:
+    struct Group : LaneGroup {                    // slots: whole tiles, padded with -1
+        int qt = 64, tiles = 0, ysplit = 1;       // wordSteps: of its scanned cells (NW, k >= 0: inside the length window)
+        // self batches: the rank of every slot, and the work items (query tile, first target tile, trips) of its launch
+        DevBuf<int> d_rank, d_items;
+        int numItems = 0;
+    };
+    int nt_ = 0;
+    size_t cells_ = 0;
+    std::vector<std::unique_ptr<Group>> groups_;
+    int numSorted_ = 0;                           // targets on the cross kernel
+    long long sortedCols_ = 0;                    // their columns
+    DevBuf<int> d_tlen_;
+    DevBuf<int> d_mat_;                           // [3][nt][nq]: editDistance, numLocations, endLocation
+    // d_best_: [3][nt] then [3][nq]
+    DevBuf<CrossBest2> d_partial_;
+    int targetChunk_ = 1024;
+    // cells of the other engines: each out-of-envelope target's column (shared Batch), the long queries' cells (pair Batch)
+    std::vector<std::unique_ptr<Batch>> outShared_;
+    std::vector<int> outTargets_;
+    std::unique_ptr<Batch> longPairs_;
+    std::vector<long long> longCells_;
+    long long otherCells_ = 0;
+    PinnedPart mat_;
+    // hit-list batches: nothing here scales with numQueries x numTargets; the list starts at max(2^20, nq + nt) entries
+    // and grows to the count of a Run that overflowed it (that Run scans again)
+    bool hits_ = false;
+    long long hitCap_ = 0, numHits_ = 0;
+    DevBuf<unsigned long long> d_hcount_, d_hkey_, d_skey_;
+    DevBuf<int> d_hval_, d_hout_;                 // [3][hitCap_] as appended; [4][numHits_] in CSR order
+    DevBuf<uint32_t> d_hidx_, d_sidx_;
+    DevBuf<uint8_t> d_sortTmp_;
+    DevBuf<long long> d_htoff_;                   // [nt + 1]
+    PinBuf h_hcount_;
+    PinnedPart hitList_;
+    std::vector<long long> otherCellIdx_;         // cells of the internal sessions (t * nq + q), host side
+    std::vector<unsigned long long> xKey_;        // their cells within k of the last Run
+    std::vector<int> xVal_;
+    // both strands: a strand byte (bit 0 reverse complement, bit 1 the other strand reaches the same distance) per cell
+    // [nt][nq] or per hit, and per best hit [nt] then [nq]
+    bool strands_ = false;
+    DevBuf<uint8_t> d_smat_, d_sbest_, d_hstrand_, d_hsout_, d_svals_;
+    PinnedPart cellStrand_, bestStrand_;
+    PinBuf h_svals_;
+    std::vector<uint8_t> xStrand_;                // strand bytes of xKey_
+    // self batches: d_mat_ is the condensed vector [n (n - 1) / 2] (cells_), longPairs_ the i < j pairs outside the
+    // kernel's envelope; selfOther_ the keys (i << 32) | j of the pairs answered off the kernel -- first the selfEmpty_
+    // pairs with an empty sequence (distance: the other's length), then the pairs of longPairs_
+    bool self_ = false;
+    std::vector<unsigned long long> selfOther_;
+    std::vector<int> selfEmptyVal_;
+    DevBuf<int> d_near_;                          // [3][n]: nearest, nearestDistance, secondDistance
+    PinnedPart near_;
+    int runSelf();
+    int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
+    int scanGroups();
+    int growHits(long long cap);
+    int finishHits();
+    int fetchHits(int planes, int rows, size_t* offBytes);       // the offsets of `rows` rows, then planes x numHits_ ints
+};
+// tile width of a word group: the lanes a tile shape leaves idle decide it (engine_cross.hip)
+int choose_qt(long long nq, long long nt, int minQt = 1);
+
+// Units over one resident target (engine_windows.hip, DESIGN.md "Window batches"): unit u is query unitQuery[u] against
+// the window [unitStart[u], unitStart[u] + unitLength[u]) of the target, DISTANCE only, a cross batch's cell contract per
+// unit and the best unit per query, both made on the device.  The target is packed once and every query's Peq is built
+// once per Run whatever the number of units that name them; units outside the window kernel's envelope (query above 256
+// bases, window above 65,536 columns, more than 16 target symbols) run through one internal pair Batch over slices
+// materialised at Create and are scattered into the unit arrays.
+class WindowBatch : public LaneEngine {
+public:
+    ~WindowBatch() { closeStream(); }
+    // unitStrand (NULL: all forward): 1 = the unit is the reverse complement of its query; the query pool then holds both
+    // strands of every query (made on the device) and a Peq slot goes to each (query, strand) a kernel unit names
+    int init(const char* queries, const long long* qoff, int nq, const char* target, int targetLength,
+             const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
+             int numUnits, EdlibAlignConfig cfg, int device);
+    int run();
+    int view(int what, EdlibAmdWindowView* out);
+
+private:
+    struct Group : LaneGroup {                    // slots: the (query, strand) entries its units name, unpadded
+        int numSorted = 0;                        // wordSteps: of its scanned units (not the empty or the NW-skipped ones)
+        DevBuf<int> d_uslot, d_ustart, d_ulen, d_uperm;        // per unit, sorted by window length
+    };
+    int nu_ = 0, targetLength_ = 0;
+    std::vector<std::unique_ptr<Group>> groups_;
+    DevBuf<int> d_uq_;                            // [nu] query of every unit (the best reduction)
+    DevBuf<int> d_units_;                         // [3][nu]: editDistance, numLocations, endLocation
+    // d_best_: [3][nq], d_bkey_: [2][nq]
+    // units outside the kernel's envelope: one pair Batch over their materialised slices
+    std::unique_ptr<Batch> pairs_;
+    std::vector<long long> pairUnits_;
+    PinnedPart units_;
+};
+
+}  // namespace edlib_amd

@@ -5,7 +5,7 @@
 // Run builds the Peq rows, scans the items of every group, lets the internal pair batch take the pairs outside the
 // kernel's envelope, and reduces the nearest other sequence of each on the device.  The pack, the Peq build, the hit
 // list and its finish are the cross batch's own (engine_cross.hip, cross_hits.hip).
-#include "engine.hpp"
+#include "engine_lanes.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -33,18 +33,9 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
         return 1;
     }
     if (n < 0 || (n > 0 && !offIn)) { set_error("bad batch shape"); return 1; }
-    std::vector<long long> off(n + 1, 0);
-    if (n > 0) off.assign(offIn, offIn + n + 1);
-    for (int i = 0; i < n; ++i)
-        if (off[i + 1] < off[i] || off[i + 1] - off[i] > 0x7fffffffLL) { set_error("bad sequence offsets"); return 1; }
-    const int ndev = device_count();
-    if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
-    cfg_ = cfg;
-    if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0)
-        eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
-    cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
-    cfg_.additionalEqualitiesLength = (int)eqs_.size();
+    std::vector<long long> off;
+    if (copy_offsets(offIn, n, "sequence", off) || check_device(device)) return 1;      // (the offsets first: edlib_amd.h)
+    keep_config(cfg, cfg_, eqs_);
     device_ = device; nq_ = nt_ = n; hits_ = hits; strands_ = false; self_ = true;
     const long long base = off[0], bytes = off[n] - base;
     auto len = [&](int i) { return (int)(off[i + 1] - off[i]); };
@@ -64,7 +55,7 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
 
     build_tables(tab_, reinterpret_cast<const uint8_t*>(seqs) + base, bytes, eqs_.data(), (int)eqs_.size());
     const bool wide = tab_.sigmaT > kCrossMaxSyms;
-    syms_ = tab_.sigmaT <= 4 ? 4 : (tab_.sigmaT <= 8 ? 8 : 16);
+    syms_ = peq_syms(tab_.sigmaT);
     // the kernel's sequences in the order (length, index); the empty ones are answered here, the others by the pair batch
     std::vector<int> inK, empties, outK;
     for (int i = 0; i < n; ++i) {
@@ -77,8 +68,7 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    EDLIB_AMD_HIP(pool_stream(&stream_));
-    EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
+    if (openStream()) return 1;
     EDLIB_AMD_HIP(d_near_.alloc(3 * (size_t)n));
     if (!hits_) EDLIB_AMD_HIP(d_mat_.alloc(std::max<size_t>(cells_, 1)));
     else {
@@ -92,12 +82,10 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     // ---- the kernel's share
     if (inK.size() >= 2) {
         numSorted_ = (int)inK.size();
-        std::vector<long long> tdw(numSorted_), colsBelow(numSorted_ + 1, 0);
+        std::vector<long long> colsBelow(numSorted_ + 1, 0);
         std::vector<int> tl(numSorted_);
-        long long dw = 0;
         for (int r = 0; r < numSorted_; ++r) {
-            tdw[r] = dw; tl[r] = len(inK[r]);
-            dw += (tl[r] + 7) / 8;
+            tl[r] = len(inK[r]);
             sortedCols_ += tl[r];
             colsBelow[r + 1] = sortedCols_;
         }
@@ -106,27 +94,10 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
             if (cfg.k < 0) return numSorted_;
             return (int)(std::upper_bound(tl.begin(), tl.end(), (long long)m + cfg.k) - tl.begin());
         };
-        std::vector<long long> offR(off);
-        for (auto& v : offR) v -= base;
         // the pool goes up once: the pack reads it as the targets, the Peq build as the queries
-        EDLIB_AMD_HIP(d_qpool_.alloc((size_t)bytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc((size_t)n + 1));
-        EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, seqs + base, (size_t)bytes, hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, offR.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(d_tpk_.alloc((size_t)std::max(dw, 1LL)));
-        EDLIB_AMD_HIP(d_tdw_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_)); EDLIB_AMD_HIP(d_tperm_.alloc(numSorted_));
-        EDLIB_AMD_HIP(hipMemcpy(d_tdw_.p, tdw.data(), numSorted_ * sizeof(long long), hipMemcpyHostToDevice));
+        if (uploadQueries(seqs, off, false) || packTargets(d_qpool_.p, d_qoff_.p, inK, tl)) return 1;
+        EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_));
         EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, tl.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_tperm_.p, inK.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
-        {
-            DevBuf<uint8_t> d_tlut;
-            EDLIB_AMD_HIP(d_tlut.alloc(256));
-            EDLIB_AMD_HIP(hipMemcpy(d_tlut.p, tab_.tlut, 256, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(launch_pack_cross_targets(d_qpool_.p, d_qoff_.p, d_tperm_.p, d_tdw_.p, numSorted_, d_tlut.p, d_tpk_.p, stream_));
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        }
-        EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
-        EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
         // a word group is a run of ranks [r0, r1): its slot s holds rank r0 + s, so the rank rises with the slot
         for (int r0 = 0; r0 < numSorted_;) {
             const int w = (tl[r0] + 31) / 32;
@@ -137,9 +108,8 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
             g->words = w;
             g->qt = choose_qt(cnt, numSorted_);
             g->tiles = (cnt + g->qt - 1) / g->qt;
-            g->slots = g->tiles * g->qt;
             const int tpt = 64 / g->qt;
-            std::vector<int> perm(g->slots, -1), rank(g->slots, -1);
+            std::vector<int> perm((size_t)g->tiles * g->qt, -1), rank(perm.size(), -1);      // whole tiles
             for (int s = 0; s < cnt; ++s) {
                 perm[s] = inK[r0 + s]; rank[s] = r0 + s;
                 g->wordSteps += (long long)w * (colsBelow[windowEnd(tl[r0 + s])] - colsBelow[r0 + s + 1]);
@@ -168,12 +138,8 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
                 }
             }
             g->numItems = (int)(items.size() / 3);
-            const size_t blocks = (size_t)(g->slots + 63) / 64;
-            EDLIB_AMD_HIP(g->d_perm.alloc(g->slots)); EDLIB_AMD_HIP(g->d_qlen.alloc(g->slots));
-            EDLIB_AMD_HIP(g->d_kinit.alloc(g->slots)); EDLIB_AMD_HIP(g->d_alpha.alloc(g->slots));
+            if (allocGroup(*g, perm)) return 1;
             EDLIB_AMD_HIP(g->d_rank.alloc(g->slots)); EDLIB_AMD_HIP(g->d_items.alloc(std::max<size_t>(items.size(), 3)));
-            EDLIB_AMD_HIP(g->d_peq.alloc(blocks * syms_ * w * 64));
-            EDLIB_AMD_HIP(hipMemcpy(g->d_perm.p, perm.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
             EDLIB_AMD_HIP(hipMemcpy(g->d_rank.p, rank.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
             if (!items.empty())
                 EDLIB_AMD_HIP(hipMemcpy(g->d_items.p, items.data(), items.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -190,15 +156,12 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
             selfEmptyVal_.push_back(len(x));
         }
     {
-        std::vector<char> qp, tp;
-        std::vector<long long> qo(1, 0), to(1, 0);
+        PairPool pool;
         long long np = 0;
         auto add = [&](int i, int j) {                                // i < j, both with bases
             if (!inWindow(i, j)) return;
             if (++np > 0x7fffffffLL) return;
-            qp.insert(qp.end(), seqs + off[i], seqs + off[i + 1]);
-            tp.insert(tp.end(), seqs + off[j], seqs + off[j + 1]);
-            qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
+            pool.add(seqs + off[i], len(i), false, seqs + off[j], len(j));
             selfOther_.push_back(key(i, j));
         };
         std::vector<char> isOut(n, 0);
@@ -215,7 +178,7 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
         }
         if (np > 0) {
             longPairs_.reset(new Batch);
-            if (longPairs_->init(qp.data(), qo.data(), (int)np, tp.data(), to.data(), (int)np, cfg_, device)) return 1;
+            if (pool.init(*longPairs_, cfg_, device)) return 1;
         }
     }
     otherCells_ = (long long)selfOther_.size();
@@ -240,25 +203,12 @@ int CrossBatch::runSelf()
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
-    EDLIB_AMD_HIP(guard.status);
-    haveRun_ = matFetched_ = nearFetched_ = hitsFetched_ = false;
-    const long long cells = stats.cells;
-    stats = EdlibAmdBatchStats{};
-    stats.cells = cells;
+    if (beginRun(guard.status, {&mat_, &near_, &hitList_})) return 1;
     if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
     // the pairs outside the length window are visited by no work item and are in no pair batch: -1 from here
     else if (cfg_.k >= 0 && cells_ > 0) EDLIB_AMD_HIP(hipMemsetAsync(d_mat_.p, 0xff, cells_ * sizeof(int), stream_));
 
-    if (!groups_.empty()) {
-        for (auto& g : groups_)
-            EDLIB_AMD_HIP(launch_build_peq_reads(g->words, syms_, d_qpool_.p, d_qoff_.p, g->d_perm.p, g->slots, d_eqtbl_.p,
-                                                 d_presence_.p, cfg_.k, g->d_peq.p, g->d_qlen.p, g->d_kinit.p, g->d_alpha.p,
-                                                 stream_));
-        EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
-        if (scanGroups()) return 1;
-        EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
-        stats.path |= 8;
-    }
+    if (scanRun(groups_, 8, [&] { return scanGroups(); })) return 1;
     xKey_.clear(); xVal_.clear();
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
@@ -268,10 +218,7 @@ int CrossBatch::runSelf()
             std::vector<int> rec(3 * np);
             if (gather(*longPairs_, np, rec.data(), nullptr)) return 1;
             for (size_t c = 0; c < np; ++c) vals[ne + c] = rec[3 * c];
-            longPairs_->finishStats();
-            const EdlibAmdBatchStats& s = longPairs_->stats;
-            stats.scan_launches += s.scan_launches;
-            stats.path |= s.path; stats.overflow_units += s.overflow_units; stats.wide_retries += s.wide_retries;
+            addSessionStats(*longPairs_, false);
         }
         if (!hits_) {
             EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
@@ -293,16 +240,7 @@ int CrossBatch::runSelf()
     } else {
         EDLIB_AMD_HIP(launch_self_nearest_dense(d_mat_.p, nq_, d_near_.p, stream_));
     }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (!groups_.empty()) {
-        float ms = 0.f;
-        EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evScan0_.e, evScan1_.e));
-        stats.scan_ms = ms;
-    }
-    stats.algo_bytes = 0;
-    stats.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    haveRun_ = true;
-    return 0;
+    return endRun(t0, !groups_.empty());
 }
 
 int CrossBatch::selfView(int what, EdlibAmdSelfView* out)
@@ -314,22 +252,13 @@ int CrossBatch::selfView(int what, EdlibAmdSelfView* out)
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     const size_t matBytes = cells_ * sizeof(int), nearBytes = 3 * (size_t)nq_ * sizeof(int);
-    if ((what & EDLIB_AMD_SELF_DISTANCES) && !matFetched_) {
-        if (h_mat_.n < matBytes || !h_mat_.p) EDLIB_AMD_HIP(h_mat_.alloc(matBytes));
-        if (matBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_mat_.p, d_mat_.p, matBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    if ((what & EDLIB_AMD_SELF_NEAREST) && !nearFetched_) {
-        if (h_near_.n < nearBytes || !h_near_.p) EDLIB_AMD_HIP(h_near_.alloc(nearBytes));
-        if (nearBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_near_.p, d_near_.p, nearBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (what & EDLIB_AMD_SELF_DISTANCES) matFetched_ = true;
-    if (what & EDLIB_AMD_SELF_NEAREST) nearFetched_ = true;
+    if (fetchParts({{what & EDLIB_AMD_SELF_DISTANCES, &mat_, d_mat_.p, matBytes},
+                    {what & EDLIB_AMD_SELF_NEAREST, &near_, d_near_.p, nearBytes}})) return 1;
     memset(out, 0, sizeof *out);
     out->numSequences = nq_; out->numPairs = (long long)cells_;
-    if (what & EDLIB_AMD_SELF_DISTANCES) out->editDistance = reinterpret_cast<const int*>(h_mat_.p);
+    if (what & EDLIB_AMD_SELF_DISTANCES) out->editDistance = reinterpret_cast<const int*>(mat_.h.p);
     if (what & EDLIB_AMD_SELF_NEAREST) {
-        const int* b = reinterpret_cast<const int*>(h_near_.p);
+        const int* b = reinterpret_cast<const int*>(near_.h.p);
         out->nearest = b; out->nearestDistance = b + nq_; out->secondDistance = b + 2 * (size_t)nq_;
     }
     return 0;
@@ -347,19 +276,12 @@ int CrossBatch::selfHitsView(EdlibAmdSelfHits* out)
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     // the finished list is [4][numHits] (partner, editDistance, numLocations, endLocation): the first two planes travel
-    const size_t offBytes = ((size_t)nq_ + 1) * sizeof(long long), listBytes = 2 * (size_t)numHits_ * sizeof(int);
-    if (!hitsFetched_) {
-        if (h_hits_.n < offBytes + listBytes || !h_hits_.p) EDLIB_AMD_HIP(h_hits_.alloc(offBytes + listBytes));
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p, d_htoff_.p, offBytes, hipMemcpyDeviceToHost, stream_));
-        if (listBytes)
-            EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p + offBytes, d_hout_.p, listBytes, hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        hitsFetched_ = true;
-    }
+    size_t offBytes = 0;
+    if (fetchHits(2, nq_, &offBytes)) return 1;
     memset(out, 0, sizeof *out);
     out->numSequences = nq_; out->numHits = numHits_;
-    out->rowOffsets = reinterpret_cast<const long long*>(h_hits_.p);
-    const int* l = reinterpret_cast<const int*>(h_hits_.p + offBytes);
+    out->rowOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
+    const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
     out->partner = l; out->editDistance = l + (size_t)numHits_;
     return 0;
 }

@@ -8,18 +8,12 @@
 // Units with a strand: where a unit names the reverse complement of its query the query pool holds both
 // strands of every query, made on the device (entry 2 q + strand), and a Peq slot goes to each (query, strand) a kernel
 // unit names; the scan and the best reduction do not know about strands.
-#include "engine.hpp"
+#include "engine_lanes.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 namespace edlib_amd {
-
-WindowBatch::~WindowBatch()
-{
-    DeviceGuard guard(device_);
-    if (stream_) { (void)hipStreamSynchronize(stream_); pool_stream_release(stream_); }
-}
 
 int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, const char* target, int targetLength,
                       const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
@@ -38,10 +32,8 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
         set_error("bad batch shape");
         return 1;
     }
-    std::vector<long long> qoff(nq + 1, 0);
-    if (nq > 0) qoff.assign(qoffIn, qoffIn + nq + 1);
-    for (int i = 0; i < nq; ++i)
-        if (qoff[i + 1] < qoff[i] || qoff[i + 1] - qoff[i] > 0x7fffffffLL) { set_error("bad query offsets"); return 1; }
+    std::vector<long long> qoff;
+    if (copy_offsets(qoffIn, nq, "query", qoff)) return 1;
     for (int u = 0; u < nu; ++u) {
         if (unitQuery[u] < 0 || unitQuery[u] >= nq) {
             set_error("window batch: unit %d names query %d, outside [0, numQueries = %d)", u, unitQuery[u], nq);
@@ -63,26 +55,17 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
     for (int u = 0; u < nu && unitStrand && !stranded; ++u) stranded = unitStrand[u] != 0;
     if (stranded && nq > 0x3fffffff) { set_error("bad batch shape"); return 1; }
     auto strandOf = [&](int u) { return stranded ? (int)unitStrand[u] : 0; };
-    const int ndev = device_count();
-    if (ndev == 0) { set_error("no usable HIP device (this library has no CPU fallback)"); return 1; }
-    if (device < 0 || device >= ndev) { set_error("device %d out of range (%d devices)", device, ndev); return 1; }
+    if (check_device(device)) return 1;
 
-    cfg_ = cfg;
-    if (cfg.additionalEqualities && cfg.additionalEqualitiesLength > 0)
-        eqs_.assign(cfg.additionalEqualities, cfg.additionalEqualities + cfg.additionalEqualitiesLength);
-    cfg_.additionalEqualities = eqs_.empty() ? nullptr : eqs_.data();
-    cfg_.additionalEqualitiesLength = (int)eqs_.size();
+    keep_config(cfg, cfg_, eqs_);
     device_ = device; nq_ = nq; nu_ = nu; targetLength_ = targetLength;
-    const long long qb = qoff[0], qbytes = qoff[nq] - qb;
     auto qlen = [&](int q) { return (int)(qoff[q + 1] - qoff[q]); };
     stats = EdlibAmdBatchStats{};
-    cellsSum_ = 0;
-    for (int u = 0; u < nu; ++u) cellsSum_ += (long long)qlen(unitQuery[u]) * unitLength[u];
-    stats.cells = cellsSum_;
+    for (int u = 0; u < nu; ++u) stats.cells += (long long)qlen(unitQuery[u]) * unitLength[u];
 
     build_tables(tab_, reinterpret_cast<const uint8_t*>(target), targetLength, eqs_.data(), (int)eqs_.size());
     const bool wide = tab_.sigmaT > kCrossMaxSyms;
-    syms_ = tab_.sigmaT <= 4 ? 4 : (tab_.sigmaT <= 8 ? 8 : 16);
+    syms_ = peq_syms(tab_.sigmaT);
     auto onKernel = [&](int u) {
         return !wide && qlen(unitQuery[u]) <= 32 * kCrossMaxQueryWords && unitLength[u] <= kCrossMaxTarget;
     };
@@ -90,8 +73,7 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    EDLIB_AMD_HIP(pool_stream(&stream_));
-    EDLIB_AMD_HIP(evScan0_.create()); EDLIB_AMD_HIP(evScan1_.create());
+    if (openStream()) return 1;
     EDLIB_AMD_HIP(d_units_.alloc(3 * (size_t)std::max(nu, 1)));
     EDLIB_AMD_HIP(d_uq_.alloc((size_t)std::max(nu, 1)));
     EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)std::max(nq, 1)));
@@ -107,36 +89,9 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
         ++kernelUnits;
     }
     if (kernelUnits > 0) {
-        {   // the target: 4-bit codes from dword 0; the raw bytes are only needed by the pack
-            const long long toff[2] = {0, targetLength}, tdw[1] = {0};
-            const int tperm[1] = {0};
-            DevBuf<uint8_t> d_traw, d_tlut; DevBuf<long long> d_toff, d_tdw; DevBuf<int> d_tperm;
-            EDLIB_AMD_HIP(d_tpk_.alloc((size_t)std::max(1, (targetLength + 7) / 8)));
-            EDLIB_AMD_HIP(d_traw.alloc((size_t)targetLength + 16)); EDLIB_AMD_HIP(d_tlut.alloc(256));
-            EDLIB_AMD_HIP(d_toff.alloc(2)); EDLIB_AMD_HIP(d_tdw.alloc(1)); EDLIB_AMD_HIP(d_tperm.alloc(1));
-            if (targetLength) EDLIB_AMD_HIP(hipMemcpy(d_traw.p, target, (size_t)targetLength, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_tlut.p, tab_.tlut, 256, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_toff.p, toff, sizeof toff, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_tdw.p, tdw, sizeof tdw, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_tperm.p, tperm, sizeof tperm, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(launch_pack_cross_targets(d_traw.p, d_toff.p, d_tperm.p, d_tdw.p, 1, d_tlut.p, d_tpk_.p, stream_));
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        }
-        // queries (rebased), their tables
-        std::vector<long long> qoffR(qoff);
-        for (auto& v : qoffR) v -= qb;
-        if (!stranded) {
-            EDLIB_AMD_HIP(d_qpool_.alloc((size_t)qbytes + 16)); EDLIB_AMD_HIP(d_qoff_.alloc(nq + 1));
-            if (qbytes) EDLIB_AMD_HIP(hipMemcpy(d_qpool_.p, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice));
-            EDLIB_AMD_HIP(hipMemcpy(d_qoff_.p, qoffR.data(), (nq + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        } else {
-            // the caller's pool goes up as it is; query i and its reverse complement are written from it on the device as
-            // the entries 2i and 2i + 1 of a pool twice its size
-            if (make_strand_pool(queries + qb, qoffR.data(), nq, d_qpool_, d_qoff_, stream_)) return 1;
-        }
-        EDLIB_AMD_HIP(d_eqtbl_.alloc(256)); EDLIB_AMD_HIP(d_presence_.alloc(8));
-        EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
+        // the target: 4-bit codes from dword 0
+        if (packHostTargets(target, {0, targetLength}, {0}, {targetLength})) return 1;
+        if (uploadQueries(queries, qoff, stranded)) return 1;
         // a pool entry's slot in its group; the entry of a unit is its query, or 2 * query + strand in a stranded batch
         std::vector<int> slotOf((size_t)nq * (stranded ? 2 : 1), -1);
         for (int w = 1; w <= kCrossMaxQueryWords; ++w) {
@@ -154,14 +109,10 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
                 uslot[i] = slotOf[e]; ustart[i] = unitStart[u]; ulen[i] = n;
                 if (m > 0 && n > 0 && !cross_nw_outside((int)cfg.mode, cfg.k, m, n)) g->wordSteps += (long long)w * n;
             }
-            g->slots = (int)perm.size();
-            const size_t blocks = (size_t)(g->slots + 63) / 64, ns = us.size();
-            EDLIB_AMD_HIP(g->d_perm.alloc(g->slots)); EDLIB_AMD_HIP(g->d_qlen.alloc(g->slots));
-            EDLIB_AMD_HIP(g->d_kinit.alloc(g->slots)); EDLIB_AMD_HIP(g->d_alpha.alloc(g->slots));
-            EDLIB_AMD_HIP(g->d_peq.alloc(blocks * syms_ * w * 64));
+            const size_t ns = us.size();
+            if (allocGroup(*g, perm)) return 1;
             EDLIB_AMD_HIP(g->d_uslot.alloc(ns)); EDLIB_AMD_HIP(g->d_ustart.alloc(ns));
             EDLIB_AMD_HIP(g->d_ulen.alloc(ns)); EDLIB_AMD_HIP(g->d_uperm.alloc(ns));
-            EDLIB_AMD_HIP(hipMemcpy(g->d_perm.p, perm.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
             EDLIB_AMD_HIP(hipMemcpy(g->d_uslot.p, uslot.data(), ns * sizeof(int), hipMemcpyHostToDevice));
             EDLIB_AMD_HIP(hipMemcpy(g->d_ustart.p, ustart.data(), ns * sizeof(int), hipMemcpyHostToDevice));
             EDLIB_AMD_HIP(hipMemcpy(g->d_ulen.p, ulen.data(), ns * sizeof(int), hipMemcpyHostToDevice));
@@ -172,21 +123,14 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
 
     // ---- the pair engine's share: these units' bytes are replicated, query and window
     if (!pairUnits_.empty()) {
-        std::vector<char> qp, tp;
-        std::vector<long long> qo(1, 0), to(1, 0);
+        PairPool pool;
         for (long long u : pairUnits_) {
             const int q = unitQuery[u];
-            if (!strandOf((int)u)) qp.insert(qp.end(), queries + qoff[q], queries + qoff[q + 1]);
-            else
-                for (long long j = qoff[q + 1] - 1; j >= qoff[q]; --j) qp.push_back((char)complement_byte((uint8_t)queries[j]));
-            tp.insert(tp.end(), target + unitStart[u], target + unitStart[u] + unitLength[u]);
-            qo.push_back((long long)qp.size()); to.push_back((long long)tp.size());
+            pool.add(queries + qoff[q], qlen(q), strandOf((int)u) != 0, target + unitStart[u], unitLength[u]);
         }
         const int np = (int)pairUnits_.size();
-        if (qp.empty()) qp.push_back(0);
-        if (tp.empty()) tp.push_back(0);
         pairs_.reset(new Batch);
-        if (pairs_->init(qp.data(), qo.data(), np, tp.data(), to.data(), np, cfg_, device)) return 1;
+        if (pool.init(*pairs_, cfg_, device)) return 1;
         EDLIB_AMD_HIP(h_vals_.alloc(3 * (size_t)np * sizeof(int)));
         EDLIB_AMD_HIP(d_cells_.alloc((size_t)np)); EDLIB_AMD_HIP(d_vals_.alloc(3 * (size_t)np));
         EDLIB_AMD_HIP(hipMemcpy(d_cells_.p, pairUnits_.data(), (size_t)np * sizeof(long long), hipMemcpyHostToDevice));
@@ -199,20 +143,12 @@ int WindowBatch::run()
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
-    EDLIB_AMD_HIP(guard.status);
-    haveRun_ = unitsFetched_ = bestFetched_ = false;
-    stats = EdlibAmdBatchStats{};
-    stats.cells = cellsSum_;
+    if (beginRun(guard.status, {&units_, &best_})) return 1;
     const size_t nu = (size_t)nu_;
     int* ed = d_units_.p; int* nloc = ed + nu; int* end = ed + 2 * nu;
 
     // the window kernel: Peq of every query a unit names, then one scan per word group
-    if (!groups_.empty()) {
-        for (auto& g : groups_)
-            EDLIB_AMD_HIP(launch_build_peq_reads(g->words, syms_, d_qpool_.p, d_qoff_.p, g->d_perm.p, g->slots, d_eqtbl_.p,
-                                                 d_presence_.p, cfg_.k, g->d_peq.p, g->d_qlen.p, g->d_kinit.p, g->d_alpha.p,
-                                                 stream_));
-        EDLIB_AMD_HIP(hipEventRecord(evScan0_.e, stream_));
+    const auto scanGroups = [&]() -> int {
         for (auto& g : groups_) {
             WindowScanArgs a{};
             a.peq = g->d_peq.p; a.qlen = g->d_qlen.p; a.tpk = d_tpk_.p; a.targetLength = targetLength_;
@@ -223,40 +159,22 @@ int WindowBatch::run()
             ++stats.scan_launches;
             stats.word_steps += g->wordSteps;
         }
-        EDLIB_AMD_HIP(hipEventRecord(evScan1_.e, stream_));
-        stats.path |= 16;
-    }
+        return 0;
+    };
+    if (scanRun(groups_, 16, scanGroups)) return 1;
     // the pair engine runs on its own streams meanwhile
     if (pairs_) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
         const size_t np = pairUnits_.size();
         if (pairs_->run()) return 1;
-        EdlibAmdResultsView v{};
-        if (pairs_->resultsView(&v)) return 1;
-        for (size_t i = 0; i < np; ++i) {
-            if (v.status[i] != EDLIB_STATUS_OK) { set_error("window batch: an internal alignment failed"); return 1; }
-            vals[3 * i] = v.editDistance[i];
-            vals[3 * i + 1] = v.numLocations[i];
-            vals[3 * i + 2] = v.numLocations[i] > 0 ? v.endLocations[v.locOffsets[i]] : -1;
-        }
-        pairs_->finishStats();
-        const EdlibAmdBatchStats& s = pairs_->stats;
-        stats.word_steps += s.word_steps; stats.scan_launches += s.scan_launches;
-        stats.path |= 2 | s.path; stats.overflow_units += s.overflow_units; stats.wide_retries += s.wide_retries;
+        if (readCells(*pairs_, np, vals, "window")) return 1;
+        addSessionStats(*pairs_, true);
+        stats.path |= 2;
         EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, 3 * np * sizeof(int), hipMemcpyHostToDevice, stream_));
         EDLIB_AMD_HIP(launch_cross_scatter(d_cells_.p, d_vals_.p, (long long)np, ed, nloc, end, stream_));
     }
     EDLIB_AMD_HIP(launch_window_best(d_uq_.p, ed, nu_, nq_, d_bkey_.p, d_best_.p, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (!groups_.empty()) {
-        float ms = 0.f;
-        EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evScan0_.e, evScan1_.e));
-        stats.scan_ms = ms;
-    }
-    stats.algo_bytes = 0;
-    stats.run_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    haveRun_ = true;
-    return 0;
+    return endRun(t0, !groups_.empty());
 }
 
 int WindowBatch::view(int what, EdlibAmdWindowView* out)
@@ -267,25 +185,16 @@ int WindowBatch::view(int what, EdlibAmdWindowView* out)
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     const size_t unitBytes = 3 * (size_t)nu_ * sizeof(int), bestBytes = 3 * (size_t)nq_ * sizeof(int);
-    if ((what & EDLIB_AMD_WINDOW_UNITS) && !unitsFetched_) {
-        if (h_units_.n < unitBytes || !h_units_.p) EDLIB_AMD_HIP(h_units_.alloc(unitBytes));
-        if (unitBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_units_.p, d_units_.p, unitBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    if ((what & EDLIB_AMD_WINDOW_BEST) && !bestFetched_) {
-        if (h_best_.n < bestBytes || !h_best_.p) EDLIB_AMD_HIP(h_best_.alloc(bestBytes));
-        if (bestBytes) EDLIB_AMD_HIP(hipMemcpyAsync(h_best_.p, d_best_.p, bestBytes, hipMemcpyDeviceToHost, stream_));
-    }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    if (what & EDLIB_AMD_WINDOW_UNITS) unitsFetched_ = true;
-    if (what & EDLIB_AMD_WINDOW_BEST) bestFetched_ = true;
+    if (fetchParts({{what & EDLIB_AMD_WINDOW_UNITS, &units_, d_units_.p, unitBytes},
+                    {what & EDLIB_AMD_WINDOW_BEST, &best_, d_best_.p, bestBytes}})) return 1;
     memset(out, 0, sizeof *out);
     out->numUnits = nu_; out->numQueries = nq_;
     if (what & EDLIB_AMD_WINDOW_UNITS) {
-        const int* p = reinterpret_cast<const int*>(h_units_.p);
+        const int* p = reinterpret_cast<const int*>(units_.h.p);
         out->editDistance = p; out->numLocations = p + nu_; out->endLocation = p + 2 * (size_t)nu_;
     }
     if (what & EDLIB_AMD_WINDOW_BEST) {
-        const int* b = reinterpret_cast<const int*>(h_best_.p);
+        const int* b = reinterpret_cast<const int*>(best_.h.p);
         out->bestUnit = b; out->bestDistance = b + nq_; out->secondDistance = b + 2 * (size_t)nq_;
     }
     return 0;

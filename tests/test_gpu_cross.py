@@ -134,6 +134,19 @@ def test_cross_out_of_envelope(engine, checker):
         b = engine.CrossBatch(queries, targets, mode=mode, k=-1 if mode == "HW" else 200)
         st = b.run()
         assert st["path"] & 8
+        if mode == "HW":
+            # word_steps: the kernel's cells, and the internal sessions' own counts (the same sessions made here)
+            small = sorted((t for t in range(len(targets)) if t != 7), key=lambda t: len(targets[t]))
+            kernel = sum((len(q) + 31) // 32 for q in queries if len(q) <= 256) * sum(len(targets[t]) for t in small)
+            parts = [kernel]
+            for s in (engine.SharedBatch(queries, big, mode="HW", k=-1),
+                      engine.PairBatch([queries[0]] * len(small), [targets[t] for t in small], mode="HW", k=-1)):
+                try:
+                    parts.append(s.run()["word_steps"])
+                finally:
+                    s.close()
+            print("word_steps", st["word_steps"], parts)
+            assert st["word_steps"] == sum(parts), (st["word_steps"], parts)
         tq = [(t, q) for t in range(len(targets)) for q in range(len(queries)) if t != 7 or q % 4 == 0 or q == len(queries) - 1]
         m = b.matrix()
         ed, nloc, first = ref_cells(queries, targets, mode, -1 if mode == "HW" else 200, None, tq)

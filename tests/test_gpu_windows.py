@@ -285,6 +285,19 @@ def test_mixed_envelope(engine, checker, mode):
         try:
             st = b.run()
             assert st["path"] & 16 and st["path"] & 2, st
+            if mode == "HW" and k == -1:
+                # word_steps: the kernel's units, and the internal pair session's own count (the same session made here)
+                out = np.array([len(queries[int(q)]) > 256 for q in uq])
+                tb = _bytes(target)
+                p = engine.PairBatch([queries[int(q)] for q in uq[out]],
+                                     [tb[int(s):int(s) + int(n)] for s, n in zip(us[out], ul[out])], mode=mode, k=k)
+                try:
+                    pair_steps = p.run()["word_steps"]
+                finally:
+                    p.close()
+                kernel = host_word_steps(queries, uq[~out], ul[~out], mode, k)
+                print("word_steps", st["word_steps"], kernel, pair_steps)
+                assert st["word_steps"] == kernel + pair_steps, (st["word_steps"], kernel, pair_steps)
             check(b, queries, target, uq, us, ul, mode, k)
         finally:
             b.close()
