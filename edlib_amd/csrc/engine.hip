@@ -597,82 +597,77 @@ int Batch::run()
     return rc;
 }
 
+// What every run does first, a hit-list Run too: nothing is counted yet, the clock of run_ms starts
+int Batch::beginRun(hipError_t guardStatus)
+{
+    EDLIB_AMD_HIP(guardStatus);
+    const long long cells = stats.cells;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = cells;
+    scanEventsUsed_ = 0;
+    wordStepsPending_ = false;                   // (a run that failed before its endRun)
+    EDLIB_AMD_HIP(hipEventRecord(evRun0_.e, stream_));
+    return 0;
+}
+
+int Batch::enqueueWordSteps()                    // read back with the run's final synchronisation (endRun adds them)
+{
+    EDLIB_AMD_HIP(h_wordSteps_.alloc(sizeof(unsigned long long)));
+    EDLIB_AMD_HIP(hipMemcpyAsync(h_wordSteps_.p, d_wordSteps_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+    wordStepsPending_ = true;
+    return 0;
+}
+
+// ... and last: the run's one wait for its stream (what a caller enqueued before is on the host behind it), then the times
+int Batch::endRun()
+{
+    EDLIB_AMD_HIP(hipEventRecord(evRun1_.e, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    float ms = 0;
+    EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evRun0_.e, evRun1_.e));
+    stats.run_ms = ms;
+    if (wordStepsPending_) { stats.word_steps += (long long)*reinterpret_cast<unsigned long long*>(h_wordSteps_.p); wordStepsPending_ = false; }
+    for (size_t i = 0; i < scanEventsUsed_; ++i) {
+        float t = 0;
+        EDLIB_AMD_HIP(hipEventElapsedTime(&t, scanEvents_[i].first, scanEvents_[i].second));
+        stats.scan_ms += t;
+    }
+    return 0;
+}
+
 int Batch::runImpl()
 {
     pool_quarantine(false);
     Lap lap;
     DeviceGuard guard(device_);
-    EDLIB_AMD_HIP(guard.status);
-    const long long cells = stats.cells;
-    stats = EdlibAmdBatchStats{};
-    stats.cells = cells;
-    scanEventsUsed_ = 0;
+    haveResults_ = hitsHaveRun_ = hitsFetched_ = false;      // (a run that fails leaves nothing of the one before readable)
+    if (beginRun(guard.status)) return 1;
     if (hits_) return runReadHits();
     hostStrandCounts_[0] = hostStrandCounts_[1] = hostStrandCounts_[2] = hostStrandCounts_[3] = 0;
-    haveResults_ = false;
     opsKeep_.clear();            // (the previous run's views die with the reset of their records below)
     knownSplits_.clear();
     wideGateRelease();           // (a run that failed between a wide launch and its check)
     wideSerial_ = false;         // every run tries the pipelined strips first
     viewReady_ = false; cigar_[0].ready = cigar_[1].ready = false; lastRunFlat_ = false;      // (views of the previous run end here)
     opsOwned_.clear();
-    // TASK_DISTANCE over reads-path units only: nothing is assembled on the host until results() asks for it, so
-    // the per-unit records (160 bytes each) are not even allocated in the timed run
-    const bool lazy = (cfg_.task == EDLIB_TASK_DISTANCE && pairUnits_.empty() && longUnits_.empty() && emptyUnits_.empty() && !groups_.empty()) || flatPairs_;
-    pairsCollected_ = true;
     // the records of the run before last are recycled (no 160-byte-per-unit allocation + page faults per run)
     std::vector<UnitResult>& res = work_;
-    bool deferReset = false;
-    deferReadsReset_ = false;
-    if (lazy) res.clear();
-    else {
-        const size_t keep = std::min(res.size(), (size_t)n_);
-        res.resize((size_t)n_);
-        // a batch of pair units only rewrites every record in its finalize loop: the recycled records are blanked there, in
-        // the same pass over the 16 MB of 100,000 records, instead of in a walk of their own (0.4 ms)
-        deferReset = emptyUnits_.empty() && groups_.empty() && longUnits_.empty() && !flatPairs_ && pairUnits_.size() == (size_t)n_;
-        // the same for a batch of reads-path units only whose records are assembled in this run (LOC / PATH): collectGroup
-        // visits every one of them (15 ms of a 1M-read run were this walk over 160 MB)
-        deferReadsReset_ = !deferReset && cfg_.task != EDLIB_TASK_DISTANCE && emptyUnits_.empty() && pairUnits_.empty() &&
-                           longUnits_.empty() && !flatPairs_ && readUnits_.size() == (size_t)n_;
-        if (!deferReset && !deferReadsReset_) for (size_t u = 0; u < keep; ++u) blank_record(res[u]);
-    }
+    resetRecords(res);
     // (results_ keeps the previous run's records until the swap at the end: they are the NEXT run's recycled `work_`, blanked
     // before they are filled; destroying and re-creating 100,000 of them was 0.4 ms of every config-4 step.  Nothing reads
     // them meanwhile: haveResults_ is false until this run has succeeded.)
-    const int mode = (int)cfg_.mode;
-    const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
-    EDLIB_AMD_HIP(hipEventRecord(evRun0_.e, stream_));
     if (d_ringSteps_.p) EDLIB_AMD_HIP(hipMemsetAsync(d_ringSteps_.p, 0, sizeof(unsigned long long), stream_));
     ringStepsUsed_ = false;
     lap("run: reset records");
-
-    // ---- empty sequences: answered without any DP (edlib.cpp:166-184)
-    for (int u : emptyUnits_) {
-        UnitResult& r = res[u];
-        const int m = qlen(u), T = tlen(u);
-        if (mode == EDLIB_MODE_NW) { r.editDistance = std::max(m, T); r.ends.assign(1, T - 1); r.hasEnds = true; }
-        else if (mode == EDLIB_MODE_SHW || mode == EDLIB_MODE_HW) { r.editDistance = m; r.ends.assign(1, -1); r.hasEnds = true; }
-        else r.status = EDLIB_STATUS_ERROR;
-    }
+    answerEmptyUnits(res);
     // (a big NW distance batch of pairs builds the Peq of all its units beside the divergence probe, and its main scan waits
     // for that: the count -- 2 GB of reads for config 4 -- is queued BEHIND that build instead of next to it
     // (solveGlobalDistances).  Not behind the main scan: that holds every wave slot of the chip, and the count took 17 ms.)
     alphaDeferred_ = !flatPairs_ && cfg_.mode == EDLIB_MODE_NW && cfg_.task == EDLIB_TASK_DISTANCE && pairUnits_.size() >= 8192 &&
                      groups_.empty() && longUnits_.empty();
     if (!alphaDeferred_ && alphabetLengthsBegin()) return 1;
-    bool flatDone = false;
-    if (flatPairs_) {                                   // ---- a flat pair batch: everything stays on the device
-        bool over = false, fell = false;
-        if (runPairsFlat(over, fell)) return 1;
-        if (fell) {
-            // something the flat layouts do not hold (more than 16 end locations with starts / paths asked for, a band
-            // level that failed): this run takes the general path from the start
-            res.resize((size_t)n_);
-            for (size_t u = 0; u < res.size(); ++u) blank_record(res[u]);
-        } else { flatDone = true; pairsCollected_ = false; lastRunFlat_ = true; }
-        lap("run: flat pairs");
-    }
+    flatDone_ = false;
+    if (flatPairs_ && runFlatPhase(res, lap)) return 1;
     // ---- phase 1: distance + end locations
     if (packTarget()) return 1;
     if (runReads()) return 1;
@@ -684,244 +679,29 @@ int Batch::runImpl()
     // long HW queries against the shared target: piece filter + window verification; what it hands back (low
     // complexity, thresholds beyond a quarter of the piece) joins the pair units below
     pairNow_ = pairUnits_;
-    if (!longUnits_.empty()) {
-        std::vector<int> fb;
-        if (solveLongReads(res, fb)) return 1;
-        lap("run: long reads");
-        // What the filter hands back is mostly unrelated sequence: every row of every column is needed.  Up to 1024 rows
-        // (512 above four target symbols) the lane-per-read full-height kernel does that at ~20 VALU ops per 64 rows and
-        // column with every lane busy; longer queries take kernel W's strips.
-        const int fullMax = syms_ == 4 ? 32 * kMaxLongReadWords4 : (syms_ == 8 ? 32 * kMaxLongReadWords : 0);
-        std::vector<std::vector<int>> byWords(kMaxLongReadWords4 + 1);
-        std::vector<int> tall;
-        for (int u : fb) {
-            if (qlen(u) <= fullMax) byWords[read_group_words(qlen(u))].push_back(u);
-            else if (fullMax > 0) tall.push_back(u);
-            else pairNow_.push_back(u);
-        }
-        for (int w = 1; w <= kMaxLongReadWords4; ++w) {
-            if (byWords[w].empty()) continue;
-            std::unique_ptr<ReadGroup> g;
-            // (many short segments here: a single strip warms up over at most 2047 columns, and 7,930 waves balance themselves
-            // over the SIMDs where one round of 1,014 does not -- 513 / 768 / 1024-base reads: 110 / 125 / 166 ms against
-            // 129 / 144 / 172 with makeGroup's oneRoundWaves; the chained strips of solveTallFull warm up over 2m - 1 columns
-            // of the WHOLE query, which is what makes one round the better plan there)
-            if (makeGroup(byWords[w], w, g)) return 1;
-            stats.path |= 1;
-            if (runGroupScans(*g, true) || runGroupExact(*g) || collectGroup(*g, res)) return 1;
-        }
-        if (!tall.empty()) {                    // taller: strips of fullMax rows on the same kernel, chained through HBM
-            std::vector<int> back;
-            if (solveTallFull(tall, res, back)) return 1;
-            pairNow_.insert(pairNow_.end(), back.begin(), back.end());
-        }
-        lap("run: handed back (full height)");
-    }
-    if (banded_ && (!groups_.empty() || !longUnits_.empty())) {   // read back with the run's final synchronisation
-        EDLIB_AMD_HIP(h_wordSteps_.alloc(sizeof(unsigned long long)));
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_wordSteps_.p, d_wordSteps_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
-        wordStepsPending_ = true;
-    }
-    if (flatDone) pairNow_.clear();
-    const std::vector<int>& pairUnits_ = pairNow_;          // (shadows the member: the units of THIS run's pair phase)
-    if (!pairUnits_.empty()) {
-        // scratch that a run needs per unit lives in the batch: a fresh 10 MB std::vector is an mmap, its page faults
-        // and a munmap (45 MB of them were 5 of the 9 ms a run over 262,144 short pairs took)
-        std::vector<UnitSpec>& units = pairSpecs_;
-        // (the specs depend on the batch only: a run over the same pair units as the last one keeps them)
-        if (pairSpecsFor_ != pairUnits_) {
-            units.resize(pairUnits_.size());
-            for (size_t i = 0; i < units.size(); ++i) {
-                const int u = pairUnits_[i], m = qlen(u);
-                // (SHW: D[m][j] >= j - m > m >= best beyond column 2m: the rest of a long target cannot matter)
-                const int T = scanMode == EDLIB_MODE_SHW ? (int)std::min<long long>(tlen(u), 2LL * m + 1) : tlen(u);
-                units[i] = UnitSpec{qoff_[u], m, 1, tbase(u), T, 1,
-                                    (cfg_.k < 0 || cfg_.k > m) ? m : cfg_.k};
-            }
-            pairSpecsFor_ = pairUnits_;
-            ++pairSpecsVersion_;
-        }
-        SolveOut& so = soMain_;
-        if (scanMode == EDLIB_MODE_NW) {
-            std::vector<int>& score = scoreMain_;
-            // TASK_PATH over pairs that all stay below the 1 MiB rule (edlib.cpp:1188-1190): the reference scans twice
-            // (distance, then the storing scan with k = distance, :1196-1199); here a unit's first successful level
-            // stores its columns and is traced back right away -- any threshold >= the distance gives the same walk
-            // (every neighbour that could be "one less than here" is <= the distance, hence exact inside the band)
-            bool fuse = cfg_.task == EDLIB_TASK_PATH && mode == EDLIB_MODE_NW;
-            for (size_t i = 0; fuse && i < units.size(); ++i) fuse = !needs_hirschberg(units[i].qlen, units[i].tlen);
-            fusedOps_.clear();
-            lap("run: pair specs");
-            // What the records of NW units hold besides the distance does not depend on the scan (one end location, T - 1:
-            // edlib.cpp:221-225; alphabetLength from the side stream): a level that takes every unit (runLevelAll) runs this
-            // pass over the 16 MB of 100,000 records while the chip scans, and only the distances are filled in behind it.
-            bool prefilled = false;
-            if (!fuse && mode == EDLIB_MODE_NW) {
-                whileScanning_ = [&]() {
-                    if (alphaIsPairsVersion_ != pairSpecsVersion_) { alphaIsPairs_ = alphaUnits_ == pairUnits_; alphaIsPairsVersion_ = pairSpecsVersion_; }
-                    const int* alphaOut = nullptr;
-                    if (alphaPending_ && alphaIsPairs_ && !alphaOnHost_ && hipStreamSynchronize(side_) == hipSuccess) {
-                        alphaPending_ = false;
-                        alphaOut = reinterpret_cast<const int*>(alphaPin_.p);
-                    }
-                    for (size_t i = 0; i < units.size(); ++i) {
-                        UnitResult& r = res[pairUnits_[i]];
-                        if (deferReset) blank_record(r);
-                        r.hasEnds = true; r.ends.assign(1, units[i].tlen - 1);
-                        if (alphaOut) r.alphabetLength = alphaOut[i];
-                    }
-                    prefilled = true;
-                };
-            }
-            const int solved = solveGlobalDistances(units, score, fuse ? &fusedOps_ : nullptr);
-            whileScanning_ = nullptr;
-            if (solved) return 1;
-            lap("run: global distances");
-            // (alphabetLength of the same units, counted on the side stream meanwhile: set in this pass over the records
-            // instead of in one of its own -- alphabetLengthsEnd() then finds nothing pending)
-            if (alphaIsPairsVersion_ != pairSpecsVersion_) { alphaIsPairs_ = alphaUnits_ == pairUnits_; alphaIsPairsVersion_ = pairSpecsVersion_; }
-            const int* alphaOut = nullptr;
-            if (alphaPending_ && alphaIsPairs_ && !alphaOnHost_) {
-                EDLIB_AMD_HIP(hipStreamSynchronize(side_));
-                alphaPending_ = false;
-                alphaOut = reinterpret_cast<const int*>(alphaPin_.p);
-            }
-            if (prefilled) {
-                for (size_t i = 0; i < units.size(); ++i) {
-                    UnitResult& r = res[pairUnits_[i]];
-                    if (cfg_.k >= 0 && score[i] > cfg_.k) { r.editDistance = -1; r.hasEnds = false; r.ends.clear(); }      // as finalize_global
-                    else r.editDistance = score[i];
-                    if (alphaOut) r.alphabetLength = alphaOut[i];
-                }
-            } else
-            for (size_t i = 0; i < units.size(); ++i) {
-                UnitResult& r = res[pairUnits_[i]];
-                if (deferReset) blank_record(r);
-                finalize_global(r, cfg_.k, mode, units[i].tlen, score[i]);
-                if (alphaOut) r.alphabetLength = alphaOut[i];
-            }
-            if (fuse)
-                for (size_t i = 0; i < units.size(); ++i) {
-                    UnitResult& r = res[pairUnits_[i]];
-                    if (r.editDistance >= 0 && fusedOps_[i].p) { r.opsView = fusedOps_[i].p; r.opsViewLen = fusedOps_[i].len; r.hasAlignment = true; }
-                }
-        } else {
-            if (solveSemiGlobal(scanMode, true, units, so)) return 1;
-            for (size_t i = 0; i < units.size(); ++i) {
-                UnitResult& r = res[pairUnits_[i]];
-                if (deferReset) blank_record(r);
-                finalize_semiglobal(r, cfg_.k, units[i].qlen, so.score[i],
-                                    so.posFlat.data() + so.posStart[i], so.posStart[i + 1] - so.posStart[i]);
-            }
-        }
-    }
+    if (!longUnits_.empty() && runLongReads(res, lap)) return 1;
+    if (banded_ && (!groups_.empty() || !longUnits_.empty()) && enqueueWordSteps()) return 1;
+    if (flatDone_) pairNow_.clear();
+    if (!pairNow_.empty() && runPairPhase(res, lap)) return 1;
     lap("run: finalize pairs");
-    if (!flatDone && alphabetLengthsEnd(res)) return 1;      // alphabetLength for everything the reads path did not cover (flat pairs: at collection)
+    if (!flatDone_ && alphabetLengthsEnd(res)) return 1;      // alphabetLength for everything the reads path did not cover (flat pairs: at collection)
     lap("run: phase 1 (distance)");
     // both strands: the distance phase decides the strand; the later phases see the reported record only
     if (strands_ && !res.empty() && resolveStrandsOnHost(res)) return 1;
-    std::vector<int>& live = live_;            // non-empty units with a solution (only the later phases want them)
-    live.clear();
+    live_.clear();                             // non-empty units with a solution (only the later phases want them)
     // (a flat batch has done its phases 2 and 3 on the device: its records do not exist yet)
-    const bool laterPhases = !flatDone && (cfg_.task == EDLIB_TASK_LOC || cfg_.task == EDLIB_TASK_PATH);
+    const bool laterPhases = !flatDone_ && (cfg_.task == EDLIB_TASK_LOC || cfg_.task == EDLIB_TASK_PATH);
     if (laterPhases)
         for (int u = 0; u < n_; ++u)
-            if (qlen(u) > 0 && tlen(u) > 0 && res[u].editDistance >= 0) live.push_back(u);
-
-    // ---- phase 2: start locations (edlib.cpp:228-272)
-    if (laterPhases) {
-        std::vector<UnitSpec>& units = startUnits_; std::vector<std::pair<int, int>>& where = startWhere_;   // capacity kept across runs
-        units.clear(); where.clear();
-        units.reserve(live.size() + live.size() / 8); where.reserve(live.size() + live.size() / 8);
-        for (int u : live) {
-            UnitResult& r = res[u];
-            r.hasStarts = true;
-            r.starts.assign(r.ends.size(), 0);
-            if (mode != EDLIB_MODE_HW) continue;
-            const int m = qlen(u);
-            for (size_t j = 0; j < r.ends.size(); ++j) {
-                const int e = r.ends[j];
-                if (e == -1) continue;                                   // :237-249
-                // reverse query against the reversed prefix target[0..e], prefix mode, k = distance
-                // (:253-257); columns past m+distance cannot score <= distance, so the window stops there
-                const long long win = std::min<long long>((long long)e + 1, (long long)m + r.editDistance);
-                units.push_back(UnitSpec{qoff_[u] + m - 1, m, -1, tbase(u) + e, (int)win, -1, r.editDistance});
-                where.push_back({u, (int)j});
-            }
-        }
-        lap("starts: units");
-        if (!units.empty()) {
-            SolveOut so;
-            if (solveSemiGlobal(EDLIB_MODE_SHW, false, units, so)) return 1;
-            lap("starts: solve");
-            for (size_t i = 0; i < units.size(); ++i) {
-                UnitResult& r = res[where[i].first];
-                // last reported position of the reverse scan (:260); -1 when only the empty prefix qualifies
-                r.starts[where[i].second] = r.ends[where[i].second] - so.last[i];
-            }
-        }
-    }
+            if (qlen(u) > 0 && tlen(u) > 0 && res[u].editDistance >= 0) live_.push_back(u);
+    if (laterPhases && runStartsPhase(res, lap)) return 1;
     lap("run: phase 2 (starts)");
-    // ---- phase 3: alignment path of the first location (edlib.cpp:276-289, 1161-1213)
-    if (cfg_.task == EDLIB_TASK_PATH) {
-        std::vector<PathPiece> jobs; std::vector<int> where;
-        jobs.reserve(live.size()); where.reserve(live.size());
-        for (int u : live) {
-            UnitResult& r = res[u];
-            if (r.ends.empty() || r.hasAlignment) continue;         // (hasAlignment: traced back in phase 1)
-            const int m = qlen(u);
-            const int s = r.starts[0], e = r.ends[0];
-            const int len = e - s + 1;
-            if (len <= 0) {                                                                         // :1168-1175
-                opsOwned_.emplace_back((size_t)m, (uint8_t)EDLIB_EDOP_INSERT);
-                r.opsView = opsOwned_.back().data(); r.opsViewLen = m; r.hasAlignment = true; continue;
-            }
-            jobs.push_back(PathPiece{qoff_[u], m, tbase(u) + s, len, r.editDistance});
-            where.push_back(u);
-        }
-        lap("paths: jobs");
-        if (!jobs.empty()) {
-            std::vector<OpsOut> ops; std::vector<int> st;
-            if (solvePaths(jobs, ops, st)) return 1;
-            for (size_t i = 0; i < jobs.size(); ++i) {
-                UnitResult& r = res[where[i]];
-                if (st[i] != EDLIB_STATUS_OK) { r.status = EDLIB_STATUS_ERROR; continue; }
-                if (!ops[i].own.empty()) {
-                    opsOwned_.emplace_back(std::move(ops[i].own));
-                    r.opsView = opsOwned_.back().data(); r.opsViewLen = (int)opsOwned_.back().size();
-                } else { r.opsView = ops[i].p; r.opsViewLen = ops[i].len; }
-                r.hasAlignment = true;
-            }
-        }
-    }
+    if (cfg_.task == EDLIB_TASK_PATH && runPathsPhase(res, lap)) return 1;
     lap("run: phase 3 (paths)");
     if (ringStepsUsed_) EDLIB_AMD_HIP(hipMemcpyAsync(h_ringSteps_.p, d_ringSteps_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
-    EDLIB_AMD_HIP(hipEventRecord(evRun1_.e, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (endRun()) return 1;
     if (ringStepsUsed_) stats.word_steps += (long long)*reinterpret_cast<unsigned long long*>(h_ringSteps_.p);
-    float ms = 0;
-    EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evRun0_.e, evRun1_.e));
-    stats.run_ms = ms;
-    if (wordStepsPending_) { stats.word_steps += (long long)*reinterpret_cast<unsigned long long*>(h_wordSteps_.p); wordStepsPending_ = false; }
-    for (size_t i = 0; i < scanEventsUsed_; ++i) {
-        float t = 0;
-        EDLIB_AMD_HIP(hipEventElapsedTime(&t, scanEvents_[i].first, scanEvents_[i].second));
-        stats.scan_ms += t;
-    }
-    // algorithmic bytes: target + query + Peq + result header + end locations
-    if ((!readsCollected_ && pairUnits_.empty() && longUnits_.empty() && emptyUnits_.empty()) || flatDone) {
-        // everything is still resident on the device (reads path or flat pairs, TASK_DISTANCE): every unit is priced with
-        // sigma = |target alphabet| and one end location -- a constant of the batch, summed once
-        if (algoBase_ < 0) {
-            algoBase_ = 0;
-            for (int u = 0; u < n_; ++u) {
-                const long long m = qlen(u);
-                algoBase_ += tlen(u) + m + 8LL * (tab_.sigmaT + 1) * ((m + 63) / 64) + 16 + 4;
-            }
-        }
-        stats.algo_bytes = algoBase_;
-        algoDirty_ = false;
-    } else algoDirty_ = true;                   // a walk over every record: done when somebody asks (finishStats)
+    startStats();
     results_.swap(res);
     haveResults_ = true;
     lap("run: stats");
@@ -930,7 +710,245 @@ int Batch::runImpl()
         int c[4];
         if (strandCounts(c)) return 1;
         fprintf(stderr, "[edlib_amd] strands: %d reads, forward %d, reverse %d, both %d, none %d, located %zu\n", outN(), c[0], c[1],
-                c[2], c[3], laterPhases ? live.size() : (size_t)0);
+                c[2], c[3], laterPhases ? live_.size() : (size_t)0);
+    }
+    return 0;
+}
+
+void Batch::resetRecords(std::vector<UnitResult>& res)
+{
+    // TASK_DISTANCE over reads-path units only: nothing is assembled on the host until results() asks for it, so
+    // the per-unit records (160 bytes each) are not even allocated in the timed run
+    const bool lazy = (cfg_.task == EDLIB_TASK_DISTANCE && pairUnits_.empty() && longUnits_.empty() && emptyUnits_.empty() && !groups_.empty()) || flatPairs_;
+    pairsCollected_ = true;
+    deferReset_ = false;
+    deferReadsReset_ = false;
+    if (lazy) { res.clear(); return; }
+    const size_t keep = std::min(res.size(), (size_t)n_);
+    res.resize((size_t)n_);
+    // a batch of pair units only rewrites every record in its finalize loop: the recycled records are blanked there, in
+    // the same pass over the 16 MB of 100,000 records, instead of in a walk of their own (0.4 ms)
+    deferReset_ = emptyUnits_.empty() && groups_.empty() && longUnits_.empty() && !flatPairs_ && pairUnits_.size() == (size_t)n_;
+    // the same for a batch of reads-path units only whose records are assembled in this run (LOC / PATH): collectGroup
+    // visits every one of them (15 ms of a 1M-read run were this walk over 160 MB)
+    deferReadsReset_ = !deferReset_ && cfg_.task != EDLIB_TASK_DISTANCE && emptyUnits_.empty() && pairUnits_.empty() &&
+                       longUnits_.empty() && !flatPairs_ && readUnits_.size() == (size_t)n_;
+    if (!deferReset_ && !deferReadsReset_) for (size_t u = 0; u < keep; ++u) blank_record(res[u]);
+}
+
+// ---- empty sequences: answered without any DP (edlib.cpp:166-184)
+void Batch::answerEmptyUnits(std::vector<UnitResult>& res)
+{
+    const int mode = (int)cfg_.mode;
+    for (int u : emptyUnits_) {
+        UnitResult& r = res[u];
+        const int m = qlen(u), T = tlen(u);
+        if (mode == EDLIB_MODE_NW) { r.editDistance = std::max(m, T); r.ends.assign(1, T - 1); r.hasEnds = true; }
+        else if (mode == EDLIB_MODE_SHW || mode == EDLIB_MODE_HW) { r.editDistance = m; r.ends.assign(1, -1); r.hasEnds = true; }
+        else r.status = EDLIB_STATUS_ERROR;
+    }
+}
+
+// ---- a flat pair batch: everything stays on the device (flatDone_), unless the run falls back to the general path
+int Batch::runFlatPhase(std::vector<UnitResult>& res, Lap& lap)
+{
+    bool fell = false;
+    if (runPairsFlat(fell)) return 1;
+    if (fell) {
+        // something the flat layouts do not hold (more than 16 end locations with starts / paths asked for, a band
+        // level that failed): this run takes the general path from the start
+        res.resize((size_t)n_);
+        for (size_t u = 0; u < res.size(); ++u) blank_record(res[u]);
+    } else { flatDone_ = true; pairsCollected_ = false; lastRunFlat_ = true; }
+    lap("run: flat pairs");
+    return 0;
+}
+
+int Batch::runLongReads(std::vector<UnitResult>& res, Lap& lap)
+{
+    std::vector<int> fb;
+    if (solveLongReads(res, fb)) return 1;
+    lap("run: long reads");
+    // What the filter hands back is mostly unrelated sequence: every row of every column is needed.  Up to 1024 rows
+    // (512 above four target symbols) the lane-per-read full-height kernel does that at ~20 VALU ops per 64 rows and
+    // column with every lane busy; longer queries take kernel W's strips.
+    const int fullMax = syms_ == 4 ? 32 * kMaxLongReadWords4 : (syms_ == 8 ? 32 * kMaxLongReadWords : 0);
+    std::vector<std::vector<int>> byWords(kMaxLongReadWords4 + 1);
+    std::vector<int> tall;
+    for (int u : fb) {
+        if (qlen(u) <= fullMax) byWords[read_group_words(qlen(u))].push_back(u);
+        else if (fullMax > 0) tall.push_back(u);
+        else pairNow_.push_back(u);
+    }
+    for (int w = 1; w <= kMaxLongReadWords4; ++w) {
+        if (byWords[w].empty()) continue;
+        std::unique_ptr<ReadGroup> g;
+        // (many short segments here: a single strip warms up over at most 2047 columns, and 7,930 waves balance themselves
+        // over the SIMDs where one round of 1,014 does not -- 513 / 768 / 1024-base reads: 110 / 125 / 166 ms against
+        // 129 / 144 / 172 with makeGroup's oneRoundWaves; the chained strips of solveTallFull warm up over 2m - 1 columns
+        // of the WHOLE query, which is what makes one round the better plan there)
+        if (makeGroup(byWords[w], w, g)) return 1;
+        stats.path |= 1;
+        if (runGroupScans(*g, true) || runGroupExact(*g) || collectGroup(*g, res)) return 1;
+    }
+    if (!tall.empty()) {                    // taller: strips of fullMax rows on the same kernel, chained through HBM
+        std::vector<int> back;
+        if (solveTallFull(tall, res, back)) return 1;
+        pairNow_.insert(pairNow_.end(), back.begin(), back.end());
+    }
+    lap("run: handed back (full height)");
+    return 0;
+}
+
+int Batch::runPairPhase(std::vector<UnitResult>& res, Lap& lap)
+{
+    const int mode = (int)cfg_.mode;
+    const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
+    // scratch that a run needs per unit lives in the batch: a fresh 10 MB std::vector is an mmap, its page faults
+    // and a munmap (45 MB of them were 5 of the 9 ms a run over 262,144 short pairs took)
+    std::vector<UnitSpec>& units = pairSpecs_;
+    // (the specs depend on the batch only: a run over the same pair units as the last one keeps them)
+    if (pairSpecsFor_ != pairNow_) {
+        units.resize(pairNow_.size());
+        for (size_t i = 0; i < units.size(); ++i) {
+            const int u = pairNow_[i], m = qlen(u);
+            // (SHW: D[m][j] >= j - m > m >= best beyond column 2m: the rest of a long target cannot matter)
+            const int T = scanMode == EDLIB_MODE_SHW ? (int)std::min<long long>(tlen(u), 2LL * m + 1) : tlen(u);
+            units[i] = UnitSpec{qoff_[u], m, 1, tbase(u), T, 1,
+                                (cfg_.k < 0 || cfg_.k > m) ? m : cfg_.k};
+        }
+        pairSpecsFor_ = pairNow_;
+        ++pairSpecsVersion_;
+    }
+    bool fuse = false, prefilled = false;
+    const int* alphaOut = nullptr;
+    // alphabetLength of these units, in the order of pairNow_, once: when the side stream counted exactly these units (null
+    // otherwise).  Taking them waits for the side stream: `e` is what that wait said (a failed one leaves them pending).
+    auto takePairAlphabet = [&](hipError_t& e) -> const int* {
+        e = hipSuccess;
+        if (alphaIsPairsVersion_ != pairSpecsVersion_) { alphaIsPairs_ = alphaUnits_ == pairNow_; alphaIsPairsVersion_ = pairSpecsVersion_; }
+        if (!alphaPending_ || !alphaIsPairs_ || alphaOnHost_) return nullptr;
+        if ((e = hipStreamSynchronize(side_)) != hipSuccess) return nullptr;
+        alphaPending_ = false;
+        return reinterpret_cast<const int*>(alphaPin_.p);
+    };
+    if (scanMode == EDLIB_MODE_NW) {
+        // TASK_PATH over pairs that all stay below the 1 MiB rule (edlib.cpp:1188-1190): the reference scans twice
+        // (distance, then the storing scan with k = distance, :1196-1199); here a unit's first successful level
+        // stores its columns and is traced back right away -- any threshold >= the distance gives the same walk
+        // (every neighbour that could be "one less than here" is <= the distance, hence exact inside the band)
+        fuse = cfg_.task == EDLIB_TASK_PATH && mode == EDLIB_MODE_NW;
+        for (size_t i = 0; fuse && i < units.size(); ++i) fuse = !needs_hirschberg(units[i].qlen, units[i].tlen);
+        fusedOps_.clear();
+        lap("run: pair specs");
+        // What the records of NW units hold besides the distance does not depend on the scan (one end location, T - 1:
+        // edlib.cpp:221-225; alphabetLength from the side stream): a level that takes every unit (runLevelAll) runs this
+        // pass over the 16 MB of 100,000 records while the chip scans, and only the distances are filled in behind it.
+        if (!fuse && mode == EDLIB_MODE_NW) {
+            whileScanning_ = [&]() {
+                hipError_t e;                        // (ignored here, as before: the pass after the scan reports it)
+                const int* counts = takePairAlphabet(e);
+                for (size_t i = 0; i < units.size(); ++i) {
+                    UnitResult& r = res[pairNow_[i]];
+                    if (deferReset_) blank_record(r);
+                    r.hasEnds = true; r.ends.assign(1, units[i].tlen - 1);
+                    if (counts) r.alphabetLength = counts[i];
+                }
+                prefilled = true;
+            };
+        }
+        const int solved = solveGlobalDistances(units, scoreMain_, fuse ? &fusedOps_ : nullptr);
+        whileScanning_ = nullptr;
+        if (solved) return 1;
+        lap("run: global distances");
+        // (alphabetLength of the same units, counted on the side stream meanwhile: set in this pass over the records
+        // instead of in one of its own -- alphabetLengthsEnd() then finds nothing pending)
+        hipError_t e;
+        alphaOut = takePairAlphabet(e);
+        EDLIB_AMD_HIP(e);
+    } else if (solveSemiGlobal(scanMode, true, units, soMain_)) return 1;
+    for (size_t i = 0; i < units.size(); ++i) {
+        UnitResult& r = res[pairNow_[i]];
+        if (deferReset_ && !prefilled) blank_record(r);
+        if (scanMode != EDLIB_MODE_NW)
+            finalize_semiglobal(r, cfg_.k, units[i].qlen, soMain_.score[i],
+                                soMain_.posFlat.data() + soMain_.posStart[i], soMain_.posStart[i + 1] - soMain_.posStart[i]);
+        else if (!prefilled) finalize_global(r, cfg_.k, mode, units[i].tlen, scoreMain_[i]);
+        else if (cfg_.k >= 0 && scoreMain_[i] > cfg_.k) { r.editDistance = -1; r.hasEnds = false; r.ends.clear(); }      // as finalize_global
+        else r.editDistance = scoreMain_[i];
+        if (alphaOut) r.alphabetLength = alphaOut[i];
+        if (fuse && r.editDistance >= 0 && fusedOps_[i].p) { r.opsView = fusedOps_[i].p; r.opsViewLen = fusedOps_[i].len; r.hasAlignment = true; }
+    }
+    return 0;
+}
+
+// ---- phase 2: start locations (edlib.cpp:228-272)
+int Batch::runStartsPhase(std::vector<UnitResult>& res, Lap& lap)
+{
+    std::vector<UnitSpec>& units = startUnits_; std::vector<std::pair<int, int>>& where = startWhere_;   // capacity kept across runs
+    units.clear(); where.clear();
+    units.reserve(live_.size() + live_.size() / 8); where.reserve(live_.size() + live_.size() / 8);
+    for (int u : live_) {
+        UnitResult& r = res[u];
+        r.hasStarts = true;
+        r.starts.assign(r.ends.size(), 0);
+        if (cfg_.mode != EDLIB_MODE_HW) continue;
+        const int m = qlen(u);
+        for (size_t j = 0; j < r.ends.size(); ++j) {
+            const int e = r.ends[j];
+            if (e == -1) continue;                                   // :237-249
+            // reverse query against the reversed prefix target[0..e], prefix mode, k = distance
+            // (:253-257); columns past m+distance cannot score <= distance, so the window stops there
+            const long long win = std::min<long long>((long long)e + 1, (long long)m + r.editDistance);
+            units.push_back(UnitSpec{qoff_[u] + m - 1, m, -1, tbase(u) + e, (int)win, -1, r.editDistance});
+            where.push_back({u, (int)j});
+        }
+    }
+    lap("starts: units");
+    if (!units.empty()) {
+        SolveOut so;
+        if (solveSemiGlobal(EDLIB_MODE_SHW, false, units, so)) return 1;
+        lap("starts: solve");
+        for (size_t i = 0; i < units.size(); ++i) {
+            UnitResult& r = res[where[i].first];
+            // last reported position of the reverse scan (:260); -1 when only the empty prefix qualifies
+            r.starts[where[i].second] = r.ends[where[i].second] - so.last[i];
+        }
+    }
+    return 0;
+}
+
+// ---- phase 3: alignment path of the first location (edlib.cpp:276-289, 1161-1213)
+int Batch::runPathsPhase(std::vector<UnitResult>& res, Lap& lap)
+{
+    std::vector<PathPiece> jobs; std::vector<int> where;
+    jobs.reserve(live_.size()); where.reserve(live_.size());
+    for (int u : live_) {
+        UnitResult& r = res[u];
+        if (r.ends.empty() || r.hasAlignment) continue;         // (hasAlignment: traced back in phase 1)
+        const int m = qlen(u);
+        const int s = r.starts[0], e = r.ends[0];
+        const int len = e - s + 1;
+        if (len <= 0) {                                                                         // :1168-1175
+            opsOwned_.emplace_back((size_t)m, (uint8_t)EDLIB_EDOP_INSERT);
+            r.opsView = opsOwned_.back().data(); r.opsViewLen = m; r.hasAlignment = true; continue;
+        }
+        jobs.push_back(PathPiece{qoff_[u], m, tbase(u) + s, len, r.editDistance});
+        where.push_back(u);
+    }
+    lap("paths: jobs");
+    if (!jobs.empty()) {
+        std::vector<OpsOut> ops; std::vector<int> st;
+        if (solvePaths(jobs, ops, st)) return 1;
+        for (size_t i = 0; i < jobs.size(); ++i) {
+            UnitResult& r = res[where[i]];
+            if (st[i] != EDLIB_STATUS_OK) { r.status = EDLIB_STATUS_ERROR; continue; }
+            if (!ops[i].own.empty()) {
+                opsOwned_.emplace_back(std::move(ops[i].own));
+                r.opsView = opsOwned_.back().data(); r.opsViewLen = (int)opsOwned_.back().size();
+            } else { r.opsView = ops[i].p; r.opsViewLen = ops[i].len; }
+            r.hasAlignment = true;
+        }
     }
     return 0;
 }
@@ -999,6 +1017,24 @@ void Batch::finishStats()
     }
 }
 
+// ... at the end of a run where they cost nothing; else left to finishStats()
+void Batch::startStats()
+{
+    if ((!readsCollected_ && pairNow_.empty() && longUnits_.empty() && emptyUnits_.empty()) || flatDone_) {
+        // everything is still resident on the device (reads path or flat pairs, TASK_DISTANCE): every unit is priced with
+        // sigma = |target alphabet| and one end location -- a constant of the batch, summed once
+        if (algoBase_ < 0) {
+            algoBase_ = 0;
+            for (int u = 0; u < n_; ++u) {
+                const long long m = qlen(u);
+                algoBase_ += tlen(u) + m + 8LL * (tab_.sigmaT + 1) * ((m + 63) / 64) + 16 + 4;
+            }
+        }
+        stats.algo_bytes = algoBase_;
+        algoDirty_ = false;
+    } else algoDirty_ = true;                   // a walk over every record: done when somebody asks (finishStats)
+}
+
 // ------------------------------------------------------------ marshalling
 
 static int* malloc_ints(const LocList& v) {
@@ -1010,8 +1046,8 @@ static int* malloc_ints(const LocList& v) {
 int Batch::results(EdlibAlignResult* out)
 {
     // the failure contract of edlib_amd.h: on ANY failure every entry is blank with status ERROR (nothing to free)
-    const int n_ = outN();                        // (shadows the member: the units the caller sees)
-    for (int u = 0; u < n_; ++u) {
+    const int nOut = outN();                      // the units the caller sees
+    for (int u = 0; u < nOut; ++u) {
         EdlibAlignResult& o = out[u];
         o.status = EDLIB_STATUS_ERROR; o.editDistance = -1; o.endLocations = nullptr; o.startLocations = nullptr;
         o.numLocations = 0; o.alignment = nullptr; o.alignmentLength = 0; o.alphabetLength = 0;
@@ -1062,7 +1098,7 @@ int Batch::results(EdlibAlignResult* out)
     };
     // one malloc per array is the reference's ownership contract (edlib.h:177-205); a million of them are worth a
     // few threads (glibc arenas are per thread; free() of a block from any thread is fine)
-    if (n_ >= 65536) {
+    if (nOut >= 65536) {
         const int nthreads = host_threads(6);
         std::vector<std::thread> th;
         th.reserve(nthreads);
@@ -1071,16 +1107,16 @@ int Batch::results(EdlibAlignResult* out)
             ThreadJoiner join(th);
             try {
                 for (int t = 0; t < nthreads; ++t) {
-                    const int hi = (int)((long long)n_ * (t + 1) / nthreads);
+                    const int hi = (int)((long long)nOut * (t + 1) / nthreads);
                     th.emplace_back(marshal, done, hi);
                     done = hi;
                 }
             } catch (const std::system_error&) {}     // thread limit: this thread does the rest
         }
-        if (done < n_) marshal(done, n_);
-    } else marshal(0, n_);
+        if (done < nOut) marshal(done, nOut);
+    } else marshal(0, nOut);
     if (oom.load()) {                             // all or nothing: the caller gets no half-filled array to clean up
-        for (int u = 0; u < n_; ++u) {
+        for (int u = 0; u < nOut; ++u) {
             EdlibAlignResult& o = out[u];
             free(o.endLocations); free(o.startLocations); free(o.alignment);
             o.endLocations = nullptr; o.startLocations = nullptr; o.alignment = nullptr;
@@ -1098,7 +1134,6 @@ int Batch::buildHostView()
     if (viewReady_) return 0;
     if (ensureCollected()) return 1;
     const size_t n = (size_t)outN();
-    const int n_ = outN();                        // (shadows the member: the units the caller sees)
     long long nloc = 0, naln = 0;
     bool anyStarts = false;
     for (size_t u = 0; u < n; ++u) {
@@ -1123,7 +1158,7 @@ int Batch::buildHostView()
     }
     lo[n] = li; ao[n] = ai;
     view_ = EdlibAmdResultsView{};
-    view_.numUnits = n_; view_.status = st; view_.editDistance = ed; view_.numLocations = nl; view_.alphabetLength = al;
+    view_.numUnits = (int)n; view_.status = st; view_.editDistance = ed; view_.numLocations = nl; view_.alphabetLength = al;
     view_.locOffsets = lo; view_.endLocations = ends; view_.startLocations = anyStarts ? starts : nullptr;
     view_.alnOffsets = ao; view_.alignment = cfg_.task == EDLIB_TASK_PATH ? viewOps_.data() : nullptr;
     viewAlnDev_ = nullptr; viewAlnOffDev_ = nullptr;
@@ -1208,10 +1243,10 @@ int Batch::cigarView(int format, const char** chars, const long long** offsets)
                     const unsigned char op = v.alignment[i];
                     if (op > 3) { set_error("CIGAR: invalid op code"); return 1; }
                     const char ch = letters[op];
-                    long long run = 0;
-                    while (i < a1 && v.alignment[i] <= 3 && letters[v.alignment[i]] == ch) { ++run; ++i; }
+                    long long runLen = 0;
+                    while (i < a1 && v.alignment[i] <= 3 && letters[v.alignment[i]] == ch) { ++runLen; ++i; }
                     char buf[24];
-                    const int w = snprintf(buf, sizeof buf, "%lld", run);
+                    const int w = snprintf(buf, sizeof buf, "%lld", runLen);
                     c.hostChars.insert(c.hostChars.end(), buf, buf + w);
                     c.hostChars.push_back(ch);
                 }

@@ -148,6 +148,9 @@ struct UnitResult {
     int opsViewLen = 0;
 };
 
+struct Lap;                        // (below)
+struct ViewLayout;                 // engine_flat.hip
+
 class Batch {
 public:
     virtual ~Batch();
@@ -204,6 +207,19 @@ private:
     std::vector<int> emptyUnits_, readUnits_, pairUnits_;
     std::vector<int> longUnits_;                 // HW queries above 256 rows against the shared target (long_reads.hip)
     std::vector<int> pairNow_;                   // pair units of the current run: pairUnits_ + what the piece filter handed back
+    // ---- a run: beginRun, the phases in runImpl()'s order, endRun (engine.hip); a hit-list Run has the same frame
+    int beginRun(hipError_t guardStatus);
+    int enqueueWordSteps();
+    int endRun();
+    void resetRecords(std::vector<UnitResult>& res);
+    void answerEmptyUnits(std::vector<UnitResult>& res);
+    int runFlatPhase(std::vector<UnitResult>& res, Lap& lap);
+    int runLongReads(std::vector<UnitResult>& res, Lap& lap);
+    int runPairPhase(std::vector<UnitResult>& res, Lap& lap);
+    int runStartsPhase(std::vector<UnitResult>& res, Lap& lap);
+    int runPathsPhase(std::vector<UnitResult>& res, Lap& lap);
+    void startStats();                           // algo_bytes where the run knows it; finishStats() is its other half
+    bool flatDone_ = false;                      // this run stayed on the flat pair path: no records, no later phases
 
     // ---- reads-per-lane path
     struct ReadGroup {
@@ -409,7 +425,7 @@ private:
     std::vector<int> flatOvfUnit_; std::vector<long long> flatOvfOff_; std::vector<int> flatOvfPos_;   // exact lists of the last run's overflowing units
     PairDesc flatDesc(int u) const;
     int initFlatPairs();
-    int runPairsFlat(bool& overflowed, bool& fellBack);
+    int runPairsFlat(bool& fellBack);
     // flat LOC / PATH (round 4): start locations and paths of a flat batch are found and kept on the device as well.
     // HW starts: one reverse prefix scan per end location, descriptors written by a kernel from the phase-1 results;
     // paths: one storing scan per unit over its window + the traceback into resident op slots.  What the fixed layouts
@@ -430,6 +446,7 @@ private:
     // rings of 32-row words for the storing scans and walks of a flat PATH batch (ring32_kernels.hip)
     bool flatRing32_ = false; int flatG32_ = 8, flatMaxWords_ = 0;
     bool deferReadsReset_ = false;                // this run blanks the recycled records of reads-path units where it fills them (collectGroup)
+    bool deferReset_ = false;                     // ... and of pair units where it fills them (runPairPhase)
     std::vector<int> flatChunkStart_;             // ring32 NW store: unit ranges whose store fits 32-bit offsets (one range = the usual case)
     DevBuf<uint8_t> d_tsym_;
     // the caller-facing arrays of the last run: made on the device for a flat batch (buildFlatView), from the records otherwise
@@ -440,6 +457,7 @@ private:
     DevBuf<int> d_flatOvfAt_, d_flatOvfPool_; DevBuf<long long> d_flatOvfOff_;
     int buildFlatView();
     int buildHostView();
+    int fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln, const char* who, long long& nloc, long long& naln);
     // CIGAR strings of the last run (edlibAlignmentToCigar, edlib.cpp:303-350, over the batch): [0] extended, [1] standard
     struct CigarOut { bool ready = false; PinBuf chars, offs; std::vector<char> hostChars; std::vector<long long> hostOffs; const char* p = nullptr; const long long* off = nullptr; };
     CigarOut cigar_[2];

@@ -273,7 +273,7 @@ int Batch::initFlatPairs()
     return 0;
 }
 
-int Batch::runPairsFlat(bool& overflowed, bool& fellBack)
+int Batch::runPairsFlat(bool& fellBack)
 {
     fellBack = false;
     const int mode = (int)cfg_.mode;
@@ -302,7 +302,6 @@ int Batch::runPairsFlat(bool& overflowed, bool& fellBack)
         else EDLIB_AMD_HIP(launch_scan_pairs_ring(flatRing_, scanMode, flatNwStore_, a, stream_));
         scanTimerStop();
     }
-    overflowed = false;
     if (flatNwStore_) {
         // NW paths: the distance scan was the storing scan (one band level); walk it, and see whether every unit got its answer
         TracebackArgs tb{};
@@ -471,6 +470,57 @@ int Batch::fetchCigars(int f, hipStream_t st)
     return 0;
 }
 
+// The block of a device-made view, the same on the device and in pinned host memory (the members' order IS the layout)
+// (what the host wants first -- the D2H of this head is most of what a DISTANCE batch brings over -- then the device's
+// scratch; status is all zeros for such a batch and is filled in on the host)
+struct ViewLayout {
+    const size_t n, nblocks = (n + 255) / 256;
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t o = at; at = (at + bytes + 63) & ~(size_t)63; return o; }
+    const size_t oTotals = take(16);
+    const size_t oEd = take(n * 4), oNloc = take(n * 4), oAlpha = take(n * 4);
+    const size_t oLocOff = take((n + 1) * 8), oAlnOff = take((n + 1) * 8);
+    const size_t headBytes = at;
+    const size_t oStatus = take(n * 4), oAlnLen = take(n * 4), oBlockLoc = take(nblocks * 8), oBlockAln = take(nblocks * 8);
+    const size_t hostHead = headBytes + ((n * 4 + 63) & ~(size_t)63);     // host: the head + the status array
+    size_t oEnds = 0, oStarts = 0, oAln = 0;      // the view appends its own areas and sets these (oStarts = 0: no start locations)
+    void bind(FlatResultArgs& a, uint8_t* dv) const {                      // what flat_results.hip writes, into the block at dv
+        a.status = reinterpret_cast<int*>(dv + oStatus); a.editDistance = reinterpret_cast<int*>(dv + oEd);
+        a.numLocations = reinterpret_cast<int*>(dv + oNloc); a.alphabetLength = reinterpret_cast<int*>(dv + oAlpha);
+        a.alnLen = reinterpret_cast<int*>(dv + oAlnLen);
+        a.locOff = reinterpret_cast<long long*>(dv + oLocOff); a.alnOff = reinterpret_cast<long long*>(dv + oAlnOff);
+        a.blockLoc = reinterpret_cast<long long*>(dv + oBlockLoc); a.blockAln = reinterpret_cast<long long*>(dv + oBlockAln);
+        a.ends = reinterpret_cast<int*>(dv + oEnds); a.starts = oStarts ? reinterpret_cast<int*>(dv + oStarts) : nullptr;
+        a.aln = dv + oAln;
+    }
+};
+
+// ---- the fixed part (per-unit fields, offsets, totals): waited for, checked, published; then the variable part's block
+int Batch::fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln, const char* who, long long& nloc, long long& naln)
+{
+    uint8_t* const hv = h_view_.p;
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));        // (the caller queued the head copy, and what rides the same wait)
+    const long long* totals = reinterpret_cast<const long long*>(hv + L.oTotals);
+    nloc = totals[0]; naln = totals[1];
+    if (nloc < 0 || nloc > capLoc || naln < 0 || naln > capAln) { set_error("%s: totals out of range", who); return 1; }
+    // the variable part in a pinned block of its own, sized by what there is (a block for everything a batch COULD have --
+    // 146 MB of op slots for 262,144 x 150 bp HW paths that come to 39 MB -- cost its pinning on the first collection)
+    const size_t vStarts = ((size_t)nloc * 4 + 63) & ~(size_t)63, vAln = vStarts + (L.oStarts ? vStarts : 0);
+    const size_t varBytes = vAln + (size_t)naln + 64;
+    if (h_viewVar_.n < varBytes) EDLIB_AMD_HIP(h_viewVar_.alloc(varBytes + varBytes / 8));
+    uint8_t* const hvar = h_viewVar_.p;
+    view_ = EdlibAmdResultsView{};
+    view_.numUnits = (int)L.n;
+    memset(hv + L.headBytes, 0, L.n * 4);                // status: every unit of such a batch is EDLIB_STATUS_OK
+    view_.status = reinterpret_cast<const int*>(hv + L.headBytes); view_.editDistance = reinterpret_cast<const int*>(hv + L.oEd);
+    view_.numLocations = reinterpret_cast<const int*>(hv + L.oNloc); view_.alphabetLength = reinterpret_cast<const int*>(hv + L.oAlpha);
+    view_.locOffsets = reinterpret_cast<const long long*>(hv + L.oLocOff); view_.alnOffsets = reinterpret_cast<const long long*>(hv + L.oAlnOff);
+    view_.endLocations = reinterpret_cast<const int*>(hvar);
+    view_.startLocations = L.oStarts ? reinterpret_cast<const int*>(hvar + vStarts) : nullptr;
+    viewAlnDev_ = nullptr; viewAlnOffDev_ = nullptr;
+    return 0;
+}
+
 // The caller-facing arrays of the last flat run, made on the device (flat_results.hip) and brought over as ONE block of
 // pinned host memory: what edlibAmdBatchResultsView() hands out, what the per-unit records and the malloc'd arrays of the
 // older entry points are copied from.  Valid until the next run().
@@ -481,24 +531,13 @@ int Batch::buildFlatView()
     const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
     const size_t n = (size_t)n_;
     const bool wantStarts = cfg_.task != EDLIB_TASK_DISTANCE, wantPath = flatPaths_;
-    const size_t nblocks = (n + 255) / 256;
     const long long capLoc = (scanMode == EDLIB_MODE_NW ? (long long)n : (long long)n * (kFlatPosCap + 1)) + (flatOvfOff_.empty() ? 0 : flatOvfOff_.back());
     const long long capAln = wantPath ? flatOpsTotal_ : 0;
-    // ---- layout of the block (the same offsets on the device and in pinned host memory)
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 63) & ~(size_t)63; return o; };
-    // (what the host wants first -- the D2H of this head is most of what a DISTANCE batch brings over -- then the device's
-    // scratch; status is all zeros for a flat batch and is filled in on the host)
-    const size_t oTotals = take(16);
-    const size_t oEd = take(n * 4), oNloc = take(n * 4), oAlpha = take(n * 4);
-    const size_t oLocOff = take((n + 1) * 8), oAlnOff = take((n + 1) * 8);
-    const size_t headBytes = at;
-    const size_t oStatus = take(n * 4), oAlnLen = take(n * 4), oBlockLoc = take(nblocks * 8), oBlockAln = take(nblocks * 8);
-    const size_t hostHead = headBytes + ((n * 4 + 63) & ~(size_t)63);     // host: the head + the status array
+    ViewLayout L{n};
     // (device: room for every location / op byte the batch could have; host: the fixed part now, the rest once the totals are known)
-    const size_t oEnds = take((size_t)capLoc * 4), oStarts = wantStarts ? take((size_t)capLoc * 4) : 0, oAln = take((size_t)capAln + 16);
-    EDLIB_AMD_HIP(d_view_.ensure(at));
-    if (h_view_.n < hostHead) EDLIB_AMD_HIP(h_view_.alloc(hostHead));
+    L.oEnds = L.take((size_t)capLoc * 4); L.oStarts = wantStarts ? L.take((size_t)capLoc * 4) : 0; L.oAln = L.take((size_t)capAln + 16);
+    EDLIB_AMD_HIP(d_view_.ensure(L.at));
+    if (h_view_.n < L.hostHead) EDLIB_AMD_HIP(h_view_.alloc(L.hostHead));
     uint8_t* const dv = d_view_.p; uint8_t* const hv = h_view_.p;
     FlatResultArgs a{};
     a.descs = d_flatDescs_.p; a.n = n_; a.mode = scanMode; a.k = cfg_.k; a.wantPath = wantPath ? 1 : 0; a.posCap = kFlatPosCap;
@@ -509,14 +548,8 @@ int Batch::buildFlatView()
     const bool alphaOnDevice = alphaPending_ && !alphaOnHost_ && alphaUnits_.size() == n;
     if (alphaOnDevice) { EDLIB_AMD_HIP(hipStreamWaitEvent(stream_, evB_.e, 0)); a.alphabet = d_alphaOut_.p; }
     if (wantPath) { a.opsLen = d_flatOpsLen_.p; a.opsOff = d_flatOpsOff_.p; a.ops = d_flatOps_.p; }
-    a.status = reinterpret_cast<int*>(dv + oStatus); a.editDistance = reinterpret_cast<int*>(dv + oEd);
-    a.numLocations = reinterpret_cast<int*>(dv + oNloc); a.alphabetLength = reinterpret_cast<int*>(dv + oAlpha);
-    a.alnLen = reinterpret_cast<int*>(dv + oAlnLen);
-    a.locOff = reinterpret_cast<long long*>(dv + oLocOff); a.alnOff = reinterpret_cast<long long*>(dv + oAlnOff);
-    a.blockLoc = reinterpret_cast<long long*>(dv + oBlockLoc); a.blockAln = reinterpret_cast<long long*>(dv + oBlockAln);
-    a.ends = reinterpret_cast<int*>(dv + oEnds); a.starts = wantStarts ? reinterpret_cast<int*>(dv + oStarts) : nullptr;
-    a.aln = dv + oAln;
-    EDLIB_AMD_HIP(launch_flat_results(a, reinterpret_cast<long long*>(dv + oTotals), stream_));
+    L.bind(a, dv);
+    EDLIB_AMD_HIP(launch_flat_results(a, reinterpret_cast<long long*>(dv + L.oTotals), stream_));
     // A PATH batch whose caller asked for CIGARs after an earlier run gets them made NOW, on the side stream, while the op
     // bytes travel: the run-length encoding of both formats (0.16 ms of kernels for config 5) overlaps the 10 MB copy
     // instead of following it, and shares its synchronisations.  (The first request of a session is served on demand.)
@@ -530,28 +563,21 @@ int Batch::buildFlatView()
         // before the totals are known.  When that does not fit the device the view is still good -- the strings are then made
         // on demand (cigarView), sized by what there is.
         for (int f = 0; f < 2 && prefetchCigars; ++f)
-            if (enqueueCigars(f, dv + oAln, reinterpret_cast<const long long*>(dv + oAlnOff), (size_t)(2 * capAln) + n + 64, side_)) {
+            if (enqueueCigars(f, dv + L.oAln, reinterpret_cast<const long long*>(dv + L.oAlnOff), (size_t)(2 * capAln) + n + 64, side_)) {
                 prefetchCigars = false;
                 (void)hipGetLastError();
                 (void)hipStreamSynchronize(side_);               // (whatever of it was queued is over before its buffers are asked for again)
                 d_cigChars_.release(); d_cigChars2_.release();
             }
     }
-    // ---- the fixed part (per-unit fields, offsets, totals), then exactly as many locations / op bytes as there are
-    EDLIB_AMD_HIP(hipMemcpyAsync(hv, dv, headBytes, hipMemcpyDeviceToHost, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    const long long* totals = reinterpret_cast<const long long*>(hv + oTotals);
-    const long long nloc = totals[0], naln = totals[1];
-    if (nloc < 0 || nloc > capLoc || naln < 0 || naln > capAln) { set_error("flat results: totals out of range"); return 1; }
-    // the variable part in a pinned block of its own, sized by what there is (a block for everything a batch COULD have --
-    // 146 MB of op slots for 262,144 x 150 bp HW paths that come to 39 MB -- cost its pinning on the first collection)
-    const size_t vEnds = 0, vStarts = ((size_t)nloc * 4 + 63) & ~(size_t)63, vAln = vStarts + (wantStarts ? vStarts : 0);
-    const size_t varBytes = vAln + (size_t)naln + 64;
-    if (h_viewVar_.n < varBytes) EDLIB_AMD_HIP(h_viewVar_.alloc(varBytes + varBytes / 8));
+    EDLIB_AMD_HIP(hipMemcpyAsync(hv, dv, L.headBytes, hipMemcpyDeviceToHost, stream_));
+    long long nloc, naln;
+    if (fetchViewHead(L, capLoc, capAln, "flat results", nloc, naln)) return 1;
+    const size_t vStarts = ((size_t)nloc * 4 + 63) & ~(size_t)63, vAln = vStarts + (wantStarts ? vStarts : 0);
     uint8_t* const hvar = h_viewVar_.p;
-    if (nloc) EDLIB_AMD_HIP(hipMemcpyAsync(hvar + vEnds, dv + oEnds, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
-    if (nloc && wantStarts) EDLIB_AMD_HIP(hipMemcpyAsync(hvar + vStarts, dv + oStarts, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
-    if (naln) EDLIB_AMD_HIP(hipMemcpyAsync(hvar + vAln, dv + oAln, (size_t)naln, hipMemcpyDeviceToHost, stream_));
+    if (nloc) EDLIB_AMD_HIP(hipMemcpyAsync(hvar, dv + L.oEnds, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
+    if (nloc && wantStarts) EDLIB_AMD_HIP(hipMemcpyAsync(hvar + vStarts, dv + L.oStarts, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
+    if (naln) EDLIB_AMD_HIP(hipMemcpyAsync(hvar + vAln, dv + L.oAln, (size_t)naln, hipMemcpyDeviceToHost, stream_));
     if (prefetchCigars) {                              // the strings: as many characters as the offsets say (the side stream has them)
         EDLIB_AMD_HIP(hipStreamSynchronize(side_));
         for (int f = 0; f < 2; ++f) if (fetchCigars(f, side_)) return 1;
@@ -561,18 +587,10 @@ int Batch::buildFlatView()
     if (alphaPending_ && !alphaOnDevice) { EDLIB_AMD_HIP(hipStreamSynchronize(side_)); }
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     alphaPending_ = false;
-    view_ = EdlibAmdResultsView{};
-    view_.numUnits = n_;
-    memset(hv + headBytes, 0, n * 4);
-    view_.status = reinterpret_cast<const int*>(hv + headBytes); view_.editDistance = reinterpret_cast<const int*>(hv + oEd);
-    view_.numLocations = reinterpret_cast<const int*>(hv + oNloc); view_.alphabetLength = reinterpret_cast<const int*>(hv + oAlpha);
-    view_.locOffsets = reinterpret_cast<const long long*>(hv + oLocOff); view_.alnOffsets = reinterpret_cast<const long long*>(hv + oAlnOff);
-    view_.endLocations = reinterpret_cast<const int*>(hvar + vEnds);
-    view_.startLocations = wantStarts ? reinterpret_cast<const int*>(hvar + vStarts) : nullptr;
     view_.alignment = wantPath ? hvar + vAln : nullptr;
-    viewAlnDev_ = dv + oAln; viewAlnOffDev_ = reinterpret_cast<const long long*>(dv + oAlnOff);
+    viewAlnDev_ = dv + L.oAln; viewAlnOffDev_ = reinterpret_cast<const long long*>(dv + L.oAlnOff);
     // ---- what the device does not know
-    int* alpha = reinterpret_cast<int*>(hv + oAlpha);
+    int* alpha = reinterpret_cast<int*>(hv + L.oAlpha);
     if (!alphaOnDevice) {
         if (alphaOnHost_) {
             // a handful of short sequences: counted on the host from the staging block of init() (alphabetLengthsEnd's rule)
@@ -683,29 +701,21 @@ int Batch::buildReadsView()
     const int mode = (int)cfg_.mode;
     // (both strands: the units of the view are the reads, each the reported one of its two slots -- n of them cross the link)
     const size_t n = (size_t)outN();
-    const size_t nblocks = (n + 255) / 256;
     const bool inPlace = groups_.size() == 1 && !strands_;   // slot == unit (makeGroup lists a group's units in unit order)
     size_t novf = 0; long long ovfTotal = 0;
     for (auto& gp : groups_) { novf += gp->ovfSlots.size(); ovfTotal += gp->ovfOff.empty() ? 0 : gp->ovfOff.back(); }
     const int posCap = mode == EDLIB_MODE_NW ? 0 : kFlatPosCap;
     const long long capLoc = (mode == EDLIB_MODE_NW ? (long long)n : (long long)n * (kFlatPosCap + 1)) + ovfTotal;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 63) & ~(size_t)63; return o; };
-    const size_t oTotals = take(16);
-    const size_t oEd = take(n * 4), oNloc = take(n * 4), oAlpha = take(n * 4);
-    const size_t oLocOff = take((n + 1) * 8), oAlnOff = take((n + 1) * 8);
-    const size_t headBytes = at;
-    const size_t oStatus = take(n * 4), oAlnLen = take(n * 4), oBlockLoc = take(nblocks * 8), oBlockAln = take(nblocks * 8);
-    const size_t oOvfAt = take(novf ? n * 4 : 4), oOvfOff = take((novf + 1) * 8), oOvfUnits = take((novf + 1) * 4);
-    const size_t oOvfPool = take(inPlace ? 4 : (size_t)ovfTotal * 4 + 4);
-    const size_t oUScore = take(inPlace ? 4 : n * 4), oUCount = take(inPlace ? 4 : n * 4), oUQlen = take(inPlace ? 4 : n * 4), oUAlpha = take(inPlace ? 4 : n * 4);
-    const size_t oUPos = take(inPlace ? 4 : n * (size_t)posCap * 4 + 4);
-    const size_t oUStrand = take(strands_ ? 2 * n : 4);
-    const size_t hostHead = headBytes + ((n * 4 + 63) & ~(size_t)63);
-    const size_t oEnds = take((size_t)capLoc * 4), oAln = take(64);
-    EDLIB_AMD_HIP(d_view_.ensure(at));
-    if (h_view_.n < hostHead) EDLIB_AMD_HIP(h_view_.alloc(hostHead));
-    uint8_t* const dv = d_view_.p; uint8_t* const hv = h_view_.p;
+    ViewLayout L{n};
+    const size_t oOvfAt = L.take(novf ? n * 4 : 4), oOvfOff = L.take((novf + 1) * 8), oOvfUnits = L.take((novf + 1) * 4);
+    const size_t oOvfPool = L.take(inPlace ? 4 : (size_t)ovfTotal * 4 + 4);
+    const size_t oUScore = L.take(inPlace ? 4 : n * 4), oUCount = L.take(inPlace ? 4 : n * 4), oUQlen = L.take(inPlace ? 4 : n * 4), oUAlpha = L.take(inPlace ? 4 : n * 4);
+    const size_t oUPos = L.take(inPlace ? 4 : n * (size_t)posCap * 4 + 4);
+    const size_t oUStrand = L.take(strands_ ? 2 * n : 4);
+    L.oEnds = L.take((size_t)capLoc * 4); L.oAln = L.take(64);
+    EDLIB_AMD_HIP(d_view_.ensure(L.at));
+    if (h_view_.n < L.hostHead) EDLIB_AMD_HIP(h_view_.alloc(L.hostHead));
+    uint8_t* const dv = d_view_.p;
     FlatResultArgs a{};
     a.descs = nullptr; a.sharedT = tlen(0); a.alphaBase = tab_.sigmaT;
     a.n = (int)n; a.mode = mode; a.k = cfg_.k; a.wantPath = 0; a.posCap = kFlatPosCap;
@@ -753,31 +763,14 @@ int Batch::buildReadsView()
         EDLIB_AMD_HIP(hipGetLastError());
         a.ovfAt = reinterpret_cast<const int*>(dv + oOvfAt); a.ovfOff = reinterpret_cast<const long long*>(dv + oOvfOff);
     } else a.ovfPos = nullptr;
-    a.status = reinterpret_cast<int*>(dv + oStatus); a.editDistance = reinterpret_cast<int*>(dv + oEd);
-    a.numLocations = reinterpret_cast<int*>(dv + oNloc); a.alphabetLength = reinterpret_cast<int*>(dv + oAlpha);
-    a.alnLen = reinterpret_cast<int*>(dv + oAlnLen);
-    a.locOff = reinterpret_cast<long long*>(dv + oLocOff); a.alnOff = reinterpret_cast<long long*>(dv + oAlnOff);
-    a.blockLoc = reinterpret_cast<long long*>(dv + oBlockLoc); a.blockAln = reinterpret_cast<long long*>(dv + oBlockAln);
-    a.ends = reinterpret_cast<int*>(dv + oEnds); a.starts = nullptr; a.aln = dv + oAln;
-    EDLIB_AMD_HIP(launch_flat_results(a, reinterpret_cast<long long*>(dv + oTotals), stream_));
-    EDLIB_AMD_HIP(hipMemcpyAsync(hv, dv, headBytes, hipMemcpyDeviceToHost, stream_));
+    L.bind(a, dv);
+    EDLIB_AMD_HIP(launch_flat_results(a, reinterpret_cast<long long*>(dv + L.oTotals), stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(h_view_.p, dv, L.headBytes, hipMemcpyDeviceToHost, stream_));
     if (strands_ && n) EDLIB_AMD_HIP(hipMemcpyAsync(h_strand_.p, dv + oUStrand, 2 * n, hipMemcpyDeviceToHost, stream_));
+    long long nloc, naln;
+    if (fetchViewHead(L, capLoc, 0, "reads view", nloc, naln)) return 1;
+    if (nloc) EDLIB_AMD_HIP(hipMemcpyAsync(h_viewVar_.p, dv + L.oEnds, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    const long long nloc = reinterpret_cast<const long long*>(hv + oTotals)[0];
-    if (nloc < 0 || nloc > capLoc) { set_error("reads view: totals out of range"); return 1; }
-    const size_t varBytes = (size_t)nloc * 4 + 64;
-    if (h_viewVar_.n < varBytes) EDLIB_AMD_HIP(h_viewVar_.alloc(varBytes + varBytes / 8));
-    if (nloc) EDLIB_AMD_HIP(hipMemcpyAsync(h_viewVar_.p, dv + oEnds, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    memset(hv + headBytes, 0, n * 4);                    // status: every unit of a reads group is EDLIB_STATUS_OK
-    view_ = EdlibAmdResultsView{};
-    view_.numUnits = (int)n;
-    view_.status = reinterpret_cast<const int*>(hv + headBytes); view_.editDistance = reinterpret_cast<const int*>(hv + oEd);
-    view_.numLocations = reinterpret_cast<const int*>(hv + oNloc); view_.alphabetLength = reinterpret_cast<const int*>(hv + oAlpha);
-    view_.locOffsets = reinterpret_cast<const long long*>(hv + oLocOff); view_.alnOffsets = reinterpret_cast<const long long*>(hv + oAlnOff);
-    view_.endLocations = reinterpret_cast<const int*>(h_viewVar_.p);
-    view_.startLocations = nullptr; view_.alignment = nullptr;
-    viewAlnDev_ = nullptr; viewAlnOffDev_ = nullptr;
     viewReady_ = true;
     if (getenv("EDLIB_AMD_DEBUG")) fprintf(stderr, "[edlib_amd] reads view made on the device: %d units in %zu group(s), %lld locations, %zu lists of the exact pass\n", (int)n, groups_.size(), nloc, novf);
     return 0;

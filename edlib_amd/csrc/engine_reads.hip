@@ -660,8 +660,6 @@ int Batch::runReadHits()
 {
     const int T = tlen(0);
     stats.path |= 1;
-    hitsHaveRun_ = hitsFetched_ = false;
-    EDLIB_AMD_HIP(hipEventRecord(evRun0_.e, stream_));
     if (!d_hitCount_.p) {
         // the batch-wide slot table: the groups' slots one after the other, then a slot per empty unit
         std::vector<int> slotUnit;
@@ -731,22 +729,9 @@ int Batch::runReadHits()
                                               d_hitTmp_.p, d_hitTmp_.n, d_hitOut_.p, stream_));
         EDLIB_AMD_HIP(hipMemcpyAsync(hc, d_hitTotal_.p, sizeof(long long), hipMemcpyDeviceToHost, stream_));
     } else EDLIB_AMD_HIP(hipMemsetAsync(uoffDev, 0, ((size_t)n_ + 1) * sizeof(long long), stream_));
-    if (banded_ && !groups_.empty()) {
-        EDLIB_AMD_HIP(h_wordSteps_.alloc(sizeof(unsigned long long)));
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_wordSteps_.p, d_wordSteps_.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
-    }
-    EDLIB_AMD_HIP(hipEventRecord(evRun1_.e, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (banded_ && !groups_.empty() && enqueueWordSteps()) return 1;
+    if (endRun()) return 1;
     if (total > 0) numHits_ = (long long)*hc;
-    if (banded_ && !groups_.empty()) stats.word_steps += (long long)*reinterpret_cast<unsigned long long*>(h_wordSteps_.p);
-    float ms = 0;
-    EDLIB_AMD_HIP(hipEventElapsedTime(&ms, evRun0_.e, evRun1_.e));
-    stats.run_ms = ms;
-    for (size_t i = 0; i < scanEventsUsed_; ++i) {
-        float t = 0;
-        EDLIB_AMD_HIP(hipEventElapsedTime(&t, scanEvents_[i].first, scanEvents_[i].second));
-        stats.scan_ms += t;
-    }
     stats.algo_bytes = 0;
     hitsHaveRun_ = true;
     return 0;
