@@ -102,6 +102,11 @@ class SelfHits(C.Structure):             # edlib_amd.h EdlibAmdSelfHits
                 ("partner", C.POINTER(C.c_int)), ("editDistance", C.POINTER(C.c_int))]
 
 
+class SelfStrands(C.Structure):          # edlib_amd.h EdlibAmdSelfStrands
+    _fields_ = [("numSequences", C.c_int), ("numPairs", C.c_longlong), ("numHits", C.c_longlong)] + [
+        (f, C.POINTER(C.c_ubyte)) for f in ("pairStrand", "hitStrand", "nearestStrand")]
+
+
 SELF_DISTANCES = 1                        # EDLIB_AMD_SELF_DISTANCES
 SELF_NEAREST = 2                          # EDLIB_AMD_SELF_NEAREST
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
@@ -176,6 +181,12 @@ def lib():
             L.edlibAmdBatchCreateSelfHits.argtypes = L.edlibAmdBatchCreateSelf.argtypes
             L.edlibAmdBatchSelfView.argtypes = [C.c_void_p, C.c_int, C.POINTER(SelfView)]
             L.edlibAmdBatchSelfHits.argtypes = [C.c_void_p, C.POINTER(SelfHits)]
+        if hasattr(L, "edlibAmdBatchSelfStrands"):
+            L.edlibAmdBatchCreateSelfBothStrands.restype = C.c_void_p
+            L.edlibAmdBatchCreateSelfBothStrands.argtypes = L.edlibAmdBatchCreateSelf.argtypes
+            L.edlibAmdBatchCreateSelfHitsBothStrands.restype = C.c_void_p
+            L.edlibAmdBatchCreateSelfHitsBothStrands.argtypes = L.edlibAmdBatchCreateSelf.argtypes
+            L.edlibAmdBatchSelfStrands.argtypes = [C.c_void_p, C.c_int, C.POINTER(SelfStrands)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -795,15 +806,26 @@ class SelfBatch(_Batch):
     ``for i: for j > i: edlib.align(seqs[i], seqs[j], "NW")`` as one resident batch that computes every unordered pair
     once.  condensed() is the int32 vector of the n (n - 1) / 2 distances in scipy's pdist order (-1: above k),
     nearest() the nearest other sequence of each.  hits=True (edlibAmdBatchCreateSelfHits, k >= 0): no vector; hits()
-    lists the pairs i < j within k."""
+    lists the pairs i < j within k.
+    strands="both" (edlibAmdBatchCreateSelfBothStrands / ...HitsBothStrands): pair (i, j), i < j, is the better of seqs[i]
+    and reverse_complement(seqs[i]) against seqs[j] (ties: forward); condensed(), hits() and nearest() describe these
+    combined distances, and strands() says which orientation each reports."""
 
-    def __init__(self, seqs, k=-1, additionalEqualities=None, device=0, hits=False):
+    both_strands = False
+
+    def __init__(self, seqs, k=-1, additionalEqualities=None, device=0, hits=False, strands="forward"):
+        if strands not in ("forward", "both"):
+            raise ValueError("strands must be 'forward' or 'both'")
         sd, so = _pack(seqs)
         cfg, keep = _make_config("NW", "distance", k, additionalEqualities)
         self.numSequences = len(so) - 1
         self.numPairs = self.numSequences * (self.numSequences - 1) // 2
         self.is_hits = bool(hits)
-        create = lib().edlibAmdBatchCreateSelfHits if hits else lib().edlibAmdBatchCreateSelf
+        self.both_strands = strands == "both"
+        if self.both_strands:
+            create = lib().edlibAmdBatchCreateSelfHitsBothStrands if hits else lib().edlibAmdBatchCreateSelfBothStrands
+        else:
+            create = lib().edlibAmdBatchCreateSelfHits if hits else lib().edlibAmdBatchCreateSelf
         h = create(sd.ctypes.data, so.ctypes.data, self.numSequences, cfg, device)
         super().__init__(h, self.numPairs, keep)
 
@@ -840,14 +862,40 @@ class SelfBatch(_Batch):
             out[f] = CrossBatch._arr(getattr(v, f), (n,), copy) if n else np.zeros(0, dtype=np.int32)
         return out
 
+    def strands(self, copy=True, pairs=True):
+        """The strand bytes of a strands="both" batch (edlibAmdBatchSelfStrands), uint8: pairStrand [n (n - 1) / 2] in
+        condensed order -- or hitStrand [numHits], in the order of hits(), for a hits=True batch -- and nearestStrand [n],
+        the byte of the pair (x, nearest[x]).  Bit 0: the pair reports the reverse orientation; bit 1: the other
+        orientation reaches the same distance; 0 where the distance or the nearest is -1.
+        pairs=False: only nearestStrand crosses the link."""
+        if not self.both_strands:
+            raise RuntimeError("edlib_amd: not a both-strand self batch: create it with strands='both'")
+        v = SelfStrands()
+        if lib().edlibAmdBatchSelfStrands(self._h, (SELF_DISTANCES if pairs else 0) | SELF_NEAREST, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: self strands failed: " + last_error())
+
+        def arr(ptr, count):
+            if not ptr or count == 0:
+                return np.zeros(count, dtype=np.uint8)
+            a = np.ctypeslib.as_array(ptr, shape=(count,))
+            return a.copy() if copy else a
+        out = {}
+        if pairs and self.is_hits:
+            out["hitStrand"] = arr(v.hitStrand, int(v.numHits))
+        elif pairs:
+            out["pairStrand"] = arr(v.pairStrand, self.numPairs)
+        out["nearestStrand"] = arr(v.nearestStrand, self.numSequences)
+        return out
+
     def results(self, raw=True):
         raise RuntimeError("edlib_amd: a self batch has no per-unit results: use condensed() / hits() / nearest()")
 
 
-def pdist(seqs, k=-1, additionalEqualities=None):
+def pdist(seqs, k=-1, additionalEqualities=None, strands="forward"):
     """NW edit distances of every pair of seqs in one device batch: the int32 condensed vector of
-    scipy.spatial.distance.pdist's order (squareform() makes the matrix); -1 where a distance is above k >= 0."""
-    b = SelfBatch(seqs, k, additionalEqualities)
+    scipy.spatial.distance.pdist's order (squareform() makes the matrix); -1 where a distance is above k >= 0.
+    strands="both": every pair in its better orientation (SelfBatch)."""
+    b = SelfBatch(seqs, k, additionalEqualities, strands=strands)
     try:
         b.run()
         return b.condensed()
@@ -855,14 +903,17 @@ def pdist(seqs, k=-1, additionalEqualities=None):
         b.close()
 
 
-def pairs_within(seqs, k, additionalEqualities=None):
+def pairs_within(seqs, k, additionalEqualities=None, strands="forward"):
     """Every pair i < j of seqs within k NW edits, each once, and the nearest other sequence of each, in one device batch:
-    the hits() and nearest() arrays of SelfBatch(..., hits=True) in one dictionary."""
-    b = SelfBatch(seqs, k, additionalEqualities, hits=True)
+    the hits() and nearest() arrays of SelfBatch(..., hits=True) in one dictionary; strands="both": in either
+    orientation, with the strands() arrays merged in."""
+    b = SelfBatch(seqs, k, additionalEqualities, hits=True, strands=strands)
     try:
         b.run()
         out = b.hits()
         out.update(b.nearest())
+        if b.both_strands:
+            out.update(b.strands())
         return out
     finally:
         b.close()
@@ -934,6 +985,17 @@ def cross_strands_model(fwd, rev):
              for f in ("editDistance", "numLocations", "endLocation")}
     strand = take_rev.astype(np.uint8) | (((df >= 0) & (df == dr)).astype(np.uint8) << 1)
     return cells, strand
+
+
+def self_strands_model(fwd, rev):
+    """The strand rule of a both-strand self batch stated in numpy (what its pairs must equal): fwd / rev are the
+    condensed distances of seqs[i] and of reverse_complement(seqs[i]) against seqs[j], i < j.  Returns (ed, strand): the
+    combined int32 distances and the uint8 strand bytes, by the rule of cross_strands_model()."""
+    df, dr = np.asarray(fwd, dtype=np.int32), np.asarray(rev, dtype=np.int32)
+    one, none = np.ones_like(df), np.full_like(df, -1)
+    cells, strand = cross_strands_model({"editDistance": df, "numLocations": one, "endLocation": none},
+                                        {"editDistance": dr, "numLocations": one, "endLocation": none})
+    return cells["editDistance"], strand
 
 
 def find_all(queries, target, k, additionalEqualities=None):

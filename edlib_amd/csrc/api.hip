@@ -276,10 +276,10 @@ EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
 }
 
 static EdlibAmdBatch* create_self(const char* where, const char* seqs, const long long* offsets, int numSequences,
-                                  EdlibAlignConfig config, int device, bool hits) {
+                                  EdlibAlignConfig config, int device, bool hits, bool strands = false) {
     return create_batch(where, [&](EdlibAmdBatch& b) {
         b.cross.reset(new CrossBatch);
-        return b.cross->initSelf(seqs, offsets, numSequences, config, device, hits); });
+        return b.cross->initSelf(seqs, offsets, numSequences, config, device, hits, strands); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelf(const char* seqs, const long long* offsets, int numSequences,
@@ -302,6 +302,22 @@ EDLIB_API int edlibAmdBatchSelfHits(EdlibAmdBatch* b, EdlibAmdSelfHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
     if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfHits: not a self batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSelfHits", 1, [&] { return b->cross->selfHitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfBothStrands(const char* seqs, const long long* offsets, int numSequences,
+                                                            EdlibAlignConfig config, int device) {
+    return create_self("edlibAmdBatchCreateSelfBothStrands", seqs, offsets, numSequences, config, device, false, true);
+}
+
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHitsBothStrands(const char* seqs, const long long* offsets,
+                                                                int numSequences, EdlibAlignConfig config, int device) {
+    return create_self("edlibAmdBatchCreateSelfHitsBothStrands", seqs, offsets, numSequences, config, device, true, true);
+}
+
+EDLIB_API int edlibAmdBatchSelfStrands(EdlibAmdBatch* b, int what, EdlibAmdSelfStrands* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfStrands: not a self batch"); return EDLIB_STATUS_ERROR; }
+    return guarded("edlibAmdBatchSelfStrands", 1, [&] { return b->cross->selfStrandsView(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 static EdlibAmdBatch* create_windows(const char* where, const char* queries, const long long* queryOffsets, int numQueries,

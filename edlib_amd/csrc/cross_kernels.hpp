@@ -105,11 +105,13 @@ struct CrossScanArgs {
     // even, numQueries the number of queries (not of slots); one strand byte (bit 0 reverse complement, bit 1 the other
     // strand reaches the same distance) per stored cell [numTargets][numQueries], per appended hit [hitCap] in a hit list
     uint8_t* strand;
-    // self batches (launch_scan_cross_self; DESIGN.md §4h "Self batches"): queries and targets are one set, the targets
+    // self batches (launch_scan_cross_self / launch_scan_cross_self_strands; DESIGN.md §4h "Self batches"): queries and targets are one set, the targets
     // in the order (length, index) -- a sequence's position there is its rank --, the query slots of a group in the same
     // order.  A lane scans cell (slot, ts) only where ts > qrank[slot]; block b takes work item b, the query tile
     // items[3b] against the target tiles [items[3b + 1], items[3b + 1] + items[3b + 2]).  ed is the condensed vector of
     // numQueries sequences (pair (i, j), i < j, at numQueries i - i (i + 1) / 2 + j - i - 1), a hit's key (i << 32) | j.
+    // Both strands: qperm = 2 * sequence + strand, mates in the slots s and s ^ 1 with one qrank, a tile holds qt / 2
+    // sequences; strand is [numPairs] in condensed order, [hitCap] in a hit list.
     const int* qrank;           // [slots] rank of the slot's sequence, -1 for a padding slot
     const int* items;           // [3][numItems] as triples
     int numItems;
@@ -126,12 +128,21 @@ hipError_t launch_scan_cross_strands(int nwords, int syms, int mode, bool hits, 
                                      hipStream_t stream);
 // the self scan (cross_kernels_self.hip): NW only, one block per work item
 hipError_t launch_scan_cross_self(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
+// the self scan over both strands of the row sequence (cross_kernels_self_strands.hip): the combined pair per mate pair
+hipError_t launch_scan_cross_self_strands(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
 // nearest other sequence of each of n sequences from the condensed vector: out [3][n] = nearest, nearestDistance,
 // secondDistance (the key rule of CrossBest2 over all partners on either side of the triangle)
 hipError_t launch_self_nearest_dense(const int* ed, int n, int* out, hipStream_t stream);
 // the same from the best hits of a finished hit list (launch_cross_hits_finish with numQueries = numTargets = n and keys
 // (i << 32) | j, i < j): best [3][n] over the partners above, then [3][n] over the partners below
 hipError_t launch_self_nearest_hits(const int* best, int n, int* out, hipStream_t stream);
+// out [n]: the strand byte of the pair (i, nearest[i]) from the condensed strand vector, 0 where nearest is -1
+hipError_t launch_self_nearest_strand_dense(const uint8_t* pairStrand, const int* nearest, int n, uint8_t* out,
+                                            hipStream_t stream);
+// the same from a finished both-strand hit list: best as for launch_self_nearest_hits, bestStrand [n] over the partners
+// above then [n] over the partners below
+hipError_t launch_self_nearest_strand_hits(const int* best, const uint8_t* bestStrand, int n, uint8_t* out,
+                                           hipStream_t stream);
 // distances computed by other engines into the condensed vector: ed[cell[i]] = vals[i]
 hipError_t launch_self_scatter(const long long* cell, const int* vals, long long n, int* ed, hipStream_t stream);
 // per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are

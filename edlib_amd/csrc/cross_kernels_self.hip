@@ -6,39 +6,13 @@
 
 namespace edlib_amd {
 
-template <int NWD, bool HITS>
-static hipError_t launch_scan_self_w(int syms, const CrossScanArgs& a, hipStream_t stream)
-{
-    const dim3 grid((unsigned)a.numItems);
-    if (syms == 4) hipLaunchKernelGGL((scan_cross_kernel<NWD, 4, 0, HITS, false, true>), grid, dim3(64), 0, stream, a);
-    else if (syms == 8) hipLaunchKernelGGL((scan_cross_kernel<NWD, 8, 0, HITS, false, true>), grid, dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL((scan_cross_kernel<NWD, 16, 0, HITS, false, true>), grid, dim3(64), 0, stream, a);
-    return hipGetLastError();
-}
-
-template <bool HITS>
-static hipError_t launch_scan_self_h(int nwords, int syms, const CrossScanArgs& a, hipStream_t stream)
-{
-    switch (nwords) {
-    case 1: return launch_scan_self_w<1, HITS>(syms, a, stream);
-    case 2: return launch_scan_self_w<2, HITS>(syms, a, stream);
-    case 3: return launch_scan_self_w<3, HITS>(syms, a, stream);
-    case 4: return launch_scan_self_w<4, HITS>(syms, a, stream);
-    case 5: return launch_scan_self_w<5, HITS>(syms, a, stream);
-    case 6: return launch_scan_self_w<6, HITS>(syms, a, stream);
-    case 7: return launch_scan_self_w<7, HITS>(syms, a, stream);
-    case 8: return launch_scan_self_w<8, HITS>(syms, a, stream);
-    default: return hipErrorInvalidValue;
-    }
-}
-
 hipError_t launch_scan_cross_self(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream)
 {
     if (a.numItems == 0) return hipSuccess;
     const int st = cross_scan_args_state(syms, 0, hits, a);
     if (st) return st > 0 ? hipSuccess : hipErrorInvalidValue;
     if (a.numItems < 0 || !a.items || !a.qrank || (!hits && !a.ed)) return hipErrorInvalidValue;
-    return hits ? launch_scan_self_h<true>(nwords, syms, a, stream) : launch_scan_self_h<false>(nwords, syms, a, stream);
+    return hits ? launch_scan_self_h<true, false>(nwords, syms, a, stream) : launch_scan_self_h<false, false>(nwords, syms, a, stream);
 }
 
 // ---------------------------------------------------------------- nearest

@@ -1,7 +1,7 @@
 // cross_scan.hpp -- the lane-per-cell scan of cross batches (DESIGN.md "Cross batches"): the kernel template and its
-// launch ladder, included by the translation units that instantiate it -- cross_kernels.hip (one strand) and
-// cross_kernels_strands.hip (both strands), each half of the cross instantiations, and cross_kernels_self.hip (self
-// batches, NW only).
+// launch ladders, included by the translation units that instantiate it -- cross_kernels.hip (one strand) and
+// cross_kernels_strands.hip (both strands), each half of the cross instantiations, and cross_kernels_self.hip /
+// cross_kernels_self_strands.hip (self batches, NW only, one strand / both).
 #pragma once
 #include "cross_kernels.hpp"
 #include "cross_column.hpp"
@@ -23,15 +23,18 @@ typedef unsigned long long u64;
 // even), so mates are the lanes l and l ^ 1 of the wave: the same target, `live`, n, query length, NW length window and
 // trip count.  Peq staging and the column loop are as for one strand; behind cross_cell_result() the mates exchange their
 // records, the even (forward) lane decides by resolve_strands() and is the only one that stores or appends.
-// SELF (NW, one strand): one set against itself, every unordered pair once (CrossScanArgs::qrank / items).  Block b is
+// SELF (NW): one set against itself, every unordered pair once (CrossScanArgs::qrank / items).  Block b is
 // work item b: a query tile over a run of consecutive target tiles; a lane whose target's rank is not above its query's
 // is not live.  The rows are then the shorter sequence of the pair (ranks ascend with the length), a cell is stored at
 // the condensed index of its two sequence indices or appended with the key (lower << 32) | higher.
+// SELF with STRANDS: a tile of qt slots holds qt / 2 sequences, mates carry the same qrank (so the same `live`), the
+// targets are the forward copies; the row sequence is the one that is reverse-complemented, which the host allows only
+// where that equals the definition by index (engine_self.hip, complement condition).
 template <int NWD, int S, int MODE, bool HITS, bool STRANDS, bool SELF = false>
 __global__ void __launch_bounds__(64)
 scan_cross_kernel(CrossScanArgs a)
 {
-    static_assert(!SELF || (MODE == 0 && !STRANDS), "self batches are NW on one strand");
+    static_assert(!SELF || MODE == 0, "self batches are NW");
     __shared__ u32 s_peq[S * NWD * 64];                 // [symbol][word][query of the tile]
     const int lane = threadIdx.x;
     const int qt = a.qt;
@@ -102,11 +105,13 @@ scan_cross_kernel(CrossScanArgs a)
         const int qout = STRANDS ? q >> 1 : q;
         if (!HITS) {
             if (SELF) {
-                if (live) {
+                if (live && mine) {
                     // the pair's two sequence indices, lower first
-                    const u32 other = (u32)a.tperm[ts];
-                    const size_t slo = (u32)q < other ? (u32)q : other, shi = (u32)q < other ? other : (u32)q;
-                    a.ed[(size_t)a.numQueries * slo - (slo * (slo + 1)) / 2 + (shi - slo - 1)] = ed;
+                    const u32 self = (u32)qout, other = (u32)a.tperm[ts];
+                    const size_t slo = self < other ? self : other, shi = self < other ? other : self;
+                    const size_t at = (size_t)a.numQueries * slo - (slo * (slo + 1)) / 2 + (shi - slo - 1);
+                    a.ed[at] = ed;
+                    if (STRANDS) a.strand[at] = (uint8_t)sbyte;
                 }
                 continue;
             }
@@ -129,8 +134,9 @@ scan_cross_kernel(CrossScanArgs a)
             if (at < a.hitCap) {
                 const u32 other = (u32)a.tperm[ts];
                 // self: the pair's two sequence indices, lower first
-                a.hitKey[at] = SELF ? ((u64)((u32)q < other ? (u32)q : other) << 32) | ((u32)q < other ? other : (u32)q)
-                                    : ((u64)other << 32) | (u32)qout;
+                const u32 self = (u32)qout;
+                a.hitKey[at] = SELF ? ((u64)(self < other ? self : other) << 32) | (self < other ? other : self)
+                                    : ((u64)other << 32) | self;
                 a.hitVal[at] = ed; a.hitVal[a.hitCap + at] = nloc; a.hitVal[2 * a.hitCap + at] = end;
                 if (STRANDS) a.strand[at] = (uint8_t)sbyte;
             }
@@ -172,7 +178,34 @@ static hipError_t launch_scan_cross_h(int nwords, int syms, int mode, const Cros
     }
 }
 
-// the checks both launchers make before the ladder; 1: nothing to launch, -1: bad arguments
+// the self ladder: one block per work item
+template <int NWD, bool HITS, bool STRANDS>
+static hipError_t launch_scan_self_w(int syms, const CrossScanArgs& a, hipStream_t stream)
+{
+    const dim3 grid((unsigned)a.numItems);
+    if (syms == 4) hipLaunchKernelGGL((scan_cross_kernel<NWD, 4, 0, HITS, STRANDS, true>), grid, dim3(64), 0, stream, a);
+    else if (syms == 8) hipLaunchKernelGGL((scan_cross_kernel<NWD, 8, 0, HITS, STRANDS, true>), grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((scan_cross_kernel<NWD, 16, 0, HITS, STRANDS, true>), grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+template <bool HITS, bool STRANDS>
+static hipError_t launch_scan_self_h(int nwords, int syms, const CrossScanArgs& a, hipStream_t stream)
+{
+    switch (nwords) {
+    case 1: return launch_scan_self_w<1, HITS, STRANDS>(syms, a, stream);
+    case 2: return launch_scan_self_w<2, HITS, STRANDS>(syms, a, stream);
+    case 3: return launch_scan_self_w<3, HITS, STRANDS>(syms, a, stream);
+    case 4: return launch_scan_self_w<4, HITS, STRANDS>(syms, a, stream);
+    case 5: return launch_scan_self_w<5, HITS, STRANDS>(syms, a, stream);
+    case 6: return launch_scan_self_w<6, HITS, STRANDS>(syms, a, stream);
+    case 7: return launch_scan_self_w<7, HITS, STRANDS>(syms, a, stream);
+    case 8: return launch_scan_self_w<8, HITS, STRANDS>(syms, a, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// the checks every launcher makes before its ladder; 1: nothing to launch, -1: bad arguments
 static inline int cross_scan_args_state(int syms, int mode, bool hits, const CrossScanArgs& a)
 {
     if (a.numQueryTiles == 0 || a.numSorted == 0) return 1;

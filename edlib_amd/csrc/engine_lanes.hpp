@@ -102,16 +102,20 @@ protected:
 // Its internal shared-target sessions are both-strand batches, its pair session holds both strands of every long query.
 // A self batch (initSelf; engine_self.hip, DESIGN.md §4h "Self batches") is one set against itself, NW only: every
 // unordered pair once, as a condensed vector or an i < j hit list, and the nearest other sequence of each.  nq_ = nt_ = n,
-// the packed targets, the Peq build, the hit list and its finish are the cross batch's own.
+// the packed targets, the Peq build, the hit list and its finish are the cross batch's own.  On both strands (initSelf's
+// strands) a pair is the better of its two sequences as they are and of the lower-indexed one's reverse complement
+// against the other, with a strand byte per pair, per hit and per nearest partner.
 class CrossBatch : public LaneEngine {
 public:
     ~CrossBatch() { closeStream(); }
     int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
              EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false);
-    int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits);
+    int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits,
+                 bool strands = false);
     int run();
     int selfView(int what, EdlibAmdSelfView* out);
     int selfHitsView(EdlibAmdSelfHits* out);
+    int selfStrandsView(int what, EdlibAmdSelfStrands* out);
     bool isSelf() const { return self_; }
     int view(int what, EdlibAmdCrossView* out);
     int hitsView(EdlibAmdCrossHits* out);
@@ -171,6 +175,10 @@ private:
     std::vector<int> selfEmptyVal_;
     DevBuf<int> d_near_;                          // [3][n]: nearest, nearestDistance, secondDistance
     PinnedPart near_;
+    // both-strand self batches: d_smat_ is the condensed strand vector, cellStrand_ its (or the hit list's) pinned part;
+    // d_sbest_ is [2 n] for the hits finish, then [n] the strand byte of every nearest partner (bestStrand_); a pair of
+    // selfOther_ behind the empty ones is the pairs 2c (forward) and 2c + 1 (the lower index reverse-complemented) of
+    // longPairs_
     int runSelf();
     int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
     int scanGroups();

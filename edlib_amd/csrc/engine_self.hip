@@ -5,6 +5,9 @@
 // Run builds the Peq rows, scans the items of every group, lets the internal pair batch take the pairs outside the
 // kernel's envelope, and reduces the nearest other sequence of each on the device.  The pack, the Peq build, the hit
 // list and its finish are the cross batch's own (engine_cross.hip, cross_hits.hip).
+// A both-strand self batch reports for every pair i < j the better of NW(seq i, seq j) and NW(revcomp(seq i), seq j).  The
+// kernel reverse-complements the row sequence, the shorter one, which is the same only under the complement condition
+// below; a set that fails it goes through the pair batch whole, in index order.
 #include "engine_lanes.hpp"
 
 #include <algorithm>
@@ -14,7 +17,22 @@ namespace edlib_amd {
 
 typedef unsigned long long u64;
 
-int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibAlignConfig cfg, int device, bool hits)
+// The complement condition of a both-strand self batch: Eq(c(x), y) <=> Eq(x, c(y)) for all bytes x, y of the set, with
+// c = complement_byte and Eq the batch's match relation.  Then NW(revcomp(a), b) == NW(revcomp(b), a), so the kernel may
+// reverse-complement whichever sequence of a pair it has in the rows.
+static bool complement_symmetric(const Tables& tab)
+{
+    auto eq = [&](int x, int y) { return tab.eq8.empty() ? x == y : tab.eq8[(size_t)x * 256 + y] != 0; };
+    for (int s = 0; s < tab.sigmaT; ++s)
+        for (int t = 0; t < tab.sigmaT; ++t) {
+            const int x = tab.idToByte[s], y = tab.idToByte[t];
+            if (eq(complement_byte((uint8_t)x), y) != eq(x, complement_byte((uint8_t)y))) return false;
+        }
+    return true;
+}
+
+int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibAlignConfig cfg, int device, bool hits,
+                         bool strands)
 {
     if (cfg.task != EDLIB_TASK_DISTANCE) {
         set_error("self batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
@@ -33,10 +51,11 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
         return 1;
     }
     if (n < 0 || (n > 0 && !offIn)) { set_error("bad batch shape"); return 1; }
+    if (strands && n > 0x3fffffff) { set_error("bad both-strand batch shape"); return 1; }
     std::vector<long long> off;
     if (copy_offsets(offIn, n, "sequence", off) || check_device(device)) return 1;      // (the offsets first: edlib_amd.h)
     keep_config(cfg, cfg_, eqs_);
-    device_ = device; nq_ = nt_ = n; hits_ = hits; strands_ = false; self_ = true;
+    device_ = device; nq_ = nt_ = n; hits_ = hits; strands_ = strands; self_ = true;
     const long long base = off[0], bytes = off[n] - base;
     auto len = [&](int i) { return (int)(off[i + 1] - off[i]); };
     const long long numPairs = (long long)n * (n - 1) / 2;
@@ -45,7 +64,7 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     {   // sum over i < j of m_i m_j = ((sum m)^2 - sum m^2) / 2
         unsigned __int128 sq = 0;
         for (int i = 0; i < n; ++i) sq += (unsigned __int128)len(i) * (unsigned __int128)len(i);
-        stats.cells = (long long)((((unsigned __int128)bytes * (unsigned __int128)bytes) - sq) / 2);
+        stats.cells = (long long)((((unsigned __int128)bytes * (unsigned __int128)bytes) - sq) / 2) * (strands ? 2 : 1);
     }
     auto key = [](int i, int j) { return ((u64)(uint32_t)std::min(i, j) << 32) | (uint32_t)std::max(i, j); };
     auto inWindow = [&](int a, int b) {
@@ -54,7 +73,8 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     };
 
     build_tables(tab_, reinterpret_cast<const uint8_t*>(seqs) + base, bytes, eqs_.data(), (int)eqs_.size());
-    const bool wide = tab_.sigmaT > kCrossMaxSyms;
+    // (both strands: a set that fails the complement condition is the pair batch's whole, like one of too many symbols)
+    const bool wide = tab_.sigmaT > kCrossMaxSyms || (strands && !complement_symmetric(tab_));
     syms_ = peq_syms(tab_.sigmaT);
     // the kernel's sequences in the order (length, index); the empty ones are answered here, the others by the pair batch
     std::vector<int> inK, empties, outK;
@@ -70,6 +90,10 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     EDLIB_AMD_HIP(guard.status);
     if (openStream()) return 1;
     EDLIB_AMD_HIP(d_near_.alloc(3 * (size_t)n));
+    if (strands_) {
+        EDLIB_AMD_HIP(d_sbest_.alloc(3 * (size_t)std::max(n, 1)));
+        if (!hits_) EDLIB_AMD_HIP(d_smat_.alloc(std::max<size_t>(cells_, 1)));
+    }
     if (!hits_) EDLIB_AMD_HIP(d_mat_.alloc(std::max<size_t>(cells_, 1)));
     else {
         EDLIB_AMD_HIP(d_best_.alloc(6 * (size_t)n));
@@ -95,10 +119,21 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
             return (int)(std::upper_bound(tl.begin(), tl.end(), (long long)m + cfg.k) - tl.begin());
         };
         // the pool goes up once: the pack reads it as the targets, the Peq build as the queries
-        if (uploadQueries(seqs, off, false) || packTargets(d_qpool_.p, d_qoff_.p, inK, tl)) return 1;
+        if (!strands_) {
+            if (uploadQueries(seqs, off, false) || packTargets(d_qpool_.p, d_qoff_.p, inK, tl)) return 1;
+        } else {
+            // sequence i and its reverse complement are the entries 2 i and 2 i + 1 of the pool: the targets are packed
+            // from the forward copies, and d_tperm_ names sequences again behind the pack
+            std::vector<int> fwd(inK);
+            for (int& i : fwd) i *= 2;
+            if (uploadQueries(seqs, off, true) || packTargets(d_qpool_.p, d_qoff_.p, fwd, tl)) return 1;
+            EDLIB_AMD_HIP(hipMemcpy(d_tperm_.p, inK.data(), inK.size() * sizeof(int), hipMemcpyHostToDevice));
+        }
         EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_));
         EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, tl.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
         // a word group is a run of ranks [r0, r1): its slot s holds rank r0 + s, so the rank rises with the slot
+        // (both strands: the slots 2 s and 2 s + 1 hold rank r0 + s and its reverse complement, `per` = 2 slots a rank)
+        const int per = strands_ ? 2 : 1;
         for (int r0 = 0; r0 < numSorted_;) {
             const int w = (tl[r0] + 31) / 32;
             int r1 = r0;
@@ -106,20 +141,29 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
             const int cnt = r1 - r0;
             std::unique_ptr<Group> g(new Group);
             g->words = w;
-            g->qt = choose_qt(cnt, numSorted_);
-            g->tiles = (cnt + g->qt - 1) / g->qt;
+            g->qt = choose_qt((long long)per * cnt, numSorted_, per);
+            const int spt = g->qt / per;                                   // sequences of a query tile
+            g->tiles = (cnt + spt - 1) / spt;
             const int tpt = 64 / g->qt;
             std::vector<int> perm((size_t)g->tiles * g->qt, -1), rank(perm.size(), -1);      // whole tiles
             for (int s = 0; s < cnt; ++s) {
-                perm[s] = inK[r0 + s]; rank[s] = r0 + s;
-                g->wordSteps += (long long)w * (colsBelow[windowEnd(tl[r0 + s])] - colsBelow[r0 + s + 1]);
+                for (int st = 0; st < per; ++st) { perm[per * s + st] = per * inK[r0 + s] + st; rank[per * s + st] = r0 + s; }
+                g->wordSteps += (long long)per * w * (colsBelow[windowEnd(tl[r0 + s])] - colsBelow[r0 + s + 1]);
+            }
+            if (strands_) {
+                // what the kernel's lane exchange rests on: mates in the slots s and s ^ 1, padding in pairs, an even tile
+                bool ok = !(g->qt & 1) && !(perm.size() & 1);
+                for (size_t sl = 0; ok && sl < perm.size(); sl += 2)
+                    ok = perm[sl] < 0 ? perm[sl + 1] < 0
+                                      : (!(perm[sl] & 1) && perm[sl + 1] == perm[sl] + 1 && rank[sl + 1] == rank[sl]);
+                if (!ok) { set_error("both strands: mates are not in adjacent slots"); return 1; }
             }
             // per query tile the target tiles that hold a wanted cell inside the length window: from the tile of the rank
             // behind the tile's lowest to the tile of the last rank within k of the tile's longest query
             std::vector<int> first(g->tiles), trips(g->tiles);
             long long allTrips = 0;
             for (int t = 0; t < g->tiles; ++t) {
-                const int lo = r0 + t * g->qt + 1, hi = windowEnd(tl[r0 + std::min(cnt, (t + 1) * g->qt) - 1]);
+                const int lo = r0 + t * spt + 1, hi = windowEnd(tl[r0 + std::min(cnt, (t + 1) * spt) - 1]);
                 first[t] = lo / tpt;
                 trips[t] = hi > lo ? (hi - 1) / tpt - first[t] + 1 : 0;
                 allTrips += trips[t];
@@ -157,11 +201,13 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
         }
     {
         PairPool pool;
+        const int per = strands_ ? 2 : 1;
         long long np = 0;
         auto add = [&](int i, int j) {                                // i < j, both with bases
             if (!inWindow(i, j)) return;
-            if (++np > 0x7fffffffLL) return;
-            pool.add(seqs + off[i], len(i), false, seqs + off[j], len(j));
+            if ((np += per) > 0x7fffffffLL) return;
+            // (both strands: the pairs 2c and 2c + 1 of pair c, the second with the lower index's reverse complement)
+            for (int st = 0; st < per; ++st) pool.add(seqs + off[i], len(i), st != 0, seqs + off[j], len(j));
             selfOther_.push_back(key(i, j));
         };
         std::vector<char> isOut(n, 0);
@@ -172,8 +218,10 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
                 add(std::min(i, x), std::max(i, x));
             }
         if (np > 0x7fffffffLL) {
-            set_error("self batch: too many pairs outside the kernel's envelope (more than 2^31 - 1): sequences above %d "
-                      "bases or a set with more than %d symbols", 32 * kCrossMaxQueryWords, kCrossMaxSyms);
+            set_error("self batch: too many pairs outside the kernel's envelope (more than 2^31 - 1%s): sequences above %d "
+                      "bases or a set with more than %d symbols%s", strands_ ? ", both strands counted" : "",
+                      32 * kCrossMaxQueryWords, kCrossMaxSyms,
+                      strands_ ? ", or one whose equalities are not closed under complement" : "");
             return 1;
         }
         if (np > 0) {
@@ -185,6 +233,12 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     if (otherCells_ > 0) {
         EDLIB_AMD_HIP(h_vals_.alloc((size_t)otherCells_ * sizeof(int)));
         std::copy(selfEmptyVal_.begin(), selfEmptyVal_.end(), reinterpret_cast<int*>(h_vals_.p));
+        if (strands_) {
+            // an empty sequence is its own reverse complement: both strands reach the other's length
+            EDLIB_AMD_HIP(h_svals_.alloc((size_t)otherCells_));
+            std::fill(h_svals_.p, h_svals_.p + selfEmptyVal_.size(), (uint8_t)kStrandBoth);
+            if (!hits_) EDLIB_AMD_HIP(d_svals_.alloc((size_t)otherCells_));
+        }
         if (!hits_) {
             std::vector<long long> cellIdx((size_t)otherCells_);
             for (size_t c = 0; c < cellIdx.size(); ++c) {
@@ -203,26 +257,41 @@ int CrossBatch::runSelf()
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
-    if (beginRun(guard.status, {&mat_, &near_, &hitList_})) return 1;
+    if (beginRun(guard.status, {&mat_, &near_, &hitList_, &cellStrand_, &bestStrand_})) return 1;
     if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
     // the pairs outside the length window are visited by no work item and are in no pair batch: -1 from here
-    else if (cfg_.k >= 0 && cells_ > 0) EDLIB_AMD_HIP(hipMemsetAsync(d_mat_.p, 0xff, cells_ * sizeof(int), stream_));
+    else if (cfg_.k >= 0 && cells_ > 0) {
+        EDLIB_AMD_HIP(hipMemsetAsync(d_mat_.p, 0xff, cells_ * sizeof(int), stream_));
+        if (strands_) EDLIB_AMD_HIP(hipMemsetAsync(d_smat_.p, 0, cells_, stream_));
+    }
 
     if (scanRun(groups_, 8, [&] { return scanGroups(); })) return 1;
-    xKey_.clear(); xVal_.clear();
+    xKey_.clear(); xVal_.clear(); xStrand_.clear();
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
+        uint8_t* svals = strands_ ? h_svals_.p : nullptr;
         const size_t ne = selfEmptyVal_.size(), np = (size_t)otherCells_ - ne;
         if (longPairs_) {
             if (longPairs_->run()) return 1;
-            std::vector<int> rec(3 * np);
-            if (gather(*longPairs_, np, rec.data(), nullptr)) return 1;
-            for (size_t c = 0; c < np; ++c) vals[ne + c] = rec[3 * c];
+            const size_t per = strands_ ? 2 : 1;
+            std::vector<int> rec(3 * per * np);
+            if (gather(*longPairs_, per * np, rec.data(), nullptr)) return 1;
+            for (size_t c = 0; c < np; ++c) {
+                if (!strands_) { vals[ne + c] = rec[3 * c]; continue; }
+                // the pairs 2c (forward) and 2c + 1 (reverse complement) of every pair, decided here
+                const int w = resolve_strands(rec[6 * c], rec[6 * c + 3]);
+                vals[ne + c] = rec[6 * c + ((w & kStrandReverse) ? 3 : 0)];
+                svals[ne + c] = (uint8_t)(w & (kStrandReverse | kStrandBoth));
+            }
             addSessionStats(*longPairs_, false);
         }
         if (!hits_) {
             EDLIB_AMD_HIP(hipMemcpyAsync(d_vals_.p, vals, (size_t)otherCells_ * sizeof(int), hipMemcpyHostToDevice, stream_));
             EDLIB_AMD_HIP(launch_self_scatter(d_cells_.p, d_vals_.p, otherCells_, d_mat_.p, stream_));
+            if (strands_) {
+                EDLIB_AMD_HIP(hipMemcpyAsync(d_svals_.p, svals, (size_t)otherCells_, hipMemcpyHostToDevice, stream_));
+                EDLIB_AMD_HIP(launch_cross_scatter_bytes(d_cells_.p, d_svals_.p, otherCells_, d_smat_.p, stream_));
+            }
         } else {
             // their pairs within k behind the kernel's, as [key], [ed][nloc][end] (NW: one location, the last column)
             std::vector<int> e3[3];
@@ -230,6 +299,7 @@ int CrossBatch::runSelf()
                 if (vals[c] == -1) continue;
                 xKey_.push_back(selfOther_[(size_t)c]);
                 e3[0].push_back(vals[c]); e3[1].push_back(1); e3[2].push_back(-1);      // (only the distance is reported)
+                if (strands_) xStrand_.push_back(svals[c]);
             }
             for (int f = 0; f < 3; ++f) xVal_.insert(xVal_.end(), e3[f].begin(), e3[f].end());
         }
@@ -237,8 +307,12 @@ int CrossBatch::runSelf()
     if (hits_) {
         if (finishHits()) return 1;
         EDLIB_AMD_HIP(launch_self_nearest_hits(d_best_.p, nq_, d_near_.p, stream_));
+        if (strands_)
+            EDLIB_AMD_HIP(launch_self_nearest_strand_hits(d_best_.p, d_sbest_.p, nq_, d_sbest_.p + 2 * (size_t)nq_, stream_));
     } else {
         EDLIB_AMD_HIP(launch_self_nearest_dense(d_mat_.p, nq_, d_near_.p, stream_));
+        if (strands_)
+            EDLIB_AMD_HIP(launch_self_nearest_strand_dense(d_smat_.p, d_near_.p, nq_, d_sbest_.p + 2 * (size_t)nq_, stream_));
     }
     return endRun(t0, !groups_.empty());
 }
@@ -283,6 +357,28 @@ int CrossBatch::selfHitsView(EdlibAmdSelfHits* out)
     out->rowOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
     const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
     out->partner = l; out->editDistance = l + (size_t)numHits_;
+    return 0;
+}
+
+int CrossBatch::selfStrandsView(int what, EdlibAmdSelfStrands* out)
+{
+    if (!strands_) {
+        set_error("edlibAmdBatchSelfStrands: not a both-strand self batch (create it with edlibAmdBatchCreateSelfBothStrands "
+                  "or edlibAmdBatchCreateSelfHitsBothStrands)");
+        return 1;
+    }
+    if (!haveRun_) { set_error("self batch: no results (Run it first)"); return 1; }
+    if (what & ~(EDLIB_AMD_SELF_DISTANCES | EDLIB_AMD_SELF_NEAREST)) { set_error("self strands: unknown parts %d", what); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    const size_t pairBytes = hits_ ? (size_t)numHits_ : cells_;
+    if (fetchParts({{what & EDLIB_AMD_SELF_DISTANCES, &cellStrand_, hits_ ? d_hsout_.p : d_smat_.p, pairBytes},
+                    {what & EDLIB_AMD_SELF_NEAREST, &bestStrand_, d_sbest_.p + 2 * (size_t)nq_, (size_t)nq_}})) return 1;
+    memset(out, 0, sizeof *out);
+    out->numSequences = nq_; out->numPairs = (long long)cells_; out->numHits = hits_ ? numHits_ : 0;
+    if (what & EDLIB_AMD_SELF_DISTANCES) (hits_ ? out->hitStrand : out->pairStrand) = cellStrand_.h.p;
+    if (what & EDLIB_AMD_SELF_NEAREST) out->nearestStrand = bestStrand_.h.p;
     return 0;
 }
 

@@ -306,6 +306,45 @@ typedef struct {
 } EdlibAmdSelfHits;
 EDLIB_API int edlibAmdBatchSelfHits(EdlibAmdBatch* batch, EdlibAmdSelfHits* out);
 
+/* Self batches on both strands (sequences of unknown orientation: amplicons, UMIs, barcodes, k-mer sets): the same
+ * arguments, routing and refusals as the two Creates above -- checked before the device is looked for, with the same
+ * messages, and numSequences above 0x3fffffff is refused too -- but pair (i, j), i < j, is the better of
+ *   fwd = edlibAlign(seq i, seq j, config).editDistance  and  rev = edlibAlign(revcomp(seq i), seq j, config).editDistance
+ * by the table above edlibAmdBatchCreateSharedBothStrands: the forward orientation wins a tie, and the pair is -1 where
+ * neither is within k.  revcomp is edlibAmdReverseComplement of the LOWER-INDEXED sequence.  With c the complement of a
+ * byte and Eq the match relation (identity and additionalEqualities, both directions), that equals the reverse complement
+ * of the other sequence against this one exactly when Eq(c(x), y) <=> Eq(x, c(y)) for all bytes x, y present in the set:
+ * true for ACGT, ACGTN, mixed case and IUPAC codes whose equalities are closed under complement; false where U or u is
+ * present (c(U) = A, c(A) = T) and for an equality such as (R, A) without (Y, T).  Create evaluates the condition over
+ * the bytes present.  Where it holds, pairs inside the kernel's envelope run on the self kernel with the two
+ * orientations of a pair in neighbouring lanes (Stats.path bit 3); where it fails, EVERY pair runs through the internal
+ * pair batch in index order (Stats.path bit 3 stays clear), so the answers equal the definition either way.  A pair with
+ * an empty sequence is the other's length on both orientations.
+ * edlibAmdBatchSelfView and edlibAmdBatchSelfHits work unchanged and describe the COMBINED distances; nearest,
+ * nearestDistance and secondDistance run over them with the same key rule.  Stats.cells and Stats.word_steps count both
+ * orientations (twice a one-strand self batch's). */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfBothStrands(
+    const char* seqs, const long long* offsets, int numSequences, EdlibAlignConfig config, int device);
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHitsBothStrands(
+    const char* seqs, const long long* offsets, int numSequences, EdlibAlignConfig config, int device);
+
+/* The strand bytes of the last Run of such a batch (it fails on a one-strand self batch, on every other kind, on NULL
+ * and before the first Run, with the reason in edlibAmdLastError()): pointers into pinned memory the batch owns, valid
+ * until the next Run / Destroy.  A strand byte has bit 0 set when the reverse orientation is reported and bit 1 set when
+ * the other orientation reaches the same distance (then bit 0 is clear: ties go forward); it is 0 where the distance is
+ * -1.  `what`: EDLIB_AMD_SELF_DISTANCES asks for the byte of every pair -- pairStrand of a dense batch, hitStrand of a
+ * hit-list batch --, EDLIB_AMD_SELF_NEAREST for nearestStrand, the byte of the pair (x, nearest[x]), 0 where nearest is
+ * -1; the parts not asked for, and the part of the other form, are NULL. */
+typedef struct {
+    int numSequences;
+    long long numPairs;
+    long long numHits;
+    const unsigned char* pairStrand;    /* [numPairs]     dense batches, condensed order, asked with EDLIB_AMD_SELF_DISTANCES */
+    const unsigned char* hitStrand;     /* [numHits]      hit-list batches, in the order of edlibAmdBatchSelfHits           */
+    const unsigned char* nearestStrand; /* [numSequences] asked with EDLIB_AMD_SELF_NEAREST                                 */
+} EdlibAmdSelfStrands;
+EDLIB_API int edlibAmdBatchSelfStrands(EdlibAmdBatch* batch, int what, EdlibAmdSelfStrands* out);
+
 /* A shared-target batch whose results are, per read, EVERY occurrence within k along the target -- the search question of
  * adapter / primer trimming, concatemer splitting, repeat finding and multi-mapping reads, which no choice of k makes
  * edlibAlign() answer (it keeps the columns of the single best score only).
