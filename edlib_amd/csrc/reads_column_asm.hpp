@@ -14,9 +14,12 @@
 //   * rows built bottom-aligned (RC_SCORE_B, scan_reads_kernel<NWD, 2, true>: the dense last level of HW): the followed row is
 //     bit 31 of the last word in every lane, so its delta is v_lshrrev_b32 / v_ashrrev_i32 by 31 and two v_add_u32, all full
 //     rate, where the per-lane bit `sh` takes two v_bfe and a v_add3_u32.
-// The five-word bottom-aligned column is 54 instructions: 41 full-rate, 13 half-rate (the 5 adds of the carry chain, the 8
-// v_alignbit_b32 of words 1..4), then the compare of the tracking test; the other word counts and layouts keep their chains
-// the same way.  Shifts on register pairs (v_lshl_add_u64 on two words at once): see DESIGN.md 3, the dropped table.
+//   * rows built bottom-aligned, two to five words (RP_*, below): Ph << 1 and Mh << 1 on register pairs, one 64-bit shift
+//     where two v_alignbit_b32 stood.
+// The five-word bottom-aligned column is 52 instructions: 41 full-rate, 11 half-rate (the 5 adds of the carry chain, two
+// v_lshlrev_b64, two v_lshl_add_u64, the two v_alignbit_b32 of word 4), then the compare of the tracking test.  On the
+// alignbit chain (RC_WORD: the other layouts, six to eight words, the banded kernel, the seed verifier) it is 54: 41 + 13
+// (8 v_alignbit_b32 for words 1..4).
 #pragma once
 
 #define RC_HEAD ".p2align 3\n\ts_nop 0\n\t"
@@ -80,6 +83,77 @@
 #define RC_SCORE_BX(c) RC_SCORE_B(c)
 #define RC_COLUMN_ASM(N, WORD0) asm(RC_HEAD WORD0 RC_REST_##N RC_SCORE_X(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score), [sh] "v"(sh))
 #define RC_COLUMN_ASM_B(N, WORD0) asm(RC_HEAD WORD0 RC_REST_##N RC_SCORE_BX(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score))
+// The pair form of the bottom-aligned column (RP_*, scan_reads_kernel<NWD, 2, true> at two to five words): Ph << 1 and Mh << 1
+// on register pairs, two words per half-rate 64-bit shift.  The column is interleaved by pairs, so one pair of ph and one of mh
+// is live at a time:
+//   stage 1 of words 0 and 1 (t, s, xh in ONE temporary; ph0:ph1 and mh0:mh1 in the even-aligned pairs RP_PP, RP_MM);
+//   cp = ph1 >> 31, cm = mh1 >> 31 (v_lshrrev_b32, full rate) into the low halves of RP_CPP / RP_CMM, whose high halves are
+//   standing zeros (the kernel's `zr0`, `zr1`, inputs bound to the odd registers);
+//   v_lshlrev_b64 of both pairs by 1 (HW: a zero comes in from row -1);  stage 2 of words 0 and 1 (it writes no SGPR: the
+//   carry of the add chain lives on);  stage 1 of words 2, 3 and the lone word 4, the score from bit 31 of the last word;
+//   v_alignbit_b32 for word 4 from ph4, ph3 BEFORE pair 2:3 is shifted in place;  v_lshl_add_u64 pair, pair, 1, {cp, 0};
+//   stage 2 of words 2, 3, 4.
+// Five words: 52 instructions, 41 full-rate + 11 half-rate (5 carry-chain adds, 2 v_lshlrev_b64, 2 v_alignbit_b32,
+// 2 v_lshl_add_u64) against 41 + 13; two and three words trade the two v_add_u32 and two v_alignbit_b32 of words 0..1 for
+// two v_lshlrev_b64, four words as five without the lone word.  A third pair would need a second carry pair (the carry out
+// of pair 2:3 has to be taken before the shift that consumes the carry into it): six to eight words keep the alignbit chain.
+// An asm operand cannot name the halves of a 64-bit register, so the pairs are physical registers, bound as operands
+// ("{v56}") so that the compiler knows them; none of these instructions has a wait-state rule against its VALU producers or
+// consumers on gfx950 (plain VALU, no SDWA / op_sel destination, no trans op, no lane select, SGPR carry read by VALU only).
+#define RP_P0 "v56"
+#define RP_P1 "v57"
+#define RP_PP "v[56:57]"
+#define RP_M0 "v58"
+#define RP_M1 "v59"
+#define RP_MM "v[58:59]"
+#define RP_CP "v60"
+#define RP_CPP "v[60:61]"
+#define RP_CM "v62"
+#define RP_CMM "v[62:63]"
+#define RP_PL "%[phl]"
+#define RP_ML "%[mhl]"
+#define RP_W_A(i)          "v_and_b32_e64 %[t], %[e" #i "], %[p" #i "]\n\t"
+#define RP_W_ADD0(i)       "v_add_co_u32_e64 %[t], %[cy], %[t], %[p" #i "]\n\t"
+#define RP_W_ADDC(i)       "v_addc_co_u32_e64 %[t], %[cy], %[t], %[p" #i "], %[cy]\n\t"
+#define RP_W_B(i, PH, MH)  "v_bitop3_b32 %[t], %[t], %[e" #i "], %[p" #i "] bitop3:0xde\n\t" \
+                           "v_bitop3_b32 " PH ", %[m" #i "], %[t], %[p" #i "] bitop3:0xf1\n\t" \
+                           "v_and_b32_e64 " MH ", %[p" #i "], %[t]\n\t"
+#define RP_S1_0(PH, MH)    RP_W_A(0) RP_W_ADD0(0) RP_W_B(0, PH, MH)
+#define RP_S1(i, PH, MH)   RP_W_A(i) RP_W_ADDC(i) RP_W_B(i, PH, MH)
+#define RP_S2(i, PH, MH)   "v_or_b32_e64 %[t], %[e" #i "], %[m" #i "]\n\t" \
+                           "v_bitop3_b32 %[pn" #i "], " MH ", %[t], " PH " bitop3:0xf1\n\t" \
+                           "v_and_b32_e64 %[mn" #i "], " PH ", %[t]\n\t"
+#define RP_CARRY           "v_lshrrev_b32_e64 " RP_CP ", 31, " RP_P1 "\n\t" "v_lshrrev_b32_e64 " RP_CM ", 31, " RP_M1 "\n\t"
+#define RP_SHL             "v_lshlrev_b64 " RP_PP ", 1, " RP_PP "\n\t" "v_lshlrev_b64 " RP_MM ", 1, " RP_MM "\n\t"
+#define RP_SHLADD          "v_lshl_add_u64 " RP_PP ", " RP_PP ", 1, " RP_CPP "\n\t" "v_lshl_add_u64 " RP_MM ", " RP_MM ", 1, " RP_CMM "\n\t"
+#define RP_LONE            "v_alignbit_b32 " RP_PL ", " RP_PL ", " RP_P1 ", 31\n\t" "v_alignbit_b32 " RP_ML ", " RP_ML ", " RP_M1 ", 31\n\t"
+#define RP_SCORE(PH, MH)   "v_lshrrev_b32_e64 %[t], 31, " PH "\n\t" "v_add_u32_e64 %[scoreN], %[score], %[t]\n\t" \
+                           "v_ashrrev_i32_e64 %[t], 31, " MH "\n\t" "v_add_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
+#define RP_PAIR01          RP_S1_0(RP_P0, RP_M0) RP_S1(1, RP_P1, RP_M1)
+#define RP_BODY_2 RP_PAIR01 RP_SCORE(RP_P1, RP_M1) RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1)
+#define RP_BODY_3 RP_PAIR01 RP_S1(2, RP_PL, RP_ML) RP_SCORE(RP_PL, RP_ML) RP_LONE RP_SHL \
+                  RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) RP_S2(2, RP_PL, RP_ML)
+#define RP_BODY_4 RP_PAIR01 RP_CARRY RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) \
+                  RP_S1(2, RP_P0, RP_M0) RP_S1(3, RP_P1, RP_M1) RP_SCORE(RP_P1, RP_M1) RP_SHLADD RP_S2(2, RP_P0, RP_M0) RP_S2(3, RP_P1, RP_M1)
+#define RP_BODY_5 RP_PAIR01 RP_CARRY RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) \
+                  RP_S1(2, RP_P0, RP_M0) RP_S1(3, RP_P1, RP_M1) RP_S1(4, RP_PL, RP_ML) RP_SCORE(RP_PL, RP_ML) RP_LONE RP_SHLADD \
+                  RP_S2(2, RP_P0, RP_M0) RP_S2(3, RP_P1, RP_M1) RP_S2(4, RP_PL, RP_ML)
+#define RP_TEMPS [t] "=&v"(t_), [ph0] "=&{v56}"(ph0_), [ph1] "=&{v57}"(ph1_), [mh0] "=&{v58}"(mh0_), [mh1] "=&{v59}"(mh1_), [cy] "=&s"(cy_)
+#define RP_TEMPS_LONE , [phl] "=&v"(phl_), [mhl] "=&v"(mhl_)
+#define RP_TEMPS_CARRY , [cp] "=&{v60}"(cp_), [cm] "=&{v62}"(cm_)
+#define RP_INS_CARRY , [z0] "{v61}"(zr0), [z1] "{v63}"(zr1)
+#define RP_XT_2
+#define RP_XI_2
+#define RP_XT_3 RP_TEMPS_LONE
+#define RP_XI_3
+#define RP_XT_4 RP_TEMPS_CARRY
+#define RP_XI_4 RP_INS_CARRY
+#define RP_XT_5 RP_TEMPS_LONE RP_TEMPS_CARRY
+#define RP_XI_5 RP_INS_CARRY
+#define RP_COLUMN_ASM_B(N) asm(RC_HEAD RP_BODY_##N : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
+#define RP_COLUMN_DISPATCH_B(NWD) \
+    if constexpr (NWD == 2) RP_COLUMN_ASM_B(2); if constexpr (NWD == 3) RP_COLUMN_ASM_B(3); \
+    if constexpr (NWD == 4) RP_COLUMN_ASM_B(4); if constexpr (NWD == 5) RP_COLUMN_ASM_B(5);
 // the same column without a followed row (the band of scan_reads_banded_kernel below its full height)
 #define RC_COLUMN_ASM_NS(N, WORD0) asm(RC_HEAD WORD0 RC_REST_##N : RC_OUTS_##N, RC_TEMPS : RC_INS_##N)
 #define RC_COLUMN_DISPATCH_NS(NA, WORD0) \

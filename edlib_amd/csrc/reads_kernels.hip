@@ -236,10 +236,10 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 // into one body fed by v_mov/v_cndmask of the Peq row.
 #define EDLIB_AMD_DISPATCH_COLUMN(sym)                                                     \
     switch (sym) {                                                                         \
-        case 0:  column_step<NWD, MODE, BOTTOM>(E0, Pv, Mv, score, sh); asm volatile("; sym0"); break; \
-        case 1:  column_step<NWD, MODE, BOTTOM>(E1, Pv, Mv, score, sh); asm volatile("; sym1"); break; \
-        case 2:  column_step<NWD, MODE, BOTTOM>(E2, Pv, Mv, score, sh); asm volatile("; sym2"); break; \
-        default: column_step<NWD, MODE, BOTTOM>(E3, Pv, Mv, score, sh); asm volatile("; sym3"); break; \
+        case 0:  column_step<NWD, MODE, BOTTOM>(E0, Pv, Mv, score, sh, zr0, zr1); asm volatile("; sym0"); break; \
+        case 1:  column_step<NWD, MODE, BOTTOM>(E1, Pv, Mv, score, sh, zr0, zr1); asm volatile("; sym1"); break; \
+        case 2:  column_step<NWD, MODE, BOTTOM>(E2, Pv, Mv, score, sh, zr0, zr1); asm volatile("; sym2"); break; \
+        default: column_step<NWD, MODE, BOTTOM>(E3, Pv, Mv, score, sh, zr0, zr1); asm volatile("; sym3"); break; \
     }
 
 // Record column `col` if it ties or improves the best bottom-row score
@@ -294,6 +294,14 @@ scan_reads_kernel(const ReadScanArgs a)
         }
     }
     const u32 sh = (u32)(m - 1) & 31u;
+    // the pair form of the bottom-aligned column (reads_column_asm.hpp) adds its carries as (carry, 0) register pairs: the
+    // zeros of the two high halves stand in registers through the whole scan (opaque and apart, so that neither is
+    // rematerialised or copied per column)
+    u32 zr0 = 0, zr1 = 0;
+    if constexpr (BOTTOM && (NWD == 4 || NWD == 5)) {
+        asm volatile("v_mov_b32 %0, 0" : "=v"(zr0));
+        asm volatile("v_mov_b32 %0, 0" : "=v"(zr1));
+    }
     int score = m;
     int best = a.kinit[slot];
     int cnt = 0;

@@ -22,10 +22,20 @@ typedef uint32_t u32;
 // not read, and the delta comes out of two full-rate shifts instead of two v_bfe.
 template <int NWD, int MODE, bool BOTTOM = false>
 __device__ __forceinline__ void column_step(const u32 (&Eq)[NWD], u32 (&Pv)[NWD], u32 (&Mv)[NWD],
-                                            int& score, const u32 sh)
+                                            int& score, const u32 sh, const u32 zr0 = 0, const u32 zr1 = 0)
 {
     static_assert(!BOTTOM || (MODE == 2 && NWD <= 8), "bottom-aligned rows: HW, up to 8 words");
-    if constexpr (BOTTOM) {
+    if constexpr (BOTTOM && NWD >= 2 && NWD <= 5) {
+        // the pair form (reads_column_asm.hpp): zr0, zr1 are the caller's standing zeros, the high halves of the two carry pairs
+        u32 t_, ph0_, ph1_, mh0_, mh1_, phl_, mhl_, cp_, cm_, Pn[NWD], Mn[NWD];
+        int scoreN;
+        unsigned long long cy_;
+        RP_COLUMN_DISPATCH_B(NWD)
+#pragma unroll
+        for (int i = 0; i < NWD; ++i) { Pv[i] = Pn[i]; Mv[i] = Mn[i]; }
+        score = scoreN;
+        return;
+    } else if constexpr (BOTTOM) {
         u32 t_, s_, xh_, ph0_, ph1_, mh0_, mh1_, phs_, mhs_, xv_, Pn[NWD], Mn[NWD];
         int scoreN;
         unsigned long long cy_;
