@@ -4,7 +4,7 @@ Mirrors the reference's Python binding (bindings/python/edlib.pyx): ``align()`` 
 ``getNiceAlignment()`` have the same arguments, defaults, result dictionary and
 error behaviour (edlib.pyx:56-155, 158-238), so the reference's own binding tests
 (bindings/python/test.py) read the same against this package.  Additive:
-``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``align_windows()`` / ``find_all()`` / ``pdist()`` /
+``align_batch()`` / ``align_pairs()`` / ``align_cross()`` / ``align_windows()`` / ``find_all()`` / ``find_all_cross()`` / ``pdist()`` /
 ``pairs_within()``, ``reverse_complement()``, ``cross_strands_model()`` and the resident ``SharedBatch`` / ``BothStrandsBatch`` /
 ``PairBatch`` / ``CrossBatch`` / ``WindowBatch`` / ``SelfBatch`` sessions over include/edlib_amd.h.
 
@@ -70,6 +70,12 @@ class CrossHits(C.Structure):            # edlib_amd.h EdlibAmdCrossHits
     _fields_ = [("numQueries", C.c_int), ("numTargets", C.c_int), ("numHits", C.c_longlong),
                 ("targetOffsets", C.POINTER(C.c_longlong))] + [
         (f, C.POINTER(C.c_int)) for f in ("query", "editDistance", "numLocations", "endLocation")]
+
+
+class CrossOccurrences(C.Structure):     # edlib_amd.h EdlibAmdCrossOccurrences
+    _fields_ = [("numQueries", C.c_int), ("numTargets", C.c_int), ("numHits", C.c_longlong),
+                ("targetOffsets", C.POINTER(C.c_longlong))] + [
+        (f, C.POINTER(C.c_int)) for f in ("query", "firstEnd", "lastEnd", "editDistance", "endLocation", "numLocations")]
 
 
 class CrossStrands(C.Structure):         # edlib_amd.h EdlibAmdCrossStrands
@@ -165,6 +171,10 @@ def lib():
             L.edlibAmdBatchCreateCrossHitsBothStrands.restype = C.c_void_p
             L.edlibAmdBatchCreateCrossHitsBothStrands.argtypes = L.edlibAmdBatchCreateCross.argtypes
             L.edlibAmdBatchCrossStrands.argtypes = [C.c_void_p, C.c_int, C.POINTER(CrossStrands)]
+        if hasattr(L, "edlibAmdBatchCrossOccurrences"):
+            L.edlibAmdBatchCreateCrossOccurrences.restype = C.c_void_p
+            L.edlibAmdBatchCreateCrossOccurrences.argtypes = L.edlibAmdBatchCreateCross.argtypes
+            L.edlibAmdBatchCrossOccurrences.argtypes = [C.c_void_p, C.POINTER(CrossOccurrences)]
         L.edlibAmdBatchCreateWindows.restype = C.c_void_p
         L.edlibAmdBatchCreateWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -608,21 +618,35 @@ class CrossBatch(_Batch):
     hits=True (edlibAmdBatchCreateCrossHits, k >= 0): no matrix; hits() lists the cells within k per target.
     strands="both" (edlibAmdBatchCreateCrossBothStrands / ...HitsBothStrands): every cell is the better of the query and
     its reverse complement against the target (ties: forward); matrix(), hits() and best() describe these combined
-    cells, and strands() says which strand each reports."""
+    cells, and strands() says which strand each reports.
+    occurrences=True (edlibAmdBatchCreateCrossOccurrences; HW, k >= 0, queries up to 256 bases): no matrix and no best
+    hits; occurrences() lists, per target and query, every maximal run of target columns that end an occurrence of the
+    query within k.  Exclusive with hits=True and strands="both"."""
 
     both_strands = False
+    is_occurrences = False
 
     def __init__(self, queries, targets, mode="HW", k=-1, additionalEqualities=None, device=0, hits=False,
-                 strands="forward"):
+                 strands="forward", occurrences=False):
         if strands not in ("forward", "both"):
             raise ValueError("strands must be 'forward' or 'both'")
+        if occurrences:
+            if hits:
+                raise ValueError("occurrences=True and hits=True exclude each other (two kinds of batch)")
+            if strands == "both":
+                raise ValueError("occurrences=True has no both-strand form: pass the reverse complements as queries of their own")
+            if mode != "HW":
+                raise ValueError("occurrences=True needs mode='HW'")
         qd, qo = _pack(queries)
         td, to = _pack(targets)
         cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
         self.numQueries, self.numTargets = len(qo) - 1, len(to) - 1
         self.is_hits = bool(hits)
         self.both_strands = strands == "both"
-        if self.both_strands:
+        self.is_occurrences = bool(occurrences)
+        if self.is_occurrences:
+            create = lib().edlibAmdBatchCreateCrossOccurrences
+        elif self.both_strands:
             create = lib().edlibAmdBatchCreateCrossHitsBothStrands if hits else lib().edlibAmdBatchCreateCrossBothStrands
         else:
             create = lib().edlibAmdBatchCreateCrossHits if hits else lib().edlibAmdBatchCreateCross
@@ -677,6 +701,22 @@ class CrossBatch(_Batch):
         n = int(v.numHits)
         out = {"targetOffsets": self._arr(v.targetOffsets, (self.numTargets + 1,), copy).astype(np.int64, copy=False)}
         for f in ("query", "editDistance", "numLocations", "endLocation"):
+            out[f] = self._arr(getattr(v, f), (n,), copy) if n else np.zeros(0, dtype=np.int32)
+        return out
+
+    def occurrences(self, copy=True):
+        """The occurrences of an occurrences=True batch, grouped by target (CSR), inside a target by ascending query,
+        inside a (target, query) cell by ascending firstEnd: targetOffsets int64 [numTargets + 1] and query / firstEnd /
+        lastEnd / editDistance / endLocation / numLocations int32 [numHits].  copy=False: views of the batch's pinned
+        memory, valid until its next run() / close()."""
+        if not self.is_occurrences:
+            raise RuntimeError("edlib_amd: not an occurrence batch: create it with occurrences=True")
+        v = CrossOccurrences()
+        if lib().edlibAmdBatchCrossOccurrences(self._h, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: cross occurrences failed: " + last_error())
+        n = int(v.numHits)
+        out = {"targetOffsets": self._arr(v.targetOffsets, (self.numTargets + 1,), copy).astype(np.int64, copy=False)}
+        for f in ("query", "firstEnd", "lastEnd", "editDistance", "endLocation", "numLocations"):
             out[f] = self._arr(getattr(v, f), (n,), copy) if n else np.zeros(0, dtype=np.int32)
         return out
 
@@ -1006,6 +1046,17 @@ def find_all(queries, target, k, additionalEqualities=None):
     try:
         b.run()
         return b.hits()
+    finally:
+        b.close()
+
+
+def find_all_cross(queries, targets, k, additionalEqualities=None):
+    """Every occurrence of every query within k edits along every target, in one device batch: the occurrences() arrays of
+    CrossBatch(..., occurrences=True) -- find_all() over many targets (adapters or barcodes against a set of reads)."""
+    b = CrossBatch(queries, targets, "HW", k, additionalEqualities, occurrences=True)
+    try:
+        b.run()
+        return b.occurrences()
     finally:
         b.close()
 

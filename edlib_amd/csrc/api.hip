@@ -25,6 +25,12 @@ static int not_on_windows(EdlibAmdBatch* b, const char* what) {
     return 1;
 }
 
+static int not_on_occurrences(EdlibAmdBatch* b, const char* what) {
+    if (!b->cross || !b->cross->isOccurrences()) return 0;
+    set_error("%s: not available on an occurrence batch (edlibAmdBatchCrossOccurrences has its results)", what);
+    return 1;
+}
+
 static int not_on_self(EdlibAmdBatch* b, const char* what) {
     if (!b->cross || !b->cross->isSelf()) return 0;
     set_error("%s: not available on a self batch (edlibAmdBatchSelfView and edlibAmdBatchSelfHits have its results)", what);
@@ -32,7 +38,7 @@ static int not_on_self(EdlibAmdBatch* b, const char* what) {
 }
 
 static int not_on_cross(EdlibAmdBatch* b, const char* what) {
-    if (not_on_windows(b, what) || not_on_self(b, what)) return 1;
+    if (not_on_windows(b, what) || not_on_self(b, what) || not_on_occurrences(b, what)) return 1;
     if (!b->cross) return 0;
     set_error("%s: not available on a cross batch (edlibAmdBatchCrossView has its results)", what);
     return 1;
@@ -193,6 +199,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedHits(const char* queries, cons
 EDLIB_API int edlibAmdBatchSharedHits(EdlibAmdBatch* b, EdlibAmdReadHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
     if (not_on_windows(b, "edlibAmdBatchSharedHits") || not_on_self(b, "edlibAmdBatchSharedHits")) return EDLIB_STATUS_ERROR;
+    if (not_on_occurrences(b, "edlibAmdBatchSharedHits")) return EDLIB_STATUS_ERROR;
     if (b->cross) { set_error("edlibAmdBatchSharedHits: not a hit-list read batch (a cross batch has edlibAmdBatchCrossHits)"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSharedHits", 1, [&] { return b->impl.hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
@@ -214,11 +221,12 @@ EDLIB_API void edlibAmdReverseComplement(const char* in, int n, char* out) {
 
 static EdlibAmdBatch* create_cross(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
                                    const char* targets, const long long* targetOffsets, int numTargets,
-                                   EdlibAlignConfig config, int device, bool hits, bool strands = false) {
+                                   EdlibAlignConfig config, int device, bool hits, bool strands = false,
+                                   bool occurrences = false) {
     return create_batch(where, [&](EdlibAmdBatch& b) {
         b.cross.reset(new CrossBatch);
         return b.cross->init(queries, queryOffsets, numQueries, targets, targetOffsets, numTargets, config, device, hits,
-                             strands); });
+                             strands, occurrences); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCross(const char* queries, const long long* queryOffsets, int numQueries,
@@ -275,6 +283,25 @@ EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* b, EdlibAmdCrossHits* out) {
     return guarded("edlibAmdBatchCrossHits", 1, [&] { return b->cross->hitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossOccurrences(const char* queries, const long long* queryOffsets,
+                                                             int numQueries, const char* targets,
+                                                             const long long* targetOffsets, int numTargets,
+                                                             EdlibAlignConfig config, int device) {
+    return create_cross("edlibAmdBatchCreateCrossOccurrences", queries, queryOffsets, numQueries, targets, targetOffsets,
+                        numTargets, config, device, /*hits=*/true, false, /*occurrences=*/true);
+}
+
+EDLIB_API int edlibAmdBatchCrossOccurrences(EdlibAmdBatch* b, EdlibAmdCrossOccurrences* out) {
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_windows(b, "edlibAmdBatchCrossOccurrences") || not_on_self(b, "edlibAmdBatchCrossOccurrences")) return EDLIB_STATUS_ERROR;
+    if (!b->cross) {
+        set_error("edlibAmdBatchCrossOccurrences: not an occurrence batch (create it with edlibAmdBatchCreateCrossOccurrences; "
+                  "a hit-list read batch has edlibAmdBatchSharedHits)");
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchCrossOccurrences", 1, [&] { return b->cross->occurrencesView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 static EdlibAmdBatch* create_self(const char* where, const char* seqs, const long long* offsets, int numSequences,
                                   EdlibAlignConfig config, int device, bool hits, bool strands = false) {
     return create_batch(where, [&](EdlibAmdBatch& b) {
@@ -294,12 +321,14 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHits(const char* seqs, const lon
 
 EDLIB_API int edlibAmdBatchSelfView(EdlibAmdBatch* b, int what, EdlibAmdSelfView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_occurrences(b, "edlibAmdBatchSelfView")) return EDLIB_STATUS_ERROR;
     if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfView: not a self batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSelfView", 1, [&] { return b->cross->selfView(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchSelfHits(EdlibAmdBatch* b, EdlibAmdSelfHits* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_occurrences(b, "edlibAmdBatchSelfHits")) return EDLIB_STATUS_ERROR;
     if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfHits: not a self batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSelfHits", 1, [&] { return b->cross->selfHitsView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
@@ -316,6 +345,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHitsBothStrands(const char* seqs
 
 EDLIB_API int edlibAmdBatchSelfStrands(EdlibAmdBatch* b, int what, EdlibAmdSelfStrands* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (not_on_occurrences(b, "edlibAmdBatchSelfStrands")) return EDLIB_STATUS_ERROR;
     if (!b->cross || !b->cross->isSelf()) { set_error("edlibAmdBatchSelfStrands: not a self batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchSelfStrands", 1, [&] { return b->cross->selfStrandsView(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
@@ -349,7 +379,7 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindowsStranded(const char* queries,
 
 EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* b, int what, EdlibAmdWindowView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
-    if (not_on_self(b, "edlibAmdBatchWindowView")) return EDLIB_STATUS_ERROR;
+    if (not_on_self(b, "edlibAmdBatchWindowView") || not_on_occurrences(b, "edlibAmdBatchWindowView")) return EDLIB_STATUS_ERROR;
     if (!b->windows) { set_error("edlibAmdBatchWindowView: not a window batch"); return EDLIB_STATUS_ERROR; }
     return guarded("edlibAmdBatchWindowView", 1, [&] { return b->windows->view(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }

@@ -159,4 +159,34 @@ hipError_t launch_cross_hits_finish(const u64* key, const int* val, long long ca
     return hipGetLastError();
 }
 
+// out [6][n]: query, firstEnd, lastEnd, editDistance, endLocation, numLocations of sorted run i
+__global__ void __launch_bounds__(256)
+cross_occ_gather_kernel(const u64* __restrict__ skey, const u32* __restrict__ sidx, const int* __restrict__ val,
+                        long long cap, long long n, int* __restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long long j = sidx[i];
+    out[i] = (int)(u32)skey[i];
+#pragma unroll
+    for (int f = 0; f < 5; ++f) out[(f + 1) * n + i] = val[f * cap + j];
+}
+
+hipError_t launch_cross_occ_finish(const u64* key, const int* val, long long cap, long long n, int numTargets,
+                                   const u32* idx, u64* skey, u32* sidx, void* tmp, size_t tmpBytes,
+                                   long long* targetOffsets, int* out, hipStream_t stream)
+{
+    if (n > 0) {
+        size_t bytes = tmpBytes;
+        // (a radix sort is stable: equal keys -- the runs of one cell -- keep the order of the list)
+        const hipError_t e = rocprim::radix_sort_pairs(tmp, bytes, key, skey, idx, sidx, (size_t)n, 0u, key_end_bit(numTargets), stream);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(cross_occ_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, skey, sidx, val,
+                           cap, n, out);
+    }
+    hipLaunchKernelGGL(cross_hits_offsets_kernel, dim3((unsigned)((numTargets + 1 + 255) / 256)), dim3(256), 0, stream,
+                       skey, n, numTargets, targetOffsets);
+    return hipGetLastError();
+}
+
 }  // namespace edlib_amd

@@ -126,6 +126,10 @@ hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const Cr
 // the same scan over both strands of every query (cross_kernels_strands.hip): the combined cell per mate pair
 hipError_t launch_scan_cross_strands(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
                                      hipStream_t stream);
+// the occurrence scan (cross_kernels_occ.hip; HW, kcfg >= 0): every maximal run of columns scoring <= kcfg of every cell
+// appended at slot atomicAdd(hitCount) as the key (target << 32) | query and, in hitVal as [5][hitCap], its firstEnd,
+// lastEnd, editDistance, endLocation, numLocations; a cell's runs are appended in ascending column order
+hipError_t launch_scan_cross_occ(int nwords, int syms, const CrossScanArgs& a, int ysplit, hipStream_t stream);
 // the self scan (cross_kernels_self.hip): NW only, one block per work item
 hipError_t launch_scan_cross_self(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
 // the self scan over both strands of the row sequence (cross_kernels_self_strands.hip): the combined pair per mate pair
@@ -174,5 +178,11 @@ hipError_t launch_cross_hits_finish(const unsigned long long* key, const int* va
                                     uint32_t* sidx, void* tmp, size_t tmpBytes, long long* targetOffsets, int* out,
                                     unsigned long long* bkey, int* best, const uint8_t* strand, uint8_t* strandOut,
                                     uint8_t* bestStrand, hipStream_t stream);
+// The n runs of an occurrence batch (key, val [5][cap]) into CSR order: the same stable sort by key -- a cell's runs were
+// appended in ascending column order, so they stay so behind it: (target, query, firstEnd) --, gathered into out [6][n]
+// (query, firstEnd, lastEnd, editDistance, endLocation, numLocations), targetOffsets [nt + 1] as above.
+hipError_t launch_cross_occ_finish(const unsigned long long* key, const int* val, long long cap, long long n,
+                                   int numTargets, const uint32_t* idx, unsigned long long* skey, uint32_t* sidx,
+                                   void* tmp, size_t tmpBytes, long long* targetOffsets, int* out, hipStream_t stream);
 
 }  // namespace edlib_amd

@@ -144,6 +144,121 @@ scan_cross_kernel(CrossScanArgs a)
     }
 }
 
+// ------------------------------------------------------------- occurrences
+
+// Appends the closed run of every lane with `emit` to the occurrence list (CrossScanArgs::hitKey / hitVal as [5][hitCap]:
+// firstEnd, lastEnd, editDistance, endLocation, numLocations): one 64-bit atomic per wave among the lanes that are active
+// at the call (ballot, mbcnt rank, readlane from the leader -- hit_append of reads_scan.hpp), so it holds inside the
+// divergent column loop.  Entries past the capacity are counted, not written.
+__device__ __forceinline__ void occ_append(const CrossScanArgs& a, const bool emit, const u64 key, const int first,
+                                           const int last, const int ed, const int pos, const int cnt)
+{
+    const u64 bal = __builtin_amdgcn_ballot_w64(emit);
+    if (!bal) return;
+    const int lead = __builtin_ctzll(bal);
+    const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
+    u64 base = 0;
+    if (emit && rank == 0) base = atomicAdd(a.hitCount, (u64)__popcll(bal));
+    base = ((u64)(u32)__builtin_amdgcn_readlane((int)(base >> 32), lead) << 32) | (u32)__builtin_amdgcn_readlane((int)base, lead);
+    const u64 at = base + rank;
+    if (emit && at < a.hitCap) {
+        a.hitKey[at] = key;
+        a.hitVal[at] = first; a.hitVal[a.hitCap + at] = last; a.hitVal[2 * a.hitCap + at] = ed;
+        a.hitVal[3 * a.hitCap + at] = pos; a.hitVal[4 * a.hitCap + at] = cnt;
+    }
+}
+
+// Occurrence batches (DESIGN.md §4h "Occurrence batches"; HW, k >= 0): the tiles, the Peq staging, the column and the
+// target walk of scan_cross_kernel, but in place of best / count / first a lane follows its open run of columns scoring
+// <= k in registers (rFirst < 0: none; its least score, the first column holding it, how many columns hold it).  A column
+// within k opens or extends the run, the first column above k behind it closes it, the end of the target closes the last
+// one; closed runs go to the list by occ_append with the key (target << 32) | query.  A wave none of whose active lanes
+// is within k or has a run open pays the compare and one not-taken uniform branch per column; the tracking of the eight
+// columns of a target word follows their arithmetic, so that the branches do not cut the column block into eight.  A lane appends its cell's
+// runs in ascending column order and the counter only grows: a cell's runs ascend by list index.
+template <int NWD, int S>
+__global__ void __launch_bounds__(64)
+scan_cross_occ_kernel(CrossScanArgs a)
+{
+    __shared__ u32 s_peq[S * NWD * 64];                 // [symbol][word][query of the tile]
+    const int lane = threadIdx.x;
+    const int qt = a.qt;
+    const int slot0 = (int)blockIdx.x * qt;
+    {
+        const u32* src = a.peq + (size_t)(slot0 >> 6) * (S * NWD * 64) + (slot0 & 63);
+        for (int i = lane; i < S * NWD * qt; i += 64) {
+            const int r = i / qt;
+            s_peq[i] = src[r * 64 + (i - r * qt)];
+        }
+    }
+    __syncthreads();
+    const int qi = lane & (qt - 1);
+    const int ti = lane / qt;
+    const int tpt = 64 / qt;
+    const int slot = slot0 + qi;
+    const int q = a.qperm[slot];
+    const int m = a.qlen[slot];
+    const int sh = (m - 1) & 31;
+    const int k = a.kcfg;
+    if (q < 0) return;                                  // (no barrier below; the appends are among the active lanes)
+    const int numTT = (a.numSorted + tpt - 1) / tpt;
+    for (int tt = (int)blockIdx.y; tt < numTT; tt += (int)gridDim.y) {      // wave-uniform trip count
+        const int ts = tt * tpt + ti;
+        if (ts >= a.numSorted) continue;
+        const int n = a.tlen[ts];
+        const u64 key = ((u64)(u32)a.tperm[ts] << 32) | (u32)q;
+        if (m == 0) {                                   // the empty query: one run over a non-empty target, no columns
+            occ_append(a, n > 0, key, 0, n - 1, 0, 0, n);
+            continue;
+        }
+        const u32* __restrict__ tp = a.tpk + a.tdw[ts];
+        u32 Pv[NWD], Mv[NWD];
+#pragma unroll
+        for (int d = 0; d < NWD; ++d) { Pv[d] = ~0u; Mv[d] = 0u; }
+        int score = m, rFirst = -1, rMin = 0, rPos = 0, rCnt = 0;
+        auto column = [&](u32 c) { cross_column<NWD, 2>(s_peq + c * (NWD * qt) + qi, qt, Pv, Mv, sh, score); };
+        auto track = [&](int sc, int j) {
+            const bool in = sc <= k;
+            if (__builtin_amdgcn_ballot_w64(in || rFirst >= 0) != 0ull) {       // wave-uniform
+                const bool close = !in && rFirst >= 0;
+                occ_append(a, close, key, rFirst, j - 1, rMin, rPos, rCnt);
+                if (close) rFirst = -1;
+                if (in) {
+                    if (rFirst < 0) { rFirst = j; rMin = sc; rPos = j; rCnt = 1; }
+                    else if (sc < rMin) { rMin = sc; rPos = j; rCnt = 1; }
+                    else if (sc == rMin) ++rCnt;
+                }
+            }
+        };
+        int j = 0;
+        for (; j + 8 <= n; j += 8) {
+            // the eight columns of a target word in one straight-line block (their LDS reads issue ahead of the arithmetic,
+            // as in scan_cross_kernel), their scores kept; then the compare and branch of each
+            u32 w = tp[j >> 3];
+            int sc[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) { column(w & 15u); sc[c] = score; w >>= 4; }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) track(sc[c], j + c);
+        }
+        if (j < n) {
+            u32 w = tp[j >> 3];
+            for (; j < n; ++j) { column(w & 15u); track(score, j); w >>= 4; }
+        }
+        occ_append(a, rFirst >= 0, key, rFirst, n - 1, rMin, rPos, rCnt);        // the run open at the end of the target
+    }
+}
+
+template <int NWD>
+static hipError_t launch_scan_cross_occ_w(int syms, const CrossScanArgs& a, int ysplit, hipStream_t stream)
+{
+    const dim3 grid((unsigned)a.numQueryTiles, (unsigned)ysplit);
+    if (syms == 4) hipLaunchKernelGGL((scan_cross_occ_kernel<NWD, 4>), grid, dim3(64), 0, stream, a);
+    else if (syms == 8) hipLaunchKernelGGL((scan_cross_occ_kernel<NWD, 8>), grid, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((scan_cross_occ_kernel<NWD, 16>), grid, dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
 template <int NWD, int S, bool HITS, bool STRANDS>
 static hipError_t launch_scan_cross_ws(int mode, const CrossScanArgs& a, int ysplit, hipStream_t stream)
 {

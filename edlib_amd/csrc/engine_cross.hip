@@ -8,6 +8,9 @@
 // (cross_hits.hip): sorted into CSR order, target offsets, best hits from the list.
 // A both-strand batch makes the pool of every query and its reverse complement on the device, gives mates
 // the slots s and s ^ 1 of their word group, and keeps a strand byte beside every cell, hit and best hit.
+// An occurrence batch (DESIGN.md §4h "Occurrence batches") is a hit-list batch whose entries are the maximal runs of
+// columns within k of every cell: the occurrence scan appends them, each target outside the kernel's envelope runs through
+// an internal hit-list shared-target session, and the finish sorts the runs into CSR order without best hits.
 #include "engine_lanes.hpp"
 
 #include <algorithm>
@@ -30,8 +33,40 @@ int choose_qt(long long nq, long long nt, int minQt)
 }
 
 int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const char* targets,
-                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device, bool hits, bool strands)
+                     const long long* toffIn, int nt, EdlibAlignConfig cfg, int device, bool hits, bool strands, bool occ)
 {
+    std::vector<long long> qoff, toff;
+    if (occ) {
+        // what an occurrence batch takes (edlib_amd.h): everything else is refused with the limit named, before the device
+        if (cfg.mode != EDLIB_MODE_HW) {
+            set_error("occurrence cross batch: config.mode must be EDLIB_MODE_HW (NW and SHW have no occurrence list)");
+            return 1;
+        }
+        if (cfg.task != EDLIB_TASK_DISTANCE) {
+            set_error("occurrence cross batch: config.task must be EDLIB_TASK_DISTANCE (start locations and paths: align "
+                      "the chosen windows with a pair or window batch)");
+            return 1;
+        }
+        if (cfg.k < 0) { set_error("occurrence cross batch: config.k must be >= 0 (got %d)", cfg.k); return 1; }
+        if (nq < 0 || nt < 0 || (nq > 0 && !qoffIn) || (nt > 0 && !toffIn) || strands || !hits) { set_error("bad batch shape"); return 1; }
+        if (copy_offsets(qoffIn, nq, "query", qoff) || copy_offsets(toffIn, nt, "target", toff)) return 1;
+        for (int q = 0; q < nq; ++q)
+            if (qoff[q + 1] - qoff[q] > 32LL * kCrossMaxQueryWords) {
+                set_error("occurrence cross batch: query %d has %lld bases, the limit is %d", q, qoff[q + 1] - qoff[q],
+                          32 * kCrossMaxQueryWords);
+                return 1;
+            }
+        for (int t = 0; t < nt; ++t) {
+            unsigned long long seen[4] = {0, 0, 0, 0};
+            for (long long j = toff[t]; j < toff[t + 1]; ++j) { const uint8_t c = (uint8_t)targets[j]; seen[c >> 6] |= 1ull << (c & 63); }
+            const int sigma = __builtin_popcountll(seen[0]) + __builtin_popcountll(seen[1]) + __builtin_popcountll(seen[2]) +
+                              __builtin_popcountll(seen[3]);
+            if (sigma > kCrossMaxSyms) {
+                set_error("occurrence cross batch: target %d has %d distinct symbols, the limit is %d", t, sigma, kCrossMaxSyms);
+                return 1;
+            }
+        }
+    }
     if (cfg.task != EDLIB_TASK_DISTANCE) {
         set_error("cross batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
                   "for locations or paths");
@@ -47,9 +82,8 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     if (strands && nq > 0x3fffffff) { set_error("bad both-strand batch shape"); return 1; }
     if (check_device(device)) return 1;
     keep_config(cfg, cfg_, eqs_);
-    device_ = device; nq_ = nq; nt_ = nt; hits_ = hits; strands_ = strands;
-    std::vector<long long> qoff, toff;
-    if (copy_offsets(qoffIn, nq, "query", qoff) || copy_offsets(toffIn, nt, "target", toff)) return 1;
+    device_ = device; nq_ = nq; nt_ = nt; hits_ = hits; strands_ = strands; occ_ = occ;
+    if (!occ && (copy_offsets(qoffIn, nq, "query", qoff) || copy_offsets(toffIn, nt, "target", toff))) return 1;
     const long long tb = toff[0];
     const long long qbytes = qoff[nq] - qoff[0], tbytes = toff[nt] - tb;
     auto qlen = [&](int q) { return (int)(qoff[q + 1] - qoff[q]); };
@@ -74,7 +108,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     if (openStream()) return 1;
-    EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
+    if (!occ_) EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
     if (strands_) {
         EDLIB_AMD_HIP(d_sbest_.alloc(std::max<size_t>((size_t)nt + (size_t)nq, 1)));
         if (!hits_) EDLIB_AMD_HIP(d_smat_.alloc(std::max<size_t>(cells_, 1)));
@@ -86,7 +120,7 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     } else {
         EDLIB_AMD_HIP(d_hcount_.alloc(1)); EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
         EDLIB_AMD_HIP(d_htoff_.alloc((size_t)nt + 1));
-        EDLIB_AMD_HIP(d_bkey_.alloc(2 * ((size_t)nt + (size_t)nq)));
+        if (!occ_) EDLIB_AMD_HIP(d_bkey_.alloc(2 * ((size_t)nt + (size_t)nq)));
         if (growHits(std::max<long long>(1LL << 20, (long long)nq + nt))) return 1;
     }
 
@@ -157,9 +191,9 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         for (int t : outTargets_) {
             std::unique_ptr<Batch> b(new Batch);
             const long long to[2] = {toff[t], toff[t + 1]};
-            if (b->init(queries, qoffIn, nq, targets, to, 1, cfg_, device, strands_)) return 1;
+            if (b->init(queries, qoffIn, nq, targets, to, 1, cfg_, device, strands_, /*hits=*/occ_)) return 1;
             outShared_.push_back(std::move(b));
-            otherCells_ += nq;
+            if (!occ_) otherCells_ += nq;             // (an occurrence batch reads the sessions' own lists)
         }
         if (!longQ.empty() && !inT.empty()) {
             // every long query against every target the kernel takes, as pairs (their bytes replicated per cell)
@@ -238,8 +272,10 @@ int CrossBatch::scanGroups()
             stats.word_steps += g->wordSteps;
             continue;
         }
-        EDLIB_AMD_HIP((strands_ ? launch_scan_cross_strands : launch_scan_cross)(g->words, syms_, (int)cfg_.mode, hits_, a,
-                                                                                 g->ysplit, stream_));
+        if (occ_) EDLIB_AMD_HIP(launch_scan_cross_occ(g->words, syms_, a, g->ysplit, stream_));
+        else
+            EDLIB_AMD_HIP((strands_ ? launch_scan_cross_strands : launch_scan_cross)(g->words, syms_, (int)cfg_.mode, hits_, a,
+                                                                                     g->ysplit, stream_));
         ++stats.scan_launches;
         stats.word_steps += g->wordSteps;
     }
@@ -252,18 +288,19 @@ int CrossBatch::growHits(long long cap)
     hitCap_ = 0;
     size_t tmp = 0;
     hipError_t e = d_hkey_.alloc((size_t)cap);
-    if (e == hipSuccess) e = d_hval_.alloc(3 * (size_t)cap);
+    if (e == hipSuccess) e = d_hval_.alloc((size_t)valPlanes() * (size_t)cap);
     if (e == hipSuccess) e = d_hidx_.alloc((size_t)cap);
     if (e == hipSuccess) e = d_skey_.alloc((size_t)cap);
     if (e == hipSuccess) e = d_sidx_.alloc((size_t)cap);
-    if (e == hipSuccess) e = d_hout_.alloc(4 * (size_t)cap);
+    if (e == hipSuccess) e = d_hout_.alloc(((size_t)valPlanes() + 1) * (size_t)cap);
     if (e == hipSuccess && strands_) e = d_hstrand_.alloc((size_t)cap);
     if (e == hipSuccess && strands_) e = d_hsout_.alloc((size_t)cap);
     if (e == hipSuccess) e = cross_hits_sort_bytes(cap, nt_, &tmp);
     if (e == hipSuccess) e = d_sortTmp_.alloc(tmp);
     if (e == hipSuccess) e = launch_cross_hits_iota(d_hidx_.p, cap, stream_);
     if (e != hipSuccess) {
-        set_error("cross batch: no room on the device for a hit list of %lld hits (%s)", cap, hipGetErrorString(e));
+        set_error("cross batch: no room on the device for a hit list of %lld %s (%s)", cap, occ_ ? "runs" : "hits",
+                  hipGetErrorString(e));
         return 1;
     }
     hitCap_ = cap;
@@ -280,7 +317,8 @@ int CrossBatch::finishHits()
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     const long long kernelHits = (long long)*hc, extra = (long long)xKey_.size(), total = kernelHits + extra;
     if (total > 0xffffffffLL) {
-        set_error("cross batch: %lld hits, more than a hit list holds (2^32 - 1): lower k or split the batch", total);
+        set_error("cross batch: %lld %s, more than a hit list holds (2^32 - 1): lower k or split the batch", total,
+                  occ_ ? "runs" : "hits");
         return 1;
     }
     if (total > hitCap_) {
@@ -291,7 +329,7 @@ int CrossBatch::finishHits()
         const size_t cap = (size_t)hitCap_;
         EDLIB_AMD_HIP(hipMemcpyAsync(d_hkey_.p + kernelHits, xKey_.data(), (size_t)extra * sizeof(unsigned long long),
                                      hipMemcpyHostToDevice, stream_));
-        for (int f = 0; f < 3; ++f)
+        for (int f = 0; f < valPlanes(); ++f)
             EDLIB_AMD_HIP(hipMemcpyAsync(d_hval_.p + f * cap + kernelHits, xVal_.data() + f * (size_t)extra,
                                          (size_t)extra * sizeof(int), hipMemcpyHostToDevice, stream_));
         if (strands_)
@@ -300,10 +338,37 @@ int CrossBatch::finishHits()
     size_t tmp = 0;
     EDLIB_AMD_HIP(cross_hits_sort_bytes(total, nt_, &tmp));
     if (tmp > d_sortTmp_.n) EDLIB_AMD_HIP(d_sortTmp_.alloc(tmp));
-    EDLIB_AMD_HIP(launch_cross_hits_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nq_, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
-                                           d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, d_bkey_.p, d_best_.p,
-                                           strands_ ? d_hstrand_.p : nullptr, d_hsout_.p, d_sbest_.p, stream_));
+    if (occ_)
+        EDLIB_AMD_HIP(launch_cross_occ_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
+                                              d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, stream_));
+    else
+        EDLIB_AMD_HIP(launch_cross_hits_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nq_, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
+                                               d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, d_bkey_.p, d_best_.p,
+                                               strands_ ? d_hstrand_.p : nullptr, d_hsout_.p, d_sbest_.p, stream_));
     numHits_ = total;
+    return 0;
+}
+
+// occurrence batches: each target outside the kernel's envelope through its hit-list session; the session's runs (CSR by
+// query, ascending firstEnd) re-keyed to the target's index, in that order behind what the last session left
+int CrossBatch::runOccurrenceSessions()
+{
+    std::vector<int> e5[5];
+    for (size_t s = 0; s < outShared_.size(); ++s) {
+        Batch& b = *outShared_[s];
+        if (b.run()) return 1;
+        EdlibAmdReadHits rv{};
+        if (b.hitsView(&rv)) return 1;
+        const unsigned long long t = (unsigned long long)(uint32_t)outTargets_[s];
+        for (int q = 0; q < rv.numUnits; ++q)
+            for (long long i = rv.unitOffsets[q]; i < rv.unitOffsets[q + 1]; ++i) {
+                xKey_.push_back((t << 32) | (unsigned long long)(uint32_t)q);
+                e5[0].push_back(rv.firstEnd[i]); e5[1].push_back(rv.lastEnd[i]); e5[2].push_back(rv.editDistance[i]);
+                e5[3].push_back(rv.endLocation[i]); e5[4].push_back(rv.numLocations[i]);
+            }
+        addSessionStats(b, true);
+    }
+    for (int f = 0; f < 5; ++f) xVal_.insert(xVal_.end(), e5[f].begin(), e5[f].end());
     return 0;
 }
 
@@ -321,6 +386,7 @@ int CrossBatch::run()
     if (scanRun(groups_, 8, [&] { return scanGroups(); })) return 1;
     // the other engines run on their own streams meanwhile
     xKey_.clear(); xVal_.clear(); xStrand_.clear();
+    if (occ_ && runOccurrenceSessions()) return 1;
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
         uint8_t* svals = strands_ ? h_svals_.p : nullptr;
@@ -382,6 +448,7 @@ int CrossBatch::run()
 
 int CrossBatch::view(int what, EdlibAmdCrossView* out)
 {
+    if (occ_) { set_error("edlibAmdBatchCrossView: not available on an occurrence batch (edlibAmdBatchCrossOccurrences has its results)"); return 1; }
     if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
     if (what & ~(EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST)) { set_error("cross view: unknown parts %d", what); return 1; }
     if (hits_ && (what & EDLIB_AMD_CROSS_MATRIX)) {
@@ -424,6 +491,7 @@ int CrossBatch::fetchHits(int planes, int rows, size_t* offBytes)
 
 int CrossBatch::hitsView(EdlibAmdCrossHits* out)
 {
+    if (occ_) { set_error("edlibAmdBatchCrossHits: not available on an occurrence batch (edlibAmdBatchCrossOccurrences has its results)"); return 1; }
     if (!hits_) {
         set_error("edlibAmdBatchCrossHits: not a hit-list batch (create it with edlibAmdBatchCreateCrossHits; a dense cross "
                   "batch has edlibAmdBatchCrossView)");
@@ -444,8 +512,32 @@ int CrossBatch::hitsView(EdlibAmdCrossHits* out)
     return 0;
 }
 
+int CrossBatch::occurrencesView(EdlibAmdCrossOccurrences* out)
+{
+    if (!occ_) {
+        set_error("edlibAmdBatchCrossOccurrences: not an occurrence batch (create it with edlibAmdBatchCreateCrossOccurrences; "
+                  "a hit-list cross batch has edlibAmdBatchCrossHits, a dense one edlibAmdBatchCrossView)");
+        return 1;
+    }
+    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    size_t offBytes = 0;
+    if (fetchHits(6, nt_, &offBytes)) return 1;
+    memset(out, 0, sizeof *out);
+    out->numQueries = nq_; out->numTargets = nt_; out->numHits = numHits_;
+    out->targetOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
+    const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
+    const size_t n = (size_t)numHits_;
+    out->query = l; out->firstEnd = l + n; out->lastEnd = l + 2 * n; out->editDistance = l + 3 * n;
+    out->endLocation = l + 4 * n; out->numLocations = l + 5 * n;
+    return 0;
+}
+
 int CrossBatch::strandsView(int what, EdlibAmdCrossStrands* out)
 {
+    if (occ_) { set_error("edlibAmdBatchCrossStrands: not available on an occurrence batch (edlibAmdBatchCrossOccurrences has its results)"); return 1; }
     if (!strands_) {
         set_error("edlibAmdBatchCrossStrands: not a both-strand cross batch (create it with "
                   "edlibAmdBatchCreateCrossBothStrands or edlibAmdBatchCreateCrossHitsBothStrands)");

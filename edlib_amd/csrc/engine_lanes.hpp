@@ -97,6 +97,11 @@ protected:
 // A hit-list batch (hits: k >= 0) keeps no matrix: the scan appends the cells within k to a list, the internal sessions'
 // cells within k are appended behind them, and the list is sorted on the device into CSR order (per target, ascending
 // query) and reduced to the same best hits.
+// An occurrence batch (occ; HW, k >= 0, queries up to 256 bases; DESIGN.md §4h "Occurrence batches") is a hit-list batch
+// whose list holds every maximal run of columns within k of every cell (five ints a run) instead of one record a cell:
+// the scan appends closed runs, each target outside the kernel's envelope runs all queries through one internal hit-list
+// shared-target Batch whose runs are re-keyed and appended behind them, and the list is sorted into CSR order by
+// (target, query, firstEnd).  It keeps no best hits.
 // A both-strand batch (strands) scans every query and its reverse complement (made on the device at init)
 // as the mates of neighbouring slots; a cell is the better strand's record (resolve_strands) and a strand byte beside it.
 // Its internal shared-target sessions are both-strand batches, its pair session holds both strands of every long query.
@@ -109,7 +114,7 @@ class CrossBatch : public LaneEngine {
 public:
     ~CrossBatch() { closeStream(); }
     int init(const char* queries, const long long* qoff, int nq, const char* targets, const long long* toff, int nt,
-             EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false);
+             EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false, bool occ = false);
     int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits,
                  bool strands = false);
     int run();
@@ -120,7 +125,9 @@ public:
     int view(int what, EdlibAmdCrossView* out);
     int hitsView(EdlibAmdCrossHits* out);
     int strandsView(int what, EdlibAmdCrossStrands* out);
+    int occurrencesView(EdlibAmdCrossOccurrences* out);
     bool bothStrands() const { return strands_; }
+    bool isOccurrences() const { return occ_; }
 
 private:
     struct Group : LaneGroup {                    // slots: whole tiles, padded with -1
@@ -152,6 +159,10 @@ private:
     long long hitCap_ = 0, numHits_ = 0;
     DevBuf<unsigned long long> d_hcount_, d_hkey_, d_skey_;
     DevBuf<int> d_hval_, d_hout_;                 // [3][hitCap_] as appended; [4][numHits_] in CSR order
+    // occurrence batches (hits_ is set too): an entry is a run, d_hval_ [5][hitCap_] (firstEnd, lastEnd, editDistance,
+    // endLocation, numLocations), d_hout_ [6][numHits_] (query in front), xVal_ five planes; no best hits
+    bool occ_ = false;
+    int valPlanes() const { return occ_ ? 5 : 3; }
     DevBuf<uint32_t> d_hidx_, d_sidx_;
     DevBuf<uint8_t> d_sortTmp_;
     DevBuf<long long> d_htoff_;                   // [nt + 1]
@@ -181,6 +192,7 @@ private:
     // longPairs_
     int runSelf();
     int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
+    int runOccurrenceSessions();                  // the internal hit-list sessions' runs into xKey_ / xVal_
     int scanGroups();
     int growHits(long long cap);
     int finishHits();

@@ -212,6 +212,55 @@ typedef struct {
 } EdlibAmdCrossHits;
 EDLIB_API int edlibAmdBatchCrossHits(EdlibAmdBatch* batch, EdlibAmdCrossHits* out);
 
+/* A cross batch whose results are, per (query, target) cell, EVERY occurrence of the query within k along the target (an
+ * occurrence batch) -- adapter and primer trimming, a barcode at both ends of a read, concatemer splitting, repeats of a
+ * motif per read: the questions of a hit-list read batch asked of many targets at once, which a hit-list cross
+ * batch (one best cell per pair) and any number of edlibAlign() calls with a k do not answer.
+ * For query q of length m and target t of length n, D[j] (j = 0 .. n-1) is the HW bottom-row score -- the least edit
+ * distance between q and any substring of t that ends at column j (the empty one counts: D[j] <= m; there is no column
+ * -1 here).  An OCCURRENCE is a maximal run [firstEnd, lastEnd] of consecutive columns with D[j] <= k; its editDistance
+ * is the least D of the run, endLocation the lowest column of the run holding it, numLocations the number of columns of
+ * the run holding it; all columns are relative to the target's own first base.  The least editDistance over a cell's
+ * occurrences equals edlibAlign(q, t, HW, k).editDistance, a cell without one is -1 there (n > 0), and every non-negative
+ * end location of that call lies in an occurrence of that distance.  k >= m gives one occurrence [0, n-1] per non-empty
+ * target; an empty query occurs once in every non-empty target: [0, n-1], distance 0, endLocation 0, numLocations n; an
+ * empty target holds no occurrence.
+ * Accepted: config.mode == EDLIB_MODE_HW, config.task == EDLIB_TASK_DISTANCE, config.k >= 0, every query at most 256
+ * bases, every target with at most 16 distinct symbols of its own; additionalEqualities allowed; numQueries == 0 and
+ * numTargets == 0 are valid.  Anything else (NW / SHW, EDLIB_TASK_LOC / EDLIB_TASK_PATH, k < 0, a longer query, a target
+ * with more symbols, a bad shape or bad offsets) returns NULL with the limit named in edlibAmdLastError(); all of these
+ * are checked before the device is looked for.
+ * Targets up to 65,536 bases run on the cross kernel when the union alphabet of all targets has at most 16 symbols;
+ * every other target runs all queries through one internal hit-list shared-target session, and its occurrences take
+ * their place in the list.
+ * Run, Stats and Destroy work as for a cross batch: Stats.path has bit 3 set when the kernel ran and bit 0 as well when
+ * an internal session ran; Stats.cells and Stats.word_steps are those of an HW edlibAmdBatchCreateCrossHits batch over
+ * the same inputs (an internal session adds the word-steps it executed).  edlibAmdBatchCrossOccurrences has the results;
+ * CrossView, CrossHits, CrossStrands and the views of every other kind fail.
+ * The device list starts at max(2^20, numQueries + numTargets) runs; a Run that counts more grows it to its count and
+ * scans once more (later Runs of the batch fit); a list that does not fit in device memory fails the Run with the count
+ * in the message, and so does one of more than 2^32 - 1 runs.
+ * Out of scope: both strands (pass the reverse complements as queries of their own -- there is one level, so nothing to
+ * prune); start locations and paths (align the chosen windows with a pair or window batch); best-per-target and
+ * best-per-query reductions (a hit-list cross batch has those). */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateCrossOccurrences(
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const char* targets, const long long* targetOffsets, int numTargets,
+    EdlibAlignConfig config, int device);
+
+/* The occurrences of the last Run of such a batch (it fails on every other kind, and before the first Run), made on the
+ * device and copied as one block (the offsets, then six int planes): pointers into pinned memory the batch owns, valid
+ * until the next Run / Destroy.  Occurrences are grouped by target in the caller's order (CSR), inside a target by
+ * ascending query index, inside a cell by ascending firstEnd (lastEnd + 1 < the next firstEnd: runs are maximal). */
+typedef struct {
+    int numQueries, numTargets; long long numHits;
+    const long long* targetOffsets;   /* [numTargets + 1]: occurrences in target t are [targetOffsets[t], targetOffsets[t+1]) */
+    const int* query;                 /* [numHits] */
+    const int* firstEnd;  const int* lastEnd;                                   /* [numHits] each */
+    const int* editDistance;  const int* endLocation;  const int* numLocations; /* [numHits] each */
+} EdlibAmdCrossOccurrences;
+EDLIB_API int edlibAmdBatchCrossOccurrences(EdlibAmdBatch* batch, EdlibAmdCrossOccurrences* out);
+
 /* Cross batches on both strands: as edlibAmdBatchCreateCross / edlibAmdBatchCreateCrossHits (the same arguments, routing
  * and refusals, checked before the device is looked for: task other than EDLIB_TASK_DISTANCE, unknown mode, k < 0 for the
  * hit-list form), but cell (q, t) is the better of edlibAlign(query q, target t, config) and
