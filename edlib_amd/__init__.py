@@ -175,6 +175,8 @@ def lib():
             L.edlibAmdBatchCreateCrossOccurrences.restype = C.c_void_p
             L.edlibAmdBatchCreateCrossOccurrences.argtypes = L.edlibAmdBatchCreateCross.argtypes
             L.edlibAmdBatchCrossOccurrences.argtypes = [C.c_void_p, C.POINTER(CrossOccurrences)]
+        if hasattr(L, "edlibAmdBatchCrossSetTargets"):
+            L.edlibAmdBatchCrossSetTargets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.edlibAmdBatchCreateWindows.restype = C.c_void_p
         L.edlibAmdBatchCreateWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -621,7 +623,11 @@ class CrossBatch(_Batch):
     cells, and strands() says which strand each reports.
     occurrences=True (edlibAmdBatchCreateCrossOccurrences; HW, k >= 0, queries up to 256 bases): no matrix and no best
     hits; occurrences() lists, per target and query, every maximal run of target columns that end an occurrence of the
-    query within k.  Exclusive with hits=True and strands="both"."""
+    query within k.  Exclusive with hits=True and strands="both".
+    set_targets(targets) (edlibAmdBatchCrossSetTargets) passes another target set through the resident batch: the queries
+    stay, the targets are prepared on the device, and the batch is then as if created over (its queries, these targets)
+    -- run(), then the views.  A streamed set lies inside the cross kernel's envelope (targets up to 65,536 bases, at
+    most 16 distinct symbols, no query above 256 bases); outside it the call raises and the batch stays as it was."""
 
     both_strands = False
     is_occurrences = False
@@ -653,6 +659,17 @@ class CrossBatch(_Batch):
         h = create(qd.ctypes.data, qo.ctypes.data, self.numQueries, td.ctypes.data, to.ctypes.data, self.numTargets,
                    cfg, device)
         super().__init__(h, self.numQueries * self.numTargets, keep)
+
+    def set_targets(self, targets):
+        """Replace the targets (the constructor's input forms: a list of bytes / arrays, or one 2-D uint8 array); the
+        queries stay resident.  Raises RuntimeError with last_error() on a refusal, which leaves the batch as it was.
+        run() before the next view."""
+        td, to = _pack(targets)
+        nt = len(to) - 1
+        if lib().edlibAmdBatchCrossSetTargets(self._h, td.ctypes.data, to.ctypes.data, nt) != 0:
+            raise RuntimeError("edlib_amd: set_targets failed: " + last_error())
+        self.numTargets = nt
+        self.n = self.numQueries * nt
 
     def _view(self, what):
         v = CrossView()

@@ -302,6 +302,18 @@ EDLIB_API int edlibAmdBatchCrossOccurrences(EdlibAmdBatch* b, EdlibAmdCrossOccur
     return guarded("edlibAmdBatchCrossOccurrences", 1, [&] { return b->cross->occurrencesView(out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+EDLIB_API int edlibAmdBatchCrossSetTargets(EdlibAmdBatch* b, const char* targets, const long long* targetOffsets,
+                                           int numTargets) {
+    if (!b) { set_error("edlibAmdBatchCrossSetTargets: null batch"); return EDLIB_STATUS_ERROR; }
+    if (not_on_windows(b, "edlibAmdBatchCrossSetTargets") || not_on_self(b, "edlibAmdBatchCrossSetTargets")) return EDLIB_STATUS_ERROR;
+    if (!b->cross) {
+        set_error("edlibAmdBatchCrossSetTargets: not a cross batch (only the targets of a cross batch can be replaced)");
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchCrossSetTargets", 1, [&] { return b->cross->setTargets(targets, targetOffsets, numTargets); })
+               ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 static EdlibAmdBatch* create_self(const char* where, const char* seqs, const long long* offsets, int numSequences,
                                   EdlibAlignConfig config, int device, bool hits, bool strands = false) {
     return create_batch(where, [&](EdlibAmdBatch& b) {

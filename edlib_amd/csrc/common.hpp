@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace edlib_amd {
@@ -70,6 +71,7 @@ struct DevBuf {
     // grow-only; a view (alias()) is never "enough": its block belongs to somebody else and may be gone
     hipError_t ensure(size_t count) { return (count <= n && p && owned) ? hipSuccess : alloc(count); }
     size_t bytes() const { return n * sizeof(T); }
+    void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(granted, o.granted); std::swap(owned, o.owned); }
 };
 
 // Pinned host block that frees itself (back into the cache).

@@ -185,4 +185,15 @@ hipError_t launch_cross_occ_finish(const unsigned long long* key, const int* val
                                    int numTargets, const uint32_t* idx, unsigned long long* skey, uint32_t* sidx,
                                    void* tmp, size_t tmpBytes, long long* targetOffsets, int* out, hipStream_t stream);
 
+// ---- a target set prepared on the device (cross_targets.hip)
+// temporary bytes of launch_cross_targets_prepare over n targets
+hipError_t cross_targets_order_bytes(int n, size_t* bytes);
+// From the raw pool and the caller's offsets offIn [n + 1] (any base, every length at most kCrossMaxTarget): the rebased
+// offsets offR [n + 1], the presence set of the pool's bytes (8 dwords, zeroed here), the targets in the stable order
+// (length, index) as tlen / tperm [n], and tdw [n], the first dword of every packed target in that order (the exclusive
+// scan of ceil(length / 8)).  len, idx [n] and dw [n] are scratch.
+hipError_t launch_cross_targets_prepare(const uint8_t* raw, const long long* offIn, int n, long long* offR,
+                                        uint32_t* presence, uint32_t* len, uint32_t* idx, int* tlen, int* tperm,
+                                        long long* dw, long long* tdw, void* tmp, size_t tmpBytes, hipStream_t stream);
+
 }  // namespace edlib_amd

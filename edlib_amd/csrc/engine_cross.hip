@@ -11,6 +11,10 @@
 // An occurrence batch (DESIGN.md §4h "Occurrence batches") is a hit-list batch whose entries are the maximal runs of
 // columns within k of every cell: the occurrence scan appends them, each target outside the kernel's envelope runs through
 // an internal hit-list shared-target session, and the finish sorts the runs into CSR order without best hits.
+// setTargets (DESIGN.md §4h "Streamed targets") passes another target set through the resident batch: the set is prepared
+// on the device (cross_targets.hip: census, order by length, packed offsets; the way init prepares a set within the
+// kernel's target length), swapped in once it is known to lie inside the kernel's envelope, and the groups are shaped
+// again (shapeGroups, init's own).
 #include "engine_lanes.hpp"
 
 #include <algorithm>
@@ -30,6 +34,20 @@ int choose_qt(long long nq, long long nt, int minQt)
         if (bestLanes < 0 || lanes < bestLanes) { bestLanes = lanes; bestQt = qt; }
     }
     return bestQt;
+}
+
+// the host's share of a set, linear in its count: colsBelow[L] = columns of the targets shorter than L (L up to the
+// longest + 1), the dwords of the packed pool
+static void columns_by_length(const long long* toff, int nt, int maxLen, std::vector<long long>& colsBelow, long long* dwords)
+{
+    colsBelow.assign((size_t)maxLen + 2, 0);
+    *dwords = 0;
+    for (int t = 0; t < nt; ++t) {
+        const long long n = toff[t + 1] - toff[t];
+        colsBelow[(size_t)n + 1] += n;
+        *dwords += (n + 7) / 8;
+    }
+    for (size_t l = 1; l < colsBelow.size(); ++l) colsBelow[l] += colsBelow[l - 1];
 }
 
 int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const char* targets,
@@ -92,98 +110,72 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
     stats = EdlibAmdBatchStats{};
     stats.cells = qbytes * tbytes * (strands ? 2 : 1);
 
-    // the union alphabet of all targets decides the Peq rows (and whether the kernel can take any cell)
-    build_tables(tab_, reinterpret_cast<const uint8_t*>(targets) + tb, tbytes, eqs_.data(), (int)eqs_.size());
-    const bool wide = tab_.sigmaT > kCrossMaxSyms;
-    syms_ = peq_syms(tab_.sigmaT);
-    std::vector<int> inT, longQ;
-    for (int t = 0; t < nt; ++t) {
-        if (!wide && tlen(t) <= kCrossMaxTarget) inT.push_back(t);
-        else outTargets_.push_back(t);
+    // the queries as every target set finds them: word groups, each sorted by length; empty queries ride in the
+    // one-word group
+    std::vector<int> longQ;
+    qbytes_ = qbytes;
+    qlen_.resize((size_t)nq);
+    wordQueries_.assign(kCrossMaxQueryWords + 1, std::vector<int>());
+    for (int q = 0; q < nq; ++q) {
+        const int m = qlen_[q] = qlen(q);
+        if (m > maxQlen_) { maxQlen_ = m; longestQuery_ = q; }
+        if (m > 32 * kCrossMaxQueryWords) longQ.push_back(q);
+        else wordQueries_[std::max(1, (m + 31) / 32)].push_back(q);
     }
-    for (int q = 0; q < nq; ++q)
-        if (qlen(q) > 32 * kCrossMaxQueryWords) longQ.push_back(q);
+    for (auto& qs : wordQueries_)
+        std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return qlen_[a] < qlen_[b]; });
 
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     if (openStream()) return 1;
-    if (!occ_) EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)nt + 3 * (size_t)nq));
-    if (strands_) {
-        EDLIB_AMD_HIP(d_sbest_.alloc(std::max<size_t>((size_t)nt + (size_t)nq, 1)));
-        if (!hits_) EDLIB_AMD_HIP(d_smat_.alloc(std::max<size_t>(cells_, 1)));
-    }
-    if (!hits_) {
-        EDLIB_AMD_HIP(d_mat_.alloc(3 * std::max<size_t>(cells_, 1)));
-        targetChunk_ = std::max(1024, (nt + 32767) / 32768);
-        EDLIB_AMD_HIP(d_partial_.alloc((size_t)std::max(1, (nt + targetChunk_ - 1) / targetChunk_) * (size_t)std::max(nq, 1)));
-    } else {
-        EDLIB_AMD_HIP(d_hcount_.alloc(1)); EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
-        EDLIB_AMD_HIP(d_htoff_.alloc((size_t)nt + 1));
-        if (!occ_) EDLIB_AMD_HIP(d_bkey_.alloc(2 * ((size_t)nt + (size_t)nq)));
-        if (growHits(std::max<long long>(1LL << 20, (long long)nq + nt))) return 1;
+    if (sizeResults()) return 1;
+
+    // the union alphabet of all targets decides the Peq rows (and whether the kernel can take any cell).  A set whose
+    // every target fits the kernel's length is prepared on the device, the way setTargets does it; one with a longer
+    // target is read on the host, and the targets the kernel takes are packed from there.
+    int maxTlen = 0;
+    for (int t = 0; t < nt; ++t) maxTlen = std::max(maxTlen, tlen(t));
+    const bool deviceSet = nt > 0 && maxTlen <= kCrossMaxTarget;
+    TargetPrep prep;
+    std::vector<long long> colsBelow;
+    if (deviceSet) {
+        long long dwords = 0;
+        columns_by_length(toff.data(), nt, maxTlen, colsBelow, &dwords);
+        if (prepareTargets(targets, toff.data(), nt, dwords, prep, tab_)) return 1;
+    } else build_tables(tab_, reinterpret_cast<const uint8_t*>(targets) + tb, tbytes, eqs_.data(), (int)eqs_.size());
+    const bool wide = tab_.sigmaT > kCrossMaxSyms;
+    syms_ = peq_syms(tab_.sigmaT);
+    std::vector<int> inT;
+    for (int t = 0; t < nt; ++t) {
+        if (!wide && tlen(t) <= kCrossMaxTarget) inT.push_back(t);
+        else outTargets_.push_back(t);
     }
 
     // ---- the cross kernel's share
-    if (!inT.empty() && (int)longQ.size() < nq) {
+    const bool kernelShare = !inT.empty() && (int)longQ.size() < nq;
+    // (queries the kernel can take are resident even where this set leaves it nothing: a later setTargets finds them)
+    if ((kernelShare || (nq > 0 && longQ.empty())) && uploadQueries(queries, qoff, strands_)) return 1;
+    if (kernelShare && deviceSet) {
+        if (adoptTargets(prep, nt)) return 1;
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        numSorted_ = nt; sortedCols_ = tbytes;
+        if (shapeGroups(colsBelow)) return 1;
+    } else if (kernelShare) {
         std::stable_sort(inT.begin(), inT.end(), [&](int a, int b) { return tlen(a) < tlen(b); });
         numSorted_ = (int)inT.size();
-        std::vector<long long> colsBelow(numSorted_ + 1, 0);
         std::vector<int> tl(numSorted_);
         for (int i = 0; i < numSorted_; ++i) {
             tl[i] = tlen(inT[i]);
             sortedCols_ += tl[i];
-            colsBelow[i + 1] = sortedCols_;
         }
-        // columns the kernel scans for a query of length m: all of them, or under NW with k >= 0 those of the targets in
-        // the length window [m - k, m + k] (cross_nw_outside), a range of the sorted lengths
-        auto scannedCols = [&](int m) -> long long {
-            if (cfg.mode == EDLIB_MODE_NW && cfg.k >= 0) {
-                const long long lo = std::lower_bound(tl.begin(), tl.end(), (long long)m - cfg.k) - tl.begin();
-                const long long hi = std::upper_bound(tl.begin(), tl.end(), (long long)m + cfg.k) - tl.begin();
-                return colsBelow[hi] - colsBelow[lo];
-            }
-            return sortedCols_;
-        };
+        colsBelow.assign((size_t)tl.back() + 2, 0);
+        for (int l : tl) colsBelow[(size_t)l + 1] += l;
+        for (size_t l = 1; l < colsBelow.size(); ++l) colsBelow[l] += colsBelow[l - 1];
         if (packHostTargets(targets, toff, inT, tl)) return 1;
         EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_));
         EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, tl.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
-        if (uploadQueries(queries, qoff, strands_)) return 1;
-        // word groups, each sorted by length; empty queries ride in the one-word group
-        std::vector<std::vector<int>> byWords(kCrossMaxQueryWords + 1);
-        for (int q = 0; q < nq; ++q) {
-            const int m = qlen(q);
-            if (m > 32 * kCrossMaxQueryWords) continue;
-            byWords[std::max(1, (m + 31) / 32)].push_back(q);
-        }
-        for (int w = 1; w <= kCrossMaxQueryWords; ++w) {
-            auto& qs = byWords[w];
-            if (qs.empty()) continue;
-            std::stable_sort(qs.begin(), qs.end(), [&](int a, int b) { return qlen(a) < qlen(b); });
-            std::unique_ptr<Group> g(new Group);
-            g->words = w;
-            // both strands: each query of the sorted list becomes two slots, itself and its reverse complement
-            const long long need = (long long)qs.size() * (strands_ ? 2 : 1);
-            g->qt = choose_qt(need, numSorted_, strands_ ? 2 : 1);
-            g->tiles = (int)((need + g->qt - 1) / g->qt);
-            for (int q : qs) g->wordSteps += (long long)w * scannedCols(qlen(q)) * (strands_ ? 2 : 1);
-            const int tpt = 64 / g->qt;
-            const long long targetTiles = (numSorted_ + tpt - 1) / tpt;
-            // about 8,192 waves per launch (256 CUs), each persistent over a strided range of target tiles
-            g->ysplit = (int)std::min<long long>({targetTiles, std::max(1LL, (8192LL + g->tiles - 1) / g->tiles), 65535LL});
-            std::vector<int> perm((size_t)g->tiles * g->qt, -1);           // whole tiles
-            if (!strands_) std::copy(qs.begin(), qs.end(), perm.begin());
-            else {
-                for (size_t i = 0; i < qs.size(); ++i) { perm[2 * i] = 2 * qs[i]; perm[2 * i + 1] = 2 * qs[i] + 1; }
-                // what the kernel's lane exchange rests on: mates in the slots s and s ^ 1, padding in pairs, an even tile
-                bool ok = !(g->qt & 1) && !(perm.size() & 1);
-                for (size_t sl = 0; ok && sl < perm.size(); sl += 2)
-                    ok = perm[sl] < 0 ? perm[sl + 1] < 0 : (!(perm[sl] & 1) && perm[sl + 1] == perm[sl] + 1);
-                if (!ok) { set_error("both strands: mates are not in adjacent slots"); return 1; }
-            }
-            if (allocGroup(*g, perm)) return 1;
-            groups_.push_back(std::move(g));
-        }
+        if (shapeGroups(colsBelow)) return 1;
     }
 
     // ---- the other engines' share
@@ -232,6 +224,215 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
         }
     }
     return 0;
+}
+
+// the result buffers of nq_ x nt_ cells: made where there are none, grown where the counts need more, otherwise kept (a
+// hit list keeps the capacity an earlier Run grew it to)
+int CrossBatch::sizeResults()
+{
+    const size_t nq = (size_t)nq_, nt = (size_t)nt_;
+    if (!occ_) EDLIB_AMD_HIP(d_best_.ensure(3 * nt + 3 * nq));
+    if (strands_) {
+        EDLIB_AMD_HIP(d_sbest_.ensure(std::max<size_t>(nt + nq, 1)));
+        if (!hits_) EDLIB_AMD_HIP(d_smat_.ensure(std::max<size_t>(cells_, 1)));
+    }
+    if (!hits_) {
+        EDLIB_AMD_HIP(d_mat_.ensure(3 * std::max<size_t>(cells_, 1)));
+        targetChunk_ = std::max(1024, (nt_ + 32767) / 32768);
+        EDLIB_AMD_HIP(d_partial_.ensure((size_t)std::max(1, (nt_ + targetChunk_ - 1) / targetChunk_) * std::max<size_t>(nq, 1)));
+    } else {
+        EDLIB_AMD_HIP(d_hcount_.ensure(1));
+        if (!h_hcount_.p) EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
+        EDLIB_AMD_HIP(d_htoff_.ensure(nt + 1));
+        if (!occ_) EDLIB_AMD_HIP(d_bkey_.ensure(2 * (nt + nq)));
+        const long long need = std::max<long long>(1LL << 20, (long long)nq_ + nt_);
+        if (hitCap_ < need && growHits(need)) return 1;
+    }
+    return 0;
+}
+
+int CrossBatch::shapeGroups(const std::vector<long long>& colsBelow)
+{
+    std::vector<std::unique_ptr<Group>> kept;
+    kept.swap(groups_);
+    if (numSorted_ == 0) return 0;
+    const long long top = (long long)colsBelow.size() - 1;
+    // columns the kernel scans for a query of length m: all of them, or under NW with k >= 0 those of the targets in
+    // the length window [m - k, m + k] (cross_nw_outside)
+    auto scannedCols = [&](int m) -> long long {
+        if (cfg_.mode == EDLIB_MODE_NW && cfg_.k >= 0) {
+            const long long lo = std::min(std::max((long long)m - cfg_.k, 0LL), top);
+            const long long hi = std::min((long long)m + cfg_.k + 1, top);
+            return colsBelow[(size_t)hi] - colsBelow[(size_t)lo];
+        }
+        return sortedCols_;
+    };
+    for (int w = 1; w <= kCrossMaxQueryWords; ++w) {
+        const auto& qs = wordQueries_[w];
+        if (qs.empty()) continue;
+        std::unique_ptr<Group> g;
+        for (auto& o : kept)
+            if (o && o->words == w) g = std::move(o);
+        if (!g) { g.reset(new Group); g->words = w; }
+        // both strands: each query of the sorted list becomes two slots, itself and its reverse complement
+        const long long need = (long long)qs.size() * (strands_ ? 2 : 1);
+        const int qt = choose_qt(need, numSorted_, strands_ ? 2 : 1);
+        const bool fresh = g->slots == 0 || qt != g->qt || g->syms != syms_;
+        g->qt = qt;
+        g->tiles = (int)((need + g->qt - 1) / g->qt);
+        g->wordSteps = 0;
+        for (int q : qs) g->wordSteps += (long long)w * scannedCols(qlen_[q]) * (strands_ ? 2 : 1);
+        const int tpt = 64 / g->qt;
+        const long long targetTiles = (numSorted_ + tpt - 1) / tpt;
+        // about 8,192 waves per launch (256 CUs), each persistent over a strided range of target tiles
+        g->ysplit = (int)std::min<long long>({targetTiles, std::max(1LL, (8192LL + g->tiles - 1) / g->tiles), 65535LL});
+        if (fresh) {
+            std::vector<int> perm((size_t)g->tiles * g->qt, -1);           // whole tiles
+            if (!strands_) std::copy(qs.begin(), qs.end(), perm.begin());
+            else {
+                for (size_t i = 0; i < qs.size(); ++i) { perm[2 * i] = 2 * qs[i]; perm[2 * i + 1] = 2 * qs[i] + 1; }
+                // what the kernel's lane exchange rests on: mates in the slots s and s ^ 1, padding in pairs, an even tile
+                bool ok = !(g->qt & 1) && !(perm.size() & 1);
+                for (size_t sl = 0; ok && sl < perm.size(); sl += 2)
+                    ok = perm[sl] < 0 ? perm[sl + 1] < 0 : (!(perm[sl] & 1) && perm[sl + 1] == perm[sl] + 1);
+                if (!ok) { set_error("both strands: mates are not in adjacent slots"); return 1; }
+            }
+            if (allocGroup(*g, perm)) return 1;
+            g->syms = syms_;
+        }
+        groups_.push_back(std::move(g));
+    }
+    return 0;
+}
+
+// 65,536 as the messages of setTargets write it
+static std::string with_commas(long long v)
+{
+    std::string s = std::to_string(v);
+    for (int i = (int)s.size() - 3; i > 0; i -= 3) s.insert((size_t)i, ",");
+    return s;
+}
+
+// A target set (every target at most kCrossMaxTarget bases) on its way into the batch: the raw pool and the caller's
+// offsets go up as they are, one asynchronous copy each, and the device makes the rest (cross_targets.hip) -- the presence
+// set of the pool, the stable order by length, the dword offsets of the packed targets.  `dwords`: of the packed pool.
+// tab: the tables of the bytes the census found with the batch's equalities, symbol ids in ascending byte order (nothing
+// a cross batch reports depends on the ids: tlut and eqtbl only have to agree).  The stream is idle afterwards; nothing
+// of the batch has changed.
+int CrossBatch::prepareTargets(const char* targets, const long long* toffIn, int nt, long long dwords, TargetPrep& p,
+                               Tables& tab)
+{
+    if (!h_census_.p) EDLIB_AMD_HIP(h_census_.alloc(8 * sizeof(uint32_t)));
+    uint32_t* presence = reinterpret_cast<uint32_t*>(h_census_.p);
+    memset(presence, 0, 8 * sizeof(uint32_t));
+    if (nt > 0) {
+        const size_t n = (size_t)nt;
+        const long long tbytes = toffIn[nt] - toffIn[0];
+        size_t tmpBytes = 0;
+        EDLIB_AMD_HIP(cross_targets_order_bytes(nt, &tmpBytes));
+        EDLIB_AMD_HIP(p.raw.alloc((size_t)tbytes + 16)); EDLIB_AMD_HIP(p.offIn.alloc(n + 1)); EDLIB_AMD_HIP(p.offR.alloc(n + 1));
+        EDLIB_AMD_HIP(p.pres.alloc(8)); EDLIB_AMD_HIP(p.len.alloc(n)); EDLIB_AMD_HIP(p.idx.alloc(n));
+        EDLIB_AMD_HIP(p.dw.alloc(n)); EDLIB_AMD_HIP(p.tmp.alloc(tmpBytes)); EDLIB_AMD_HIP(p.tlut.alloc(256));
+        EDLIB_AMD_HIP(p.tlen.alloc(n)); EDLIB_AMD_HIP(p.tperm.alloc(n)); EDLIB_AMD_HIP(p.tdw.alloc(n));
+        EDLIB_AMD_HIP(p.tpk.alloc((size_t)std::max(dwords, 1LL)));
+        if (tbytes) EDLIB_AMD_HIP(hipMemcpyAsync(p.raw.p, targets + toffIn[0], (size_t)tbytes, hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(p.offIn.p, toffIn, (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(launch_cross_targets_prepare(p.raw.p, p.offIn.p, nt, p.offR.p, p.pres.p, p.len.p, p.idx.p, p.tlen.p,
+                                                   p.tperm.p, p.dw.p, p.tdw.p, p.tmp.p, tmpBytes, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(presence, p.pres.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    }
+    uint8_t present[256];
+    int numPresent = 0;
+    for (int b = 0; b < 256; ++b)
+        if (presence[b >> 5] >> (b & 31) & 1) present[numPresent++] = (uint8_t)b;
+    build_tables(tab, present, numPresent, eqs_.data(), (int)eqs_.size());
+    return 0;
+}
+
+// the prepared set packed with tab_'s codes and made the batch's (what the batch held goes into p and dies with it: the
+// caller synchronises the stream before that)
+int CrossBatch::adoptTargets(TargetPrep& p, int nt)
+{
+    if (nt == 0) return 0;
+    EDLIB_AMD_HIP(hipMemcpyAsync(p.tlut.p, tab_.tlut, 256, hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(launch_pack_cross_targets(p.raw.p, p.offR.p, p.tperm.p, p.tdw.p, nt, p.tlut.p, p.tpk.p, stream_));
+    d_tpk_.swap(p.tpk); d_tdw_.swap(p.tdw); d_tperm_.swap(p.tperm); d_tlen_.swap(p.tlen);
+    return 0;
+}
+
+int CrossBatch::setTargets(const char* targets, const long long* toffIn, int nt)
+{
+    static const char* const fn = "edlibAmdBatchCrossSetTargets";
+    // ---- what is refused leaves the batch as it was
+    if (self_) { set_error("%s: not available on a self batch", fn); return 1; }
+    if (nt < 0) { set_error("%s: numTargets must be >= 0 (got %d)", fn, nt); return 1; }
+    if (nt > 0 && (!targets || !toffIn)) { set_error("%s: targets and targetOffsets must not be NULL for %d targets", fn, nt); return 1; }
+    if (maxQlen_ > 32 * kCrossMaxQueryWords) {
+        set_error("%s: query %d has %s bases, the limit for a batch that streams targets is %d: create a new batch", fn,
+                  longestQuery_, with_commas(maxQlen_).c_str(), 32 * kCrossMaxQueryWords);
+        return 1;
+    }
+    // the host's share, linear in numTargets: the offsets checked, the longest target, the columns by length
+    int maxLen = 0;
+    for (int t = 0; t < nt; ++t) {
+        const long long n = toffIn[t + 1] - toffIn[t];
+        if (n < 0) { set_error("%s: bad target offsets (target %d ends before it starts)", fn, t); return 1; }
+        if (n > kCrossMaxTarget) {
+            set_error("%s: target %d has %s bases, the limit for a streamed set is %s: create a new batch", fn, t,
+                      with_commas(n).c_str(), with_commas(kCrossMaxTarget).c_str());
+            return 1;
+        }
+        maxLen = std::max(maxLen, (int)n);
+    }
+    const long long tbytes = nt > 0 ? toffIn[nt] - toffIn[0] : 0;
+    std::vector<long long> colsBelow;
+    long long dwords = 0;
+    columns_by_length(toffIn, nt, maxLen, colsBelow, &dwords);
+
+    // ---- the set prepared into buffers of its own: the pool and the offsets go up as they are, the device does the rest
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    TargetPrep prep;
+    Tables tab;
+    if (prepareTargets(targets, toffIn, nt, dwords, prep, tab)) return 1;
+    if (tab.sigmaT > kCrossMaxSyms) {
+        set_error("%s: the targets hold %d distinct symbols, the limit for a streamed set is %d: create a new batch", fn,
+                  tab.sigmaT, kCrossMaxSyms);
+        return 1;
+    }
+
+    // ---- swapped in; from here a device error leaves the batch without targets
+    noTargets_ = true;
+    haveRun_ = false;
+    tab_ = tab;
+    syms_ = peq_syms(tab_.sigmaT);
+    EDLIB_AMD_HIP(d_eqtbl_.ensure(256)); EDLIB_AMD_HIP(d_presence_.ensure(8));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice, stream_));
+    if (adoptTargets(prep, nt)) return 1;
+    // the internal sessions of the set before are gone with it: a streamed set needs none
+    outShared_.clear(); outTargets_.clear(); longPairs_.reset(); longCells_.clear(); otherCellIdx_.clear();
+    otherCells_ = 0;
+    nt_ = nt; numSorted_ = nt; sortedCols_ = tbytes;
+    cells_ = (size_t)nq_ * (size_t)nt;
+    numHits_ = 0;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = qbytes_ * tbytes * (strands_ ? 2 : 1);
+    if (sizeResults() || shapeGroups(colsBelow)) return 1;
+    // (the raw pool and the scratch die here, the set before dies here: behind the pack)
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    noTargets_ = false;
+    return 0;
+}
+
+int CrossBatch::noResults()
+{
+    if (noTargets_)
+        set_error("cross batch: it has no targets (edlibAmdBatchCrossSetTargets failed on the device): set them again");
+    else set_error("cross batch: no results (Run it first)");
+    return 1;
 }
 
 // editDistance / numLocations / first end location of the n units of an internal session's last run; sbytes (a both-strand
@@ -375,6 +576,7 @@ int CrossBatch::runOccurrenceSessions()
 int CrossBatch::run()
 {
     if (self_) return runSelf();
+    if (noTargets_) return noResults();
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
@@ -449,7 +651,7 @@ int CrossBatch::run()
 int CrossBatch::view(int what, EdlibAmdCrossView* out)
 {
     if (occ_) { set_error("edlibAmdBatchCrossView: not available on an occurrence batch (edlibAmdBatchCrossOccurrences has its results)"); return 1; }
-    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    if (!haveRun_) return noResults();
     if (what & ~(EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST)) { set_error("cross view: unknown parts %d", what); return 1; }
     if (hits_ && (what & EDLIB_AMD_CROSS_MATRIX)) {
         set_error("cross view: a hit-list batch keeps no matrix (edlibAmdBatchCrossHits has its cells within k; "
@@ -497,7 +699,7 @@ int CrossBatch::hitsView(EdlibAmdCrossHits* out)
                   "batch has edlibAmdBatchCrossView)");
         return 1;
     }
-    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    if (!haveRun_) return noResults();
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
@@ -519,7 +721,7 @@ int CrossBatch::occurrencesView(EdlibAmdCrossOccurrences* out)
                   "a hit-list cross batch has edlibAmdBatchCrossHits, a dense one edlibAmdBatchCrossView)");
         return 1;
     }
-    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    if (!haveRun_) return noResults();
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
@@ -543,7 +745,7 @@ int CrossBatch::strandsView(int what, EdlibAmdCrossStrands* out)
                   "edlibAmdBatchCreateCrossBothStrands or edlibAmdBatchCreateCrossHitsBothStrands)");
         return 1;
     }
-    if (!haveRun_) { set_error("cross batch: no results (Run it first)"); return 1; }
+    if (!haveRun_) return noResults();
     if (what & ~(EDLIB_AMD_CROSS_MATRIX | EDLIB_AMD_CROSS_BEST)) { set_error("cross strands: unknown parts %d", what); return 1; }
     pool_quarantine(false);
     DeviceGuard guard(device_);

@@ -117,6 +117,9 @@ public:
              EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false, bool occ = false);
     int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits,
                  bool strands = false);
+    // Another target set for the resident queries (DESIGN.md §4h "Streamed targets"): prepared on the device into fresh
+    // buffers and swapped in once it is known to lie inside the kernel's envelope; a refusal leaves the batch as it was
+    int setTargets(const char* targets, const long long* toff, int nt);
     int run();
     int selfView(int what, EdlibAmdSelfView* out);
     int selfHitsView(EdlibAmdSelfHits* out);
@@ -135,10 +138,35 @@ private:
         // self batches: the rank of every slot, and the work items (query tile, first target tile, trips) of its launch
         DevBuf<int> d_rank, d_items;
         int numItems = 0;
+        int syms = 0;                             // Peq rows per word its buffers were allocated for
     };
     int nt_ = 0;
     size_t cells_ = 0;
     std::vector<std::unique_ptr<Group>> groups_;
+    // the queries as init found them: their lengths, and those of each word count sorted by length (index = words); the
+    // longest decides whether the batch takes setTargets
+    std::vector<int> qlen_;
+    std::vector<std::vector<int>> wordQueries_;
+    long long qbytes_ = 0;
+    int maxQlen_ = 0, longestQuery_ = -1;
+    bool noTargets_ = false;                      // a setTargets failed on the device after it had begun to swap
+    PinBuf h_census_;
+    // The target-dependent shape of every word group over the numSorted_ targets on the kernel: choose_qt, tiles, ysplit,
+    // wordSteps, the padded slot permutation.  colsBelow[L] (L <= kCrossMaxTarget + 1): columns of the targets shorter
+    // than L.  A group's buffers are made again only where its tile or syms_ changed; no targets: no groups.
+    int shapeGroups(const std::vector<long long>& colsBelow);
+    // a target set being prepared on the device (prepareTargets), not yet the batch's (adoptTargets): the raw pool and
+    // offsets, scratch, and what takes the place of d_tpk_ / d_tdw_ / d_tperm_ / d_tlen_
+    struct TargetPrep {
+        DevBuf<uint8_t> raw, tmp, tlut;
+        DevBuf<long long> offIn, offR, dw, tdw;
+        DevBuf<uint32_t> pres, len, idx, tpk;
+        DevBuf<int> tlen, tperm;
+    };
+    int prepareTargets(const char* targets, const long long* toff, int nt, long long dwords, TargetPrep& p, Tables& tab);
+    int adoptTargets(TargetPrep& p, int nt);
+    int sizeResults();                            // the result buffers of nq_ x nt_ cells, made or grown
+    int noResults();                              // the views': sets the error of a batch that has not run (or has no targets)
     int numSorted_ = 0;                           // targets on the cross kernel
     long long sortedCols_ = 0;                    // their columns
     DevBuf<int> d_tlen_;

@@ -261,6 +261,27 @@ typedef struct {
 } EdlibAmdCrossOccurrences;
 EDLIB_API int edlibAmdBatchCrossOccurrences(EdlibAmdBatch* batch, EdlibAmdCrossOccurrences* out);
 
+/* Replace the target set of a resident cross batch.  The queries, their Peq slots, the config, the device, the stream,
+ * the hit-list capacity a previous Run grew to and the pinned view blocks stay; everything derived from the targets is
+ * made again.  Afterwards the batch is as if it had been created over (its queries, these targets): Run, then the views.
+ * Returns 0, or non-zero with edlibAmdLastError().
+ * Valid on the batches of edlibAmdBatchCreateCross, ...CrossHits, ...CrossOccurrences, ...CrossBothStrands and
+ * ...CrossHitsBothStrands; refused on self batches, window batches and every other kind.
+ * A streamed set lies inside the cross kernel's envelope: every target at most 65,536 bases, at most 16 distinct symbols
+ * over all targets, and no query of the batch above 256 bases.  Outside it the call is refused with the limit named
+ * ("... create a new batch"): a streamed set builds no internal sessions, and those a Create built are dropped by the
+ * first successful call.  targetOffsets[0] need not be 0; the caller's memory may be reused when the call returns;
+ * numTargets == 0 is valid (Run succeeds, the views are empty).
+ * A refusal (a NULL or wrong-kind batch, numTargets < 0, a NULL pointer with numTargets > 0, offsets that decrease, the
+ * three limits above) leaves the batch as it was: the previous targets, the views of the last Run, the results of the
+ * next.  A device error (out of memory) may leave the batch without targets: Run and the views then fail with a message
+ * that says so until a SetTargets succeeds.  After success the views fail ("Run it first") until the next Run, and
+ * Stats.cells describes the new set.
+ * The targets are prepared on the device (alphabet census, stable sort by length, packing); the host's share is linear in
+ * numTargets. */
+EDLIB_API int edlibAmdBatchCrossSetTargets(EdlibAmdBatch* batch, const char* targets,
+                                           const long long* targetOffsets, int numTargets);
+
 /* Cross batches on both strands: as edlibAmdBatchCreateCross / edlibAmdBatchCreateCrossHits (the same arguments, routing
  * and refusals, checked before the device is looked for: task other than EDLIB_TASK_DISTANCE, unknown mode, k < 0 for the
  * hit-list form), but cell (q, t) is the better of edlibAlign(query q, target t, config) and
