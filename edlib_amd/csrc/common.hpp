@@ -91,6 +91,23 @@ struct PinBuf {
     }
 };
 
+// A part of the results in pinned host memory, fetched from the device when a view first asks for it after a Run.
+struct PinnedPart {
+    PinBuf h;
+    bool fetched = false;
+    // enqueues the D2H of `bytes` to h + at unless the part is fetched already (room: the bytes the whole part needs, where
+    // it is fetched in pieces); the caller sets `fetched` once the stream's synchronise succeeded
+    hipError_t fetch(const void* dev, size_t bytes, hipStream_t stream, size_t at = 0, size_t room = 0) {
+        if (fetched) return hipSuccess;
+        const size_t need = at + bytes > room ? at + bytes : room;
+        if (h.n < need || !h.p) {
+            const hipError_t e = h.alloc(need);
+            if (e != hipSuccess) return e;
+        }
+        return bytes ? hipMemcpyAsync(h.p + at, dev, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
+    }
+};
+
 // Makes `device` current for the scope and restores the caller's device afterwards: a host application with
 // its own HIP context (PyTorch on cuda:3 calling the drop-in binding) must not find its device switched.
 struct DeviceGuard {

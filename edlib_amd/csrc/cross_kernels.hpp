@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hit_list.hpp"
+
 namespace edlib_amd {
 
 constexpr int kCrossMaxQueryWords = 8;          // queries up to 256 symbols (kernel A's word groups)
@@ -95,15 +97,12 @@ struct CrossScanArgs {
     int numQueries;             // row length of the matrix
     int kcfg;
     int* ed; int* nloc; int* end;   // [numTargets][numQueries] (dense batches)
-    // hit-list batches: every cell whose editDistance is not -1 is appended at slot atomicAdd(hitCount) as the key
-    // (target << 32) | query and its ed / nloc / end; slots at or past hitCap are counted but not written
-    unsigned long long* hitCount;
-    unsigned long long hitCap;
-    unsigned long long* hitKey;  // [hitCap]
-    int* hitVal;                // [3][hitCap]: editDistance, numLocations, endLocation
+    // hit-list batches: every cell whose editDistance is not -1 is appended (hit_list.hpp) as the key
+    // (target << 32) | query and three planes: editDistance, numLocations, endLocation
+    HitList hits;
     // both-strand batches (launch_scan_cross_strands): qperm = 2 * query + strand with mates in the slots s and s ^ 1, qt
     // even, numQueries the number of queries (not of slots); one strand byte (bit 0 reverse complement, bit 1 the other
-    // strand reaches the same distance) per stored cell [numTargets][numQueries], per appended hit [hitCap] in a hit list
+    // strand reaches the same distance) per stored cell [numTargets][numQueries], per appended hit [hits.cap] in a hit list
     uint8_t* strand;
     // self batches (launch_scan_cross_self / launch_scan_cross_self_strands; DESIGN.md §4h "Self batches"): queries and targets are one set, the targets
     // in the order (length, index) -- a sequence's position there is its rank --, the query slots of a group in the same
@@ -111,7 +110,7 @@ struct CrossScanArgs {
     // items[3b] against the target tiles [items[3b + 1], items[3b + 1] + items[3b + 2]).  ed is the condensed vector of
     // numQueries sequences (pair (i, j), i < j, at numQueries i - i (i + 1) / 2 + j - i - 1), a hit's key (i << 32) | j.
     // Both strands: qperm = 2 * sequence + strand, mates in the slots s and s ^ 1 with one qrank, a tile holds qt / 2
-    // sequences; strand is [numPairs] in condensed order, [hitCap] in a hit list.
+    // sequences; strand is [numPairs] in condensed order, [hits.cap] in a hit list.
     const int* qrank;           // [slots] rank of the slot's sequence, -1 for a padding slot
     const int* items;           // [3][numItems] as triples
     int numItems;
@@ -127,8 +126,8 @@ hipError_t launch_scan_cross(int nwords, int syms, int mode, bool hits, const Cr
 hipError_t launch_scan_cross_strands(int nwords, int syms, int mode, bool hits, const CrossScanArgs& a, int ysplit,
                                      hipStream_t stream);
 // the occurrence scan (cross_kernels_occ.hip; HW, kcfg >= 0): every maximal run of columns scoring <= kcfg of every cell
-// appended at slot atomicAdd(hitCount) as the key (target << 32) | query and, in hitVal as [5][hitCap], its firstEnd,
-// lastEnd, editDistance, endLocation, numLocations; a cell's runs are appended in ascending column order
+// appended to a.hits as the key (target << 32) | query and five planes: its firstEnd, lastEnd, editDistance, endLocation,
+// numLocations; a cell's runs are appended in ascending column order
 hipError_t launch_scan_cross_occ(int nwords, int syms, const CrossScanArgs& a, int ysplit, hipStream_t stream);
 // the self scan (cross_kernels_self.hip): NW only, one block per work item
 hipError_t launch_scan_cross_self(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
@@ -163,27 +162,19 @@ hipError_t launch_cross_scatter(const long long* cell, const int* vals, long lon
 hipError_t launch_cross_scatter_bytes(const long long* cell, const uint8_t* vals, long long n, uint8_t* out,
                                       hipStream_t stream);
 
-// ---- hit lists (cross_hits.hip)
-// temporary bytes of the sort of up to n hits
-hipError_t cross_hits_sort_bytes(long long n, int numTargets, size_t* bytes);
-// idx[i] = i for i < n
-hipError_t launch_cross_hits_iota(uint32_t* idx, long long n, hipStream_t stream);
-// The n hits (key, val [3][cap]) into CSR order: sorted by key (target-major, ascending query inside a target) into
-// skey / sidx, gathered into out [4][n] (query, editDistance, numLocations, endLocation), targetOffsets [nt + 1] from the
-// boundaries of the sorted keys; best hits per target and per query from the list into best ([3][nt] then [3][nq], the
-// layout of launch_cross_best) through bkey ([2][nt + nq]).  Both-strand batches (strand != NULL, [cap] as appended):
-// the strand byte travels with its hit into strandOut [n], and bestStrand ([nt] then [nq]) is the byte of every best hit.
-hipError_t launch_cross_hits_finish(const unsigned long long* key, const int* val, long long cap, long long n,
-                                    int numQueries, int numTargets, const uint32_t* idx, unsigned long long* skey,
-                                    uint32_t* sidx, void* tmp, size_t tmpBytes, long long* targetOffsets, int* out,
-                                    unsigned long long* bkey, int* best, const uint8_t* strand, uint8_t* strandOut,
+// ---- hit lists (cross_hits.hip), over a settled list (hit_list.hpp)
+// The hits (three planes) into CSR order: sorted by key (target-major, ascending query inside a target), gathered into
+// hl.out() [4][n] (query, editDistance, numLocations, endLocation), hl.off() [nt + 1] from the boundaries of the sorted
+// keys; best hits per target and per query from the list into best ([3][nt] then [3][nq], the layout of
+// launch_cross_best) through bkey ([2][nt + nq]).  Both-strand batches (bestStrand != NULL; the list carries a byte per
+// entry): the strand byte travels with its hit into hl.byteOut, and bestStrand ([nt] then [nq]) is the byte of every
+// best hit.
+hipError_t launch_cross_hits_finish(HitListBuffers& hl, int numQueries, int numTargets, unsigned long long* bkey, int* best,
                                     uint8_t* bestStrand, hipStream_t stream);
-// The n runs of an occurrence batch (key, val [5][cap]) into CSR order: the same stable sort by key -- a cell's runs were
-// appended in ascending column order, so they stay so behind it: (target, query, firstEnd) --, gathered into out [6][n]
-// (query, firstEnd, lastEnd, editDistance, endLocation, numLocations), targetOffsets [nt + 1] as above.
-hipError_t launch_cross_occ_finish(const unsigned long long* key, const int* val, long long cap, long long n,
-                                   int numTargets, const uint32_t* idx, unsigned long long* skey, uint32_t* sidx,
-                                   void* tmp, size_t tmpBytes, long long* targetOffsets, int* out, hipStream_t stream);
+// The runs of an occurrence batch (five planes) into CSR order: the same stable sort by key -- a cell's runs were
+// appended in ascending column order, so they stay so behind it: (target, query, firstEnd) --, gathered into hl.out()
+// [6][n] (query, firstEnd, lastEnd, editDistance, endLocation, numLocations), hl.off() [nt + 1] as above.
+hipError_t launch_cross_occ_finish(HitListBuffers& hl, int numTargets, hipStream_t stream);
 
 // ---- a target set prepared on the device (cross_targets.hip)
 // temporary bytes of launch_cross_targets_prepare over n targets

@@ -122,57 +122,27 @@ scan_cross_kernel(CrossScanArgs a)
             }
             continue;
         }
+        // (a wave without a hit issues no atomic: a sparse batch issues almost none)
         const bool hit = live && mine && ed != -1;
-        const u64 mask = __ballot(hit);
-        if (mask == 0) continue;                        // a sparse batch issues almost no atomics
-        const int leader = __ffsll((long long)mask) - 1;    // a lane with a hit: active
-        u64 base = 0;
-        if (lane == leader) base = atomicAdd(a.hitCount, (u64)__popcll(mask));
-        base = __shfl(base, leader, 64);
-        if (hit) {
-            const u64 at = base + __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0u));
-            if (at < a.hitCap) {
-                const u32 other = (u32)a.tperm[ts];
-                // self: the pair's two sequence indices, lower first
-                const u32 self = (u32)qout;
-                a.hitKey[at] = SELF ? ((u64)(self < other ? self : other) << 32) | (self < other ? other : self)
-                                    : ((u64)other << 32) | self;
-                a.hitVal[at] = ed; a.hitVal[a.hitCap + at] = nloc; a.hitVal[2 * a.hitCap + at] = end;
-                if (STRANDS) a.strand[at] = (uint8_t)sbyte;
-            }
-        }
+        const auto key = [&]() -> u64 {
+            const u32 other = (u32)a.tperm[ts];
+            // self: the pair's two sequence indices, lower first
+            const u32 self = (u32)qout;
+            return SELF ? ((u64)(self < other ? self : other) << 32) | (self < other ? other : self) : ((u64)other << 32) | self;
+        };
+        const u64 at = hit_list_append<3>(a.hits, hit, key, {ed, nloc, end});
+        if (STRANDS && at < a.hits.cap) a.strand[at] = (uint8_t)sbyte;
     }
 }
 
 // ------------------------------------------------------------- occurrences
 
-// Appends the closed run of every lane with `emit` to the occurrence list (CrossScanArgs::hitKey / hitVal as [5][hitCap]:
-// firstEnd, lastEnd, editDistance, endLocation, numLocations): one 64-bit atomic per wave among the lanes that are active
-// at the call (ballot, mbcnt rank, readlane from the leader -- hit_append of reads_scan.hpp), so it holds inside the
-// divergent column loop.  Entries past the capacity are counted, not written.
-__device__ __forceinline__ void occ_append(const CrossScanArgs& a, const bool emit, const u64 key, const int first,
-                                           const int last, const int ed, const int pos, const int cnt)
-{
-    const u64 bal = __builtin_amdgcn_ballot_w64(emit);
-    if (!bal) return;
-    const int lead = __builtin_ctzll(bal);
-    const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
-    u64 base = 0;
-    if (emit && rank == 0) base = atomicAdd(a.hitCount, (u64)__popcll(bal));
-    base = ((u64)(u32)__builtin_amdgcn_readlane((int)(base >> 32), lead) << 32) | (u32)__builtin_amdgcn_readlane((int)base, lead);
-    const u64 at = base + rank;
-    if (emit && at < a.hitCap) {
-        a.hitKey[at] = key;
-        a.hitVal[at] = first; a.hitVal[a.hitCap + at] = last; a.hitVal[2 * a.hitCap + at] = ed;
-        a.hitVal[3 * a.hitCap + at] = pos; a.hitVal[4 * a.hitCap + at] = cnt;
-    }
-}
-
 // Occurrence batches (DESIGN.md §4h "Occurrence batches"; HW, k >= 0): the tiles, the Peq staging, the column and the
 // target walk of scan_cross_kernel, but in place of best / count / first a lane follows its open run of columns scoring
 // <= k in registers (rFirst < 0: none; its least score, the first column holding it, how many columns hold it).  A column
 // within k opens or extends the run, the first column above k behind it closes it, the end of the target closes the last
-// one; closed runs go to the list by occ_append with the key (target << 32) | query.  A wave none of whose active lanes
+// one; closed runs go to the list (hit_list_append<5>: firstEnd, lastEnd, editDistance, endLocation, numLocations) with the
+// key (target << 32) | query, among the lanes that are active in the divergent column loop.  A wave none of whose active lanes
 // is within k or has a run open pays the compare and one not-taken uniform branch per column; the tracking of the eight
 // columns of a target word follows their arithmetic, so that the branches do not cut the column block into eight.  A lane appends its cell's
 // runs in ascending column order and the counter only grows: a cell's runs ascend by list index.
@@ -206,9 +176,10 @@ scan_cross_occ_kernel(CrossScanArgs a)
         const int ts = tt * tpt + ti;
         if (ts >= a.numSorted) continue;
         const int n = a.tlen[ts];
-        const u64 key = ((u64)(u32)a.tperm[ts] << 32) | (u32)q;
+        const u64 cell = ((u64)(u32)a.tperm[ts] << 32) | (u32)q;
+        const auto key = [&] { return cell; };
         if (m == 0) {                                   // the empty query: one run over a non-empty target, no columns
-            occ_append(a, n > 0, key, 0, n - 1, 0, 0, n);
+            hit_list_append<5>(a.hits, n > 0, key, {0, n - 1, 0, 0, n});
             continue;
         }
         const u32* __restrict__ tp = a.tpk + a.tdw[ts];
@@ -221,7 +192,7 @@ scan_cross_occ_kernel(CrossScanArgs a)
             const bool in = sc <= k;
             if (__builtin_amdgcn_ballot_w64(in || rFirst >= 0) != 0ull) {       // wave-uniform
                 const bool close = !in && rFirst >= 0;
-                occ_append(a, close, key, rFirst, j - 1, rMin, rPos, rCnt);
+                hit_list_append<5>(a.hits, close, key, {rFirst, j - 1, rMin, rPos, rCnt});
                 if (close) rFirst = -1;
                 if (in) {
                     if (rFirst < 0) { rFirst = j; rMin = sc; rPos = j; rCnt = 1; }
@@ -245,7 +216,7 @@ scan_cross_occ_kernel(CrossScanArgs a)
             u32 w = tp[j >> 3];
             for (; j < n; ++j) { column(w & 15u); track(score, j); w >>= 4; }
         }
-        occ_append(a, rFirst >= 0, key, rFirst, n - 1, rMin, rPos, rCnt);        // the run open at the end of the target
+        hit_list_append<5>(a.hits, rFirst >= 0, key, {rFirst, n - 1, rMin, rPos, rCnt});     // the run open at the end of the target
     }
 }
 
@@ -326,7 +297,7 @@ static inline int cross_scan_args_state(int syms, int mode, bool hits, const Cro
     if (a.numQueryTiles == 0 || a.numSorted == 0) return 1;
     if ((syms != 4 && syms != 8 && syms != 16) || mode < 0 || mode > 2 || a.qt < 1 || a.qt > 64 || (64 % a.qt) != 0)
         return -1;
-    if (hits && (!a.hitCount || !a.hitKey || !a.hitVal)) return -1;
+    if (hits && (!a.hits.count || !a.hits.key || !a.hits.val)) return -1;
     return 0;
 }
 

@@ -640,7 +640,7 @@ int Batch::runImpl()
     pool_quarantine(false);
     Lap lap;
     DeviceGuard guard(device_);
-    haveResults_ = hitsHaveRun_ = hitsFetched_ = false;      // (a run that fails leaves nothing of the one before readable)
+    haveResults_ = hitsHaveRun_ = hitList_.result.fetched = false;      // (a run that fails leaves nothing of the one before readable)
     if (beginRun(guard.status)) return 1;
     if (hits_) return runReadHits();
     hostStrandCounts_[0] = hostStrandCounts_[1] = hostStrandCounts_[2] = hostStrandCounts_[3] = 0;

@@ -265,20 +265,13 @@ private:
     DevBuf<uint8_t> d_seedTmp_;                                   // rocPRIM scan scratch
     // ---- hit-list read batches (reads_hits.hip): every maximal run of columns scoring <= k, HW / DISTANCE,
     // reads up to 256 bases.  A Run is Peq rows, the HITS scans of every group (seeded where seedThreshold() allows k), and the
-    // finish on the device; nothing else of runImpl() runs.  The list starts at max(2^20, n_) runs and grows to the count of
-    // a Run that overflowed it (that Run scans again).
-    bool hits_ = false, hitsHaveRun_ = false, hitsFetched_ = false;
-    long long hitCap_ = 0, numHits_ = 0;
-    int hitSlots_ = 0;                                            // slots of all groups, then one per empty unit
-    DevBuf<int> d_hitSlotUnit_;                                   // [hitSlots_] slot -> unit, -1 = padding
-    DevBuf<unsigned long long> d_hitCount_, d_hitKey_, d_hitSkey_;
-    DevBuf<int> d_hitVal_, d_hitUnit_;
-    DevBuf<uint32_t> d_hitIdx_, d_hitSidx_, d_hitHead_, d_hitAt_;
-    DevBuf<long long> d_hitTotal_;
-    DevBuf<uint8_t> d_hitTmp_, d_hitOut_;
-    PinBuf h_hitCount_, h_hits_;
-    std::vector<unsigned long long> hostHitKey_; std::vector<int> hostHitVal_;   // the empty reads' hits, answered on the host
-    int growHitList(long long cap);
+    // finish on the device; nothing else of runImpl() runs.  The list (hit_list.hpp) starts at max(2^20, n_) runs and grows to
+    // the count of a Run that overflowed it (that Run scans again).
+    bool hits_ = false, hitsHaveRun_ = false;
+    HitListBuffers hitList_;
+    HitRows hostHits_;                                            // the empty reads' hits, answered on the host
+    DevBuf<int> d_hitSlotUnit_;                                   // slot -> unit, -1 = padding: all groups' slots, then one per empty unit
+    DevBuf<long long> d_hitTotal_;                                // hits of the stitched list
     int runReadHits();                                            // the whole Run of such a batch
     int scanGroupHits(ReadGroup& g, int slotBase);                // one group's runs appended to the list
     int hitsScanBanded(ReadGroup& g, int slotBase, const int* d_slotmap, int nlanes, int numSegments, int segLen, int warm);

@@ -5,7 +5,7 @@
 // sessions of the cells outside the kernel's envelope run meanwhile, scatters their results into the matrix and reduces
 // it to the best hits.  Results stay in HBM until view() asks for a part of them.  A hit-list batch appends the cells
 // within k instead (the scan, then the internal sessions' cells behind them) and finishes the list on the device
-// (cross_hits.hip): sorted into CSR order, target offsets, best hits from the list.
+// (hit_list.hpp, cross_hits.hip): sorted into CSR order, target offsets, best hits from the list.
 // A both-strand batch makes the pool of every query and its reverse complement on the device, gives mates
 // the slots s and s ^ 1 of their word group, and keeps a strand byte beside every cell, hit and best hit.
 // An occurrence batch (DESIGN.md §4h "Occurrence batches") is a hit-list batch whose entries are the maximal runs of
@@ -241,14 +241,17 @@ int CrossBatch::sizeResults()
         targetChunk_ = std::max(1024, (nt_ + 32767) / 32768);
         EDLIB_AMD_HIP(d_partial_.ensure((size_t)std::max(1, (nt_ + targetChunk_ - 1) / targetChunk_) * std::max<size_t>(nq, 1)));
     } else {
-        EDLIB_AMD_HIP(d_hcount_.ensure(1));
-        if (!h_hcount_.p) EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
-        EDLIB_AMD_HIP(d_htoff_.ensure(nt + 1));
         if (!occ_) EDLIB_AMD_HIP(d_bkey_.ensure(2 * (nt + nq)));
-        const long long need = std::max<long long>(1LL << 20, (long long)nq_ + nt_);
-        if (hitCap_ < need && growHits(need)) return 1;
+        if (sizeHitList(std::max<long long>(1LL << 20, (long long)nq_ + nt_))) return 1;
     }
     return 0;
+}
+
+int CrossBatch::sizeHitList(long long minCap)
+{
+    // (2^32 - 1 entries: the sort's index)
+    hitList_.configure("cross batch", occ_ ? "runs" : "hits", occ_ ? 5 : 3, 32, strands_, 0);
+    return hitList_.size((size_t)nt_, minCap, stream_);
 }
 
 int CrossBatch::shapeGroups(const std::vector<long long>& colsBelow)
@@ -417,7 +420,7 @@ int CrossBatch::setTargets(const char* targets, const long long* toffIn, int nt)
     otherCells_ = 0;
     nt_ = nt; numSorted_ = nt; sortedCols_ = tbytes;
     cells_ = (size_t)nq_ * (size_t)nt;
-    numHits_ = 0;
+    hitList_.n = hitList_.outN = 0;
     stats = EdlibAmdBatchStats{};
     stats.cells = qbytes_ * tbytes * (strands_ ? 2 : 1);
     if (sizeResults() || shapeGroups(colsBelow)) return 1;
@@ -449,21 +452,19 @@ int CrossBatch::gather(Batch& b, size_t n, int* vals, uint8_t* sbytes)
     return 0;
 }
 
-// one scan per word group (the Peq is built); a hit-list batch counts its hits from 0
+// one scan per word group (the Peq is built; a hit-list batch's counter is reset)
 int CrossBatch::scanGroups()
 {
-    if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
     for (auto& g : groups_) {
         CrossScanArgs a{};
         a.peq = g->d_peq.p; a.qlen = g->d_qlen.p; a.qperm = g->d_perm.p; a.qt = g->qt; a.numQueryTiles = g->tiles;
         a.tpk = d_tpk_.p; a.tdw = d_tdw_.p; a.tlen = d_tlen_.p; a.tperm = d_tperm_.p; a.numSorted = numSorted_;
         a.numQueries = nq_; a.kcfg = cfg_.k;
-        if (hits_) {
-            a.hitCount = d_hcount_.p; a.hitCap = (unsigned long long)hitCap_; a.hitKey = d_hkey_.p; a.hitVal = d_hval_.p;
-        } else {
+        if (hits_) a.hits = hitList_.list();
+        else {
             a.ed = d_mat_.p; a.nloc = d_mat_.p + cells_; a.end = d_mat_.p + 2 * cells_;
         }
-        a.strand = !strands_ ? nullptr : (hits_ ? d_hstrand_.p : d_smat_.p);
+        a.strand = !strands_ ? nullptr : (hits_ ? hitList_.byte.p : d_smat_.p);
         if (self_) {
             // (the condensed vector is one plane: numLocations and endLocation are 1 and length - 1 for NW)
             a.nloc = a.end = nullptr;
@@ -483,70 +484,14 @@ int CrossBatch::scanGroups()
     return 0;
 }
 
-// the hit list and its sort / CSR buffers for `cap` hits (what they held is gone)
-int CrossBatch::growHits(long long cap)
-{
-    hitCap_ = 0;
-    size_t tmp = 0;
-    hipError_t e = d_hkey_.alloc((size_t)cap);
-    if (e == hipSuccess) e = d_hval_.alloc((size_t)valPlanes() * (size_t)cap);
-    if (e == hipSuccess) e = d_hidx_.alloc((size_t)cap);
-    if (e == hipSuccess) e = d_skey_.alloc((size_t)cap);
-    if (e == hipSuccess) e = d_sidx_.alloc((size_t)cap);
-    if (e == hipSuccess) e = d_hout_.alloc(((size_t)valPlanes() + 1) * (size_t)cap);
-    if (e == hipSuccess && strands_) e = d_hstrand_.alloc((size_t)cap);
-    if (e == hipSuccess && strands_) e = d_hsout_.alloc((size_t)cap);
-    if (e == hipSuccess) e = cross_hits_sort_bytes(cap, nt_, &tmp);
-    if (e == hipSuccess) e = d_sortTmp_.alloc(tmp);
-    if (e == hipSuccess) e = launch_cross_hits_iota(d_hidx_.p, cap, stream_);
-    if (e != hipSuccess) {
-        set_error("cross batch: no room on the device for a hit list of %lld %s (%s)", cap, occ_ ? "runs" : "hits",
-                  hipGetErrorString(e));
-        return 1;
-    }
-    hitCap_ = cap;
-    return 0;
-}
-
-// after the scans and the internal sessions: the kernel's count (the sort needs it anyway); a count past capacity grows
-// the list to it and scans again, so later Runs of the batch fit.  Then the internal sessions' hits behind the kernel's,
-// and the list finished on the device.
+// after the scans and the internal sessions: the list settled (a count past capacity grows it and scans again, so later
+// Runs of the batch fit; the internal sessions' hits behind the kernel's) and finished on the device
 int CrossBatch::finishHits()
 {
-    unsigned long long* hc = reinterpret_cast<unsigned long long*>(h_hcount_.p);
-    EDLIB_AMD_HIP(hipMemcpyAsync(hc, d_hcount_.p, sizeof *hc, hipMemcpyDeviceToHost, stream_));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    const long long kernelHits = (long long)*hc, extra = (long long)xKey_.size(), total = kernelHits + extra;
-    if (total > 0xffffffffLL) {
-        set_error("cross batch: %lld %s, more than a hit list holds (2^32 - 1): lower k or split the batch", total,
-                  occ_ ? "runs" : "hits");
-        return 1;
-    }
-    if (total > hitCap_) {
-        if (growHits(total)) return 1;
-        if (kernelHits > 0 && scanGroups()) return 1;
-    }
-    if (extra > 0) {
-        const size_t cap = (size_t)hitCap_;
-        EDLIB_AMD_HIP(hipMemcpyAsync(d_hkey_.p + kernelHits, xKey_.data(), (size_t)extra * sizeof(unsigned long long),
-                                     hipMemcpyHostToDevice, stream_));
-        for (int f = 0; f < valPlanes(); ++f)
-            EDLIB_AMD_HIP(hipMemcpyAsync(d_hval_.p + f * cap + kernelHits, xVal_.data() + f * (size_t)extra,
-                                         (size_t)extra * sizeof(int), hipMemcpyHostToDevice, stream_));
-        if (strands_)
-            EDLIB_AMD_HIP(hipMemcpyAsync(d_hstrand_.p + kernelHits, xStrand_.data(), (size_t)extra, hipMemcpyHostToDevice, stream_));
-    }
-    size_t tmp = 0;
-    EDLIB_AMD_HIP(cross_hits_sort_bytes(total, nt_, &tmp));
-    if (tmp > d_sortTmp_.n) EDLIB_AMD_HIP(d_sortTmp_.alloc(tmp));
-    if (occ_)
-        EDLIB_AMD_HIP(launch_cross_occ_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
-                                              d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, stream_));
+    if (hitList_.settle(otherHits_, stream_, [&] { return scanGroups(); })) return 1;
+    if (occ_) EDLIB_AMD_HIP(launch_cross_occ_finish(hitList_, nt_, stream_));
     else
-        EDLIB_AMD_HIP(launch_cross_hits_finish(d_hkey_.p, d_hval_.p, hitCap_, total, nq_, nt_, d_hidx_.p, d_skey_.p, d_sidx_.p,
-                                               d_sortTmp_.p, d_sortTmp_.n, d_htoff_.p, d_hout_.p, d_bkey_.p, d_best_.p,
-                                               strands_ ? d_hstrand_.p : nullptr, d_hsout_.p, d_sbest_.p, stream_));
-    numHits_ = total;
+        EDLIB_AMD_HIP(launch_cross_hits_finish(hitList_, nq_, nt_, d_bkey_.p, d_best_.p, strands_ ? d_sbest_.p : nullptr, stream_));
     return 0;
 }
 
@@ -554,7 +499,6 @@ int CrossBatch::finishHits()
 // query, ascending firstEnd) re-keyed to the target's index, in that order behind what the last session left
 int CrossBatch::runOccurrenceSessions()
 {
-    std::vector<int> e5[5];
     for (size_t s = 0; s < outShared_.size(); ++s) {
         Batch& b = *outShared_[s];
         if (b.run()) return 1;
@@ -563,13 +507,12 @@ int CrossBatch::runOccurrenceSessions()
         const unsigned long long t = (unsigned long long)(uint32_t)outTargets_[s];
         for (int q = 0; q < rv.numUnits; ++q)
             for (long long i = rv.unitOffsets[q]; i < rv.unitOffsets[q + 1]; ++i) {
-                xKey_.push_back((t << 32) | (unsigned long long)(uint32_t)q);
-                e5[0].push_back(rv.firstEnd[i]); e5[1].push_back(rv.lastEnd[i]); e5[2].push_back(rv.editDistance[i]);
-                e5[3].push_back(rv.endLocation[i]); e5[4].push_back(rv.numLocations[i]);
+                otherHits_.key.push_back((t << 32) | (unsigned long long)(uint32_t)q);
+                const int v[5] = {rv.firstEnd[i], rv.lastEnd[i], rv.editDistance[i], rv.endLocation[i], rv.numLocations[i]};
+                for (int f = 0; f < 5; ++f) otherHits_.val[f].push_back(v[f]);
             }
         addSessionStats(b, true);
     }
-    for (int f = 0; f < 5; ++f) xVal_.insert(xVal_.end(), e5[f].begin(), e5[f].end());
     return 0;
 }
 
@@ -580,14 +523,14 @@ int CrossBatch::run()
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
-    if (beginRun(guard.status, {&mat_, &best_, &hitList_, &cellStrand_, &bestStrand_})) return 1;
+    if (beginRun(guard.status, {&mat_, &best_, &hitList_.result, &cellStrand_, &bestStrand_})) return 1;
     int* ed = d_mat_.p; int* nloc = hits_ ? nullptr : ed + cells_; int* end = hits_ ? nullptr : ed + 2 * cells_;
-    if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
+    if (hits_) EDLIB_AMD_HIP(hitList_.reset(stream_));
 
     // the cross kernel: Peq of every query, then one scan per word group
     if (scanRun(groups_, 8, [&] { return scanGroups(); })) return 1;
     // the other engines run on their own streams meanwhile
-    xKey_.clear(); xVal_.clear(); xStrand_.clear();
+    otherHits_.clear();
     if (occ_ && runOccurrenceSessions()) return 1;
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
@@ -625,16 +568,14 @@ int CrossBatch::run()
                 EDLIB_AMD_HIP(launch_cross_scatter_bytes(d_cells_.p, d_svals_.p, otherCells_, d_smat_.p, stream_));
             }
         } else {
-            // their cells within k, as [key], [ed][nloc][end]
-            std::vector<int> e3[3];
+            // their cells within k: ed, nloc, end
             for (long long i = 0; i < otherCells_; ++i) {
                 if (vals[3 * i] == -1) continue;
                 const long long c = otherCellIdx_[(size_t)i];
-                xKey_.push_back(((unsigned long long)(c / nq_) << 32) | (unsigned long long)(c % nq_));
-                for (int f = 0; f < 3; ++f) e3[f].push_back(vals[3 * i + f]);
-                if (strands_) xStrand_.push_back(svals[i]);
+                otherHits_.key.push_back(((unsigned long long)(c / nq_) << 32) | (unsigned long long)(c % nq_));
+                for (int f = 0; f < 3; ++f) otherHits_.val[f].push_back(vals[3 * i + f]);
+                if (strands_) otherHits_.byte.push_back(svals[i]);
             }
-            for (int f = 0; f < 3; ++f) xVal_.insert(xVal_.end(), e3[f].begin(), e3[f].end());
         }
     }
     if (hits_) {
@@ -679,18 +620,6 @@ int CrossBatch::view(int what, EdlibAmdCrossView* out)
     return 0;
 }
 
-int CrossBatch::fetchHits(int planes, int rows, size_t* offBytes)
-{
-    *offBytes = ((size_t)rows + 1) * sizeof(long long);
-    const size_t listBytes = (size_t)planes * (size_t)numHits_ * sizeof(int);
-    if (hitList_.fetched) return 0;
-    EDLIB_AMD_HIP(hitList_.fetch(d_htoff_.p, *offBytes, stream_, 0, *offBytes + listBytes));
-    EDLIB_AMD_HIP(hitList_.fetch(d_hout_.p, listBytes, stream_, *offBytes));
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-    hitList_.fetched = true;
-    return 0;
-}
-
 int CrossBatch::hitsView(EdlibAmdCrossHits* out)
 {
     if (occ_) { set_error("edlibAmdBatchCrossHits: not available on an occurrence batch (edlibAmdBatchCrossOccurrences has its results)"); return 1; }
@@ -703,13 +632,11 @@ int CrossBatch::hitsView(EdlibAmdCrossHits* out)
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    size_t offBytes = 0;
-    if (fetchHits(4, nt_, &offBytes)) return 1;
+    const int* l = nullptr;
     memset(out, 0, sizeof *out);
-    out->numQueries = nq_; out->numTargets = nt_; out->numHits = numHits_;
-    out->targetOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
-    const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
-    const size_t n = (size_t)numHits_;
+    if (hitList_.fetch(4, stream_, &out->targetOffsets, &l)) return 1;
+    out->numQueries = nq_; out->numTargets = nt_; out->numHits = hitList_.outN;
+    const size_t n = (size_t)hitList_.outN;
     out->query = l; out->editDistance = l + n; out->numLocations = l + 2 * n; out->endLocation = l + 3 * n;
     return 0;
 }
@@ -725,13 +652,11 @@ int CrossBatch::occurrencesView(EdlibAmdCrossOccurrences* out)
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    size_t offBytes = 0;
-    if (fetchHits(6, nt_, &offBytes)) return 1;
+    const int* l = nullptr;
     memset(out, 0, sizeof *out);
-    out->numQueries = nq_; out->numTargets = nt_; out->numHits = numHits_;
-    out->targetOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
-    const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
-    const size_t n = (size_t)numHits_;
+    if (hitList_.fetch(6, stream_, &out->targetOffsets, &l)) return 1;
+    out->numQueries = nq_; out->numTargets = nt_; out->numHits = hitList_.outN;
+    const size_t n = (size_t)hitList_.outN;
     out->query = l; out->firstEnd = l + n; out->lastEnd = l + 2 * n; out->editDistance = l + 3 * n;
     out->endLocation = l + 4 * n; out->numLocations = l + 5 * n;
     return 0;
@@ -750,11 +675,11 @@ int CrossBatch::strandsView(int what, EdlibAmdCrossStrands* out)
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    const size_t cellBytes = hits_ ? (size_t)numHits_ : cells_, bestBytes = (size_t)nt_ + (size_t)nq_;
-    if (fetchParts({{what & EDLIB_AMD_CROSS_MATRIX, &cellStrand_, hits_ ? d_hsout_.p : d_smat_.p, cellBytes},
+    const size_t cellBytes = hits_ ? (size_t)hitList_.outN : cells_, bestBytes = (size_t)nt_ + (size_t)nq_;
+    if (fetchParts({{what & EDLIB_AMD_CROSS_MATRIX, &cellStrand_, hits_ ? hitList_.byteOut.p : d_smat_.p, cellBytes},
                     {what & EDLIB_AMD_CROSS_BEST, &bestStrand_, d_sbest_.p, bestBytes}})) return 1;
     memset(out, 0, sizeof *out);
-    out->numQueries = nq_; out->numTargets = nt_; out->numHits = hits_ ? numHits_ : 0;
+    out->numQueries = nq_; out->numTargets = nt_; out->numHits = hits_ ? hitList_.outN : 0;
     if (what & EDLIB_AMD_CROSS_MATRIX) (hits_ ? out->hitStrand : out->cellStrand) = cellStrand_.h.p;
     if (what & EDLIB_AMD_CROSS_BEST) { out->bestQueryStrand = bestStrand_.h.p; out->bestTargetStrand = bestStrand_.h.p + nt_; }
     return 0;

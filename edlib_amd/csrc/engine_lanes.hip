@@ -33,17 +33,6 @@ int copy_offsets(const long long* in, int n, const char* what, std::vector<long 
     return 0;
 }
 
-hipError_t PinnedPart::fetch(const void* dev, size_t bytes, hipStream_t stream, size_t at, size_t room)
-{
-    if (fetched) return hipSuccess;
-    const size_t need = std::max(at + bytes, room);
-    if (h.n < need || !h.p) {
-        const hipError_t e = h.alloc(need);
-        if (e != hipSuccess) return e;
-    }
-    return bytes ? hipMemcpyAsync(h.p + at, dev, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
-}
-
 void PairPool::add(const char* q, long long qn, bool reverse, const char* t, long long tn)
 {
     if (!reverse) qp.insert(qp.end(), q, q + qn);

@@ -9,14 +9,7 @@
 
 namespace edlib_amd {
 
-// A part of the results in pinned host memory, fetched from the device when a view first asks for it after a Run.
-struct PinnedPart {
-    PinBuf h;
-    bool fetched = false;
-    // enqueues the D2H of `bytes` to h + at unless the part is fetched already (room: the bytes the whole part needs, where
-    // it is fetched in pieces); the caller sets `fetched` once the stream's synchronise succeeded
-    hipError_t fetch(const void* dev, size_t bytes, hipStream_t stream, size_t at = 0, size_t room = 0);
-};
+// (PinnedPart: common.hpp)
 struct WantedPart { int asked; PinnedPart* part; const void* dev; size_t bytes; };
 
 // The pairs of an internal pair Batch: the bytes of every pair replicated, query and target
@@ -183,29 +176,22 @@ private:
     PinnedPart mat_;
     // hit-list batches: nothing here scales with numQueries x numTargets; the list starts at max(2^20, nq + nt) entries
     // and grows to the count of a Run that overflowed it (that Run scans again)
+    // (hit_list.hpp): three planes as appended (editDistance, numLocations, endLocation), [4][n] in CSR order with the
+    // query in front, offsets [nt + 1]; both strands: a strand byte per entry
     bool hits_ = false;
-    long long hitCap_ = 0, numHits_ = 0;
-    DevBuf<unsigned long long> d_hcount_, d_hkey_, d_skey_;
-    DevBuf<int> d_hval_, d_hout_;                 // [3][hitCap_] as appended; [4][numHits_] in CSR order
-    // occurrence batches (hits_ is set too): an entry is a run, d_hval_ [5][hitCap_] (firstEnd, lastEnd, editDistance,
-    // endLocation, numLocations), d_hout_ [6][numHits_] (query in front), xVal_ five planes; no best hits
+    // occurrence batches (hits_ is set too): an entry is a run, five planes (firstEnd, lastEnd, editDistance, endLocation,
+    // numLocations), [6][n] finished; no best hits
     bool occ_ = false;
-    int valPlanes() const { return occ_ ? 5 : 3; }
-    DevBuf<uint32_t> d_hidx_, d_sidx_;
-    DevBuf<uint8_t> d_sortTmp_;
-    DevBuf<long long> d_htoff_;                   // [nt + 1]
-    PinBuf h_hcount_;
-    PinnedPart hitList_;
+    HitListBuffers hitList_;
+    int sizeHitList(long long minCap);            // the list configured for this kind of batch, of nt_ rows
     std::vector<long long> otherCellIdx_;         // cells of the internal sessions (t * nq + q), host side
-    std::vector<unsigned long long> xKey_;        // their cells within k of the last Run
-    std::vector<int> xVal_;
+    HitRows otherHits_;                           // their cells within k (occurrence batches: their runs) of the last Run
     // both strands: a strand byte (bit 0 reverse complement, bit 1 the other strand reaches the same distance) per cell
     // [nt][nq] or per hit, and per best hit [nt] then [nq]
     bool strands_ = false;
-    DevBuf<uint8_t> d_smat_, d_sbest_, d_hstrand_, d_hsout_, d_svals_;
+    DevBuf<uint8_t> d_smat_, d_sbest_, d_svals_;
     PinnedPart cellStrand_, bestStrand_;
     PinBuf h_svals_;
-    std::vector<uint8_t> xStrand_;                // strand bytes of xKey_
     // self batches: d_mat_ is the condensed vector [n (n - 1) / 2] (cells_), longPairs_ the i < j pairs outside the
     // kernel's envelope; selfOther_ the keys (i << 32) | j of the pairs answered off the kernel -- first the selfEmpty_
     // pairs with an empty sequence (distance: the other's length), then the pairs of longPairs_
@@ -220,11 +206,9 @@ private:
     // longPairs_
     int runSelf();
     int gather(Batch& b, size_t n, int* vals, uint8_t* sbytes);
-    int runOccurrenceSessions();                  // the internal hit-list sessions' runs into xKey_ / xVal_
+    int runOccurrenceSessions();                  // the internal hit-list sessions' runs into otherHits_
     int scanGroups();
-    int growHits(long long cap);
-    int finishHits();
-    int fetchHits(int planes, int rows, size_t* offBytes);       // the offsets of `rows` rows, then planes x numHits_ ints
+    int finishHits();                             // the list settled (otherHits_ behind the scan's) and finished on the device
 };
 // tile width of a word group: the lanes a tile shape leaves idle decide it (engine_cross.hip)
 int choose_qt(long long nq, long long nt, int minQt = 1);

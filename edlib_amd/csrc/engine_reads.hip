@@ -583,31 +583,6 @@ int Batch::runGroupExact(ReadGroup& g)
 
 // ------------------------------------------------------- hit-list read batches (reads_hits.hip)
 
-int Batch::growHitList(long long cap)
-{
-    hitCap_ = 0;
-    size_t tmp = 0;
-    const size_t c = (size_t)cap;
-    hipError_t e = cap > 0x7fffffffLL ? hipErrorOutOfMemory : d_hitKey_.alloc(c);
-    if (e == hipSuccess) e = d_hitVal_.alloc(4 * c);
-    if (e == hipSuccess) e = d_hitIdx_.alloc(c);
-    if (e == hipSuccess) e = d_hitSkey_.alloc(c);
-    if (e == hipSuccess) e = d_hitSidx_.alloc(c);
-    if (e == hipSuccess) e = d_hitHead_.alloc(c);
-    if (e == hipSuccess) e = d_hitAt_.alloc(c);
-    if (e == hipSuccess) e = d_hitUnit_.alloc(c);
-    if (e == hipSuccess) e = d_hitOut_.alloc(((size_t)n_ + 1) * sizeof(long long) + 5 * c * sizeof(int));
-    if (e == hipSuccess) e = read_hits_scratch_bytes(cap, n_, &tmp);
-    if (e == hipSuccess) e = d_hitTmp_.alloc(tmp);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("hit-list read batch: no room on the device for a hit list of %lld runs (%s)", cap, hipGetErrorString(e));
-        return 1;
-    }
-    hitCap_ = cap;
-    return 0;
-}
-
 // The banded HITS scan of `nlanes` lanes of a group (all of its slots, or the slots of d_slotmap) at the caller's k
 int Batch::hitsScanBanded(ReadGroup& g, int slotBase, const int* d_slotmap, int nlanes, int numSegments, int segLen, int warm)
 {
@@ -617,7 +592,7 @@ int Batch::hitsScanBanded(ReadGroup& g, int slotBase, const int* d_slotmap, int 
     a.numSegments = numSegments; a.segLen = segLen; a.warm = warm;
     a.cap = 1;                                                 // (a live lane; the records of the other scans are not written)
     a.kcap = 0x3fffffff; a.wordSteps = d_wordSteps_.p;
-    a.hits = HitList{d_hitKey_.p, d_hitVal_.p, hitCap_, d_hitCount_.p, slotBase};
+    a.hits = hitList_.list(); a.slotBase = slotBase;
     scanTimerStart();
     EDLIB_AMD_HIP(launch_scan_reads_hits(g.nwords, syms_, a, stream_));
     scanTimerStop();
@@ -638,7 +613,7 @@ int Batch::scanGroupHits(ReadGroup& g, int slotBase)
     a.peq = g.d_peq.p; a.qlen = g.d_qlen.p; a.perm = g.d_perm.p; a.tpk = d_tpk_.p; a.targetLength = T;
     a.seedOff = d_seedOff_.p; a.seedPos = d_seedPos_.p; a.nslots = g.nslots; a.k = cfg_.k;
     a.backSlots = d_back.p; a.backCount = backCount; a.wordSteps = d_wordSteps_.p;
-    a.hits = HitList{d_hitKey_.p, d_hitVal_.p, hitCap_, d_hitCount_.p, slotBase};
+    a.hits = hitList_.list(); a.slotBase = slotBase;
     scanTimerStart();
     EDLIB_AMD_HIP(launch_seed_verify_hits(g.nwords, a, stream_));
     scanTimerStop();
@@ -660,28 +635,26 @@ int Batch::runReadHits()
 {
     const int T = tlen(0);
     stats.path |= 1;
-    if (!d_hitCount_.p) {
+    if (!d_hitSlotUnit_.p) {
         // the batch-wide slot table: the groups' slots one after the other, then a slot per empty unit
         std::vector<int> slotUnit;
         for (auto& gp : groups_) slotUnit.insert(slotUnit.end(), gp->perm.begin(), gp->perm.end());
-        slotUnit.insert(slotUnit.end(), emptyUnits_.begin(), emptyUnits_.end());
-        hitSlots_ = (int)slotUnit.size();
+        // empty sequences are answered here: an empty read hits once, the whole target at distance 0; an empty target has no hit
+        for (int u : emptyUnits_) {
+            if (T > 0 && qlen(u) == 0) {
+                hostHits_.key.push_back((unsigned long long)(uint32_t)slotUnit.size() << 32);
+                hostHits_.val[0].push_back(T - 1); hostHits_.val[1].push_back(0); hostHits_.val[2].push_back(0); hostHits_.val[3].push_back(T);
+            }
+            slotUnit.push_back(u);
+        }
         EDLIB_AMD_HIP(d_hitSlotUnit_.alloc(slotUnit.size()));
         if (!slotUnit.empty())
             EDLIB_AMD_HIP(hipMemcpy(d_hitSlotUnit_.p, slotUnit.data(), slotUnit.size() * sizeof(int), hipMemcpyHostToDevice));
-        EDLIB_AMD_HIP(d_hitCount_.alloc(1)); EDLIB_AMD_HIP(d_hitTotal_.alloc(1));
-        EDLIB_AMD_HIP(h_hitCount_.alloc(2 * sizeof(unsigned long long)));
-        // empty sequences are answered here: an empty read hits once, the whole target at distance 0; an empty target has no hit
-        int base = hitSlots_ - (int)emptyUnits_.size();
-        for (size_t i = 0; i < emptyUnits_.size(); ++i)
-            if (T > 0 && qlen(emptyUnits_[i]) == 0) hostHitKey_.push_back((unsigned long long)(uint32_t)(base + (int)i) << 32);
-        const size_t ne = hostHitKey_.size();
-        hostHitVal_.resize(4 * ne);
-        for (size_t i = 0; i < ne; ++i) { hostHitVal_[i] = T - 1; hostHitVal_[ne + i] = 0; hostHitVal_[2 * ne + i] = 0; hostHitVal_[3 * ne + i] = T; }
+        EDLIB_AMD_HIP(d_hitTotal_.alloc(1));
+        // (2^31 - 1 entries: the finish kernels index with int)
+        hitList_.configure("hit-list read batch", "runs", 4, 31, false, kReadHitsExtraBytes);
+        if (hitList_.size((size_t)n_, std::max<long long>(1LL << 20, n_), stream_)) return 1;
     }
-    if (hitCap_ == 0 && growHitList(std::max<long long>(1LL << 20, n_))) return 1;
-    const size_t ne = hostHitKey_.size();
-    unsigned long long* hc = reinterpret_cast<unsigned long long*>(h_hitCount_.p);
     if (packTarget()) return 1;
     bool seed = false;
     for (auto& gp : groups_) { const int ks = seedThreshold(*gp, false); seed = seed || (ks >= 0 && cfg_.k <= ks); }
@@ -690,48 +663,25 @@ int Batch::runReadHits()
         EDLIB_AMD_HIP(launch_build_peq_reads(gp->nwords, syms_, d_qpool_.p, d_qoff_.p, gp->d_perm.p, gp->nslots, d_eqtbl_.p,
                                              d_presence_.p, cfg_.k, gp->d_peq.p, gp->d_qlen.p, gp->d_kinit.p,
                                              gp->d_alphaExtra.p, stream_));
-    long long total = 0;
-    for (int attempt = 0; ; ++attempt) {
-        // the host's runs first, the scans append behind them
-        hc[1] = ne;
-        EDLIB_AMD_HIP(hipMemcpyAsync(d_hitCount_.p, hc + 1, sizeof *hc, hipMemcpyHostToDevice, stream_));
-        if (ne) {
-            EDLIB_AMD_HIP(hipMemcpyAsync(d_hitKey_.p, hostHitKey_.data(), ne * sizeof(unsigned long long), hipMemcpyHostToDevice, stream_));
-            for (int f = 0; f < 4; ++f)
-                EDLIB_AMD_HIP(hipMemcpyAsync(d_hitVal_.p + f * (size_t)hitCap_, hostHitVal_.data() + f * ne, ne * sizeof(int),
-                                             hipMemcpyHostToDevice, stream_));
-        }
+    auto scanGroups = [&]() -> int {
         int slotBase = 0;
         for (auto& gp : groups_) {
             if (scanGroupHits(*gp, slotBase)) return 1;
             slotBase += gp->nslots;
         }
-        EDLIB_AMD_HIP(hipMemcpyAsync(hc, d_hitCount_.p, sizeof *hc, hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        total = (long long)*hc;
-        if (total <= hitCap_) break;
-        // more runs than the list holds: it grows to the count and the scans run once more (later Runs fit)
-        if (attempt > 0) { set_error("hit-list read batch: %lld runs after the list grew to %lld", total, hitCap_); return 1; }
-        if (total > 0x7fffffffLL) {
-            set_error("hit-list read batch: %lld runs, more than a hit list holds (2^31 - 1): lower k or split the batch", total);
-            return 1;
-        }
-        if (growHitList(total)) return 1;
-    }
-    long long* uoffDev = reinterpret_cast<long long*>(d_hitOut_.p);
-    numHits_ = 0;
-    if (total > 0) {
-        size_t tmp = 0;
-        EDLIB_AMD_HIP(read_hits_scratch_bytes(total, n_, &tmp));
-        if (tmp > d_hitTmp_.n) EDLIB_AMD_HIP(d_hitTmp_.alloc(tmp));
-        EDLIB_AMD_HIP(launch_read_hits_finish(d_hitKey_.p, d_hitVal_.p, hitCap_, total, d_hitSlotUnit_.p, n_, d_hitIdx_.p,
-                                              d_hitSkey_.p, d_hitSidx_.p, d_hitHead_.p, d_hitAt_.p, d_hitUnit_.p, d_hitTotal_.p,
-                                              d_hitTmp_.p, d_hitTmp_.n, d_hitOut_.p, stream_));
-        EDLIB_AMD_HIP(hipMemcpyAsync(hc, d_hitTotal_.p, sizeof(long long), hipMemcpyDeviceToHost, stream_));
-    } else EDLIB_AMD_HIP(hipMemsetAsync(uoffDev, 0, ((size_t)n_ + 1) * sizeof(long long), stream_));
+        return 0;
+    };
+    EDLIB_AMD_HIP(hitList_.reset(stream_));
+    if (scanGroups() || hitList_.settle(hostHits_, stream_, scanGroups)) return 1;
+    unsigned long long* total = hitList_.pinnedWord();
+    hitList_.outN = 0;
+    if (hitList_.n > 0) {
+        EDLIB_AMD_HIP(launch_read_hits_finish(hitList_, d_hitSlotUnit_.p, n_, d_hitTotal_.p, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(total, d_hitTotal_.p, sizeof(long long), hipMemcpyDeviceToHost, stream_));
+    } else EDLIB_AMD_HIP(hipMemsetAsync(hitList_.off(), 0, ((size_t)n_ + 1) * sizeof(long long), stream_));
     if (banded_ && !groups_.empty() && enqueueWordSteps()) return 1;
     if (endRun()) return 1;
-    if (total > 0) numHits_ = (long long)*hc;
+    if (hitList_.n > 0) hitList_.outN = (long long)*total;
     stats.algo_bytes = 0;
     hitsHaveRun_ = true;
     return 0;
@@ -748,18 +698,13 @@ int Batch::hitsView(EdlibAmdReadHits* out)
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    const size_t offBytes = ((size_t)n_ + 1) * sizeof(long long), bytes = offBytes + 5 * (size_t)numHits_ * sizeof(int);
-    if (!hitsFetched_) {
-        if (h_hits_.n < bytes || !h_hits_.p) EDLIB_AMD_HIP(h_hits_.alloc(bytes));
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_hits_.p, d_hitOut_.p, bytes, hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        hitsFetched_ = true;
-    }
+    const long long* off = nullptr;
+    const int* l = nullptr;
+    if (hitList_.fetch(5, stream_, &off, &l)) return 1;
     memset(out, 0, sizeof *out);
-    out->numUnits = n_; out->numHits = numHits_;
-    out->unitOffsets = reinterpret_cast<const long long*>(h_hits_.p);
-    const int* l = reinterpret_cast<const int*>(h_hits_.p + offBytes);
-    const size_t n = (size_t)numHits_;
+    out->numUnits = n_; out->numHits = hitList_.outN;
+    out->unitOffsets = off;
+    const size_t n = (size_t)hitList_.outN;
     out->firstEnd = l; out->lastEnd = l + n; out->editDistance = l + 2 * n; out->endLocation = l + 3 * n; out->numLocations = l + 4 * n;
     return 0;
 }

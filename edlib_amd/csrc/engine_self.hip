@@ -4,7 +4,7 @@
 // query slots, and cuts every query tile's range of wanted target tiles into work items of about equal trip counts.  A
 // Run builds the Peq rows, scans the items of every group, lets the internal pair batch take the pairs outside the
 // kernel's envelope, and reduces the nearest other sequence of each on the device.  The pack, the Peq build, the hit
-// list and its finish are the cross batch's own (engine_cross.hip, cross_hits.hip).
+// list and its finish are the cross batch's own (engine_cross.hip, hit_list.hpp, cross_hits.hip).
 // A both-strand self batch reports for every pair i < j the better of NW(seq i, seq j) and NW(revcomp(seq i), seq j).  The
 // kernel reverse-complements the row sequence, the shorter one, which is the same only under the complement condition
 // below; a set that fails it goes through the pair batch whole, in index order.
@@ -97,10 +97,8 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
     if (!hits_) EDLIB_AMD_HIP(d_mat_.alloc(std::max<size_t>(cells_, 1)));
     else {
         EDLIB_AMD_HIP(d_best_.alloc(6 * (size_t)n));
-        EDLIB_AMD_HIP(d_hcount_.alloc(1)); EDLIB_AMD_HIP(h_hcount_.alloc(sizeof(unsigned long long)));
-        EDLIB_AMD_HIP(d_htoff_.alloc((size_t)n + 1));
         EDLIB_AMD_HIP(d_bkey_.alloc(4 * (size_t)n));
-        if (growHits(std::max<long long>(1LL << 20, 2LL * n))) return 1;
+        if (sizeHitList(std::max<long long>(1LL << 20, 2LL * n))) return 1;
     }
 
     // ---- the kernel's share
@@ -257,8 +255,8 @@ int CrossBatch::runSelf()
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
-    if (beginRun(guard.status, {&mat_, &near_, &hitList_, &cellStrand_, &bestStrand_})) return 1;
-    if (hits_) EDLIB_AMD_HIP(hipMemsetAsync(d_hcount_.p, 0, sizeof(unsigned long long), stream_));
+    if (beginRun(guard.status, {&mat_, &near_, &hitList_.result, &cellStrand_, &bestStrand_})) return 1;
+    if (hits_) EDLIB_AMD_HIP(hitList_.reset(stream_));
     // the pairs outside the length window are visited by no work item and are in no pair batch: -1 from here
     else if (cfg_.k >= 0 && cells_ > 0) {
         EDLIB_AMD_HIP(hipMemsetAsync(d_mat_.p, 0xff, cells_ * sizeof(int), stream_));
@@ -266,7 +264,7 @@ int CrossBatch::runSelf()
     }
 
     if (scanRun(groups_, 8, [&] { return scanGroups(); })) return 1;
-    xKey_.clear(); xVal_.clear(); xStrand_.clear();
+    otherHits_.clear();
     if (otherCells_ > 0) {
         int* vals = reinterpret_cast<int*>(h_vals_.p);
         uint8_t* svals = strands_ ? h_svals_.p : nullptr;
@@ -293,15 +291,13 @@ int CrossBatch::runSelf()
                 EDLIB_AMD_HIP(launch_cross_scatter_bytes(d_cells_.p, d_svals_.p, otherCells_, d_smat_.p, stream_));
             }
         } else {
-            // their pairs within k behind the kernel's, as [key], [ed][nloc][end] (NW: one location, the last column)
-            std::vector<int> e3[3];
+            // their pairs within k: ed, nloc, end (NW: one location, the last column; only the distance is reported)
             for (long long c = 0; c < otherCells_; ++c) {
                 if (vals[c] == -1) continue;
-                xKey_.push_back(selfOther_[(size_t)c]);
-                e3[0].push_back(vals[c]); e3[1].push_back(1); e3[2].push_back(-1);      // (only the distance is reported)
-                if (strands_) xStrand_.push_back(svals[c]);
+                otherHits_.key.push_back(selfOther_[(size_t)c]);
+                otherHits_.val[0].push_back(vals[c]); otherHits_.val[1].push_back(1); otherHits_.val[2].push_back(-1);
+                if (strands_) otherHits_.byte.push_back(svals[c]);
             }
-            for (int f = 0; f < 3; ++f) xVal_.insert(xVal_.end(), e3[f].begin(), e3[f].end());
         }
     }
     if (hits_) {
@@ -350,13 +346,11 @@ int CrossBatch::selfHitsView(EdlibAmdSelfHits* out)
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     // the finished list is [4][numHits] (partner, editDistance, numLocations, endLocation): the first two planes travel
-    size_t offBytes = 0;
-    if (fetchHits(2, nq_, &offBytes)) return 1;
+    const int* l = nullptr;
     memset(out, 0, sizeof *out);
-    out->numSequences = nq_; out->numHits = numHits_;
-    out->rowOffsets = reinterpret_cast<const long long*>(hitList_.h.p);
-    const int* l = reinterpret_cast<const int*>(hitList_.h.p + offBytes);
-    out->partner = l; out->editDistance = l + (size_t)numHits_;
+    if (hitList_.fetch(2, stream_, &out->rowOffsets, &l)) return 1;
+    out->numSequences = nq_; out->numHits = hitList_.outN;
+    out->partner = l; out->editDistance = l + (size_t)hitList_.outN;
     return 0;
 }
 
@@ -372,11 +366,11 @@ int CrossBatch::selfStrandsView(int what, EdlibAmdSelfStrands* out)
     pool_quarantine(false);
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
-    const size_t pairBytes = hits_ ? (size_t)numHits_ : cells_;
-    if (fetchParts({{what & EDLIB_AMD_SELF_DISTANCES, &cellStrand_, hits_ ? d_hsout_.p : d_smat_.p, pairBytes},
+    const size_t pairBytes = hits_ ? (size_t)hitList_.outN : cells_;
+    if (fetchParts({{what & EDLIB_AMD_SELF_DISTANCES, &cellStrand_, hits_ ? hitList_.byteOut.p : d_smat_.p, pairBytes},
                     {what & EDLIB_AMD_SELF_NEAREST, &bestStrand_, d_sbest_.p + 2 * (size_t)nq_, (size_t)nq_}})) return 1;
     memset(out, 0, sizeof *out);
-    out->numSequences = nq_; out->numPairs = (long long)cells_; out->numHits = hits_ ? numHits_ : 0;
+    out->numSequences = nq_; out->numPairs = (long long)cells_; out->numHits = hits_ ? hitList_.outN : 0;
     if (what & EDLIB_AMD_SELF_DISTANCES) (hits_ ? out->hitStrand : out->pairStrand) = cellStrand_.h.p;
     if (what & EDLIB_AMD_SELF_NEAREST) out->nearestStrand = bestStrand_.h.p;
     return 0;

@@ -1,12 +1,12 @@
 // reads_hits.hip -- hit-list read batches: every maximal run of target columns where a read scores <= k.
 //   * the HITS instantiations of the banded HW scan (reads_scan.hpp) and of the seed + verify kernel (reads_seed.hpp): the
 //     threshold stays at min(k, m), each lane follows its open run in registers and appends closed runs to one device list;
-//   * the finish: the list's keys go from slots to units, rocPRIM's radix sort orders them by (unit, firstEnd), runs that meet
-//     at a segment boundary are stitched, and the offsets per unit come from the stitched list.
-// A translation unit of its own: the other scans carry none of it, and rocPRIM's headers are most of its compile time.
+//   * the read batch's own part of the finish: the list's keys go from slots to units before the list's sort (hit_list.hpp)
+//     orders them by (unit, firstEnd), runs that meet at a segment boundary are stitched, and the offsets per unit come from
+//     the stitched list.
+// A translation unit of its own: the other scans carry none of it.
 #include "reads_seed.hpp"
 
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 namespace edlib_amd {
@@ -55,37 +55,15 @@ hipError_t launch_seed_verify_hits(int nwords, const SeedArgs& a, hipStream_t st
 
 // ------------------------------------------------------------------ the finish
 
-// key bits the sort looks at: firstEnd and as many unit bits as numUnits (the padding's key) needs
-static unsigned key_end_bit(int numUnits)
-{
-    unsigned b = 0;
-    while (b < 31 && (1u << b) <= (unsigned)numUnits) ++b;
-    return 32 + b;
-}
-
-hipError_t read_hits_scratch_bytes(long long n, int numUnits, size_t* bytes)
-{
-    *bytes = 0;
-    if (n <= 0) return hipSuccess;
-    size_t a = 0, b = 0;
-    hipError_t e = rocprim::radix_sort_pairs(nullptr, a, (const u64*)nullptr, (u64*)nullptr, (const u32*)nullptr,
-                                             (u32*)nullptr, (size_t)n, 0u, key_end_bit(numUnits));
-    if (e != hipSuccess) return e;
-    e = rocprim::exclusive_scan(nullptr, b, (const u32*)nullptr, (u32*)nullptr, 0u, (size_t)n, rocprim::plus<u32>());
-    *bytes = a > b ? a : b;
-    return e;
-}
-
 // slot keys -> unit keys; a padding slot (it scans a one-symbol read that nobody asked for) sorts behind every unit
 __global__ void __launch_bounds__(256)
-read_hits_keys_kernel(u64* __restrict__ key, long long n, const int* __restrict__ slotUnit, int numUnits, u32* __restrict__ idx)
+read_hits_keys_kernel(u64* __restrict__ key, long long n, const int* __restrict__ slotUnit, int numUnits)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const u64 k = key[i];
     const int u = slotUnit[(u32)(k >> 32)];
     key[i] = ((u64)(u32)(u < 0 ? numUnits : u) << 32) | (u32)k;
-    idx[i] = (u32)i;
 }
 
 // head[i] = 1: sorted run i starts a hit (it is no padding and does not continue the run before it)
@@ -149,28 +127,32 @@ read_hits_offsets_kernel(const int* __restrict__ outUnit, const long long* __res
     uoff[u] = lo;
 }
 
-hipError_t launch_read_hits_finish(u64* key, const int* val, long long cap, long long n, const int* slotUnit, int numUnits,
-                                   u32* idx, u64* skey, u32* sidx, u32* head, u32* at, int* outUnit, long long* total,
-                                   void* tmp, size_t tmpBytes, void* out, hipStream_t stream)
+hipError_t launch_read_hits_finish(HitListBuffers& hl, const int* slotUnit, int numUnits, long long* total, hipStream_t stream)
 {
+    const long long n = hl.n, cap = hl.cap;
     if (n <= 0 || n > 0x7fffffffLL) return hipErrorInvalidValue;
-    long long* uoff = reinterpret_cast<long long*>(out);
-    int* arrays = reinterpret_cast<int*>(uoff + numUnits + 1);
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(read_hits_keys_kernel, dim3(nb), dim3(256), 0, stream, key, n, slotUnit, numUnits, idx);
-    size_t bytes = tmpBytes;
-    hipError_t e = rocprim::radix_sort_pairs(tmp, bytes, (const u64*)key, skey, (const u32*)idx, sidx, (size_t)n, 0u,
-                                             key_end_bit(numUnits), stream);
+    u32* head = reinterpret_cast<u32*>(hl.extra.p);
+    u32* at = head + cap;
+    int* outUnit = reinterpret_cast<int*>(at + cap);
+    size_t scanBytes = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, scanBytes, (const u32*)nullptr, (u32*)nullptr, 0u, (size_t)n, rocprim::plus<u32>());
+    if (e == hipSuccess) e = hl.needScratch(scanBytes);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(read_hits_heads_kernel, dim3(nb), dim3(256), 0, stream, skey, sidx, val, n, numUnits, head);
-    bytes = tmpBytes;
-    e = rocprim::exclusive_scan(tmp, bytes, (const u32*)head, at, 0u, (size_t)n, rocprim::plus<u32>(), stream);
+    const unsigned nb = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(read_hits_keys_kernel, dim3(nb), dim3(256), 0, stream, hl.key.p, n, slotUnit, numUnits);
+    e = hl.sort((long long)numUnits + 1, stream);              // (the padding's key is numUnits)
+    if (e != hipSuccess) return e;
+    const u64* skey = hl.skey.p;
+    const u32* sidx = hl.sidx.p;
+    hipLaunchKernelGGL(read_hits_heads_kernel, dim3(nb), dim3(256), 0, stream, skey, sidx, hl.val.p, n, numUnits, head);
+    scanBytes = hl.tmp.n;
+    e = rocprim::exclusive_scan(hl.tmp.p, scanBytes, (const u32*)head, at, 0u, (size_t)n, rocprim::plus<u32>(), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(read_hits_total_kernel, dim3(1), dim3(1), 0, stream, head, at, n, total);
-    hipLaunchKernelGGL(read_hits_stitch_kernel, dim3(nb), dim3(256), 0, stream, skey, sidx, val, cap, n, numUnits, head, at,
-                       total, arrays, outUnit);
+    hipLaunchKernelGGL(read_hits_stitch_kernel, dim3(nb), dim3(256), 0, stream, skey, sidx, hl.val.p, cap, n, numUnits, head, at,
+                       total, hl.out(), outUnit);
     hipLaunchKernelGGL(read_hits_offsets_kernel, dim3((unsigned)((numUnits + 1 + 255) / 256)), dim3(256), 0, stream,
-                       outUnit, total, numUnits, uoff);
+                       outUnit, total, numUnits, hl.off());
     return hipGetLastError();
 }
 

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hit_list.hpp"
+
 namespace edlib_amd {
 
 constexpr int kMaxReadWords = 8;      // queries up to 256 symbols: one kernel instance per word count, every mode
@@ -16,15 +18,9 @@ constexpr int kFilterFromWords = 13;        // HW queries of this many words and
 inline int read_group_words(int m) { const int w = (m + 31) / 32; return w <= kMaxReadWords ? w : (w <= 10 ? 10 : (w <= 12 ? 12 : (w <= 14 ? 14 : (w <= 16 ? 16 : (w <= 24 ? 24 : 32))))); }
 constexpr int kLanes = 64;            // wave64, hard-coded (gfx950)
 
-// Hit-list read batches (reads_hits.hip): the device list the HITS scans append closed runs of columns
-// scoring <= k to.  count may pass cap (nothing is written past it): the host grows the list to the count and scans again.
-struct HitList {
-    unsigned long long* key;     // [cap] (slotBase + slot) << 32 | firstEnd
-    int* val;                    // [4][cap] lastEnd, editDistance, endLocation, numLocations of the run
-    long long cap;
-    unsigned long long* count;   // runs appended so far
-    int slotBase;                // the launch's group starts at this slot of the batch-wide slot table
-};
+// Hit-list read batches (reads_hits.hip): the HITS scans append closed runs of columns scoring <= k to the
+// device list (hit_list.hpp) with the key (slotBase + slot) << 32 | firstEnd and four planes: lastEnd, editDistance,
+// endLocation, numLocations of the run.
 
 // Everything the scan kernel needs; plain pointers into HBM.
 struct ReadScanArgs {
@@ -59,6 +55,7 @@ struct ReadScanArgs {
     int filter;               // banded HW kernel: 1 = fixed threshold, segPos lists the 16-column BLOCKS that hold a column
                               // scoring <= kinit (each once), segCnt their number (piece filter of long reads)
     HitList hits;             // HITS instantiation of the banded kernel only (launch_scan_reads_hits)
+    int slotBase;             // ... the launch's group starts at this slot of the batch-wide slot table
     int bottomAligned;        // scan_reads_kernel, HW only: peq was built with bottomAlign (row m-1 at bit 31 of the last word)
 };
 
@@ -116,6 +113,7 @@ struct SeedArgs {
     int* backSlots; int* backCount;                // slots handed back to the banded scan
     unsigned long long* wordSteps;                 // += word-columns verified
     HitList hits;                                  // HITS variant only (launch_seed_verify_hits): runs instead of best / total / pos / flags
+    int slotBase;                                  // ... the group's first slot in the batch-wide slot table
 };
 
 hipError_t seed_index_scratch_bytes(size_t* bytes);
@@ -153,15 +151,12 @@ hipError_t launch_pick_slot_records(const int* slots, int n, const int* flags, c
 hipError_t launch_scan_reads_hits(int nwords, int syms, const ReadScanArgs& a, hipStream_t stream);
 // seed_verify_kernel at threshold a.k with runs instead of the best-16 record; same hand-back list
 hipError_t launch_seed_verify_hits(int nwords, const SeedArgs& a, hipStream_t stream);
-// The finish of a Run: n appended runs -> hits per unit (CSR).  slotUnit: batch-wide slot -> unit, -1 = padding.
-//   keys become (unit << 32) | firstEnd and are sorted (rocPRIM radix sort); runs of a unit that meet at a segment boundary
-//   (lastEnd + 1 == next firstEnd) are stitched; out = [numUnits + 1] long long unitOffsets, then firstEnd, lastEnd,
-//   editDistance, endLocation, numLocations as five int arrays of *total entries each (one block for the copy).
-// idx, sidx, head, at: [n] dwords; skey: [n]; outUnit: [n] ints; total: one long long; tmp: read_hits_scratch_bytes()
-hipError_t read_hits_scratch_bytes(long long n, int numUnits, size_t* bytes);
-hipError_t launch_read_hits_finish(unsigned long long* key, const int* val, long long cap, long long n, const int* slotUnit,
-                                   int numUnits, uint32_t* idx, unsigned long long* skey, uint32_t* sidx, uint32_t* head,
-                                   uint32_t* at, int* outUnit, long long* total, void* tmp, size_t tmpBytes, void* out,
-                                   hipStream_t stream);
+// The finish of a Run over the settled list (hit_list.hpp).  slotUnit: batch-wide slot -> unit, -1 = padding.
+//   keys become (unit << 32) | firstEnd and are sorted; runs of a unit that meet at a segment boundary (lastEnd + 1 == next
+//   firstEnd) are stitched into hl.out() as firstEnd, lastEnd, editDistance, endLocation, numLocations, five int arrays of
+//   *total entries each, and hl.off() [numUnits + 1] comes from the stitched list's units.
+// hl.extra: kReadHitsExtraBytes per entry (head, at: dwords; outUnit: ints); total: one long long
+constexpr int kReadHitsExtraBytes = 12;
+hipError_t launch_read_hits_finish(HitListBuffers& hl, const int* slotUnit, int numUnits, long long* total, hipStream_t stream);
 
 }  // namespace edlib_amd

@@ -390,27 +390,14 @@ struct HwTrack {            // per-lane tracking state of the banded kernel
     // its first and last column, its least score, the first column holding that score and how many columns hold it
     int slot, rFirst, rLast, rMin, rPos, rCnt;
     HitList hl;
-};
+    int slotBase;
 
-// Appends the run of every lane with `emit` to the hit list: one atomic per wave (ballot / mbcnt, as the seed kernel's hand-back
-// list), among the lanes that are active at the call.  Entries past the capacity are counted, not written.
-__device__ __forceinline__ void hit_append(const HitList& h, const bool emit, const int slot, const int first, const int last,
-                                           const int ed, const int pos, const int cnt)
-{
-    typedef unsigned long long u64;
-    const u64 bal = __builtin_amdgcn_ballot_w64(emit);
-    if (!bal) return;
-    const int lead = __builtin_ctzll(bal);
-    const u32 rank = __builtin_amdgcn_mbcnt_hi((u32)(bal >> 32), __builtin_amdgcn_mbcnt_lo((u32)bal, 0u));
-    u64 base = 0;
-    if (emit && rank == 0) base = atomicAdd(h.count, (u64)__popcll(bal));
-    base = ((u64)(u32)__builtin_amdgcn_readlane((int)(base >> 32), lead) << 32) | (u32)__builtin_amdgcn_readlane((int)base, lead);
-    const u64 at = base + rank;
-    if (emit && at < (u64)h.cap) {
-        h.key[at] = ((u64)(u32)(h.slotBase + slot) << 32) | (u32)first;
-        h.val[at] = last; h.val[h.cap + at] = ed; h.val[2 * h.cap + at] = pos; h.val[3 * h.cap + at] = cnt;
+    // the open run to the list, from every lane with `emit` (hit_list_append: among the lanes active at the call)
+    __device__ __forceinline__ void appendRun(const bool emit) const {
+        hit_list_append<4>(hl, emit, [&] { return ((unsigned long long)(u32)(slotBase + slot) << 32) | (u32)rFirst; },
+                           {rLast, rMin, rPos, rCnt});
     }
-}
+};
 
 // Rows carried from quad to quad by the one-word band (the next quad's rows, already in registers); local to a run
 // of that band height (nothing of it is live at any other height).
@@ -431,7 +418,7 @@ typedef u32 QuadRows[4];
 // FILTER (the piece filter of long reads, long_reads.hip; its own instantiation, so that the scans of whole reads carry none of
 // it): the threshold stays where it is and the lane lists the 16-column blocks that hold a column scoring <= best, each once.
 // HITS (hit-list read batches, reads_hits.hip): the threshold stays where it is as well, and the lane follows the maximal runs
-// of consecutive columns scoring <= best: a column next to the open run extends it, any other closes it (hit_append) and
+// of consecutive columns scoring <= best: a column next to the open run extends it, any other closes it (HwTrack::appendRun) and
 // opens a new one; the kernel closes the last run at the end of the lane's segment.
 template <int NA, int NWD, int Q, int S, bool CHECK = true, bool CHAIN = false, bool FILTER = false, bool HITS = false>
 __device__ __forceinline__ int band_quad(const u32 lo, const u32 hi, const u32 nlo, const u32 nhi, QuadRows& qr,
@@ -482,7 +469,7 @@ __device__ __forceinline__ int band_quad(const u32 lo, const u32 hi, const u32 n
                 const int sc = eh[j] + tr.best + 1;
                 const bool hit = eh[j] < 0 && col < colEnd && tr.cap > 0;   // (cap 0: a lane past nlanes owns no slot)
                 const bool ext = hit && col == tr.rLast + 1, fresh = hit && !ext;
-                hit_append(tr.hl, fresh && tr.rLast >= 0, tr.slot, tr.rFirst, tr.rLast, tr.rMin, tr.rPos, tr.rCnt);
+                tr.appendRun(fresh && tr.rLast >= 0);
                 const bool better = fresh || (ext && sc < tr.rMin);
                 tr.rFirst = fresh ? col : tr.rFirst;
                 tr.rLast = hit ? col : tr.rLast;
@@ -622,7 +609,7 @@ scan_reads_banded_kernel(const ReadScanArgs a)
         tr.cap = live ? (a.posCap ? a.posCap[item] : a.cap) : 0;
         tr.pos = a.segPos + (!live ? 0 : (a.posOff ? a.posOff[item] : item * a.cap));
     }
-    if constexpr (HITS) { tr.slot = slot; tr.rFirst = 0; tr.rLast = -2; tr.rMin = 0; tr.rPos = 0; tr.rCnt = 0; tr.hl = a.hits; }
+    if constexpr (HITS) { tr.slot = slot; tr.rFirst = 0; tr.rLast = -2; tr.rMin = 0; tr.rPos = 0; tr.rCnt = 0; tr.hl = a.hits; tr.slotBase = a.slotBase; }
     int e = m - tr.best - 1;                                          // score at column -1 is m
     int flag = 0;
 
@@ -685,7 +672,7 @@ scan_reads_banded_kernel(const ReadScanArgs a)
         }
     }
     if constexpr (HITS) {
-        hit_append(tr.hl, tr.rLast >= 0, tr.slot, tr.rFirst, tr.rLast, tr.rMin, tr.rPos, tr.rCnt);   // the segment's last run
+        tr.appendRun(tr.rLast >= 0);                                  // the segment's last run
     } else if (live) {
         const long long it = (long long)(blockIdx.x * 64 + threadIdx.x) * a.numSegments + blockIdx.y;
         a.segBest[it] = tr.best;

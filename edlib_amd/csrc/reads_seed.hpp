@@ -141,6 +141,10 @@ seed_verify_kernel(const SeedArgs a)
             for (int dd = 0; dd < NWD; ++dd) { Pv[dd] = ~0u; Mv[dd] = 0u; }
             int score = m;
             int rFirst = 0, rLast = -2, rMin = 0, rPos = 0, rCnt = 0;   // HITS: the open run (rLast < 0: none)
+            auto appendRun = [&] {
+                hit_list_append<4>(a.hits, true, [&] { return ((u64)(u32)(a.slotBase + slot) << 32) | (u32)rFirst; },
+                                   {rLast, rMin, rPos, rCnt});
+            };
             u32 tw = a.tpk[wa >> 4] >> (2 * (wa & 15));
             for (int c = wa; c <= wb; ++c) {
                 if ((c & 15) == 0) tw = a.tpk[c >> 4];
@@ -159,7 +163,7 @@ seed_verify_kernel(const SeedArgs a)
                         rMin = better ? score : rMin;
                         rLast = c;
                     } else if (rLast >= 0) {
-                        hit_append(a.hits, true, slot, rFirst, rLast, rMin, rPos, rCnt);
+                        appendRun();
                         rLast = -2;
                     }
                 } else
@@ -169,7 +173,7 @@ seed_verify_kernel(const SeedArgs a)
                     ++cnt;
                 }
             }
-            if constexpr (HITS) if (rLast >= 0) hit_append(a.hits, true, slot, rFirst, rLast, rMin, rPos, rCnt);
+            if constexpr (HITS) if (rLast >= 0) appendRun();
             cols += wb - wa + 1;
         }
     }

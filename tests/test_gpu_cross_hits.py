@@ -162,6 +162,31 @@ def test_cross_hits_capacity_growth(engine):
         d.close()
 
 
+def test_cross_hits_growth_with_session_cells(engine):
+    """the shape above and one target outside the kernel's envelope (65,537 bases): its 1,200 cells come from the internal
+    session and go in behind the kernel's hits, here into a list that has just grown to hold both"""
+    rng = np.random.default_rng(32)
+    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+    qs = list(rng.choice(acgt, size=(1200, 32)).astype(np.uint8))
+    ts = list(rng.choice(acgt, size=(1000, 32)).astype(np.uint8)) + [rng.choice(acgt, size=65_537).astype(np.uint8)]
+    b = engine.CrossBatch(qs, ts, mode="HW", k=32, hits=True)      # every cell within k: 1,201,200 hits > 2^20
+    d = engine.CrossBatch(qs, ts, mode="HW", k=32)
+    try:
+        d.run()
+        m, db = d.matrix(), d.best()
+        runs = []
+        for _ in range(2):
+            st = b.run()
+            assert st["path"] & 1 and st["path"] & 8, st
+            runs.append((b.hits(), b.best()))
+        for h, hb in runs:
+            assert np.array_equal(h["targetOffsets"], np.arange(1002, dtype=np.int64) * 1200)
+            _assert_same_as_dense(h, hb, m, db)
+    finally:
+        b.close()
+        d.close()
+
+
 def test_cross_hits_none_and_empty(engine):
     rng = np.random.default_rng(41)
     qs = [_rand(rng, 32, b"ACGT") for _ in range(50)]

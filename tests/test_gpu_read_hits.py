@@ -283,17 +283,27 @@ def test_five_symbol_target_keeps_the_banded_scan(engine):
 
 # --------------------------------------------------------------------------------------------------------- list growth
 
+_GROWTH = []
+
+
+def _growth_case():
+    """a 24-mer planted 300 times in 65,536 columns and its hits at k = 1: 4,096 copies of it pass the list's first 2^20 entries"""
+    if not _GROWTH:
+        rng = np.random.default_rng(5300)
+        T = 65_536
+        target = _ACGT[rng.integers(0, 4, T)].copy()
+        mer = np.ascontiguousarray(_ACGT[rng.integers(0, 4, 24)])
+        for at in 100 + 200 * np.arange(300):                               # 300 copies, 200 columns apart
+            target[at:at + 24] = mer
+        one = H.hits_csr(H.d_rows([mer], target), 1)
+        assert one["numHits"] >= 300 and 4_096 * one["numHits"] > 1 << 20
+        _GROWTH.append((target, mer, one))
+    return _GROWTH[0]
+
+
 def test_list_grows_once_and_later_runs_fit(engine):
-    rng = np.random.default_rng(5300)
-    T = 65_536
-    target = _ACGT[rng.integers(0, 4, T)].copy()
-    mer = np.ascontiguousarray(_ACGT[rng.integers(0, 4, 24)])
-    for at in 100 + 200 * np.arange(300):                                   # 300 copies, 200 columns apart
-        target[at:at + 24] = mer
-    one = H.hits_csr(H.d_rows([mer], target), 1)
-    assert one["numHits"] >= 300
+    target, mer, one = _growth_case()
     n = 4_096
-    assert n * one["numHits"] > 1 << 20
     want = {f: np.tile(one[f], n) for f in FIELDS}
     want["unitOffsets"] = np.arange(n + 1, dtype=np.int64) * one["numHits"]
     want["numHits"] = n * one["numHits"]
@@ -305,6 +315,36 @@ def test_list_grows_once_and_later_runs_fit(engine):
         _same(B.hits(), want)
     finally:
         B.close()
+    assert st2["scan_launches"] < st1["scan_launches"], (st1, st2)
+
+
+def test_empty_reads_behind_a_list_that_grows(engine):
+    """the batch above with an empty read first, in the middle and last: the rows answered on the host go in behind the scans'
+    runs, here into a list that has just grown to hold both"""
+    target, mer, one = _growth_case()
+    T, n = len(target), 4_096
+    empty = H.hits_csr(H.d_row(b"", target)[None, :], 1)                    # (row -1 of the recurrence: zeros)
+    assert empty["numHits"] == 1 and tuple(int(empty[f][0]) for f in FIELDS) == (0, T - 1, 0, 0, T)
+    reads = [b""] + [mer] * (n // 2) + [b""] + [mer] * (n // 2) + [b""]
+    per = [empty if len(r) == 0 else one for r in reads]
+    want = {f: np.concatenate([c[f] for c in per]) for f in FIELDS}
+    want["unitOffsets"] = np.concatenate(([0], np.cumsum([c["numHits"] for c in per]))).astype(np.int64)
+    want["numHits"] = int(want["unitOffsets"][-1])
+    assert n * one["numHits"] <= 1 << 30
+    B = engine.SharedBatch(reads, target, mode="HW", task="distance", k=1, hits=True)
+    try:
+        st1 = B.run()
+        h1 = B.hits()
+        st2 = B.run()
+        h2 = B.hits()
+    finally:
+        B.close()
+    for h in (h1, h2):
+        _same(h, want)
+        off = h["unitOffsets"]
+        for u in (0, n // 2 + 1, n + 2):
+            assert off[u + 1] - off[u] == 1
+            assert tuple(int(h[f][off[u]]) for f in FIELDS) == (0, T - 1, 0, 0, T), u
     assert st2["scan_launches"] < st1["scan_launches"], (st1, st2)
 
 
