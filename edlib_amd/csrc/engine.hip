@@ -403,8 +403,8 @@ int Batch::makeGroup(const std::vector<int>& units, int w, std::unique_ptr<ReadG
     g->nwords = w;
     g->nslots = roundup((int)units.size(), 64);
     g->perm.assign(g->nslots, -1);
-    g->mMin = 0x7fffffff;
-    for (int u : units) g->mMin = std::min(g->mMin, qlen(u));
+    g->mMin = 0x7fffffff; g->mMax = 0;
+    for (int u : units) { g->mMin = std::min(g->mMin, qlen(u)); g->mMax = std::max(g->mMax, qlen(u)); }
     std::copy(units.begin(), units.end(), g->perm.begin());
     const int nrblk = g->nslots / 64;
     if (mode == EDLIB_MODE_HW) {

@@ -223,7 +223,7 @@ private:
 
     // ---- reads-per-lane path
     struct ReadGroup {
-        int nwords = 0, nslots = 0, numSegments = 1, segLen = 0, warm = 0, mMin = 0;   // mMin: the shortest query
+        int nwords = 0, nslots = 0, numSegments = 1, segLen = 0, warm = 0, mMin = 0, mMax = 0;   // mMin, mMax: the shortest and the longest query (0: not known)
         std::vector<int> perm;                 // slot -> unit (or -1)
         DevBuf<int> d_perm, d_qlen, d_kinit, d_alphaExtra, d_segBest, d_segCnt, d_segPos;
         DevBuf<int> d_best, d_total, d_pos, d_flags;
@@ -291,7 +291,7 @@ private:
                   int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                   const long long* posOff, const int* posCap, bool unbanded = false,
                   unsigned long long* wordSteps = nullptr, const uint32_t* peqDense = nullptr,
-                  const int* qlenDense = nullptr, bool peqBottom = false);
+                  const int* qlenDense = nullptr, int peqBottom = 0);
 
     // ---- block-per-lane path
     DevBuf<PairDesc> d_descs_;

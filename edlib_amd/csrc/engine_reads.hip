@@ -28,7 +28,7 @@ seed_thresholds_kernel(int* __restrict__ kinit, const int* __restrict__ best, co
 int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, int kcap, const int* d_kinit,
                      int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                      const long long* posOff, const int* posCap, bool unbanded, unsigned long long* wordSteps,
-                     const uint32_t* peqDense, const int* qlenDense, bool peqBottom)
+                     const uint32_t* peqDense, const int* qlenDense, int peqBottom)
 {
     ReadScanArgs a{};
     // peqDense / qlenDense (+ d_kinit): rows rebuilt for exactly the lanes of this launch, in lane order (pass 2)
@@ -42,15 +42,16 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     a.posOff = posOff; a.posCap = posCap;
     a.kcap = kcap; a.wordSteps = wordSteps ? wordSteps : d_wordSteps_.p;
     a.filter = filterScan_ ? 1 : 0;
-    a.bottomAligned = peqBottom ? 1 : 0;              // (only scan_reads_kernel reads such rows: launch_scan_reads below)
+    a.bottomAligned = peqBottom;                      // (only scan_reads_kernel reads such rows: launch_scan_reads below)
     a.chainIn = chain_.in; a.chainOut = chain_.out; a.chainSrc = chain_.src; a.chainInLanes = chain_.inLanes;
     a.chainBlocks = chain_.blocks; a.rowBase = chain_.rowBase;
     const bool chained = chain_.in != nullptr || chain_.out != nullptr;
     static const bool dbg = getenv("EDLIB_AMD_DEBUG") != nullptr;
     if (dbg) {
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        fprintf(stderr, "[edlib_amd] scanGroup nwords=%d mode=%d nlanes=%d S=%d segLen=%d warm=%d cap=%d kcap=%d slotmap=%p posOff=%p\n",
-                g.nwords, mode, nlanes, numSegments, segLen, warm, cap, kcap, (const void*)d_slotmap, (const void*)posOff);
+        fprintf(stderr, "[edlib_amd] scanGroup nwords=%d mode=%d nlanes=%d S=%d segLen=%d warm=%d cap=%d kcap=%d slotmap=%p posOff=%p rows=%s\n",
+                g.nwords, mode, nlanes, numSegments, segLen, warm, cap, kcap, (const void*)d_slotmap, (const void*)posOff,
+                peqBottom > 1 ? "delay" : (peqBottom ? "bottom" : "top"));
     }
     scanTimerStart();
     // full-height HW scans (pass 2 over unrelated reads): scan_reads_kernel for four symbols (register-resident rows: 288 ms
@@ -316,8 +317,11 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             // When the pass goes to the plain kernel (scanGroup: HW, four symbols, up to kMaxReadWords words, no chain), the
             // rebuilt rows are bottom-aligned: row m-1 at bit 31 of the last word, where the column reads the score's
             // delta with two full-rate shifts.  The pre-scan below shares them, on the same kernel.
-            const bool bottom = plain && mode == EDLIB_MODE_HW && syms_ == 4 && g.nwords <= kMaxReadWords &&
-                                chain_.in == nullptr && chain_.out == nullptr;
+            // Where the group's longest read leaves three rows of its last word free, the rows carry delay rows above
+            // row m-1 and the score moves once per four columns (reads_kernels.hip: scan_reads_kernel<NWD, 2, true, true>).
+            const bool bottomOk = plain && mode == EDLIB_MODE_HW && syms_ == 4 && g.nwords <= kMaxReadWords &&
+                                  chain_.in == nullptr && chain_.out == nullptr;
+            const int bottom = !bottomOk ? 0 : (delay_rows_fit(g.nwords, g.mMax) ? 1 + kDelayRows : 1);
             const size_t no64 = (no + 63) / 64 * 64;
             std::vector<int> perm2(no64, -1);
             for (size_t i = 0; i < no; ++i) perm2[i] = g.perm[todo[i]];

@@ -130,13 +130,15 @@
 #define RP_SCORE(PH, MH)   "v_lshrrev_b32_e64 %[t], 31, " PH "\n\t" "v_add_u32_e64 %[scoreN], %[score], %[t]\n\t" \
                            "v_ashrrev_i32_e64 %[t], 31, " MH "\n\t" "v_add_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
 #define RP_PAIR01          RP_S1_0(RP_P0, RP_M0) RP_S1(1, RP_P1, RP_M1)
-#define RP_BODY_2 RP_PAIR01 RP_SCORE(RP_P1, RP_M1) RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1)
-#define RP_BODY_3 RP_PAIR01 RP_S1(2, RP_PL, RP_ML) RP_SCORE(RP_PL, RP_ML) RP_LONE RP_SHL \
+// SC: what a body does about the followed row, where the last word's Ph / Mh are still unshifted -- RP_SCORE (bit 31: the score
+// moves every column), or one of the delay-row forms below (RP_SC_*).
+#define RP_BODY_2(SC) RP_PAIR01 SC(RP_P1, RP_M1) RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1)
+#define RP_BODY_3(SC) RP_PAIR01 RP_S1(2, RP_PL, RP_ML) SC(RP_PL, RP_ML) RP_LONE RP_SHL \
                   RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) RP_S2(2, RP_PL, RP_ML)
-#define RP_BODY_4 RP_PAIR01 RP_CARRY RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) \
-                  RP_S1(2, RP_P0, RP_M0) RP_S1(3, RP_P1, RP_M1) RP_SCORE(RP_P1, RP_M1) RP_SHLADD RP_S2(2, RP_P0, RP_M0) RP_S2(3, RP_P1, RP_M1)
-#define RP_BODY_5 RP_PAIR01 RP_CARRY RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) \
-                  RP_S1(2, RP_P0, RP_M0) RP_S1(3, RP_P1, RP_M1) RP_S1(4, RP_PL, RP_ML) RP_SCORE(RP_PL, RP_ML) RP_LONE RP_SHLADD \
+#define RP_BODY_4(SC) RP_PAIR01 RP_CARRY RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) \
+                  RP_S1(2, RP_P0, RP_M0) RP_S1(3, RP_P1, RP_M1) SC(RP_P1, RP_M1) RP_SHLADD RP_S2(2, RP_P0, RP_M0) RP_S2(3, RP_P1, RP_M1)
+#define RP_BODY_5(SC) RP_PAIR01 RP_CARRY RP_SHL RP_S2(0, RP_P0, RP_M0) RP_S2(1, RP_P1, RP_M1) \
+                  RP_S1(2, RP_P0, RP_M0) RP_S1(3, RP_P1, RP_M1) RP_S1(4, RP_PL, RP_ML) SC(RP_PL, RP_ML) RP_LONE RP_SHLADD \
                   RP_S2(2, RP_P0, RP_M0) RP_S2(3, RP_P1, RP_M1) RP_S2(4, RP_PL, RP_ML)
 #define RP_TEMPS [t] "=&v"(t_), [ph0] "=&{v56}"(ph0_), [ph1] "=&{v57}"(ph1_), [mh0] "=&{v58}"(mh0_), [mh1] "=&{v59}"(mh1_), [cy] "=&s"(cy_)
 #define RP_TEMPS_LONE , [phl] "=&v"(phl_), [mhl] "=&v"(mhl_)
@@ -150,7 +152,7 @@
 #define RP_XI_4 RP_INS_CARRY
 #define RP_XT_5 RP_TEMPS_LONE RP_TEMPS_CARRY
 #define RP_XI_5 RP_INS_CARRY
-#define RP_COLUMN_ASM_B(N) asm(RC_HEAD RP_BODY_##N : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
+#define RP_COLUMN_ASM_B(N) asm(RC_HEAD RP_BODY_##N(RP_SCORE) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
 #define RP_COLUMN_DISPATCH_B(NWD) \
     if constexpr (NWD == 2) RP_COLUMN_ASM_B(2); if constexpr (NWD == 3) RP_COLUMN_ASM_B(3); \
     if constexpr (NWD == 4) RP_COLUMN_ASM_B(4); if constexpr (NWD == 5) RP_COLUMN_ASM_B(5);
@@ -160,6 +162,42 @@
     if constexpr (NA == 1) RC_COLUMN_ASM_NS(1, WORD0); if constexpr (NA == 2) RC_COLUMN_ASM_NS(2, WORD0); if constexpr (NA == 3) RC_COLUMN_ASM_NS(3, WORD0); \
     if constexpr (NA == 4) RC_COLUMN_ASM_NS(4, WORD0); if constexpr (NA == 5) RC_COLUMN_ASM_NS(5, WORD0); if constexpr (NA == 6) RC_COLUMN_ASM_NS(6, WORD0); \
     if constexpr (NA == 7) RC_COLUMN_ASM_NS(7, WORD0); if constexpr (NA == 8) RC_COLUMN_ASM_NS(8, WORD0);
+// Delay rows (scan_reads_kernel<NWD, 2, true, true>: rows built bottom-aligned with three all-match rows ABOVE row m-1, which
+// then sits at bit 28 of the last word).  An all-match row copies the row above it one column late, so bits
+// 28..31 of one column's Ph / Mh are the followed row's deltas of that column and the three before it, and the score moves
+// once per group of four columns, from two popcounts.  Three bodies per word count, in both forms of the column:
+//   NONE     the first three columns of a group: no score block at all (five words: 48 instructions);
+//   CAPTURE  the fourth: Ph >> 28 and Mh >> 28 of the last word to two outputs (two full-rate shifts), taken where the score
+//            block stood -- before the last word's registers are shifted in place, which drops bit 31 -- and behind them
+//            the group's update, score += popcount(nph) - popcount(nmh): two v_bcnt_u32_b32 (half rate; the first takes the
+//            old score as its addend) and a subtract.  Inside the statement, so that a group's nibbles die with it (left
+//            to the compiler, the popcounts of a whole 16-column word sank to its end: six registers, a wave at five
+//            words).  The old score stays in its register: the kernel's hit test reads both (scan_reads_kernel);
+//   BIT28    the ragged tail of the target (up to 15 columns of the last segment): the score every column, from bit 28.
+#define RP_SC_NONE(PH, MH)
+#define RP_SC_CAPTURE(PH, MH) "v_lshrrev_b32_e64 %[nph], 28, " PH "\n\t" "v_lshrrev_b32_e64 %[nmh], 28, " MH "\n\t" RC_GROUP_UPDATE
+#define RP_SC_BIT28(PH, MH)   "v_bfe_u32 %[t], " PH ", 28, 1\n\t" "v_add_u32_e64 %[scoreN], %[score], %[t]\n\t" \
+                              "v_bfe_i32 %[t], " MH ", 28, 1\n\t" "v_add_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
+#define RP_COLUMN_ASM_D0(N) asm(RC_HEAD RP_BODY_##N(RP_SC_NONE) : RC_OUTS_##N, RP_TEMPS RP_XT_##N : RC_INS_##N RP_XI_##N)
+#define RC_GROUP_UPDATE "v_bcnt_u32_b32 %[scoreN], %[nph], %[score]\n\t" "v_bcnt_u32_b32 %[t], %[nmh], 0\n\t" \
+                        "v_sub_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
+#define RC_GROUP_OUTS [nph] "=&v"(nph), [nmh] "=&v"(nmh), [scoreN] "=&v"(scoreN)
+#define RP_COLUMN_ASM_D1(N) asm(RC_HEAD RP_BODY_##N(RP_SC_CAPTURE) : RC_OUTS_##N, RC_GROUP_OUTS, RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
+#define RP_COLUMN_ASM_D2(N) asm(RC_HEAD RP_BODY_##N(RP_SC_BIT28) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
+#define RP_COLUMN_DISPATCH_D(F, NWD) \
+    if constexpr (NWD == 2) RP_COLUMN_ASM_D##F(2); if constexpr (NWD == 3) RP_COLUMN_ASM_D##F(3); \
+    if constexpr (NWD == 4) RP_COLUMN_ASM_D##F(4); if constexpr (NWD == 5) RP_COLUMN_ASM_D##F(5);
+// ... on the alignbit chain (one word, six to eight): the last word's Ph / Mh are not shifted in place there, the block stays last
+#define RC_SC_CAPTURE(c)  "v_lshrrev_b32_e64 %[nph], 28, %[ph" #c "]\n\t" "v_lshrrev_b32_e64 %[nmh], 28, %[mh" #c "]\n\t"
+#define RC_SC_BIT28(c)    "v_bfe_u32 %[t], %[ph" #c "], 28, 1\n\t" "v_bfe_i32 %[s], %[mh" #c "], 28, 1\n\t" "v_add3_u32 %[scoreN], %[score], %[t], %[s]\n\t"
+#define RC_SC_CAPTURE_X(c) RC_SC_CAPTURE(c)
+#define RC_SC_BIT28_X(c) RC_SC_BIT28(c)
+#define RC_COLUMN_ASM_D0(N) RC_COLUMN_ASM_NS(N, RC_WORD0_HW)
+#define RC_COLUMN_ASM_D1(N) asm(RC_HEAD RC_WORD0_HW RC_REST_##N RC_SC_CAPTURE_X(RC_LAST_##N) RC_GROUP_UPDATE : RC_OUTS_##N, RC_GROUP_OUTS, RC_TEMPS : RC_INS_##N, [score] "v"(score))
+#define RC_COLUMN_ASM_D2(N) asm(RC_HEAD RC_WORD0_HW RC_REST_##N RC_SC_BIT28_X(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score))
+#define RC_COLUMN_DISPATCH_D(F, NWD) \
+    if constexpr (NWD == 1) RC_COLUMN_ASM_D##F(1); if constexpr (NWD == 6) RC_COLUMN_ASM_D##F(6); \
+    if constexpr (NWD == 7) RC_COLUMN_ASM_D##F(7); if constexpr (NWD == 8) RC_COLUMN_ASM_D##F(8);
 #define RC_COLUMN_DISPATCH_B(NWD, WORD0) \
     if constexpr (NWD == 1) RC_COLUMN_ASM_B(1, WORD0); if constexpr (NWD == 2) RC_COLUMN_ASM_B(2, WORD0); if constexpr (NWD == 3) RC_COLUMN_ASM_B(3, WORD0); \
     if constexpr (NWD == 4) RC_COLUMN_ASM_B(4, WORD0); if constexpr (NWD == 5) RC_COLUMN_ASM_B(5, WORD0); if constexpr (NWD == 6) RC_COLUMN_ASM_B(6, WORD0); \

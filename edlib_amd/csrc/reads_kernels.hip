@@ -121,6 +121,8 @@ hipError_t launch_pack_target_2bit(const uint8_t* raw, const uint8_t* lut, int T
 // row m-1 is bit 31 of the last word, and the pad bits below are set in the row of every symbol.  pad is below 32 for the
 // reads of a group (read_group_words: they reach into the last word); the padding slots of a list (m = 1) and any shorter
 // read get whole words of pad the same way, nothing here or in the scan's initial state assumes pad < 32.
+// bottomAlign = 1 + R (kDelayRows; scan_reads_kernel<NWD, 2, true, true>): R delay rows above row m-1, set in the row of every
+// symbol like the pads, and pad = 32 NWD - R - m: row m-1 is bit 31 - R of the last word.  The caller sees to m + R <= 32 NWD.
 template <int NWD>
 __global__ void __launch_bounds__(256)
 build_peq_reads_kernel(const uint8_t* __restrict__ reads, const long long* __restrict__ qoff,
@@ -157,13 +159,14 @@ build_peq_reads_kernel(const uint8_t* __restrict__ reads, const long long* __res
             unsigned long long seen0 = 0, seen1 = 0, seen2 = 0, seen3 = 0;
             int extraJ = 0;
             const bool mine = lane == j;                               // the lane that keeps read j's rows
-            const int padj = bottomAlign ? 32 * NWD - mj : 0;          // wave-uniform
+            const int delay = bottomAlign > 1 ? bottomAlign - 1 : 0;
+            const int padj = bottomAlign ? 32 * NWD - delay - mj : 0;  // wave-uniform
 #pragma unroll
             for (int c = 0; c < (NWD + 1) / 2; ++c) {                  // 64 rows = two words per trip
                 const int i = 64 * c + lane - padj;                    // query row of bit 64 c + lane
                 const bool in = i >= 0 && i < mj;
                 const u32 by = in ? reads[offj + i] : 0u;
-                const u32 mask = in ? ((u32)s_eq[by] >> g0) : (i < 0 ? 0xfu : 0u);   // pad rows match every symbol
+                const u32 mask = in ? ((u32)s_eq[by] >> g0) : ((i < 0 || i < mj + delay) ? 0xfu : 0u);   // pad and delay rows match every symbol
                 const unsigned long long b0 = __builtin_amdgcn_ballot_w64((mask & 1u) != 0), b1 = __builtin_amdgcn_ballot_w64((mask & 2u) != 0);
                 const unsigned long long b2 = __builtin_amdgcn_ballot_w64((mask & 4u) != 0), b3 = __builtin_amdgcn_ballot_w64((mask & 8u) != 0);
                 constexpr int w0 = 0;
@@ -208,19 +211,20 @@ template <int NWD>
 static hipError_t launch_build_peq_t(const uint8_t* reads, const long long* qoff, const int* perm,
                                      int nslots, int S, const uint16_t* eqtbl, const u32* tpres, int kcfg,
                                      u32* peq, int* qlen, int* kinit, int* alphaExtra,
-                                     hipStream_t stream, bool bottomAlign)
+                                     hipStream_t stream, int bottomAlign)
 {
     hipLaunchKernelGGL(build_peq_reads_kernel<NWD>, dim3((nslots + 255) / 256), dim3(256), 0, stream,
-                       reads, qoff, perm, nslots, S, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, bottomAlign ? 1 : 0);
+                       reads, qoff, perm, nslots, S, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, bottomAlign);
     return hipGetLastError();
 }
 
 hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, const long long* qoff,
                                   const int* perm, int nslots, const uint16_t* eqtbl,
                                   const u32* tpres, int kcfg, u32* peq, int* qlen, int* kinit,
-                                  int* alphaExtra, hipStream_t stream, bool bottomAlign)
+                                  int* alphaExtra, hipStream_t stream, int bottomAlign)
 {
     if (nslots == 0) return hipSuccess;
+    if (bottomAlign != 0 && bottomAlign != 1 && bottomAlign != 1 + kDelayRows) return hipErrorInvalidValue;
     if (syms != 4 && syms != 8 && syms != 16) return hipErrorInvalidValue;
     switch (nwords) {
 #define CASE(N) case N: return launch_build_peq_t<N>(reads, qoff, perm, nslots, syms, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, stream, bottomAlign);
@@ -242,6 +246,14 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
         default: column_step<NWD, MODE, BOTTOM>(E3, Pv, Mv, score, sh, zr0, zr1); asm volatile("; sym3"); break; \
     }
 
+#define EDLIB_AMD_DISPATCH_COLUMN_DELAY(FORM, sym)                                         \
+    switch (sym) {                                                                         \
+        case 0:  column_step_delay<NWD, FORM>(E0, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym0"); break; \
+        case 1:  column_step_delay<NWD, FORM>(E1, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym1"); break; \
+        case 2:  column_step_delay<NWD, FORM>(E2, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym2"); break; \
+        default: column_step_delay<NWD, FORM>(E3, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym3"); break; \
+    }
+
 // Record column `col` if it ties or improves the best bottom-row score
 // (reference edlib.cpp:658-673: "colScore <= k", "positions.clear()", "k = bestScore").
 #define EDLIB_AMD_TRACK_SCORE(sc, col)                         \
@@ -255,11 +267,17 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 // BOTTOM (HW): the Peq rows were built bottom-aligned (build_peq_reads_kernel), query row r at bit 32 NWD - m + r.  The
 // pad rows below bit 32 NWD - m match every symbol; with HW's zero row -1 they stay at D = 0 in every column, so the real
 // rows see the boundary they always saw, and the followed row m-1 is bit 31 of the last word in every lane.
-template <int NWD, int MODE, bool BOTTOM = false>
+// DELAY (with BOTTOM): the rows carry kDelayRows all-match rows above row m-1 (bit 28 of the last word).  Each copies the row
+// above it one column late, so the top nibbles of the LAST column of a group of four are the followed row's deltas of the whole
+// group: three columns of a group carry no score code, the fourth hands out the two nibbles, and the score moves once per
+// group, by two popcounts (tests/delay_rows_model.py has the identity and its boundaries).
+template <int NWD, int MODE, bool BOTTOM = false, bool DELAY = false>
 __global__ void __launch_bounds__(256)
 scan_reads_kernel(const ReadScanArgs a)
 {
+    static_assert(!DELAY || (BOTTOM && MODE == 2), "delay rows: bottom-aligned HW rows");
     constexpr int kHitGroup = 4;                                   // columns per hit test (divides 16)
+    static_assert(!DELAY || kHitGroup == kDelayRows + 1, "one nibble per group");
     const int lane = threadIdx.x & 63;
     const int rblk = blockIdx.x * 4 + (threadIdx.x >> 6);          // 4 waves / workgroup
     const int seg = blockIdx.y;
@@ -286,7 +304,7 @@ scan_reads_kernel(const ReadScanArgs a)
         // column -1 of the pad rows is 0: Pv is clear on the 32 NWD - m low bits.  Reads of a group fill their last word
         // (read_group_words), so the pad is below 32 there; the padding slots of the rebuilt rows (m = 1) and anything
         // shorter still get whole words of pad.
-        const int pad = 32 * NWD - m;
+        const int pad = 32 * NWD - (DELAY ? kDelayRows : 0) - m;   // (delay rows: Pv = 1, D[i][-1] = i + 1 like the read's own)
 #pragma unroll
         for (int d = 0; d < NWD; ++d) {
             const int lo = pad - 32 * d;
@@ -317,12 +335,19 @@ scan_reads_kernel(const ReadScanArgs a)
     cw &= ~15;
 
     // warm-up columns [cw, c0): state only, nothing is recorded (HW segments)
+    u32 nph = 0, nmh = 0;                                          // DELAY: the nibbles of the last group
     for (int w = cw >> 4; w < (c0 >> 4); ++w) {
         const u32 tw = a.tpk[w];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const u32 sym = (tw >> (2 * j)) & 3u;
-            EDLIB_AMD_DISPATCH_COLUMN(sym)
+            if constexpr (!DELAY) {
+                EDLIB_AMD_DISPATCH_COLUMN(sym)
+            } else if ((j & (kHitGroup - 1)) != kHitGroup - 1) {
+                EDLIB_AMD_DISPATCH_COLUMN_DELAY(0, sym)
+            } else {
+                EDLIB_AMD_DISPATCH_COLUMN_DELAY(1, sym)
+            }
         }
     }
     // full words of the segment
@@ -330,10 +355,51 @@ scan_reads_kernel(const ReadScanArgs a)
     // The hit test runs once per group of kHitGroup columns: bottom-row scores of neighbouring columns differ by at most 1,
     // so a last score above best + kHitGroup - 1 means that no column of the group is at or below best, and best only moves
     // at a hit.  A group that may hold one goes through the per-column test, in order, with each column's own score: best,
-    // cnt and the stored positions are what the per-column test leaves.  (Unrelated reads sit ~14 above their best: a wave
-    // takes the slow path in about 0.5 % of its groups.)  The loop carries the limit, not best: one compare per group.
+    // cnt and the stored positions are what the per-column test leaves.  (Unrelated reads sit ~14 above their best: a lane
+    // passes in about 0.5 % of its groups, a wave of 64 in three of ten.)  The loop carries the limit, not best: one compare per group.
     int lim = best + (kHitGroup - 1);
-    for (int w = c0 >> 4; w < wend; ++w) {
+    if constexpr (DELAY) {
+        // The capture column leaves the score of the group's last column next to the one before the group.  With b and a
+        // the scores before and after a group, its column k = 1..4 scores at least max(b - k, a - (4 - k)) >= (a + b - 4) / 2,
+        // so a group may hold a hit only when a + b <= 2 best + 4: one add and one compare per group, and one unit tighter
+        // than a <= best + 3 for the reads that hover above their best.  It matters: a WAVE takes the slow path when any of
+        // its 64 lanes passes (three groups in ten at a <= best + 3).  There the four scores come out of the nibbles, bit 31
+        // the first column of the group, and the per-column test runs only if their least is a hit.
+        int lim2 = 2 * best + kHitGroup;
+        for (int w = c0 >> 4; w < wend; ++w) {
+            const u32 tw = a.tpk[w];
+#pragma unroll
+            for (int j = 0; j < 16; j += kHitGroup) {
+#pragma unroll
+                for (int q = 0; q < kHitGroup - 1; ++q) {
+                    const u32 sym = (tw >> (2 * (j + q))) & 3u;
+                    EDLIB_AMD_DISPATCH_COLUMN_DELAY(0, sym)
+                }
+                const int before = score;
+                {
+                    const u32 sym = (tw >> (2 * (j + kHitGroup - 1))) & 3u;
+                    EDLIB_AMD_DISPATCH_COLUMN_DELAY(1, sym)
+                }
+                if (__builtin_expect(score + before <= lim2, 0)) {
+                    int sc[kHitGroup], acc = before, least = 0x7fffffff;
+#pragma unroll
+                    for (int q = 0; q < kHitGroup; ++q) {
+                        acc += (int)((nph >> (kHitGroup - 1 - q)) & 1u) - (int)((nmh >> (kHitGroup - 1 - q)) & 1u);
+                        sc[q] = acc;
+                        least = acc < least ? acc : least;
+                    }
+                    best = (lim2 - kHitGroup) >> 1;
+                    if (least <= best) {
+#pragma unroll
+                        for (int q = 0; q < kHitGroup; ++q) { EDLIB_AMD_TRACK_SCORE(sc[q], w * 16 + j + q) }
+                        lim2 = 2 * best + kHitGroup;
+                    }
+                }
+            }
+        }
+        lim = ((lim2 - kHitGroup) >> 1) + (kHitGroup - 1);
+    }
+    for (int w = c0 >> 4; !DELAY && w < wend; ++w) {
         const u32 tw = a.tpk[w];
 #pragma unroll
         for (int j = 0; j < 16; j += kHitGroup) {
@@ -362,7 +428,7 @@ scan_reads_kernel(const ReadScanArgs a)
         for (int j = 0; j < rem; ++j) {
             const u32 sym = tw & 3u;
             tw >>= 2;
-            EDLIB_AMD_DISPATCH_COLUMN(sym)
+            if constexpr (DELAY) { EDLIB_AMD_DISPATCH_COLUMN_DELAY(2, sym) } else { EDLIB_AMD_DISPATCH_COLUMN(sym) }
             if (MODE != 0) { EDLIB_AMD_TRACK(wend * 16 + j) }
         }
     }
@@ -381,7 +447,8 @@ static hipError_t launch_scan_mode(int mode, const ReadScanArgs& a, hipStream_t 
     switch (mode) {
         case 0: hipLaunchKernelGGL((scan_reads_kernel<NWD, 0>), grid, block, 0, stream, a); break;
         case 1: hipLaunchKernelGGL((scan_reads_kernel<NWD, 1>), grid, block, 0, stream, a); break;
-        case 2: if (a.bottomAligned) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true>), grid, block, 0, stream, a);
+        case 2: if (a.bottomAligned == 1 + kDelayRows) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true, true>), grid, block, 0, stream, a);
+                else if (a.bottomAligned) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true>), grid, block, 0, stream, a);
                 else hipLaunchKernelGGL((scan_reads_kernel<NWD, 2>), grid, block, 0, stream, a);
                 break;
         default: return hipErrorInvalidValue;
@@ -393,6 +460,7 @@ hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStr
 {
     if (a.nlanes == 0) return hipSuccess;
     if (a.bottomAligned && mode != 2) return hipErrorInvalidValue;      // only HW keeps the pad rows at zero
+    if (a.bottomAligned != 0 && a.bottomAligned != 1 && a.bottomAligned != 1 + kDelayRows) return hipErrorInvalidValue;
     switch (nwords) {
 #define CASE(N) case N: return launch_scan_mode<N>(mode, a, stream);
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)

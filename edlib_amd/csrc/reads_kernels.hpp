@@ -16,6 +16,10 @@ constexpr int kMaxLongReadWords = 16;       // targets of 5..8 symbols
 constexpr int kMaxLongReadWords4 = 32;      // targets of up to 4 symbols
 constexpr int kFilterFromWords = 13;        // HW queries of this many words and more take the piece filter (long_reads.hip)
 inline int read_group_words(int m) { const int w = (m + 31) / 32; return w <= kMaxReadWords ? w : (w <= 10 ? 10 : (w <= 12 ? 12 : (w <= 14 ? 14 : (w <= 16 ? 16 : (w <= 24 ? 24 : 32))))); }
+// HW rows built bottom-aligned may carry this many all-match rows above row m-1 (reads_kernels.hip: the score of the plain
+// full-height scan then moves once per four columns): a group whose longest read leaves them room in its last word is eligible
+constexpr int kDelayRows = 3;
+constexpr bool delay_rows_fit(int nwords, int longest) { return nwords <= kMaxReadWords && longest >= 1 && longest + kDelayRows <= 32 * nwords; }
 constexpr int kLanes = 64;            // wave64, hard-coded (gfx950)
 
 // Hit-list read batches (reads_hits.hip): the HITS scans append closed runs of columns scoring <= k to the
@@ -56,7 +60,8 @@ struct ReadScanArgs {
                               // scoring <= kinit (each once), segCnt their number (piece filter of long reads)
     HitList hits;             // HITS instantiation of the banded kernel only (launch_scan_reads_hits)
     int slotBase;             // ... the launch's group starts at this slot of the batch-wide slot table
-    int bottomAligned;        // scan_reads_kernel, HW only: peq was built with bottomAlign (row m-1 at bit 31 of the last word)
+    int bottomAligned;        // scan_reads_kernel, HW only: peq was built with this bottomAlign (1: row m-1 at bit 31 of the last
+                              // word; 1 + kDelayRows: at bit 28 under three delay rows)
 };
 
 // mode: 0 NW, 1 SHW, 2 HW (values of EdlibAlignMode).  Returns hipSuccess or the launch error.
@@ -78,12 +83,13 @@ hipError_t launch_pack_target_rows(const uint8_t* raw, const uint8_t* lut, int t
 // Builds Peq for every slot (reference buildPeq, edlib.cpp:358-384, for the <= syms target symbols; eqtbl[byte] =
 // 16-bit set of the target symbols a query byte equals),
 // the per-slot query length and the number of query byte values absent from the target.
-// bottomAlign: query row i at bit 32 nwords - m + i and the bits below set in every row (ReadScanArgs::bottomAligned).
+// bottomAlign 1: query row i at bit 32 nwords - m + i and the bits below set in every row (ReadScanArgs::bottomAligned);
+// 1 + kDelayRows: at bit 32 nwords - kDelayRows - m + i, the kDelayRows bits above row m-1 set in every row as well.
 hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, const long long* qoff,
                                   const int* perm, int nslots, const uint16_t* eqtbl,
                                   const uint32_t* targetPresence /*8 dwords*/, int kcfg,
                                   uint32_t* peq, int* qlen, int* kinit, int* alphaExtra,
-                                  hipStream_t stream, bool bottomAlign = false);
+                                  hipStream_t stream, int bottomAlign = 0);
 
 // Piece filter: gathers the (lane, block) candidates of a filter scan into one list.  out[2i] = lane, out[2i+1] = block;
 // *counter = number of candidates (may exceed maxOut: the caller retries with a larger list); overflow[lane] = 1 when a
