@@ -291,7 +291,7 @@ private:
                   int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                   const long long* posOff, const int* posCap, bool unbanded = false,
                   unsigned long long* wordSteps = nullptr, const uint32_t* peqDense = nullptr,
-                  const int* qlenDense = nullptr, int peqBottom = 0);
+                  const int* qlenDense = nullptr, int peqBottom = 0, int* liveBest = nullptr);
 
     // ---- block-per-lane path
     DevBuf<PairDesc> d_descs_;

@@ -28,7 +28,7 @@ seed_thresholds_kernel(int* __restrict__ kinit, const int* __restrict__ best, co
 int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, int kcap, const int* d_kinit,
                      int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                      const long long* posOff, const int* posCap, bool unbanded, unsigned long long* wordSteps,
-                     const uint32_t* peqDense, const int* qlenDense, int peqBottom)
+                     const uint32_t* peqDense, const int* qlenDense, int peqBottom, int* liveBest)
 {
     ReadScanArgs a{};
     // peqDense / qlenDense (+ d_kinit): rows rebuilt for exactly the lanes of this launch, in lane order (pass 2)
@@ -42,6 +42,7 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     a.posOff = posOff; a.posCap = posCap;
     a.kcap = kcap; a.wordSteps = wordSteps ? wordSteps : d_wordSteps_.p;
     a.filter = filterScan_ ? 1 : 0;
+    a.liveBest = liveBest;
     a.bottomAligned = peqBottom;                      // (only scan_reads_kernel reads such rows: launch_scan_reads below)
     a.chainIn = chain_.in; a.chainOut = chain_.out; a.chainSrc = chain_.src; a.chainInLanes = chain_.inLanes;
     a.chainBlocks = chain_.blocks; a.rowBase = chain_.rowBase;
@@ -347,8 +348,16 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
                                    d_kinit2.p, d_b0.p, d_c0.p, (int)no);
                 EDLIB_AMD_HIP(hipGetLastError());
             }
+            // On the bottom-aligned rows the segments of a lane share one running best (ReadScanArgs::liveBest), from the
+            // seeded threshold down: a segment that starts late starts from what the earlier ones found, and the out-of-line
+            // hit path of the scan is entered that much less often.
+            DevBuf<int> d_live2;
+            if (bottom && S2 > 1) {
+                EDLIB_AMD_HIP(d_live2.alloc(no64));
+                EDLIB_AMD_HIP(hipMemcpyAsync(d_live2.p, d_kinit2.p, no64 * sizeof(int), hipMemcpyDeviceToDevice, stream_));
+            }
             if (scanGroup(g, mode, nullptr, (int)no, kcapL, d_kinit2.p, S2, segLen2, warm2,
-                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p, bottom)) return 1;
+                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p, bottom, d_live2.p)) return 1;
             EDLIB_AMD_HIP(launch_merge_segments(d_sb, d_sc, d_sp, S2, capL, (int)no, d_map, 16,
                                                 g.d_best.p, g.d_total.p, g.d_pos.p, g.d_flags.p, stream_,
                                                 last ? kOvfGatherLevel : kOvfRescan));

@@ -327,6 +327,20 @@ scan_reads_kernel(const ReadScanArgs a)
     // lanes past nlanes (the tail of the last wave) own no record: they must not even read the tables
     const int cap = !live ? 0 : (a.posCap ? a.posCap[item] : a.cap);
     int* pos = a.segPos + (!live ? 0 : (a.posOff ? a.posOff[item] : item * a.cap));
+    // The lane's running best over all its segments (ReadScanArgs::liveBest).  Results do not depend on when a segment sees
+    // what another one found: liveBest only ever holds the lane's threshold or a score that some column reaches, so it is
+    // never below the read's minimum over the whole target, and under ANY bound at or above that minimum a segment records
+    // every one of its columns that scores the minimum, in order, counting past the cap (a lower score first clears what
+    // was recorded above it, an import does the same, and nothing at the minimum is ever cleared: no import is below it).
+    // A segment without such a column ends above the minimum, or at it with a count of 0; the merge takes neither.
+    constexpr int kLiveBlocks = kLivePeriod / 16;
+    constexpr int kNoImport = 0x1fffffff;                          // (twice this and a few more is still an int)
+    int* const livep = BOTTOM ? a.liveBest : nullptr;              // wave-uniform
+    // (the loop keeps ONE register for the lane's index, opaque so that the 64-bit record index is not kept beside it: the
+    // final stores work theirs out again)
+    int lidx = idx;
+    if constexpr (BOTTOM) asm volatile("" : "+v"(lidx));
+#define EDLIB_AMD_LIVE_LOAD() (live ? __hip_atomic_load(livep + lidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kNoImport)
 
     const int T = a.targetLength;
     const int c0 = seg * a.segLen;                                 // multiple of 16
@@ -366,7 +380,15 @@ scan_reads_kernel(const ReadScanArgs a)
         // its 64 lanes passes (three groups in ten at a <= best + 3).  There the four scores come out of the nibbles, bit 31
         // the first column of the group, and the per-column test runs only if their least is a hit.
         int lim2 = 2 * best + kHitGroup;
-        for (int w = c0 >> 4; w < wend; ++w) {
+        for (int w0 = c0 >> 4; w0 < wend; w0 += kLiveBlocks) {
+        if (livep) {
+            // a lower import replaces best, and what was recorded belonged to a score that is no longer the best; an equal
+            // one changes nothing, so the ties already recorded stay
+            const int got = EDLIB_AMD_LIVE_LOAD();
+            if (2 * got + kHitGroup < lim2) { lim2 = 2 * got + kHitGroup; cnt = 0; }
+        }
+        const int w1 = w0 + kLiveBlocks < wend ? w0 + kLiveBlocks : wend;
+        for (int w = w0; w < w1; ++w) {
             const u32 tw = a.tpk[w];
 #pragma unroll
             for (int j = 0; j < 16; j += kHitGroup) {
@@ -392,14 +414,22 @@ scan_reads_kernel(const ReadScanArgs a)
                     if (least <= best) {
 #pragma unroll
                         for (int q = 0; q < kHitGroup; ++q) { EDLIB_AMD_TRACK_SCORE(sc[q], w * 16 + j + q) }
+                        if (livep && live && 2 * best + kHitGroup < lim2) atomicMin(livep + lidx, best);   // improved: publish
                         lim2 = 2 * best + kHitGroup;
                     }
                 }
             }
         }
+        }
         lim = ((lim2 - kHitGroup) >> 1) + (kHitGroup - 1);
     }
-    for (int w = c0 >> 4; !DELAY && w < wend; ++w) {
+    for (int w0 = c0 >> 4; !DELAY && w0 < wend; w0 += kLiveBlocks) {
+    if (livep) {
+        const int got = EDLIB_AMD_LIVE_LOAD();
+        if (got + (kHitGroup - 1) < lim) { lim = got + (kHitGroup - 1); cnt = 0; }
+    }
+    const int w1 = w0 + kLiveBlocks < wend ? w0 + kLiveBlocks : wend;
+    for (int w = w0; w < w1; ++w) {
         const u32 tw = a.tpk[w];
 #pragma unroll
         for (int j = 0; j < 16; j += kHitGroup) {
@@ -415,11 +445,14 @@ scan_reads_kernel(const ReadScanArgs a)
                     best = lim - (kHitGroup - 1);
 #pragma unroll
                     for (int q = 0; q < kHitGroup; ++q) { EDLIB_AMD_TRACK_SCORE(sc[q], w * 16 + j + q) }
+                    if (livep && live && best + (kHitGroup - 1) < lim) atomicMin(livep + lidx, best);   // improved: publish
                     lim = best + (kHitGroup - 1);
                 }
             }
         }
     }
+    }
+#undef EDLIB_AMD_LIVE_LOAD
     best = lim - (kHitGroup - 1);
     // ragged tail of the target (last segment only)
     const int rem = c1 - (wend << 4);
@@ -433,7 +466,7 @@ scan_reads_kernel(const ReadScanArgs a)
         }
     }
     if (live) {
-        const size_t o = (size_t)idx * a.numSegments + seg;
+        const size_t o = (size_t)lidx * a.numSegments + seg;
         a.segBest[o] = (MODE == 0) ? score : best;                 // NW: D[m][T] (edlib.cpp:914-917)
         a.segCnt[o] = (MODE == 0) ? 1 : cnt;
     }

@@ -62,7 +62,12 @@ struct ReadScanArgs {
     int slotBase;             // ... the launch's group starts at this slot of the batch-wide slot table
     int bottomAligned;        // scan_reads_kernel, HW only: peq was built with this bottomAlign (1: row m-1 at bit 31 of the last
                               // word; 1 + kDelayRows: at bit 28 under three delay rows)
+    int* liveBest;            // scan_reads_kernel on bottom-aligned rows: optional [lanes] running best of the lane over ALL its
+                              // segments, set to the lane's threshold before the launch (no slotmap).  The segments start
+                              // from it, publish what they find and pick it up again every kLivePeriod columns.  Null: every
+                              // (lane, segment) keeps a best of its own, from kinit
 };
+constexpr int kLivePeriod = 1024;     // columns between two looks at liveBest (a multiple of 16)
 
 // mode: 0 NW, 1 SHW, 2 HW (values of EdlibAlignMode).  Returns hipSuccess or the launch error.
 hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStream_t stream);
