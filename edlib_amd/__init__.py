@@ -186,6 +186,9 @@ def lib():
                                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                              AlignConfig, C.c_int]
         L.edlibAmdBatchWindowView.argtypes = [C.c_void_p, C.c_int, C.POINTER(WindowView)]
+        if hasattr(L, "edlibAmdBatchWindowsSetUnits"):
+            L.edlibAmdBatchWindowsSetUnits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_int]
         if hasattr(L, "edlibAmdBatchCreateSelf"):
             L.edlibAmdBatchCreateSelf.restype = C.c_void_p
             L.edlibAmdBatchCreateSelf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -789,7 +792,29 @@ class WindowBatch(_Batch):
     ``for read, (s, e) in candidates: edlib.align(read, ref[s:e], mode)`` as one resident batch that holds the target
     and every query once.  units() has the three fields of every unit, best() the best unit per query.
     unit_strand (edlibAmdBatchCreateWindowsStranded): 0 / 1 per unit, 1 = the unit is the reverse complement of its query
-    against the window; best() runs over all units of a query whatever their strand."""
+    against the window; best() runs over all units of a query whatever their strand.
+    set_units(queries, unit_query, unit_start, unit_length, unit_strand=None) (edlibAmdBatchWindowsSetUnits) passes the
+    next chunk of reads and candidates through the resident batch: the target, its pack and the batch's buffers stay, the
+    queries and units are prepared on the device, and the batch is then as if created over (its target, these queries,
+    these units) -- run(), then the views.  A streamed set lies inside the window kernel's envelope (a target of at most
+    16 distinct symbols, queries up to 256 bases, windows up to 65,536 columns); outside it the call raises and the
+    batch stays as it was."""
+
+    @staticmethod
+    def _units(unit_query, unit_start, unit_length, unit_strand):
+        """the unit arrays as the C calls take them (an empty one padded to one element) and their count; the strand
+        array is None where unit_strand is"""
+        uq, us, ul = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (unit_query, unit_start, unit_length))
+        if not (len(uq) == len(us) == len(ul)):
+            raise ValueError("unit_query, unit_start and unit_length differ in length")
+        pad = [a if len(a) else np.zeros(1, dtype=np.int32) for a in (uq, us, ul)]
+        st = None
+        if unit_strand is not None:
+            st = np.ascontiguousarray(unit_strand, dtype=np.uint8).reshape(-1)
+            if len(st) != len(uq):
+                raise ValueError("unit_strand and unit_query differ in length")
+            st = st if len(st) else np.zeros(1, dtype=np.uint8)
+        return pad, st, len(uq)
 
     def __init__(self, queries, target, unit_query, unit_start, unit_length, mode="HW", k=-1,
                  additionalEqualities=None, device=0, unit_strand=None):
@@ -797,25 +822,30 @@ class WindowBatch(_Batch):
         t = np.frombuffer(target, dtype=np.uint8) if isinstance(target, (bytes, bytearray)) else np.asarray(target, dtype=np.uint8)
         tlen = len(t)
         t = np.ascontiguousarray(t) if tlen else np.zeros(1, dtype=np.uint8)
-        uq, us, ul = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (unit_query, unit_start, unit_length))
-        if not (len(uq) == len(us) == len(ul)):
-            raise ValueError("unit_query, unit_start and unit_length differ in length")
+        pad, st, nu = self._units(unit_query, unit_start, unit_length, unit_strand)
         cfg, keep = _make_config(mode, "distance", k, additionalEqualities)
-        self.numQueries, self.numUnits = len(qo) - 1, len(uq)
-        pad = [a if len(a) else np.zeros(1, dtype=np.int32) for a in (uq, us, ul)]
-        if unit_strand is None:
+        self.numQueries, self.numUnits = len(qo) - 1, nu
+        if st is None:
             h = lib().edlibAmdBatchCreateWindows(qd.ctypes.data, qo.ctypes.data, self.numQueries, t.ctypes.data, tlen,
                                                  pad[0].ctypes.data, pad[1].ctypes.data, pad[2].ctypes.data,
                                                  self.numUnits, cfg, device)
         else:
-            st = np.ascontiguousarray(unit_strand, dtype=np.uint8).reshape(-1)
-            if len(st) != len(uq):
-                raise ValueError("unit_strand and unit_query differ in length")
-            st = st if len(st) else np.zeros(1, dtype=np.uint8)
             h = lib().edlibAmdBatchCreateWindowsStranded(qd.ctypes.data, qo.ctypes.data, self.numQueries, t.ctypes.data,
                                                          tlen, pad[0].ctypes.data, pad[1].ctypes.data,
                                                          pad[2].ctypes.data, st.ctypes.data, self.numUnits, cfg, device)
         super().__init__(h, self.numUnits, keep)
+
+    def set_units(self, queries, unit_query, unit_start, unit_length, unit_strand=None):
+        """Replace the queries and the units (the constructor's input forms); the target stays resident.  Raises
+        RuntimeError with last_error() on a refusal, which leaves the batch as it was.  run() before the next view."""
+        qd, qo = _pack(queries)
+        pad, st, nu = self._units(unit_query, unit_start, unit_length, unit_strand)
+        nq = len(qo) - 1
+        if lib().edlibAmdBatchWindowsSetUnits(self._h, qd.ctypes.data, qo.ctypes.data, nq, pad[0].ctypes.data,
+                                              pad[1].ctypes.data, pad[2].ctypes.data,
+                                              None if st is None else st.ctypes.data, nu) != 0:
+            raise RuntimeError("edlib_amd: set_units failed: " + last_error())
+        self.numQueries, self.numUnits, self.n = nq, nu, nu
 
     def _view(self, what):
         v = WindowView()

@@ -389,6 +389,26 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindowsStranded(const char* queries,
                           unitQuery, unitStart, unitLength, unitStrand, numUnits, config, device);
 }
 
+// "a cross batch", "a self batch", ...: the kind of a batch that is not a window batch, for a refusal
+static const char* kind_of(EdlibAmdBatch* b) {
+    if (b->cross) return b->cross->isSelf() ? "a self batch" : b->cross->isOccurrences() ? "an occurrence batch" : "a cross batch";
+    return b->impl.isHits() ? "a hit-list read batch" : "a read or pair batch";
+}
+
+EDLIB_API int edlibAmdBatchWindowsSetUnits(EdlibAmdBatch* b, const char* queries, const long long* queryOffsets,
+                                           int numQueries, const int* unitQuery, const int* unitStart,
+                                           const int* unitLength, const unsigned char* unitStrand, int numUnits) {
+    if (!b) { set_error("edlibAmdBatchWindowsSetUnits: null batch"); return EDLIB_STATUS_ERROR; }
+    if (!b->windows) {
+        set_error("edlibAmdBatchWindowsSetUnits: not available on %s (only the queries and units of a window batch can be "
+                  "replaced)", kind_of(b));
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchWindowsSetUnits", 1, [&] {
+               return b->windows->setUnits(queries, queryOffsets, numQueries, unitQuery, unitStart, unitLength, unitStrand,
+                                           numUnits); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* b, int what, EdlibAmdWindowView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
     if (not_on_self(b, "edlibAmdBatchWindowView") || not_on_occurrences(b, "edlibAmdBatchWindowView")) return EDLIB_STATUS_ERROR;

@@ -308,14 +308,6 @@ int CrossBatch::shapeGroups(const std::vector<long long>& colsBelow)
     return 0;
 }
 
-// 65,536 as the messages of setTargets write it
-static std::string with_commas(long long v)
-{
-    std::string s = std::to_string(v);
-    for (int i = (int)s.size() - 3; i > 0; i -= 3) s.insert((size_t)i, ",");
-    return s;
-}
-
 // A target set (every target at most kCrossMaxTarget bases) on its way into the batch: the raw pool and the caller's
 // offsets go up as they are, one asynchronous copy each, and the device makes the rest (cross_targets.hip) -- the presence
 // set of the pool, the stable order by length, the dword offsets of the packed targets.  `dwords`: of the packed pool.

@@ -33,6 +33,13 @@ int copy_offsets(const long long* in, int n, const char* what, std::vector<long 
     return 0;
 }
 
+std::string with_commas(long long v)
+{
+    std::string s = std::to_string(v);
+    for (int i = (int)s.size() - 3; i > 0; i -= 3) s.insert((size_t)i, ",");
+    return s;
+}
+
 void PairPool::add(const char* q, long long qn, bool reverse, const char* t, long long tn)
 {
     if (!reverse) qp.insert(qp.end(), q, q + qn);

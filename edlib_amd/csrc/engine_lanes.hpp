@@ -12,6 +12,9 @@ namespace edlib_amd {
 // (PinnedPart: common.hpp)
 struct WantedPart { int asked; PinnedPart* part; const void* dev; size_t bytes; };
 
+// 65,536 as the messages of setTargets and setUnits write it
+std::string with_commas(long long v);
+
 // The pairs of an internal pair Batch: the bytes of every pair replicated, query and target
 struct PairPool {
     std::vector<char> qp, tp;
@@ -219,6 +222,9 @@ int choose_qt(long long nq, long long nt, int minQt = 1);
 // once per Run whatever the number of units that name them; units outside the window kernel's envelope (query above 256
 // bases, window above 65,536 columns, more than 16 target symbols) run through one internal pair Batch over slices
 // materialised at Create and are scattered into the unit arrays.
+// setUnits (DESIGN.md §4i "Streamed units") passes other queries and units through the resident batch: the target, its
+// pack and its tables stay, the set is checked on the host and grouped, ordered and given Peq slots on the device
+// (window_units.hip), the way init prepares a list that lies inside the kernel's envelope.
 class WindowBatch : public LaneEngine {
 public:
     ~WindowBatch() { closeStream(); }
@@ -227,16 +233,51 @@ public:
     int init(const char* queries, const long long* qoff, int nq, const char* target, int targetLength,
              const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
              int numUnits, EdlibAlignConfig cfg, int device);
+    // Other queries and units for the resident target (DESIGN.md §4i "Streamed units"): checked on the host in one pass
+    // over the offsets and one over the units, then uploaded as they are and grouped, ordered and given Peq slots on the
+    // device; a refusal leaves the batch as it was
+    int setUnits(const char* queries, const long long* qoff, int nq, const int* unitQuery, const int* unitStart,
+                 const int* unitLength, const unsigned char* unitStrand, int numUnits);
     int run();
     int view(int what, EdlibAmdWindowView* out);
 
 private:
     struct Group : LaneGroup {                    // slots: the (query, strand) entries its units name, unpadded
         int numSorted = 0;                        // wordSteps: of its scanned units (not the empty or the NW-skipped ones)
-        DevBuf<int> d_uslot, d_ustart, d_ulen, d_uperm;        // per unit, sorted by window length
+        // per unit, sorted by window length; of a set prepared on the device these and d_perm are views into prep_
+        DevBuf<int> d_uslot, d_ustart, d_ulen, d_uperm;
     };
+    // what the host's pass over a unit list finds
+    struct UnitCensus {
+        bool stranded = false;                    // a unit names a reverse complement
+        bool inside = true;                       // every unit lies inside the window kernel's envelope
+        int longUnit = -1;                        // the first window above 65,536 columns
+        long long cells = 0;
+        int units[kCrossMaxQueryWords + 1] = {};              // per word group
+        long long wordSteps[kCrossMaxQueryWords + 1] = {};
+    };
+    // the unit checks of Create and SetUnits in one pass; 0 with the census filled, or 1 with the first bad unit named
+    static int checkUnits(const long long* qoff, int nq, int targetLength, const int* unitQuery, const int* unitStart,
+                          const int* unitLength, const unsigned char* unitStrand, int nu, int mode, int k, UnitCensus& c);
+    // the device buffers of a prepared set: the uploads, the scratch of window_units.hip and its results, all grow-only
+    struct UnitPrep {
+        DevBuf<uint8_t> raw, strand, named, tmp;
+        DevBuf<long long> offIn;
+        DevBuf<int> ustart, ulen;                 // as the caller gave them (the unit queries are d_uq_)
+        DevBuf<uint32_t> ukey, uval, ukeyS, ekey, eval, ekeyS;
+        DevBuf<int> slotOf, ent, bound;
+        DevBuf<int> suslot, sustart, sulen, superm;            // the scan's arrays, every group's back to back
+        PinBuf h_bound;
+    } prep_;
+    // the queries and units of a checked set made the batch's on the device (Create and SetUnits); a device error leaves
+    // the batch without units (noUnits_)
+    int prepareUnits(const char* queries, const long long* qoff, int nq, const int* unitQuery, const int* unitStart,
+                     const int* unitLength, const unsigned char* unitStrand, int nu, const UnitCensus& c);
+    int noResults();                              // Run's and the views': the error of a batch without units or without a Run
+    bool noUnits_ = false;                        // a setUnits failed on the device after it had begun to change the batch
     int nu_ = 0, targetLength_ = 0;
-    std::vector<std::unique_ptr<Group>> groups_;
+    std::unique_ptr<Group> groupOf_[kCrossMaxQueryWords + 1];  // the group of every word count, kept for its buffers
+    std::vector<Group*> groups_;                  // those that have units
     DevBuf<int> d_uq_;                            // [nu] query of every unit (the best reduction)
     DevBuf<int> d_units_;                         // [3][nu]: editDistance, numLocations, endLocation
     // d_best_: [3][nq], d_bkey_: [2][nq]

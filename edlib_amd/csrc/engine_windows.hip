@@ -1,8 +1,11 @@
 // engine_windows.hip -- host side of window batches: units over one resident target, unit u = query unitQuery[u] against
 // the window [unitStart[u], unitStart[u] + unitLength[u]), DISTANCE only (DESIGN.md "Window batches").  Create checks the
-// unit list, packs the target to 4-bit codes once, sorts the queries into word groups (a cross batch's) and every group's
-// units by window length, and uploads per unit its query slot, start, length and place in the caller's order; nothing is
-// sized by bytes of windows.  A Run builds the Peq rows of every query, scans every group on the window kernel, lets the
+// unit list and packs the target to 4-bit codes once.  A list inside the window kernel's envelope goes up as it is and
+// the device sorts the queries into word groups (a cross batch's) and every group's units by window length
+// (prepareUnits, window_units.hip); setUnits passes the next list through the resident batch the same way.  A list with
+// units outside the envelope is grouped and sorted by the host, which sends those units to an internal pair session.
+// Either way a unit has its query slot, start, length and place in the caller's order; nothing is sized by bytes of
+// windows.  A Run builds the Peq rows of every query, scans every group on the window kernel, lets the
 // internal pair session of the units outside the kernel's envelope run meanwhile, scatters its results into the unit
 // arrays and reduces them to the best unit per query.  Results stay in HBM until view() asks for a part of them.
 // Units with a strand: where a unit names the reverse complement of its query the query pool holds both
@@ -14,6 +17,41 @@
 #include <cstring>
 
 namespace edlib_amd {
+
+int WindowBatch::checkUnits(const long long* qoff, int nq, int targetLength, const int* unitQuery, const int* unitStart,
+                            const int* unitLength, const unsigned char* unitStrand, int nu, int mode, int k, UnitCensus& c)
+{
+    for (int u = 0; u < nu; ++u) {
+        const int q = unitQuery[u], n = unitLength[u];
+        if (q < 0 || q >= nq) {
+            set_error("window batch: unit %d names query %d, outside [0, numQueries = %d)", u, q, nq);
+            return 1;
+        }
+        if (unitStart[u] < 0) { set_error("window batch: unit %d has a negative unitStart (%d)", u, unitStart[u]); return 1; }
+        if (n < 0) { set_error("window batch: unit %d has a negative unitLength (%d)", u, n); return 1; }
+        if ((long long)unitStart[u] + (long long)n > (long long)targetLength) {
+            set_error("window batch: unit %d ends past the target (unitStart %d + unitLength %d > targetLength %d)", u,
+                      unitStart[u], n, targetLength);
+            return 1;
+        }
+        if (unitStrand && unitStrand[u] > 1) {
+            set_error("window batch: unit %d has unitStrand %d (0: the query, 1: its reverse complement)", u, (int)unitStrand[u]);
+            return 1;
+        }
+        if (unitStrand && unitStrand[u]) c.stranded = true;
+        const long long m = qoff[q + 1] - qoff[q];
+        c.cells += m * n;
+        if (m > 32 * kCrossMaxQueryWords || n > kCrossMaxTarget) {
+            c.inside = false;
+            if (n > kCrossMaxTarget && c.longUnit < 0) c.longUnit = u;
+            continue;
+        }
+        const int w = std::max(1, ((int)m + 31) / 32);                    // empty queries ride in the one-word group
+        ++c.units[w];
+        if (m > 0 && n > 0 && !cross_nw_outside(mode, k, (int)m, n)) c.wordSteps[w] += (long long)w * n;
+    }
+    return 0;
+}
 
 int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, const char* target, int targetLength,
                       const int* unitQuery, const int* unitStart, const int* unitLength, const unsigned char* unitStrand,
@@ -34,25 +72,10 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
     }
     std::vector<long long> qoff;
     if (copy_offsets(qoffIn, nq, "query", qoff)) return 1;
-    for (int u = 0; u < nu; ++u) {
-        if (unitQuery[u] < 0 || unitQuery[u] >= nq) {
-            set_error("window batch: unit %d names query %d, outside [0, numQueries = %d)", u, unitQuery[u], nq);
-            return 1;
-        }
-        if (unitStart[u] < 0) { set_error("window batch: unit %d has a negative unitStart (%d)", u, unitStart[u]); return 1; }
-        if (unitLength[u] < 0) { set_error("window batch: unit %d has a negative unitLength (%d)", u, unitLength[u]); return 1; }
-        if ((long long)unitStart[u] + (long long)unitLength[u] > (long long)targetLength) {
-            set_error("window batch: unit %d ends past the target (unitStart %d + unitLength %d > targetLength %d)", u,
-                      unitStart[u], unitLength[u], targetLength);
-            return 1;
-        }
-        if (unitStrand && unitStrand[u] > 1) {
-            set_error("window batch: unit %d has unitStrand %d (0: the query, 1: its reverse complement)", u, (int)unitStrand[u]);
-            return 1;
-        }
-    }
-    bool stranded = false;                                                // a unit names a reverse complement
-    for (int u = 0; u < nu && unitStrand && !stranded; ++u) stranded = unitStrand[u] != 0;
+    UnitCensus census;
+    if (checkUnits(qoff.data(), nq, targetLength, unitQuery, unitStart, unitLength, unitStrand, nu, (int)cfg.mode, cfg.k,
+                   census)) return 1;
+    const bool stranded = census.stranded;                                // a unit names a reverse complement
     if (stranded && nq > 0x3fffffff) { set_error("bad batch shape"); return 1; }
     auto strandOf = [&](int u) { return stranded ? (int)unitStrand[u] : 0; };
     if (check_device(device)) return 1;
@@ -61,7 +84,7 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
     device_ = device; nq_ = nq; nu_ = nu; targetLength_ = targetLength;
     auto qlen = [&](int q) { return (int)(qoff[q + 1] - qoff[q]); };
     stats = EdlibAmdBatchStats{};
-    for (int u = 0; u < nu; ++u) stats.cells += (long long)qlen(unitQuery[u]) * unitLength[u];
+    stats.cells = census.cells;
 
     build_tables(tab_, reinterpret_cast<const uint8_t*>(target), targetLength, eqs_.data(), (int)eqs_.size());
     const bool wide = tab_.sigmaT > kCrossMaxSyms;
@@ -74,6 +97,18 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     if (openStream()) return 1;
+    if (!wide) {
+        // the target the window kernel can take is resident whatever this unit list leaves it (a later setUnits finds
+        // it): 4-bit codes from dword 0, and the tables of its symbols
+        if (packHostTargets(target, {0, targetLength}, {0}, {targetLength})) return 1;
+        EDLIB_AMD_HIP(d_eqtbl_.ensure(256)); EDLIB_AMD_HIP(d_presence_.ensure(8));
+        EDLIB_AMD_HIP(hipMemcpy(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice));
+        EDLIB_AMD_HIP(hipMemcpy(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice));
+        // a list that lies inside the kernel's envelope is prepared on the device, the way setUnits does it; one with a
+        // unit outside it takes the host loop below, where the pair route changes the kernel's subset
+        if (census.inside)
+            return prepareUnits(queries, qoff.data(), nq, unitQuery, unitStart, unitLength, unitStrand, nu, census);
+    }
     EDLIB_AMD_HIP(d_units_.alloc(3 * (size_t)std::max(nu, 1)));
     EDLIB_AMD_HIP(d_uq_.alloc((size_t)std::max(nu, 1)));
     EDLIB_AMD_HIP(d_best_.alloc(3 * (size_t)std::max(nq, 1)));
@@ -89,8 +124,6 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
         ++kernelUnits;
     }
     if (kernelUnits > 0) {
-        // the target: 4-bit codes from dword 0
-        if (packHostTargets(target, {0, targetLength}, {0}, {targetLength})) return 1;
         if (uploadQueries(queries, qoff, stranded)) return 1;
         // a pool entry's slot in its group; the entry of a unit is its query, or 2 * query + strand in a stranded batch
         std::vector<int> slotOf((size_t)nq * (stranded ? 2 : 1), -1);
@@ -99,7 +132,8 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
             if (us.empty()) continue;
             // neighbours in window length share a wave, so that its 64 lanes finish together
             std::stable_sort(us.begin(), us.end(), [&](int a, int b) { return unitLength[a] < unitLength[b]; });
-            std::unique_ptr<Group> g(new Group);
+            groupOf_[w].reset(new Group);
+            Group* g = groupOf_[w].get();
             g->words = w; g->numSorted = (int)us.size();
             std::vector<int> perm, uslot(us.size()), ustart(us.size()), ulen(us.size());
             for (size_t i = 0; i < us.size(); ++i) {
@@ -117,7 +151,7 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
             EDLIB_AMD_HIP(hipMemcpy(g->d_ustart.p, ustart.data(), ns * sizeof(int), hipMemcpyHostToDevice));
             EDLIB_AMD_HIP(hipMemcpy(g->d_ulen.p, ulen.data(), ns * sizeof(int), hipMemcpyHostToDevice));
             EDLIB_AMD_HIP(hipMemcpy(g->d_uperm.p, us.data(), ns * sizeof(int), hipMemcpyHostToDevice));
-            groups_.push_back(std::move(g));
+            groups_.push_back(g);
         }
     }
 
@@ -138,8 +172,155 @@ int WindowBatch::init(const char* queries, const long long* qoffIn, int nq, cons
     return 0;
 }
 
+// The queries and the units of a checked list inside the kernel's envelope made the batch's.  The raw pool, the caller's
+// offsets and the unit arrays go up as they are, one asynchronous copy each; the device makes the rest
+// (window_units.hip): the pool's offsets (and both strands where c.stranded), the units by (word group, window length,
+// unit), a Peq slot per named entry.  The host has the units of every group from its census and reads the groups' slot
+// counts back, nine ints; a group's arrays are views into the prepared ones.  What the batch held as internal pair
+// session is dropped; the stream is idle afterwards.
+int WindowBatch::prepareUnits(const char* queries, const long long* qoff, int nq, const int* unitQuery, const int* unitStart,
+                              const int* unitLength, const unsigned char* unitStrand, int nu, const UnitCensus& c)
+{
+    const bool st = c.stranded;
+    const size_t ne = (size_t)nq * (st ? 2 : 1), n = (size_t)nu;
+    const long long qb = nq > 0 ? qoff[0] : 0, qbytes = nq > 0 ? qoff[nq] - qb : 0;
+    pairs_.reset(); pairUnits_.clear();
+    d_cells_.release(); d_vals_.release(); h_vals_.release();
+    groups_.clear();
+    nq_ = nq; nu_ = nu;
+    haveRun_ = false;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = c.cells;
+    EDLIB_AMD_HIP(d_units_.ensure(3 * (size_t)std::max(nu, 1))); EDLIB_AMD_HIP(d_uq_.ensure((size_t)std::max(nu, 1)));
+    EDLIB_AMD_HIP(d_best_.ensure(3 * (size_t)std::max(nq, 1))); EDLIB_AMD_HIP(d_bkey_.ensure(2 * (size_t)std::max(nq, 1)));
+
+    // ---- the query pool
+    EDLIB_AMD_HIP(d_qoff_.ensure(ne + 1)); EDLIB_AMD_HIP(d_qpool_.ensure((st ? 2 : 1) * (size_t)qbytes + 16));
+    if (nq > 0) {
+        EDLIB_AMD_HIP(prep_.offIn.ensure((size_t)nq + 1));
+        EDLIB_AMD_HIP(hipMemcpyAsync(prep_.offIn.p, qoff, ((size_t)nq + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(launch_window_query_offsets(prep_.offIn.p, nq, st, d_qoff_.p, stream_));
+        uint8_t* raw = d_qpool_.p;
+        if (st) { EDLIB_AMD_HIP(prep_.raw.ensure((size_t)qbytes + 16)); raw = prep_.raw.p; }
+        if (qbytes) EDLIB_AMD_HIP(hipMemcpyAsync(raw, queries + qb, (size_t)qbytes, hipMemcpyHostToDevice, stream_));
+        if (st) EDLIB_AMD_HIP(launch_strand_pool(raw, d_qoff_.p, nq, d_qpool_.p, stream_));
+    }
+
+    // ---- the units
+    if (!prep_.h_bound.p) EDLIB_AMD_HIP(prep_.h_bound.alloc((kWindowNoGroup + 1) * sizeof(int)));
+    int* bound = reinterpret_cast<int*>(prep_.h_bound.p);
+    memset(bound, 0, (kWindowNoGroup + 1) * sizeof(int));
+    if (nu > 0) {
+        UnitPrep& p = prep_;
+        size_t tmpBytes = 0;
+        EDLIB_AMD_HIP(window_units_tmp_bytes(nu, (int)ne, &tmpBytes));
+        EDLIB_AMD_HIP(p.ustart.ensure(n)); EDLIB_AMD_HIP(p.ulen.ensure(n)); EDLIB_AMD_HIP(p.tmp.ensure(tmpBytes));
+        EDLIB_AMD_HIP(p.ukey.ensure(n)); EDLIB_AMD_HIP(p.uval.ensure(n)); EDLIB_AMD_HIP(p.ukeyS.ensure(n));
+        EDLIB_AMD_HIP(p.named.ensure(ne)); EDLIB_AMD_HIP(p.ekey.ensure(ne)); EDLIB_AMD_HIP(p.eval.ensure(ne));
+        EDLIB_AMD_HIP(p.ekeyS.ensure(ne)); EDLIB_AMD_HIP(p.slotOf.ensure(ne)); EDLIB_AMD_HIP(p.ent.ensure(ne));
+        EDLIB_AMD_HIP(p.bound.ensure(kWindowNoGroup + 1));
+        EDLIB_AMD_HIP(p.suslot.ensure(n)); EDLIB_AMD_HIP(p.sustart.ensure(n)); EDLIB_AMD_HIP(p.sulen.ensure(n));
+        EDLIB_AMD_HIP(p.superm.ensure(n));
+        if (st) EDLIB_AMD_HIP(p.strand.ensure(n));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_uq_.p, unitQuery, n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(p.ustart.p, unitStart, n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(p.ulen.p, unitLength, n * sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (st) EDLIB_AMD_HIP(hipMemcpyAsync(p.strand.p, unitStrand, n, hipMemcpyHostToDevice, stream_));
+        WindowUnitsArgs a{};
+        a.offIn = p.offIn.p; a.unitQuery = d_uq_.p; a.unitStart = p.ustart.p; a.unitLength = p.ulen.p;
+        a.unitStrand = st ? p.strand.p : nullptr;
+        a.numUnits = nu; a.numEntries = (int)ne;
+        a.named = p.named.p; a.ukey = p.ukey.p; a.uval = p.uval.p; a.ukeySorted = p.ukeyS.p;
+        a.ekey = p.ekey.p; a.eval = p.eval.p; a.ekeySorted = p.ekeyS.p; a.slotOf = p.slotOf.p;
+        a.entSorted = p.ent.p; a.bound = p.bound.p;
+        a.uslot = p.suslot.p; a.ustart = p.sustart.p; a.ulen = p.sulen.p; a.uperm = p.superm.p;
+        EDLIB_AMD_HIP(launch_window_units_prepare(a, p.tmp.p, tmpBytes, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(bound, p.bound.p, (kWindowNoGroup + 1) * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    }
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+
+    // ---- the groups that have units: views into the prepared arrays, Peq buffers of their own
+    size_t at = 0;
+    for (int w = 1; w <= kCrossMaxQueryWords; ++w) {
+        if (c.units[w] == 0) continue;
+        if (!groupOf_[w]) groupOf_[w].reset(new Group);
+        Group& g = *groupOf_[w];
+        const size_t ns = (size_t)c.units[w];
+        g.words = w; g.numSorted = c.units[w]; g.wordSteps = c.wordSteps[w];
+        g.slots = bound[w] - bound[w - 1];
+        if (g.slots <= 0 || bound[w - 1] < 0 || (size_t)bound[w] > ne) {
+            set_error("window batch: the device counted %d query slots for the %d units of %d words", g.slots, c.units[w], w);
+            return 1;
+        }
+        g.d_perm.alias(prep_.ent.p + bound[w - 1], (size_t)g.slots);
+        g.d_uslot.alias(prep_.suslot.p + at, ns); g.d_ustart.alias(prep_.sustart.p + at, ns);
+        g.d_ulen.alias(prep_.sulen.p + at, ns); g.d_uperm.alias(prep_.superm.p + at, ns);
+        const size_t blocks = (size_t)(g.slots + 63) / 64;
+        EDLIB_AMD_HIP(g.d_qlen.ensure(g.slots)); EDLIB_AMD_HIP(g.d_kinit.ensure(g.slots)); EDLIB_AMD_HIP(g.d_alpha.ensure(g.slots));
+        EDLIB_AMD_HIP(g.d_peq.ensure(blocks * syms_ * g.words * 64));
+        groups_.push_back(&g);
+        at += ns;
+    }
+    return 0;
+}
+
+int WindowBatch::setUnits(const char* queries, const long long* qoff, int nq, const int* unitQuery, const int* unitStart,
+                          const int* unitLength, const unsigned char* unitStrand, int nu)
+{
+    static const char* const fn = "edlibAmdBatchWindowsSetUnits";
+    // ---- what is refused leaves the batch as it was
+    if (nu < 0) { set_error("%s: numUnits must be >= 0 (got %d)", fn, nu); return 1; }
+    if (nq < 0) { set_error("%s: numQueries must be >= 0 (got %d)", fn, nq); return 1; }
+    if (nq > 0 && (!queries || !qoff)) { set_error("%s: queries and queryOffsets must not be NULL for %d queries", fn, nq); return 1; }
+    if (nu > 0 && (!unitQuery || !unitStart || !unitLength)) {
+        set_error("%s: unitQuery, unitStart and unitLength must not be NULL for %d units", fn, nu);
+        return 1;
+    }
+    if (tab_.sigmaT > kCrossMaxSyms) {
+        set_error("%s: the batch's target holds %d distinct symbols, the limit for a batch that streams units is %d: create a "
+                  "new batch", fn, tab_.sigmaT, kCrossMaxSyms);
+        return 1;
+    }
+    // the host's share, linear in numQueries + numUnits: one pass over the offsets, one over the units
+    for (int q = 0; q < nq; ++q) {
+        const long long m = qoff[q + 1] - qoff[q];
+        if (m < 0) { set_error("%s: bad query offsets (query %d ends before it starts)", fn, q); return 1; }
+        if (m > 32 * kCrossMaxQueryWords) {
+            set_error("%s: query %d has %s bases, the limit for a streamed set is %d: create a new batch", fn, q,
+                      with_commas(m).c_str(), 32 * kCrossMaxQueryWords);
+            return 1;
+        }
+    }
+    UnitCensus census;
+    if (checkUnits(qoff, nq, targetLength_, unitQuery, unitStart, unitLength, unitStrand, nu, (int)cfg_.mode, cfg_.k, census))
+        return 1;
+    if (census.longUnit >= 0) {
+        set_error("%s: unit %d has a window of %s columns, the limit for a streamed set is %s: create a new batch", fn,
+                  census.longUnit, with_commas(unitLength[census.longUnit]).c_str(), with_commas(kCrossMaxTarget).c_str());
+        return 1;
+    }
+    if (census.stranded && nq > 0x3fffffff) { set_error("%s: bad batch shape", fn); return 1; }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+
+    // ---- from here a device error leaves the batch without units
+    noUnits_ = true;
+    if (prepareUnits(queries, qoff, nq, unitQuery, unitStart, unitLength, unitStrand, nu, census)) return 1;
+    noUnits_ = false;
+    return 0;
+}
+
+int WindowBatch::noResults()
+{
+    if (noUnits_) set_error("window batch: it has no units (edlibAmdBatchWindowsSetUnits failed on the device): set them again");
+    else set_error("window batch: no results (Run it first)");
+    return 1;
+}
+
 int WindowBatch::run()
 {
+    if (noUnits_) return noResults();
     pool_quarantine(false);
     const auto t0 = std::chrono::steady_clock::now();
     DeviceGuard guard(device_);
@@ -179,7 +360,7 @@ int WindowBatch::run()
 
 int WindowBatch::view(int what, EdlibAmdWindowView* out)
 {
-    if (!haveRun_) { set_error("window batch: no results (Run it first)"); return 1; }
+    if (!haveRun_) return noResults();
     if (what & ~(EDLIB_AMD_WINDOW_UNITS | EDLIB_AMD_WINDOW_BEST)) { set_error("window view: unknown parts %d", what); return 1; }
     pool_quarantine(false);
     DeviceGuard guard(device_);

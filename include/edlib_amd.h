@@ -508,6 +508,35 @@ typedef struct {
 #define EDLIB_AMD_WINDOW_BEST  2
 EDLIB_API int edlibAmdBatchWindowView(EdlibAmdBatch* batch, int what, EdlibAmdWindowView* out);
 
+/* Replace the queries and the units of a resident window batch (a mapper's next chunk of reads and candidates over the
+ * same reference).  The target, its 4-bit pack, its tables, the config, the device, the stream, the pinned view blocks
+ * and every device buffer that is large enough stay; the query pool, the unit list and everything derived from them are
+ * made again.  Afterwards the batch is as if it had been created over (its target, its config, these queries, these
+ * units): Run, then edlibAmdBatchWindowView.  Returns 0, or non-zero with edlibAmdLastError().
+ * Valid on the batches of edlibAmdBatchCreateWindows and ...WindowsStranded, whichever of the two created it: a NULL
+ * unitStrand is all forward, a stranded set may follow a plain one and the other way round.  Refused, with this function
+ * and the kind named, on cross, self, read and pair batches.
+ * A streamed set lies inside the window kernel's envelope: the batch's target has at most 16 distinct symbols (decided
+ * at Create: a batch over a wider target refuses every call), every query is at most 256 bases -- named by a unit or not
+ * -- and every window at most 65,536 columns.  Outside it the call is refused with the first offending query or unit, its
+ * size and the limit named ("... create a new batch"): a streamed set builds no internal pair batch, and the one a
+ * Create built is dropped by the first successful call.  The unit checks are those of Create, with its messages:
+ * unitQuery outside [0, numQueries), a negative unitStart or unitLength, unitStart + unitLength > targetLength,
+ * unitStrand > 1.  Also refused: numUnits < 0, numQueries < 0, a NULL pointer with a positive count, query offsets that
+ * decrease.  queryOffsets[0] need not be 0; the caller's memory may be reused when the call returns; numUnits == 0 and
+ * numQueries == 0 are valid (Run succeeds, the views are empty).
+ * Every refusal is decided before the batch changes and leaves it as it was: the previous queries and units, the views
+ * of the last Run (pointers the caller still holds included), the results of the next.  Behind that point only a device
+ * error (out of memory) can fail the call; it may leave the batch without units: Run and the views then fail with a
+ * message that says so until a SetUnits succeeds.  After success the views fail ("Run it first") until the next Run, and
+ * Stats.cells describes the new set.
+ * The set is prepared on the device (word groups, stable sort by window length, a Peq slot per query and strand a unit
+ * names); the host's share is one pass over the offsets and one over the units, and it reads no byte of a query. */
+EDLIB_API int edlibAmdBatchWindowsSetUnits(EdlibAmdBatch* batch,
+    const char* queries, const long long* queryOffsets, int numQueries,
+    const int* unitQuery, const int* unitStart, const int* unitLength,
+    const unsigned char* unitStrand /* NULL: all forward */, int numUnits);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
