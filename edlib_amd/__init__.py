@@ -189,6 +189,8 @@ def lib():
         if hasattr(L, "edlibAmdBatchWindowsSetUnits"):
             L.edlibAmdBatchWindowsSetUnits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "edlibAmdBatchPairsSetPairs"):
+            L.edlibAmdBatchPairsSetPairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         if hasattr(L, "edlibAmdBatchCreateSelf"):
             L.edlibAmdBatchCreateSelf.restype = C.c_void_p
             L.edlibAmdBatchCreateSelf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -494,7 +496,10 @@ class _Batch:
             raise RuntimeError("edlib_amd: cigars failed: " + last_error())
         off = np.ctypeslib.as_array(C.cast(po, C.POINTER(C.c_longlong)), shape=(self.n + 1,))
         total = int(off[-1])
-        chars = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_ubyte)), shape=(max(total, 1),))[:total]
+        if total == 0:                             # (a batch of zero units: there is no character to point at)
+            chars = np.zeros(0, dtype=np.uint8)
+        else:
+            chars = np.ctypeslib.as_array(C.cast(pc, C.POINTER(C.c_ubyte)), shape=(total,))
         return (chars.copy(), off.copy()) if copy else (chars, off)
 
     def cigar_list(self, extended=True):
@@ -603,7 +608,13 @@ class BothStrandsBatch(_Batch):
 
 
 class PairBatch(_Batch):
-    """Independent (query, target) pairs."""
+    """Independent (query, target) pairs.
+    set_pairs(queries, targets) (edlibAmdBatchPairsSetPairs) passes another pair set through the resident batch: the
+    config, the stream and every buffer that is large enough stay, the set is laid out on the device, and the batch is
+    then as if created over (its config, these pairs) -- run(), then results_flat() / cigars() / results().  A streamed
+    set lies inside the flat envelope (queries of 1 to 1,024 bases, targets of 1 to 65,536; with task="path" also SHW / HW
+    queries up to 256 bases and no pair in the linear-space regime) and may have any count; outside it the call raises and
+    the batch stays as it was."""
 
     def __init__(self, queries, targets, mode="NW", task="distance", k=-1, additionalEqualities=None, device=0):
         qd, qo = _pack(queries)
@@ -614,6 +625,18 @@ class PairBatch(_Batch):
         h = lib().edlibAmdBatchCreatePairs(qd.ctypes.data, qo.ctypes.data, td.ctypes.data, to.ctypes.data,
                                            len(qo) - 1, cfg, device)
         super().__init__(h, len(qo) - 1, keep)
+
+    def set_pairs(self, queries, targets):
+        """Replace the pairs (the constructor's input forms: lists of bytes / arrays, or 2-D uint8 arrays).  Raises
+        RuntimeError with last_error() on a refusal, which leaves the batch as it was.  run() before the next results."""
+        qd, qo = _pack(queries)
+        td, to = _pack(targets)
+        if len(qo) != len(to):
+            raise ValueError("queries and targets differ in count")
+        if lib().edlibAmdBatchPairsSetPairs(self._h, qd.ctypes.data, qo.ctypes.data, td.ctypes.data, to.ctypes.data,
+                                            len(qo) - 1) != 0:
+            raise RuntimeError("edlib_amd: set_pairs failed: " + last_error())
+        self.n = len(qo) - 1
 
 
 class CrossBatch(_Batch):

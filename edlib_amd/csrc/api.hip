@@ -179,7 +179,8 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreatePairs(const char* queries, const lon
                                                   int numPairs, EdlibAlignConfig config, int device) {
     // a one-pair batch is also a shared-target batch
     return create_batch("edlibAmdBatchCreatePairs", [&](EdlibAmdBatch& b) {
-        return b.impl.init(queries, queryOffsets, numPairs, targets, targetOffsets, numPairs, config, device); });
+        return b.impl.init(queries, queryOffsets, numPairs, targets, targetOffsets, numPairs, config, device, false, false,
+                           /*pairs=*/true); });
 }
 
 EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSharedBothStrands(const char* queries, const long long* queryOffsets,
@@ -389,10 +390,24 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateWindowsStranded(const char* queries,
                           unitQuery, unitStart, unitLength, unitStrand, numUnits, config, device);
 }
 
-// "a cross batch", "a self batch", ...: the kind of a batch that is not a window batch, for a refusal
+// "a cross batch", "a self batch", ...: the kind of a batch, for a refusal
 static const char* kind_of(EdlibAmdBatch* b) {
+    if (b->windows) return "a window batch";
     if (b->cross) return b->cross->isSelf() ? "a self batch" : b->cross->isOccurrences() ? "an occurrence batch" : "a cross batch";
-    return b->impl.isHits() ? "a hit-list read batch" : "a read or pair batch";
+    if (b->impl.isPairs()) return "a pair batch";
+    return b->impl.isHits() ? "a hit-list read batch" : b->impl.isBothStrands() ? "a both-strand read batch" : "a shared-target read batch";
+}
+
+EDLIB_API int edlibAmdBatchPairsSetPairs(EdlibAmdBatch* b, const char* queries, const long long* queryOffsets,
+                                         const char* targets, const long long* targetOffsets, int numPairs) {
+    if (!b) { set_error("edlibAmdBatchPairsSetPairs: null batch"); return EDLIB_STATUS_ERROR; }
+    if (b->windows || b->cross || !b->impl.isPairs()) {
+        set_error("edlibAmdBatchPairsSetPairs: not available on %s (only the pairs of a batch made by edlibAmdBatchCreatePairs "
+                  "can be replaced)", kind_of(b));
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchPairsSetPairs", 1, [&] {
+               return b->impl.setPairs(queries, queryOffsets, targets, targetOffsets, numPairs); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
 EDLIB_API int edlibAmdBatchWindowsSetUnits(EdlibAmdBatch* b, const char* queries, const long long* queryOffsets,

@@ -70,6 +70,11 @@ struct DevBuf {
     }
     // grow-only; a view (alias()) is never "enough": its block belongs to somebody else and may be gone
     hipError_t ensure(size_t count) { return (count <= n && p && owned) ? hipSuccess : alloc(count); }
+    // grow-only like ensure(), but n becomes the count asked for: for a buffer whose readers go by n (a pool's bytes)
+    hipError_t resize(size_t count) {
+        if (p && owned && count > 0 && count * sizeof(T) <= granted) { n = count; return hipSuccess; }
+        return alloc(count);
+    }
     size_t bytes() const { return n * sizeof(T); }
     void swap(DevBuf& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(granted, o.granted); std::swap(owned, o.owned); }
 };

@@ -212,8 +212,9 @@ Batch::~Batch() {
 int roundup(int x, int q) { return (x + q - 1) / q * q; }
 
 int Batch::init(const char* queries, const long long* qoff, int n, const char* targets,
-                const long long* toff, int numTargets, EdlibAlignConfig cfg, int device, bool bothStrands, bool hits)
+                const long long* toff, int numTargets, EdlibAlignConfig cfg, int device, bool bothStrands, bool hits, bool pairs)
 {
+    pairsKind_ = pairs;
     if (n < 0 || (numTargets != 1 && numTargets != n)) { set_error("bad batch shape"); return 1; }
     if (hits) {
         // what a hit-list read batch takes (edlib_amd.h): everything else is refused with the limit named
@@ -243,13 +244,13 @@ int Batch::init(const char* queries, const long long* qoff, int n, const char* t
     shared_ = (numTargets == 1);
     if (copy_offsets(qoff, n, "query", qoff_)) return 1;
     const int numReads = n;
-    const long long qb = qoff[0];
+    const long long qb = qoff ? qoff[0] : 0;                    // (NULL offsets: a batch over zero units)
     if (strands_) {
         // units 2i / 2i + 1: read i and its reverse complement, back to back in a pool of twice the bytes (already rebased)
         n = 2 * numReads;
         qoff_.resize((size_t)n + 1);
         for (int i = 0; i < numReads; ++i) { qoff_[2 * i] = 2 * (qoff[i] - qb); qoff_[2 * i + 1] = 2 * (qoff[i] - qb) + (qoff[i + 1] - qoff[i]); }
-        qoff_[n] = 2 * (qoff[numReads] - qb);
+        qoff_[n] = qoff ? 2 * (qoff[numReads] - qb) : 0;
     }
     n_ = n;
     if (copy_offsets(toff, numTargets, "target", toff_)) return 1;
@@ -589,6 +590,7 @@ int Batch::alphabetLengthsEnd(std::vector<UnitResult>& res)
 // that no spinning launch of this batch is still on the device when the next one takes the gate.
 int Batch::run()
 {
+    if (noPairs_) return noResults("run");
     const int rc = runImpl();
     if (rc && wideGateHeld_) {
         if (stream_) { DeviceGuard guard(device_); (void)hipStreamSynchronize(stream_); (void)hipGetLastError(); }
@@ -1052,7 +1054,7 @@ int Batch::results(EdlibAlignResult* out)
         o.status = EDLIB_STATUS_ERROR; o.editDistance = -1; o.endLocations = nullptr; o.startLocations = nullptr;
         o.numLocations = 0; o.alignment = nullptr; o.alignmentLength = 0; o.alphabetLength = 0;
     }
-    if (!haveResults_) { set_error("results() before a successful run()"); return 1; }
+    if (!haveResults_) return noResults("results()");
     // a DISTANCE run over read groups: the arrays of the device-made view (engine_flat.hip: buildReadsView) are what the
     // results are copied from -- no per-read record in between (an end-location array per result is the reference's contract)
     const bool fromView = readsViewOnDevice();
@@ -1168,7 +1170,7 @@ int Batch::buildHostView()
 
 int Batch::resultsView(EdlibAmdResultsView* out)
 {
-    if (!haveResults_) { set_error("results before a successful run()"); return 1; }
+    if (!haveResults_) return noResults("results");
     DeviceGuard guard(device_);
     EDLIB_AMD_HIP(guard.status);
     if (!viewReady_ && (lastRunFlat_ ? buildFlatView() : (readsViewOnDevice() ? buildReadsView() : buildHostView()))) return 1;

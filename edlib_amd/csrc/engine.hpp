@@ -10,6 +10,7 @@
 #include "cross_kernels.hpp"
 #include "window_kernels.hpp"
 #include "strands.hpp"
+#include "flat_pairs_prepare.hpp"
 
 #include <chrono>
 #include <deque>
@@ -151,6 +152,19 @@ struct UnitResult {
 struct Lap;                        // (below)
 struct ViewLayout;                 // engine_flat.hip
 
+// The host's one pass over the offsets of a pair set (engine_flat.hip: planFlat): whether the set lies inside the flat
+// envelope -- if not, the first pair outside it and why -- and the reductions its layout needs.  No sequence byte is read.
+struct FlatPlan {
+    enum Why { kOk = 0, kBadQueryOffsets, kBadTargetOffsets, kEmptyQuery, kEmptyTarget, kLongQuery, kLongTarget, kPathBlocks,
+               kHirschberg, kStoreCap, kOpsCap };
+    Why why = kOk; int who = -1;                  // the first offending pair
+    int n = 0, maxBlocks = 0, maxT = 0, maxWords = 0;
+    long long qbytes = 0, tbytes = 0, cells = 0, lens = 0, totalBlocks = 0;
+    long long opBytes = 0, store4 = 0, store32 = 0;   // PATH: op slots; entries of the 4-lane ring stores, of the ring32 stores
+    long long chunkMax32 = 0;                         // ... and of the largest chunk of the ring32 NW store
+    std::vector<int> cuts;                            // first units of those chunks, then n
+};
+
 class Batch {
 public:
     virtual ~Batch();
@@ -158,7 +172,12 @@ public:
     int init(const char* queries, const long long* qoff, int n,
              const char* targets, const long long* toff, int numTargets,   // numTargets == 1: shared
              EdlibAlignConfig cfg, int device, bool bothStrands = false,    // bothStrands (shared only): n reads, 2n units
-             bool hits = false);                                            // hits (shared only): a hit-list read batch
+             bool hits = false,                                             // hits (shared only): a hit-list read batch
+             bool pairs = false);                                           // made by edlibAmdBatchCreatePairs (one pair is shared, too)
+    // another pair set through a resident pair batch (edlibAmdBatchPairsSetPairs; engine_flat.hip "streamed pairs")
+    int setPairs(const char* queries, const long long* qoff, const char* targets, const long long* toff, int n);
+    bool isPairs() const { return pairsKind_; }
+    bool isBothStrands() const { return strands_; }
     int run();
     int runImpl();
     int results(EdlibAlignResult* out);
@@ -178,6 +197,9 @@ private:
     std::vector<EdlibEqualityPair> eqs_;
     int device_ = 0;
     bool shared_ = false;
+    bool pairsKind_ = false;                     // created by edlibAmdBatchCreatePairs: takes setPairs
+    bool noPairs_ = false;                       // a setPairs failed on the device: no Run, no views until one succeeds
+    int noResults(const char* who);              // the error of a view that has nothing to show
     int n_ = 0;
     std::vector<long long> qoff_, toff_;
     // ---- both strands: unit 2i is read i, unit 2i + 1 its reverse complement (made on the device at init);
@@ -414,9 +436,15 @@ private:
     DevBuf<PairDesc> d_flatDescs_;
     DevBuf<int> d_flatOut3_, d_flatPos_, d_flatCensus_;
     PinBuf h_flatCensus_;
-    std::vector<long long> flatPeqOff_;
     std::vector<int> flatOvfUnit_; std::vector<long long> flatOvfOff_; std::vector<int> flatOvfPos_;   // exact lists of the last run's overflowing units
-    PairDesc flatDesc(int u) const;
+    FlatShape flatShape() const;
+    void planFlat(const long long* qoff, const long long* toff, int n, bool sharedTarget, FlatPlan& plan,
+                  std::vector<long long>* qout, std::vector<long long>* tout) const;
+    int prepareFlat(const FlatPlan& plan, bool census);      // the set's layout, made on the device: Create and setPairs
+    int streamFlat(const char* queries, const char* targets, const FlatPlan& plan);
+    DevBuf<long long> d_flatPrep_; DevBuf<uint8_t> d_flatPrepTmp_; DevBuf<int> d_flatCuts_;
+    DevBuf<uint8_t> d_flatPrepOut_; PinBuf h_flatPrepOut_;   // presence [8] and word-steps [2] of the prepared set
+    DevBuf<uint8_t> d_tabs_; PinBuf h_tabs_;                 // tlut, idToByte, eqtbl of a streamed set
     int initFlatPairs();
     int runPairsFlat(bool& fellBack);
     // flat LOC / PATH (round 4): start locations and paths of a flat batch are found and kept on the device as well.
@@ -431,7 +459,6 @@ private:
     DevBuf<int> d_flatSlotOf_, d_flatStartOut3_, d_flatStartsOut_, d_flatPathOut3_, d_flatOpsLen_;
     DevBuf<long long> d_flatOpsOff_, d_flatStoreBase_;
     DevBuf<uint8_t> d_flatOps_;
-    std::vector<long long> flatOpsOffHost_;
     int runFlatStartsAndPaths(bool& fellBack);
     int collectPairsFlat(std::vector<UnitResult>& res);
     bool readsViewOnDevice() const;               // a DISTANCE run over read groups only: its view is made by flat_results.hip
@@ -501,6 +528,7 @@ void build_tables(Tables& tab, const uint8_t* targets, long long totalTargetByte
 int check_device(int device);                     // 1 and the error text: no usable device, or `device` out of range
 void keep_config(const EdlibAlignConfig& cfg, EdlibAlignConfig& kept, std::vector<EdlibEqualityPair>& eqs);   // kept points into eqs
 int copy_offsets(const long long* in, int n, const char* what, std::vector<long long>& out);    // "bad <what> offsets"
+std::string with_commas(long long v);                // thousands separators for the sizes a refusal names
 inline int peq_syms(int sigmaT) { return sigmaT <= 4 ? 4 : (sigmaT <= 8 ? 8 : 16); }   // Peq rows per word: 4, 8 or 16
 
 int device_count();

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <string>
 
 namespace edlib_amd {
 
@@ -104,39 +105,77 @@ flat_path_descs_kernel(const PairDesc* __restrict__ descs, const int* __restrict
 
 // ------------------------------------------------------------ flat pair path
 
-static const int kFlatPosCap = 16;
-
 // Batches of short independent pairs (the verification step of a seed-and-extend mapper: 262,144 x 150 bp in 400 bp
 // windows) were host-bound: every run rebuilt 88-byte descriptors for every unit, uploaded them, downloaded 16 end
 // positions per unit and walked 160-byte records five times (22..28 ns per pair with the kernels a fifth of it).  When
 // every unit is a pair of at most 16 blocks and only distances are asked for, nothing about the descriptors depends on a
-// run: they are built once, here, and stay resident; a run is Peq build + one ring scan (whole matrix on a 4- or 16-lane
-// ring: exact for any distance, no levels) + a census of overflowing end-location lists, and the results stay in HBM until
-// results() asks for them -- the lazy form the reads path has had since round 1.
-PairDesc Batch::flatDesc(int u) const
+// run: they are built once, on the device (flat_pairs_prepare.hip), and stay resident; a run is Peq build + one ring scan
+// (whole matrix on a 4- or 16-lane ring: exact for any distance, no levels) + a census of overflowing end-location lists,
+// and the results stay in HBM until results() asks for them -- the lazy form the reads path has had since round 1.
+FlatShape Batch::flatShape() const
+{
+    const int mode = (int)cfg_.mode;
+    FlatShape s{};
+    s.scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
+    s.k = cfg_.k; s.ring = flatRing_; s.g32 = flatG32_; s.nwStore = flatNwStore_ ? 1 : 0; s.ring32 = flatRing32_ ? 1 : 0;
+    return s;
+}
+
+// One pass over the two offset arrays (n + 1 entries each, any base; sharedTarget: toff has two entries, every unit's target
+// is [toff[0], toff[1]) -- a shared-target batch whose units are all pair units): are they offsets, does every pair lie
+// inside the flat envelope, and the reductions the layout needs.  It stops at the first pair that fails (plan.why,
+// plan.who).  qout / tout (may be null): the rebased copies.
+void Batch::planFlat(const long long* qoff, const long long* toff, int n, bool sharedTarget, FlatPlan& p,
+                     std::vector<long long>* qout, std::vector<long long>* tout) const
 {
     const int mode = (int)cfg_.mode;
     const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
-    const int m = qlen(u);
-    const int T = scanMode == EDLIB_MODE_SHW ? (int)std::min<long long>(tlen(u), 2LL * m + 1) : tlen(u);   // (SHW: nothing beyond column 2m can tie the best)
-    PairDesc x{};
-    x.qoff = qoff_[u]; x.toff = tbase(u); x.qlen = m; x.tlen = T; x.qstep = 1; x.tstep = 1;
-    // NW: the ring holds every block of the unit, so the band is the whole matrix (threshold max(m, T)); SHW / HW:
-    // columns scoring <= min(k, m) are end-location candidates
-    x.kinit = scanMode == EDLIB_MODE_NW ? std::max(m, T) : ((cfg_.k < 0 || cfg_.k > m) ? m : cfg_.k);
-    // NW with the column store (flatNwStore_): the first level of solveGlobalDistances -- the ring's band limit for a unit of
-    // more blocks than the ring has lanes, capped by the caller's k; a unit that fails it sends the run to the general path
-    if (flatNwStore_) {
-        const int kcap = cfg_.k >= 0 ? cfg_.k : 0x3fffffff;
-        // (words of 32 rows on 8-lane rings, ring32_kernels.hip: a query of up to 8 words sits whole on its ring; above, the
-        // first band level K = 128 -- well inside what the 4-lane rings of 64-row blocks hold, and inside ring32_max_k(8) = 192)
-        if (flatRing32_) x.kinit = std::min(kcap, (m + 31) / 32 <= flatG32_ ? std::max(m, T) : 128);
-        else x.kinit = std::min(kcap, (m + 63) / 64 <= flatRing_ ? std::max(m, T) : ring_max_k(flatRing_));
+    const bool paths = cfg_.task == EDLIB_TASK_PATH, nwStore = paths && scanMode == EDLIB_MODE_NW;
+    const long long chunkCap = 0xE0000000LL / 8;                      // 8-byte entries a ring32 launch can address
+    p = FlatPlan{};
+    p.n = n;
+    if (qout) { qout->assign((size_t)n + 1, 0); tout->assign((size_t)n + 1, 0); }
+    if (nwStore) p.cuts.push_back(0);
+    const long long q0 = n > 0 ? qoff[0] : 0, t0 = n > 0 ? toff[0] : 0;
+    long long chunk32 = 0;
+    for (int u = 0; u < n; ++u) {
+        const long long ml = qoff[u + 1] - qoff[u], tl = sharedTarget ? toff[1] - toff[0] : toff[u + 1] - toff[u];
+        if (qout) { (*qout)[u + 1] = qoff[u + 1] - q0; (*tout)[u + 1] = toff[u + 1] - t0; }
+        p.who = u;
+        if (ml < 0) { p.why = FlatPlan::kBadQueryOffsets; return; }
+        if (tl < 0) { p.why = FlatPlan::kBadTargetOffsets; return; }
+        if (ml == 0) { p.why = FlatPlan::kEmptyQuery; return; }
+        if (tl == 0) { p.why = FlatPlan::kEmptyTarget; return; }
+        if (ml > kFlatMaxQuery) { p.why = FlatPlan::kLongQuery; return; }
+        // (long targets: the general path cuts HW targets into segments when the batch alone does not fill the chip)
+        if (tl > kFlatMaxTarget) { p.why = FlatPlan::kLongTarget; return; }
+        const int m = (int)ml, T = (int)tl, w = flat_window(scanMode, m, T), blocks = (m + 63) / 64;
+        p.maxBlocks = std::max(p.maxBlocks, blocks); p.maxT = std::max(p.maxT, T); p.maxWords = std::max(p.maxWords, (m + 31) / 32);
+        p.totalBlocks += blocks; p.cells += (long long)m * T; p.lens += m + T;
+        if (!paths) continue;
+        // paths stay flat when every unit's store fits a 4-lane ring: SHW / HW queries of at most 4 blocks (whole matrix of
+        // the window), NW pairs of up to 16 blocks inside the first band level; never in the Hirschberg regime (:1188-1190)
+        if (scanMode != EDLIB_MODE_NW && blocks > 4) { p.why = FlatPlan::kPathBlocks; return; }
+        if (needs_hirschberg(m, w)) { p.why = FlatPlan::kHirschberg; return; }
+        // (the resident column store and op slots are upper bounds per unit: a batch whose bounds add up to more than a
+        // slice of the HBM keeps the general path, which sizes them per chunk)
+        // (8-lane rings of words.  16-lane rings -- one DPP row rotation per carried word instead of two moves and a select,
+        // 34 instructions per step against 38, twice the waves -- were measured at config 5: 0.195 against 0.180 ms of scan,
+        // A/B on one box; the scan is not bound by its instruction count alone, DESIGN.md 4d)
+        const long long e32 = ring32_store_entries(flatG32_, m, w);
+        p.store4 += ring_store_entries(4, m, w); p.store32 += e32; p.opBytes += m + w + 8;
+        if (16 * p.store4 > (32LL << 30)) { p.why = FlatPlan::kStoreCap; return; }
+        if (p.opBytes > (8LL << 30)) { p.why = FlatPlan::kOpsCap; return; }
+        // NW (the phase-1 scan IS the storing scan): a batch whose store exceeds what 32-bit offsets reach runs in chunks of
+        // units, each scanned and walked before the next reuses the store (160,000 x 1 kb: 6.4 GB of store as two chunks)
+        if (nwStore) {
+            if (chunk32 + e32 > chunkCap && chunk32 > 0) { p.cuts.push_back(u); p.chunkMax32 = std::max(p.chunkMax32, chunk32); chunk32 = 0; }
+            chunk32 += e32;
+        }
     }
-    x.peqOff = flatPeqOff_[u];
-    x.storeOff = 0; x.auxOff = 0; x.posCap = scanMode == EDLIB_MODE_NW ? 0 : kFlatPosCap; x.posOff = (long long)u * kFlatPosCap;
-    x.colOff = -1; x.bandT = 0; x.skip = 0; x.ring = flatRing_;
-    return x;
+    p.who = -1;
+    p.qbytes = n > 0 ? qoff[n] - q0 : 0; p.tbytes = n > 0 ? toff[sharedTarget ? 1 : n] - t0 : 0;
+    if (nwStore) { p.cuts.push_back(n); p.chunkMax32 = std::max(p.chunkMax32, chunk32); }
 }
 
 int Batch::initFlatPairs()
@@ -149,128 +188,258 @@ int Batch::initFlatPairs()
     if ((int)pairUnits_.size() != n_ || n_ < 1024) return 0;       // (a handful of units: the zero-copy path of solveChunk)
     const int mode = (int)cfg_.mode;
     if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) return 0;
+    FlatPlan plan;
+    planFlat(qoff_.data(), toff_.data(), n_, shared_, plan, nullptr, nullptr);
+    if (plan.why != FlatPlan::kOk) return 0;
+    return prepareFlat(plan, false);
+}
+
+// The layout of a flat set, made on the batch's stream from the resident pools and offsets (flat_pairs_prepare.hip) and
+// waited for once.  census: the tables come from the device's census of the target pool (a streamed set); otherwise they
+// are init()'s.  Every buffer grows only.
+int Batch::prepareFlat(const FlatPlan& p, bool census)
+{
+    const int mode = (int)cfg_.mode;
     const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
-    int maxBlocks = 0, maxT = 0;
-    for (int u = 0; u < n_; ++u) { maxBlocks = std::max(maxBlocks, (qlen(u) + 63) / 64); maxT = std::max(maxT, tlen(u)); }
-    // (long targets: the general path cuts HW targets into segments when the batch alone does not fill the chip)
-    if (maxBlocks > 16 || maxT > 65536) return 0;
-    flatMaxBlocks_ = maxBlocks;
-    flatRing_ = maxBlocks <= 4 ? 4 : (maxBlocks <= 8 ? 8 : 16);      // (the smallest ring that holds every query whole)
-    // window of a unit's alignment: the whole target (NW), at most 2 m + 1 columns (SHW: the scan stops there; HW: m + distance)
-    auto window = [&](int u) { return scanMode == EDLIB_MODE_NW ? tlen(u) : (int)std::min<long long>(tlen(u), 2LL * qlen(u) + 1); };
-    if (cfg_.task == EDLIB_TASK_PATH) {
-        // paths stay flat when every unit's store fits a 4-lane ring: SHW / HW queries of at most 4 blocks (whole matrix of
-        // the window), NW pairs of up to 16 blocks inside the first band level; never in the Hirschberg regime (:1188-1190)
-        if (scanMode != EDLIB_MODE_NW && maxBlocks > 4) return 0;
-        for (int u = 0; u < n_; ++u) if (needs_hirschberg(qlen(u), window(u))) return 0;
-        // (the resident column store and op slots are upper bounds per unit: a batch whose bounds add up to more than a
-        // slice of the HBM keeps the general path, which sizes them per chunk)
-        long long storeBytes = 0, opBytes = 0, store32 = 0;
-        int maxWords = 0;
-        // (8-lane rings of words.  16-lane rings -- one DPP row rotation per carried word instead of two moves and a select,
-        // 34 instructions per step against 38, twice the waves -- were measured at config 5: 0.195 against 0.180 ms of scan,
-        // A/B on one box; the scan is not bound by its instruction count alone, DESIGN.md 4d)
-        for (int u = 0; u < n_; ++u) {
-            storeBytes += 16LL * ring_store_entries(4, qlen(u), window(u));
-            store32 += 8LL * ring32_store_entries(flatG32_, qlen(u), window(u));
-            opBytes += qlen(u) + window(u) + 8;
-            maxWords = std::max(maxWords, (qlen(u) + 31) / 32);
-        }
-        if (storeBytes > (32LL << 30) || opBytes > (8LL << 30)) return 0;
-        flatPaths_ = true;
-        flatNwStore_ = scanMode == EDLIB_MODE_NW;
-        flatRing_ = 4;
-        // Storing scans and walks on rings of 32-row words (ring32_kernels.hip) whenever the batch allows it: a store the
-        // kernel's 32-bit offsets reach, a Peq table per unit that fits a wave's LDS.  SHW / HW paths: queries of at most
-        // 4 blocks = 8 words, whole on an 8-lane ring.
-        flatMaxWords_ = maxWords;
-        // NW (the phase-1 scan IS the storing scan): a batch whose store exceeds what 32-bit offsets reach runs in chunks of
-        // units, each scanned and walked before the next reuses the store (160,000 x 1 kb: 6.4 GB of store as two chunks)
-        flatRing32_ = (flatNwStore_ || store32 < 0xF0000000LL) && ring32_lds_bytes(flatG32_, tab_.sigmaT, maxWords) <= 48 * 1024;
-    }
+    const size_t n = (size_t)p.n;
+    flatPairs_ = false;
+    flatPaths_ = cfg_.task == EDLIB_TASK_PATH;
+    flatNwStore_ = flatPaths_ && scanMode == EDLIB_MODE_NW;
     flatStarts_ = cfg_.task != EDLIB_TASK_DISTANCE && mode == EDLIB_MODE_HW;
-    PinBuf pin;
-    EDLIB_AMD_HIP(pin.alloc((size_t)n_ * sizeof(PairDesc)));
-    PairDesc* d = reinterpret_cast<PairDesc*>(pin.p);
-    long long peqWords = 0;
-    flatPeqOff_.resize((size_t)n_);
-    for (int u = 0; u < n_; ++u) {
-        const long long nb = (qlen(u) + 63) / 64;
-        flatPeqOff_[u] = peqWords; peqWords += nb * tab_.sigmaT;
-        d[u] = flatDesc(u);
-    }
-    EDLIB_AMD_HIP(d_flatDescs_.alloc((size_t)n_));
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_flatDescs_.p, d, (size_t)n_ * sizeof(PairDesc), hipMemcpyHostToDevice, stream_));
-    EDLIB_AMD_HIP(d_peq64_.ensure((size_t)peqWords));
-    EDLIB_AMD_HIP(d_flatOut3_.alloc(3 * (size_t)n_));
-    EDLIB_AMD_HIP(d_flatPos_.alloc(scanMode == EDLIB_MODE_NW ? 1 : (size_t)n_ * kFlatPosCap));
-    EDLIB_AMD_HIP(d_flatCensus_.alloc(2));
-    EDLIB_AMD_HIP(h_flatCensus_.alloc(2 * sizeof(int)));
+    flatMaxBlocks_ = p.maxBlocks; flatMaxWords_ = p.maxWords;
+    // (the smallest ring that holds every query whole; storing scans: 4 lanes)
+    flatRing_ = (flatPaths_ || p.maxBlocks <= 4) ? 4 : (p.maxBlocks <= 8 ? 8 : 16);
+    flatRing32_ = false;                                            // (decided below, with the alphabet)
+    flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0); flatOvfPos_.clear();
+    flatChunkStart_ = p.cuts;
+    if (flatChunkStart_.size() < 2) { flatChunkStart_.assign(1, 0); flatChunkStart_.push_back(p.n); }
+
+    EDLIB_AMD_HIP(d_flatDescs_.ensure(n));
+    EDLIB_AMD_HIP(d_flatOut3_.ensure(3 * n));
+    EDLIB_AMD_HIP(d_flatPos_.ensure(scanMode == EDLIB_MODE_NW ? 1 : n * kFlatPosCap));
+    EDLIB_AMD_HIP(d_flatCensus_.ensure(2));
+    if (!h_flatCensus_.p) EDLIB_AMD_HIP(h_flatCensus_.alloc(2 * sizeof(int)));
     if (flatStarts_) {
-        // reversed-query Peq rows (same layout as the forward ones, behind them) and their builder's descriptors
-        flatRevPeqBase_ = peqWords;
-        EDLIB_AMD_HIP(d_peq64_.ensure((size_t)(2 * peqWords)));
-        PinBuf rp;
-        EDLIB_AMD_HIP(rp.alloc((size_t)n_ * sizeof(PairDesc)));
-        PairDesc* r = reinterpret_cast<PairDesc*>(rp.p);
-        for (int u = 0; u < n_; ++u) { r[u] = d[u]; r[u].qoff = d[u].qoff + d[u].qlen - 1; r[u].qstep = -1; r[u].peqOff = flatRevPeqBase_ + d[u].peqOff; }
-        EDLIB_AMD_HIP(d_flatRevDescs_.alloc((size_t)n_));
-        EDLIB_AMD_HIP(hipMemcpyAsync(d_flatRevDescs_.p, r, (size_t)n_ * sizeof(PairDesc), hipMemcpyHostToDevice, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        flatStartCap_ = 2 * (size_t)n_ + 1024;
-        EDLIB_AMD_HIP(d_flatStartDescs_.alloc(flatStartCap_));
-        EDLIB_AMD_HIP(d_flatStartOut3_.alloc(3 * flatStartCap_));
-        EDLIB_AMD_HIP(d_flatSlotOf_.alloc((size_t)n_ * kFlatPosCap));
-        EDLIB_AMD_HIP(d_flatStartsOut_.alloc((size_t)n_ * kFlatPosCap));
+        EDLIB_AMD_HIP(d_flatRevDescs_.ensure(n));
+        flatStartCap_ = 2 * n + 1024;
+        EDLIB_AMD_HIP(d_flatStartDescs_.ensure(flatStartCap_));
+        EDLIB_AMD_HIP(d_flatStartOut3_.ensure(3 * flatStartCap_));
+        EDLIB_AMD_HIP(d_flatSlotOf_.ensure(n * kFlatPosCap));
+        EDLIB_AMD_HIP(d_flatStartsOut_.ensure(n * kFlatPosCap));
     }
     if (flatPaths_) {
-        // op slots (m + window + 8 bytes per unit, filled from the back) and store ranges (a 4-lane ring over the window):
-        // upper bounds that depend on the batch only, laid out once
-        flatOpsOffHost_.assign((size_t)n_ + 1, 0);
-        std::vector<long long> storeBase((size_t)n_);
-        long long entries = 0, maxEntries = 0;
-        flatChunkStart_.assign(1, 0);
-        const long long chunkCap = 0xE0000000LL / 8;                      // 8-byte entries a ring32 launch can address
-        for (int u = 0; u < n_; ++u) {
-            flatOpsOffHost_[u + 1] = flatOpsOffHost_[u] + qlen(u) + window(u) + 8;
-            const long long e = flatRing32_ ? ring32_store_entries(flatG32_, qlen(u), window(u)) : ring_store_entries(flatRing_, qlen(u), window(u));
-            if (flatRing32_ && flatNwStore_ && entries + e > chunkCap && entries > 0) { flatChunkStart_.push_back(u); maxEntries = std::max(maxEntries, entries); entries = 0; }
-            storeBase[u] = entries;
-            entries += e;
-        }
-        flatChunkStart_.push_back(n_);
-        entries = std::max(maxEntries, entries);
-        flatOpsTotal_ = flatOpsOffHost_[n_];
-        EDLIB_AMD_HIP(d_flatOpsOff_.alloc((size_t)n_ + 1)); EDLIB_AMD_HIP(d_flatStoreBase_.alloc((size_t)n_));
-        EDLIB_AMD_HIP(hipMemcpyAsync(d_flatOpsOff_.p, flatOpsOffHost_.data(), ((size_t)n_ + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
-        EDLIB_AMD_HIP(hipMemcpyAsync(d_flatStoreBase_.p, storeBase.data(), (size_t)n_ * sizeof(long long), hipMemcpyHostToDevice, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        EDLIB_AMD_HIP(d_flatOps_.alloc((size_t)flatOpsTotal_)); EDLIB_AMD_HIP(d_flatOpsLen_.alloc((size_t)n_));
+        // op slots (m + window + 8 bytes per unit, filled from the back) and store ranges: upper bounds that depend on the
+        // set only, laid out once
+        flatOpsTotal_ = p.opBytes;
+        EDLIB_AMD_HIP(d_flatOpsOff_.ensure(n + 1)); EDLIB_AMD_HIP(d_flatStoreBase_.ensure(n));
+        EDLIB_AMD_HIP(d_flatOps_.ensure((size_t)flatOpsTotal_)); EDLIB_AMD_HIP(d_flatOpsLen_.ensure(n));
+        if (!flatNwStore_) { EDLIB_AMD_HIP(d_flatPathDescs_.ensure(n)); EDLIB_AMD_HIP(d_flatPathOut3_.ensure(3 * n)); }
+    }
+    size_t tmpBytes = 0;
+    EDLIB_AMD_HIP(flat_prepare_tmp_bytes(p.n, &tmpBytes));
+    EDLIB_AMD_HIP(d_flatPrepTmp_.ensure(tmpBytes + 16));
+    EDLIB_AMD_HIP(d_flatPrep_.ensure(5 * (n + 1)));
+    EDLIB_AMD_HIP(d_flatCuts_.ensure(flatChunkStart_.size()));
+    const size_t outBytes = 8 * sizeof(uint32_t) + 2 * sizeof(unsigned long long);
+    if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(outBytes));
+    if (!h_flatPrepOut_.p) EDLIB_AMD_HIP(h_flatPrepOut_.alloc(outBytes));
+    // (the cut points are a member: the copy may still be on its way when this function returns on an error)
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_flatCuts_.p, flatChunkStart_.data(), flatChunkStart_.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+
+    FlatPrepareArgs a{};
+    a.n = p.n; a.shape = flatShape(); a.paths = flatPaths_ ? 1 : 0; a.starts = flatStarts_ ? 1 : 0;
+    a.maxWords = p.maxWords; a.store32Bytes = 8 * p.store32;
+    a.tpool = census ? d_tpool_.p : nullptr; a.tbytes = p.tbytes;
+    a.qoff = d_qoff_.p; a.toff = d_toff_.p; a.sharedTarget = shared_ ? 1 : 0;
+    a.presence = census ? reinterpret_cast<uint32_t*>(d_flatPrepOut_.p) : d_presence_.p;
+    a.cuts = d_flatCuts_.p; a.ncuts = (int)flatChunkStart_.size();
+    a.sizes = d_flatPrep_.p; a.peqOff = d_flatPrep_.p + 3 * (n + 1); a.storeCum = d_flatPrep_.p + 4 * (n + 1);
+    a.opsOff = d_flatOpsOff_.p; a.storeBase = d_flatStoreBase_.p;
+    a.descs = d_flatDescs_.p; a.revDescs = d_flatRevDescs_.p;
+    a.iota = census ? d_alphaIdx_.p : nullptr;
+    a.steps = reinterpret_cast<unsigned long long*>(d_flatPrepOut_.p + 8 * sizeof(uint32_t));
+    a.tmp = d_flatPrepTmp_.p; a.tmpBytes = tmpBytes;
+    EDLIB_AMD_HIP(launch_flat_prepare(a, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(h_flatPrepOut_.p, d_flatPrepOut_.p, outBytes, hipMemcpyDeviceToHost, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));                // the call's one wait: the caller's memory is free behind it
+
+    if (census) {
+        // the tables of the set, over the bytes the census found, in ascending order (nothing a pair batch reports depends
+        // on symbol ids); they follow on the stream from a pinned block of the batch's own
+        const uint32_t* pres = reinterpret_cast<const uint32_t*>(h_flatPrepOut_.p);
+        uint8_t present[256]; int count = 0;
+        for (int b = 0; b < 256; ++b) if ((pres[b >> 5] >> (b & 31)) & 1u) present[count++] = (uint8_t)b;
+        build_tables(tab_, present, count, eqs_.data(), (int)eqs_.size());
+        if (!d_tabs_.p) EDLIB_AMD_HIP(d_tabs_.alloc(1024));
+        if (!h_tabs_.p) EDLIB_AMD_HIP(h_tabs_.alloc(1024));
+        memcpy(h_tabs_.p, tab_.tlut, 256); memcpy(h_tabs_.p + 256, tab_.idToByte, 256); memcpy(h_tabs_.p + 512, tab_.eqtbl, 512);
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_tabs_.p, h_tabs_.p, 1024, hipMemcpyHostToDevice, stream_));
+        d_tlut_.alias(d_tabs_.p, 256); d_idToByte_.alias(d_tabs_.p + 256, 256); d_eqtbl_.alias(d_tabs_.p + 512, 256);
+        d_presence_.alias(d_flatPrepOut_.p, 8);
+        syms_ = peq_syms(tab_.sigmaT);
+    }
+    // Storing scans and walks on rings of 32-row words (ring32_kernels.hip) whenever the set allows it (flat_uses_ring32: the
+    // kernels decided the same from the same census).  SHW / HW paths: queries of at most 4 blocks = 8 words, whole on an
+    // 8-lane ring.
+    flatRing32_ = flat_uses_ring32(flatPaths_, flatNwStore_, 8 * p.store32, flatG32_, tab_.sigmaT, p.maxWords);
+    const bool chunked32 = flatRing32_ && flatNwStore_;
+    if (!chunked32) { flatChunkStart_.assign(1, 0); flatChunkStart_.push_back(p.n); }
+    const long long peqWords = p.totalBlocks * tab_.sigmaT;
+    // reversed-query Peq rows (same layout as the forward ones, behind them)
+    flatRevPeqBase_ = peqWords;
+    EDLIB_AMD_HIP(d_peq64_.ensure((size_t)(flatStarts_ ? 2 * peqWords : peqWords)));
+    if (flatPaths_) {
+        const long long entries = chunked32 ? p.chunkMax32 : (flatRing32_ ? p.store32 : p.store4);
         EDLIB_AMD_HIP(d_store_.ensure(flatRing32_ ? (size_t)(entries + 1) / 2 : (size_t)entries));      // (ring32: 8-byte entries)
-        if (flatRing32_) EDLIB_AMD_HIP(d_tsym_.alloc(d_tpool_.n));
-        if (flatNwStore_) {
-            // the phase-1 descriptors ARE the storing scans: give them their store ranges
-            for (int u = 0; u < n_; ++u) d[u].storeOff = storeBase[u];
-            EDLIB_AMD_HIP(hipMemcpyAsync(d_flatDescs_.p, d, (size_t)n_ * sizeof(PairDesc), hipMemcpyHostToDevice, stream_));
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        } else {
-            EDLIB_AMD_HIP(d_flatPathDescs_.alloc((size_t)n_)); EDLIB_AMD_HIP(d_flatPathOut3_.alloc(3 * (size_t)n_));
-        }
+        if (flatRing32_) EDLIB_AMD_HIP(d_tsym_.ensure(d_tpool_.n));
     }
-    // the word-steps of a run over the resident descriptors never change: counted here, once
-    {
-        unsigned long long* ctr = ringStepsCounter();
-        if (!ctr) return 1;
-        EDLIB_AMD_HIP(hipMemsetAsync(ctr, 0, sizeof(unsigned long long), stream_));
-        EDLIB_AMD_HIP(launch_count_ring_steps(d_flatDescs_.p, n_, scanMode, 1, ctr, stream_));
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_ringSteps_.p, ctr, sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
-    }
-    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));                // `pin` dies here
-    flatWordSteps_ = (long long)*reinterpret_cast<unsigned long long*>(h_ringSteps_.p);
-    if (flatRing32_ && flatNwStore_) flatWordSteps_ = ring32_word_steps(flatG32_, d, n_);      // (phase 1 runs on the rings of 32-row words)
+    // the word-steps of a run over the resident descriptors never change (phase 1 of a ring32 NW batch runs on the rings of
+    // 32-row words)
+    const unsigned long long* steps = reinterpret_cast<const unsigned long long*>(h_flatPrepOut_.p + 8 * sizeof(uint32_t));
+    flatWordSteps_ = (long long)steps[chunked32 ? 1 : 0];
     ringStepsUsed_ = false;
     flatPairs_ = true;
     return 0;
+}
+
+
+// ------------------------------------------------------------ streamed pairs
+
+// edlibAmdBatchPairsSetPairs: another pair set through a resident pair batch (DESIGN.md §4b "Streamed pairs").  A streamed
+// set is a flat set of any count; the host walks the two offset arrays once and reads no sequence byte, everything
+// derived from the pairs is made on the device (prepareFlat).  What is refused leaves the batch as it was.
+int Batch::setPairs(const char* queries, const long long* qoff, const char* targets, const long long* toff, int n)
+{
+    static const char* const fn = "edlibAmdBatchPairsSetPairs";
+    if (n < 0) { set_error("%s: numPairs must be >= 0 (got %d)", fn, n); return 1; }
+    if (n > 0 && (!queries || !qoff || !targets || !toff)) {
+        set_error("%s: queries, queryOffsets, targets and targetOffsets must not be NULL for %d pairs", fn, n);
+        return 1;
+    }
+    const int mode = (int)cfg_.mode;
+    if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) {
+        set_error("%s: the batch's config.mode (%d) has no flat form: create a new batch", fn, mode);
+        return 1;
+    }
+    FlatPlan plan;
+    std::vector<long long> qnew, tnew;
+    planFlat(qoff, toff, n, false, plan, &qnew, &tnew);
+    if (plan.why != FlatPlan::kOk) {
+        const int u = plan.who;
+        const long long m = qoff[u + 1] - qoff[u], T = toff[u + 1] - toff[u];
+        const char* const modeName = mode == EDLIB_MODE_HW ? "HW" : (mode == EDLIB_MODE_SHW ? "SHW" : "NW");
+        switch (plan.why) {
+        case FlatPlan::kBadQueryOffsets: set_error("%s: bad query offsets (query %d ends before it starts)", fn, u); break;
+        case FlatPlan::kBadTargetOffsets: set_error("%s: bad target offsets (target %d ends before it starts)", fn, u); break;
+        case FlatPlan::kEmptyQuery:
+            set_error("%s: pair %d has an empty query (0 bases), a streamed set takes queries of 1 to %s bases: create a new batch",
+                      fn, u, with_commas(kFlatMaxQuery).c_str());
+            break;
+        case FlatPlan::kEmptyTarget:
+            set_error("%s: pair %d has an empty target (0 bases), a streamed set takes targets of 1 to %s bases: create a new batch",
+                      fn, u, with_commas(kFlatMaxTarget).c_str());
+            break;
+        case FlatPlan::kLongQuery:
+            set_error("%s: pair %d has a query of %s bases, the limit for a streamed set is %s: create a new batch", fn, u,
+                      with_commas(m).c_str(), with_commas(kFlatMaxQuery).c_str());
+            break;
+        case FlatPlan::kLongTarget:
+            set_error("%s: pair %d has a target of %s bases, the limit for a streamed set is %s: create a new batch", fn, u,
+                      with_commas(T).c_str(), with_commas(kFlatMaxTarget).c_str());
+            break;
+        case FlatPlan::kPathBlocks:
+            set_error("%s: pair %d has a query of %s bases, the limit for a streamed set with EDLIB_TASK_PATH in mode %s is 256: "
+                      "create a new batch", fn, u, with_commas(m).c_str(), modeName);
+            break;
+        case FlatPlan::kHirschberg:
+            set_error("%s: pair %d (%s x %s bases) needs the linear-space path (its matrix reaches the 1 MiB rule), a streamed "
+                      "set with EDLIB_TASK_PATH stays below it: create a new batch", fn, u, with_commas(m).c_str(), with_commas(T).c_str());
+            break;
+        case FlatPlan::kStoreCap:
+            set_error("%s: at pair %d the column stores of the set pass 32 GB, the limit for a streamed set with EDLIB_TASK_PATH: "
+                      "create a new batch", fn, u);
+            break;
+        default:
+            set_error("%s: at pair %d the op slots of the set pass 8 GB, the limit for a streamed set with EDLIB_TASK_PATH: "
+                      "create a new batch", fn, u);
+            break;
+        }
+        return 1;
+    }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+
+    // ---- from here a device error leaves the batch without pairs
+    noPairs_ = true;
+    // (a Run whose alphabetLength nobody collected: its kernel still reads the pools that are about to change)
+    if (alphaPending_ && side_) EDLIB_AMD_HIP(hipStreamSynchronize(side_));
+    alphaPending_ = false;
+    // everything that caches something about the units: the general path walks it when a Run of the new set falls back
+    shared_ = false;
+    n_ = n;
+    qoff_.swap(qnew); toff_.swap(tnew);
+    emptyUnits_.clear(); readUnits_.clear(); longUnits_.clear(); groups_.clear(); pairNow_.clear();
+    pairUnits_.resize((size_t)n);
+    for (int u = 0; u < n; ++u) pairUnits_[u] = u;
+    alphaUnits_ = pairUnits_; alphaOnHost_ = false; alphaBytes_ = plan.lens;
+    pairSpecsFor_.clear(); ++pairSpecsVersion_;
+    levelAllReady_ = laneReady_ = false;
+    results_.clear(); work_.clear(); live_.clear(); startUnits_.clear(); startWhere_.clear();
+    opsKeep_.clear(); opsOwned_.clear(); fusedOps_.clear(); knownSplits_.clear();
+    haveResults_ = false; viewReady_ = false; cigar_[0].ready = cigar_[1].ready = false;
+    lastRunFlat_ = false; flatDone_ = false; pairsCollected_ = readsCollected_ = true;
+    view_ = EdlibAmdResultsView{}; viewAlnDev_ = nullptr; viewAlnOffDev_ = nullptr;
+    stats = EdlibAmdBatchStats{};
+    stats.cells = plan.cells;
+    algoBase_ = -1; algoDirty_ = false;
+    flatPairs_ = false;
+    if (streamFlat(queries + (n > 0 ? qoff[0] : 0), targets + (n > 0 ? toff[0] : 0), plan)) return 1;
+    noPairs_ = false;
+    return 0;
+}
+
+// the device's share of setPairs: the pools and the offsets go up as they are, the rest is prepareFlat
+int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& p)
+{
+    const size_t n = (size_t)p.n;
+    // (pools and offsets that were views into init()'s one block become buffers of their own; the block goes)
+    EDLIB_AMD_HIP(d_qpool_.resize((size_t)p.qbytes + 16)); EDLIB_AMD_HIP(d_tpool_.resize((size_t)p.tbytes + 16));
+    EDLIB_AMD_HIP(d_qoff_.resize(n + 1)); EDLIB_AMD_HIP(d_toff_.resize(n + 1));
+    if (!d_tabs_.p) EDLIB_AMD_HIP(d_tabs_.alloc(1024));
+    if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(8 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)));
+    d_tlut_.alias(d_tabs_.p, 256); d_idToByte_.alias(d_tabs_.p + 256, 256); d_eqtbl_.alias(d_tabs_.p + 512, 256);
+    d_presence_.alias(d_flatPrepOut_.p, 8);
+    if (p.qbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_qpool_.p, queries, (size_t)p.qbytes, hipMemcpyHostToDevice, stream_));
+    if (p.tbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_tpool_.p, targets, (size_t)p.tbytes, hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p + p.qbytes, 0, 16, stream_));
+    EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p + p.tbytes, 0, 16, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_qoff_.p, qoff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_toff_.p, toff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
+    // alphabetLength is counted per unit as before: its unit list (0, 1, ...) is written with the layout
+    EDLIB_AMD_HIP(d_alphaIdx_.ensure(n)); EDLIB_AMD_HIP(d_alphaOut_.ensure(n));
+    if (alphaPin_.n < n * sizeof(int) || !alphaPin_.p) EDLIB_AMD_HIP(alphaPin_.alloc(n * sizeof(int)));
+    if (p.n == 0) {
+        // no pairs: nothing to lay out; Run and the views are those of a batch created over zero pairs
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        d_in_.release(); h_in_.release();
+        build_tables(tab_, nullptr, 0, eqs_.data(), (int)eqs_.size());
+        flatStarts_ = flatPaths_ = flatNwStore_ = flatRing32_ = false;
+        flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0); flatOvfPos_.clear();
+        return 0;
+    }
+    if (prepareFlat(p, true)) return 1;
+    d_in_.release(); h_in_.release();                            // (behind the wait: init()'s upload came from it)
+    // algorithmic bytes of a Run whose results stay on the device (startStats): a constant of the set
+    algoBase_ = p.lens + 8LL * (tab_.sigmaT + 1) * p.totalBlocks + 20LL * p.n;
+    return 0;
+}
+
+int Batch::noResults(const char* who)
+{
+    if (noPairs_) set_error("pair batch: it has no pairs (edlibAmdBatchPairsSetPairs failed on the device): set them again");
+    else set_error("%s before a successful run() (Run it first)", who);
+    return 1;
 }
 
 int Batch::runPairsFlat(bool& fellBack)
@@ -349,9 +518,11 @@ int Batch::runPairsFlat(bool& fellBack)
             EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
             const int* score = reinterpret_cast<const int*>(sc.p); const int* count = score + n;
             std::vector<PairDesc> d2;
-            for (int u = 0; u < n_; ++u)
+            const FlatShape shape = flatShape();
+            long long peqOff = 0;                                    // (the scan of flat_pairs_prepare.hip, recomputed on the way)
+            for (int u = 0; u < n_; peqOff += (long long)((qlen(u) + 63) / 64) * tab_.sigmaT, ++u)
                 if (count[u] > kFlatPosCap) {
-                    PairDesc x = flatDesc(u);
+                    PairDesc x = flat_desc(shape, u, qoff_[u], qlen(u), tbase(u), tlen(u), peqOff);
                     x.kinit = score[u]; x.posCap = count[u]; x.posOff = flatOvfOff_.back(); x.ring = 0;
                     d2.push_back(x); flatOvfUnit_.push_back(u); flatOvfOff_.push_back(flatOvfOff_.back() + count[u]);
                 }

@@ -13,7 +13,6 @@ namespace edlib_amd {
 struct WantedPart { int asked; PinnedPart* part; const void* dev; size_t bytes; };
 
 // 65,536 as the messages of setTargets and setUnits write it
-std::string with_commas(long long v);
 
 // The pairs of an internal pair Batch: the bytes of every pair replicated, query and target
 struct PairPool {

@@ -371,9 +371,6 @@ template <int G> __device__ __forceinline__ int ring_ror(const int v, const int 
 __host__ __device__ static inline long long ring_index(int G, int c, int b) {
     return (long long)(c + b) * G + (b % G);
 }
-long long ring_store_entries(int G, int qlen, int tlen) {
-    return ((long long)tlen + num_blocks(qlen)) * G;
-}
 
 // PEQ: where a lane finds the Peq word of (symbol, its block):
 //   0  HBM pool (more than 32 target symbols)

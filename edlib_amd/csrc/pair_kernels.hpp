@@ -112,7 +112,9 @@ constexpr int kMaxBandK = ring_max_k(64);
 // limit is ring_max_k(16, H), modes 1 / 2 take units of up to 16 H blocks.
 hipError_t launch_scan_pairs_ring(int ringLanes, int mode, bool store, const PairScanArgs& a, hipStream_t stream,
                                   int blocksPerLane = 1);
-long long ring_store_entries(int ringLanes, int qlen, int tlen);
+__host__ __device__ inline long long ring_store_entries(int ringLanes, int qlen, int tlen) {
+    return ((long long)tlen + ((qlen + 63) >> 6)) * ringLanes;
+}
 // adds the word-steps inside the bands of `numUnits` ring units (64 H rows per ring-lane block, scan mode `mode`) to *out:
 // what launch_scan_pairs_ring does behind its scan when PairScanArgs::wordSteps is set
 hipError_t launch_count_ring_steps(const PairDesc* descs, int numUnits, int mode, int H, unsigned long long* out, hipStream_t stream);
@@ -140,9 +142,23 @@ hipError_t launch_build_peq_pairs(const PairDesc* descs, int numUnits, const uin
 // G in {4, 8, 16}; the band of desc.kinit must fit the ring (kinit <= ring32_max_k(G)) or all words sit on it (any kinit).
 // Forward units only (qstep = tstep = 1, no bandT / colOff); needs PairScanArgs::tsym; a launch's store stays below 4 GB.
 constexpr int ring32_max_k(int G) { return 32 * (G - 2); }
-long long ring32_store_entries(int ringLanes, int qlen, int tlen);          // u64 entries of one unit
-size_t ring32_lds_bytes(int ringLanes, int sigmaT, int maxWords);           // dynamic LDS of a wave (the launcher refuses > 48 KB)
+__host__ __device__ inline long long ring32_store_entries(int ringLanes, int qlen, int tlen) {      // u64 entries of one unit
+    return ((((long long)tlen + ((qlen + 31) >> 5) + 1) >> 3) + 2) * ringLanes * 8;
+}
+// LDS words (u32) of one unit's Peq on this kernel: [symbol][rowStride] + a skew of G words, so that the rings of a wave
+// (whose lanes hold the same word indices at the same time) start in different banks
+__host__ __device__ inline int ring32_row_stride(int G, int maxWords) {
+    int s = G;
+    while (s < maxWords && s < 32) s <<= 1;
+    if (maxWords > 32) s = (maxWords + 31) / 32 * 32;
+    return s;
+}
+__host__ __device__ inline int ring32_peq_stride(int G, int sigmaT, int maxWords) { return (sigmaT * ring32_row_stride(G, maxWords) + 63) / 64 * 64 + G; }
+// dynamic LDS of a wave (the launcher refuses > 48 KB)
+__host__ __device__ inline size_t ring32_lds_bytes(int G, int sigmaT, int maxWords) { return (size_t)(64 / G) * (512 + 4 * (size_t)ring32_peq_stride(G, sigmaT, maxWords)); }
 long long ring32_word_steps(int ringLanes, const PairDesc* hostDescs, int n);   // 32-row word-columns inside the bands (host)
+// the same count by a kernel over resident descriptors, added to *out
+hipError_t launch_ring32_word_steps(int ringLanes, const PairDesc* descs, int n, unsigned long long* out, hipStream_t stream);
 hipError_t launch_target_symbols(const uint8_t* tpool, const uint8_t* tlut, long long n, uint8_t* tsym, hipStream_t stream);
 hipError_t launch_scan_pairs_ring32(int ringLanes, bool store, const PairScanArgs& a, int maxWords, hipStream_t stream);
 

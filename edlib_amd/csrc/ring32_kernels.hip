@@ -58,48 +58,60 @@ __host__ __device__ static inline int num_words(int m) { return (m + 31) >> 5; }
 // group are one 64-byte line -- written by that lane alone (a lane outside its word's life for the whole group writes
 // nothing), and what the walk reads when it follows a word through consecutive columns.
 __host__ __device__ static inline long long ring32_entry(int G, long long t, int ringLane) { return (((t >> 3) * G + ringLane) << 3) + (t & 7); }
-long long ring32_store_entries(int G, int qlen, int tlen) { return ((((long long)tlen + num_words(qlen) + 1) >> 3) + 2) * G * 8; }
-
-// LDS words (u32) of one unit's Peq on this kernel: [symbol][rowStride] + a skew of G words, so that the rings of a wave
-// (whose lanes hold the same word indices at the same time) start in different banks
-static inline int ring32_row_stride(int G, int maxWords) {
-    int s = G;
-    while (s < maxWords && s < 32) s <<= 1;
-    if (maxWords > 32) s = (maxWords + 31) / 32 * 32;
-    return s;
-}
-int ring32_peq_stride(int G, int sigmaT, int maxWords) { return (sigmaT * ring32_row_stride(G, maxWords) + 63) / 64 * 64 + G; }
-size_t ring32_lds_bytes(int G, int sigmaT, int maxWords) { return (size_t)(64 / G) * (512 + 4 * (size_t)ring32_peq_stride(G, sigmaT, maxWords)); }
-
-// 32-row word-columns scan_pairs_ring32_kernel computes inside its bands for these units (host; the kernel's own rule:
-// one band geometry per wave of 64 / G units when the union of their bands fits the ring)
-long long ring32_word_steps(int G, const PairDesc* descs, int n)
+// 32-row word-columns scan_pairs_ring32_kernel computes inside its bands for the units [w0, w1) of one wave (the kernel's
+// own rule: one band geometry per wave of 64 / G units when the union of their bands fits the ring); `only` >= 0: that
+// unit's share alone
+__host__ __device__ static inline long long ring32_wave_steps(int G, const PairDesc* descs, int w0, int w1, int only)
 {
-    const int U = 64 / G, big = 1 << 28;
+    const int big = 1 << 28;
     long long v = 0;
-    for (int w0 = 0; w0 < n; w0 += U) {
-        const int w1 = w0 + U < n ? w0 + U : n;
-        int lo = big, hi = -big;
-        for (int u = w0; u < w1; ++u) {
-            const int D = descs[u].tlen - descs[u].qlen, absD = D < 0 ? -D : D, K = descs[u].kinit;
-            if (K < absD) continue;
-            const int p = (K - absD) >> 1, dmin = (D < 0 ? D : 0) - p, dmax = (D > 0 ? D : 0) + p;
-            lo = dmin < lo ? dmin : lo; hi = dmax > hi ? dmax : hi;
-        }
-        const bool uniform = hi - lo <= 32 * (G - 2);
-        for (int u = w0; u < w1; ++u) {
-            const int m = descs[u].qlen, T = descs[u].tlen, D = T - m, absD = D < 0 ? -D : D, K = descs[u].kinit;
-            if (K < absD) continue;
-            const int p = (K - absD) >> 1;
-            const long long dmin = uniform ? lo : (D < 0 ? D : 0) - p, dmax = uniform ? hi : (D > 0 ? D : 0) + p;
-            for (int b = 0; b < num_words(m); ++b) {
-                long long f = 32LL * b + dmin, l = 32LL * b + 31 + dmax;
-                f = f < 0 ? 0 : f; l = l > T - 1 ? T - 1 : l;
-                if (f <= l) v += l - f + 1;
-            }
+    int lo = big, hi = -big;
+    for (int u = w0; u < w1; ++u) {
+        const int D = descs[u].tlen - descs[u].qlen, absD = D < 0 ? -D : D, K = descs[u].kinit;
+        if (K < absD) continue;
+        const int p = (K - absD) >> 1, dmin = (D < 0 ? D : 0) - p, dmax = (D > 0 ? D : 0) + p;
+        lo = dmin < lo ? dmin : lo; hi = dmax > hi ? dmax : hi;
+    }
+    const bool uniform = hi - lo <= 32 * (G - 2);
+    for (int u = only >= 0 ? only : w0; u < (only >= 0 ? only + 1 : w1); ++u) {
+        const int m = descs[u].qlen, T = descs[u].tlen, D = T - m, absD = D < 0 ? -D : D, K = descs[u].kinit;
+        if (K < absD) continue;
+        const int p = (K - absD) >> 1;
+        const long long dmin = uniform ? lo : (D < 0 ? D : 0) - p, dmax = uniform ? hi : (D > 0 ? D : 0) + p;
+        for (int b = 0; b < num_words(m); ++b) {
+            long long f = 32LL * b + dmin, l = 32LL * b + 31 + dmax;
+            f = f < 0 ? 0 : f; l = l > T - 1 ? T - 1 : l;
+            if (f <= l) v += l - f + 1;
         }
     }
     return v;
+}
+long long ring32_word_steps(int G, const PairDesc* descs, int n)
+{
+    const int U = 64 / G;
+    long long v = 0;
+    for (int w0 = 0; w0 < n; w0 += U) v += ring32_wave_steps(G, descs, w0, w0 + U < n ? w0 + U : n, -1);
+    return v;
+}
+// ... and over resident descriptors: a thread per unit, which looks at the (at most 16) units of its wave
+__global__ void __launch_bounds__(256)
+ring32_word_steps_kernel(const PairDesc* __restrict__ descs, const int n, const int G, unsigned long long* out)
+{
+    const int u = blockIdx.x * 256 + threadIdx.x, U = 64 / G;
+    unsigned long long v = 0;
+    if (u < n) {
+        const int w0 = u / U * U;
+        v = (unsigned long long)ring32_wave_steps(G, descs, w0, w0 + U < n ? w0 + U : n, u);
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(out, v);
+}
+hipError_t launch_ring32_word_steps(int G, const PairDesc* descs, int n, unsigned long long* out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(ring32_word_steps_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, descs, n, G, out);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ target symbols

@@ -537,6 +537,34 @@ EDLIB_API int edlibAmdBatchWindowsSetUnits(EdlibAmdBatch* batch,
     const int* unitQuery, const int* unitStart, const int* unitLength,
     const unsigned char* unitStrand /* NULL: all forward */, int numUnits);
 
+/* Replace the pairs of a resident pair batch (a mapper's next chunk of winners, whose start locations or paths are
+ * wanted).  The config with its equalities, the device, the stream, the pinned view blocks and every device buffer that
+ * is large enough stay; the pools, the offsets and everything derived from the pairs are made again.  Afterwards the batch
+ * is as if it had been created over (its config, its device, these pairs): Run, then edlibAmdBatchResults, ...ResultsFlat,
+ * ...ResultsView, ...CigarView, ...Stats.  Returns 0, or non-zero with edlibAmdLastError().
+ * Valid on the batches of edlibAmdBatchCreatePairs, whatever they were created over: zero pairs, a handful, a set with a
+ * long pair or an empty sequence (the state of their general path is dropped by the first successful call).  Refused, with
+ * this function and the kind named, on shared-target, both-strand and hit-list read batches and on cross, self,
+ * occurrence and window batches.
+ * A streamed set is a flat set: every query has 1 to 1,024 bases and every target 1 to 65,536; under
+ * EDLIB_TASK_PATH also SHW / HW queries have at most 256 bases, no pair reaches the linear-space regime (the reference's
+ * 1 MiB rule) and the column stores and op slots of the set stay below 32 GB / 8 GB.  The count is free: numPairs from 0
+ * up, the last chunk of a stream is usually short.  Outside the envelope the call is refused with the first offending
+ * pair, its size and the limit named ("... create a new batch").  Also refused: numPairs < 0, a NULL pointer with a
+ * positive count, offsets that decrease.  The offsets need not start at 0; the caller's memory may be reused when the call
+ * returns; numPairs == 0 is valid (Run succeeds, the views are empty).
+ * Every refusal is decided from the offsets and the config alone, before the batch changes, and leaves it as it was: the
+ * previous pairs, the views of the last Run (pointers the caller still holds included), the results of the next.  Behind
+ * that point only a device error (out of memory) can fail the call; it may leave the batch without pairs: Run and the
+ * views then fail with a message that says so until a SetPairs succeeds.  After success the views fail ("Run it first")
+ * until the next Run, and Stats.cells describes the new set.
+ * The set is prepared on the device (a census of the target bytes for the alphabet, exclusive scans for the Peq offsets,
+ * op slots and store bases, the descriptors by a kernel); the host's share is one pass over the two offset arrays, and it
+ * reads no byte of a sequence. */
+EDLIB_API int edlibAmdBatchPairsSetPairs(EdlibAmdBatch* batch,
+    const char* queries, const long long* queryOffsets,
+    const char* targets, const long long* targetOffsets, int numPairs);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
