@@ -191,6 +191,9 @@ def lib():
                                                        C.c_void_p, C.c_void_p, C.c_int]
         if hasattr(L, "edlibAmdBatchPairsSetPairs"):
             L.edlibAmdBatchPairsSetPairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        if hasattr(L, "edlibAmdBatchPairsSetWindows"):
+            L.edlibAmdBatchPairsSetWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int]
         if hasattr(L, "edlibAmdBatchCreateSelf"):
             L.edlibAmdBatchCreateSelf.restype = C.c_void_p
             L.edlibAmdBatchCreateSelf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -614,7 +617,11 @@ class PairBatch(_Batch):
     then as if created over (its config, these pairs) -- run(), then results_flat() / cigars() / results().  A streamed
     set lies inside the flat envelope (queries of 1 to 1,024 bases, targets of 1 to 65,536; with task="path" also SHW / HW
     queries up to 256 bases and no pair in the linear-space regime) and may have any count; outside it the call raises and
-    the batch stays as it was."""
+    the batch stays as it was.
+    set_windows(window_batch, unit_query, unit_start, unit_length, unit_strand=None) (edlibAmdBatchPairsSetWindows) makes
+    the same streamed set from (query, strand, window) tuples over a WindowBatch on the same device: the sequences are
+    gathered on the device from its resident query pool and packed target, only the tuples cross the link, and the
+    window batch stays as it was -- the mapper loop set_units, run, best(), set_windows, run, cigars()."""
 
     def __init__(self, queries, targets, mode="NW", task="distance", k=-1, additionalEqualities=None, device=0):
         qd, qo = _pack(queries)
@@ -637,6 +644,20 @@ class PairBatch(_Batch):
                                             len(qo) - 1) != 0:
             raise RuntimeError("edlib_amd: set_pairs failed: " + last_error())
         self.n = len(qo) - 1
+
+    def set_windows(self, window_batch, unit_query, unit_start, unit_length, unit_strand=None):
+        """Replace the pairs by pairs gathered on the device from a WindowBatch (edlibAmdBatchPairsSetWindows): pair i is
+        query unit_query[i] of window_batch -- its reverse complement where unit_strand[i] == 1 -- against
+        target[unit_start[i] : unit_start[i] + unit_length[i]] of its target.  The batch is then what set_pairs over the
+        materialised pairs would have made; the bytes are copied, so window_batch may change or close afterwards, and it
+        is itself left as it was.  Raises RuntimeError with last_error() on a refusal, which leaves the batch as it was.
+        run() before the next results."""
+        pad, st, n = WindowBatch._units(unit_query, unit_start, unit_length, unit_strand)
+        if lib().edlibAmdBatchPairsSetWindows(self._h, getattr(window_batch, "_h", None), pad[0].ctypes.data,
+                                              pad[1].ctypes.data, pad[2].ctypes.data,
+                                              None if st is None else st.ctypes.data, n) != 0:
+            raise RuntimeError("edlib_amd: set_windows failed: " + last_error())
+        self.n = n
 
 
 class CrossBatch(_Batch):

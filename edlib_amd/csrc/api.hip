@@ -410,6 +410,36 @@ EDLIB_API int edlibAmdBatchPairsSetPairs(EdlibAmdBatch* b, const char* queries, 
                return b->impl.setPairs(queries, queryOffsets, targets, targetOffsets, numPairs); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+EDLIB_API int edlibAmdBatchPairsSetWindows(EdlibAmdBatch* pairs, EdlibAmdBatch* windows, const int* pairQuery,
+                                           const int* pairStart, const int* pairLength, const unsigned char* pairStrand,
+                                           int numPairs) {
+    static const char* const fn = "edlibAmdBatchPairsSetWindows";
+    if (!pairs || !windows) {                     // (both handles before either is read)
+        set_error("%s: %s%s%s", fn, pairs ? "" : "null pair batch", !pairs && !windows ? " and " : "",
+                  windows ? "" : "null window batch");
+        return EDLIB_STATUS_ERROR;
+    }
+    if (pairs->windows || pairs->cross || !pairs->impl.isPairs()) {
+        set_error("%s: not available on %s (only the pairs of a batch made by edlibAmdBatchCreatePairs can be replaced)", fn,
+                  kind_of(pairs));
+        return EDLIB_STATUS_ERROR;
+    }
+    if (!windows->windows) {
+        set_error("%s: the pairs cannot be gathered from %s (only from a window batch)", fn, kind_of(windows));
+        return EDLIB_STATUS_ERROR;
+    }
+    if (pairs->impl.device() != windows->windows->device()) {
+        set_error("%s: the pair batch is on device %d and the window batch on device %d: the gather does not cross devices", fn,
+                  pairs->impl.device(), windows->windows->device());
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded(fn, 1, [&] {
+               WindowSource src;
+               if (windows->windows->gatherSource(fn, src)) return 1;
+               return pairs->impl.setWindows(src, pairQuery, pairStart, pairLength, pairStrand, numPairs);
+           }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchWindowsSetUnits(EdlibAmdBatch* b, const char* queries, const long long* queryOffsets,
                                            int numQueries, const int* unitQuery, const int* unitStart,
                                            const int* unitLength, const unsigned char* unitStrand, int numUnits) {

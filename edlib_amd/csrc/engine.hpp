@@ -11,6 +11,7 @@
 #include "window_kernels.hpp"
 #include "strands.hpp"
 #include "flat_pairs_prepare.hpp"
+#include "pairs_gather.hpp"
 
 #include <chrono>
 #include <deque>
@@ -176,7 +177,12 @@ public:
              bool pairs = false);                                           // made by edlibAmdBatchCreatePairs (one pair is shared, too)
     // another pair set through a resident pair batch (edlibAmdBatchPairsSetPairs; engine_flat.hip "streamed pairs")
     int setPairs(const char* queries, const long long* qoff, const char* targets, const long long* toff, int n);
+    // the same with the pairs named as (query, strand, window) tuples over a window batch and gathered from its resident
+    // pools on the device (edlibAmdBatchPairsSetWindows; engine_flat.hip "pairs from a window batch")
+    int setWindows(const WindowSource& src, const int* pairQuery, const int* pairStart, const int* pairLength,
+                   const unsigned char* pairStrand, int n);
     bool isPairs() const { return pairsKind_; }
+    int device() const { return device_; }
     bool isBothStrands() const { return strands_; }
     int run();
     int runImpl();
@@ -441,7 +447,16 @@ private:
     void planFlat(const long long* qoff, const long long* toff, int n, bool sharedTarget, FlatPlan& plan,
                   std::vector<long long>* qout, std::vector<long long>* tout) const;
     int prepareFlat(const FlatPlan& plan, bool census);      // the set's layout, made on the device: Create and setPairs
+    // a streamed set (setPairs, setWindows): the refusal of a plan that failed; what the batch drops before the set
+    // changes; the device's share in two halves with the filling of the pools between them
+    void refuseFlat(const char* fn, const FlatPlan& plan, long long m, long long T) const;
+    int dropForStreamedSet(const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew);
+    int streamFlatBegin(const FlatPlan& plan);
+    int streamFlatEnd(const FlatPlan& plan);
     int streamFlat(const char* queries, const char* targets, const FlatPlan& plan);
+    int gatherFlat(const WindowSource& src, const int* pairQuery, const int* pairStart, const unsigned char* pairStrand,
+                   const FlatPlan& plan);
+    DevBuf<int> d_gatherTuples_;                             // setWindows: pairQuery [n], pairStart [n], pairStrand (bytes)
     DevBuf<long long> d_flatPrep_; DevBuf<uint8_t> d_flatPrepTmp_; DevBuf<int> d_flatCuts_;
     DevBuf<uint8_t> d_flatPrepOut_; PinBuf h_flatPrepOut_;   // presence [8] and word-steps [2] of the prepared set
     DevBuf<uint8_t> d_tabs_; PinBuf h_tabs_;                 // tlut, idToByte, eqtbl of a streamed set

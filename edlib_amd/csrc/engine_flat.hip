@@ -326,44 +326,7 @@ int Batch::setPairs(const char* queries, const long long* qoff, const char* targ
     planFlat(qoff, toff, n, false, plan, &qnew, &tnew);
     if (plan.why != FlatPlan::kOk) {
         const int u = plan.who;
-        const long long m = qoff[u + 1] - qoff[u], T = toff[u + 1] - toff[u];
-        const char* const modeName = mode == EDLIB_MODE_HW ? "HW" : (mode == EDLIB_MODE_SHW ? "SHW" : "NW");
-        switch (plan.why) {
-        case FlatPlan::kBadQueryOffsets: set_error("%s: bad query offsets (query %d ends before it starts)", fn, u); break;
-        case FlatPlan::kBadTargetOffsets: set_error("%s: bad target offsets (target %d ends before it starts)", fn, u); break;
-        case FlatPlan::kEmptyQuery:
-            set_error("%s: pair %d has an empty query (0 bases), a streamed set takes queries of 1 to %s bases: create a new batch",
-                      fn, u, with_commas(kFlatMaxQuery).c_str());
-            break;
-        case FlatPlan::kEmptyTarget:
-            set_error("%s: pair %d has an empty target (0 bases), a streamed set takes targets of 1 to %s bases: create a new batch",
-                      fn, u, with_commas(kFlatMaxTarget).c_str());
-            break;
-        case FlatPlan::kLongQuery:
-            set_error("%s: pair %d has a query of %s bases, the limit for a streamed set is %s: create a new batch", fn, u,
-                      with_commas(m).c_str(), with_commas(kFlatMaxQuery).c_str());
-            break;
-        case FlatPlan::kLongTarget:
-            set_error("%s: pair %d has a target of %s bases, the limit for a streamed set is %s: create a new batch", fn, u,
-                      with_commas(T).c_str(), with_commas(kFlatMaxTarget).c_str());
-            break;
-        case FlatPlan::kPathBlocks:
-            set_error("%s: pair %d has a query of %s bases, the limit for a streamed set with EDLIB_TASK_PATH in mode %s is 256: "
-                      "create a new batch", fn, u, with_commas(m).c_str(), modeName);
-            break;
-        case FlatPlan::kHirschberg:
-            set_error("%s: pair %d (%s x %s bases) needs the linear-space path (its matrix reaches the 1 MiB rule), a streamed "
-                      "set with EDLIB_TASK_PATH stays below it: create a new batch", fn, u, with_commas(m).c_str(), with_commas(T).c_str());
-            break;
-        case FlatPlan::kStoreCap:
-            set_error("%s: at pair %d the column stores of the set pass 32 GB, the limit for a streamed set with EDLIB_TASK_PATH: "
-                      "create a new batch", fn, u);
-            break;
-        default:
-            set_error("%s: at pair %d the op slots of the set pass 8 GB, the limit for a streamed set with EDLIB_TASK_PATH: "
-                      "create a new batch", fn, u);
-            break;
-        }
+        refuseFlat(fn, plan, qoff[u + 1] - qoff[u], toff[u + 1] - toff[u]);
         return 1;
     }
     pool_quarantine(false);
@@ -372,6 +335,60 @@ int Batch::setPairs(const char* queries, const long long* qoff, const char* targ
 
     // ---- from here a device error leaves the batch without pairs
     noPairs_ = true;
+    if (dropForStreamedSet(plan, qnew, tnew)) return 1;
+    if (streamFlat(queries + (n > 0 ? qoff[0] : 0), targets + (n > 0 ? toff[0] : 0), plan)) return 1;
+    noPairs_ = false;
+    return 0;
+}
+
+// the first pair outside the flat envelope (plan.who, of m x T bases) and the limit it passes
+void Batch::refuseFlat(const char* fn, const FlatPlan& plan, long long m, long long T) const
+{
+    const int u = plan.who, mode = (int)cfg_.mode;
+    const char* const modeName = mode == EDLIB_MODE_HW ? "HW" : (mode == EDLIB_MODE_SHW ? "SHW" : "NW");
+    switch (plan.why) {
+    case FlatPlan::kBadQueryOffsets: set_error("%s: bad query offsets (query %d ends before it starts)", fn, u); break;
+    case FlatPlan::kBadTargetOffsets: set_error("%s: bad target offsets (target %d ends before it starts)", fn, u); break;
+    case FlatPlan::kEmptyQuery:
+        set_error("%s: pair %d has an empty query (0 bases), a streamed set takes queries of 1 to %s bases: create a new batch",
+                  fn, u, with_commas(kFlatMaxQuery).c_str());
+        break;
+    case FlatPlan::kEmptyTarget:
+        set_error("%s: pair %d has an empty target (0 bases), a streamed set takes targets of 1 to %s bases: create a new batch",
+                  fn, u, with_commas(kFlatMaxTarget).c_str());
+        break;
+    case FlatPlan::kLongQuery:
+        set_error("%s: pair %d has a query of %s bases, the limit for a streamed set is %s: create a new batch", fn, u,
+                  with_commas(m).c_str(), with_commas(kFlatMaxQuery).c_str());
+        break;
+    case FlatPlan::kLongTarget:
+        set_error("%s: pair %d has a target of %s bases, the limit for a streamed set is %s: create a new batch", fn, u,
+                  with_commas(T).c_str(), with_commas(kFlatMaxTarget).c_str());
+        break;
+    case FlatPlan::kPathBlocks:
+        set_error("%s: pair %d has a query of %s bases, the limit for a streamed set with EDLIB_TASK_PATH in mode %s is 256: "
+                  "create a new batch", fn, u, with_commas(m).c_str(), modeName);
+        break;
+    case FlatPlan::kHirschberg:
+        set_error("%s: pair %d (%s x %s bases) needs the linear-space path (its matrix reaches the 1 MiB rule), a streamed "
+                  "set with EDLIB_TASK_PATH stays below it: create a new batch", fn, u, with_commas(m).c_str(), with_commas(T).c_str());
+        break;
+    case FlatPlan::kStoreCap:
+        set_error("%s: at pair %d the column stores of the set pass 32 GB, the limit for a streamed set with EDLIB_TASK_PATH: "
+                  "create a new batch", fn, u);
+        break;
+    default:
+        set_error("%s: at pair %d the op slots of the set pass 8 GB, the limit for a streamed set with EDLIB_TASK_PATH: "
+                  "create a new batch", fn, u);
+        break;
+    }
+}
+
+// What a resident pair batch drops before another set takes its place (the device is current): everything that caches
+// something about the units, and the results of the last Run.  The rebased offsets of the new set become the batch's.
+int Batch::dropForStreamedSet(const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew)
+{
+    const int n = plan.n;
     // (a Run whose alphabetLength nobody collected: its kernel still reads the pools that are about to change)
     if (alphaPending_ && side_) EDLIB_AMD_HIP(hipStreamSynchronize(side_));
     alphaPending_ = false;
@@ -394,13 +411,11 @@ int Batch::setPairs(const char* queries, const long long* qoff, const char* targ
     stats.cells = plan.cells;
     algoBase_ = -1; algoDirty_ = false;
     flatPairs_ = false;
-    if (streamFlat(queries + (n > 0 ? qoff[0] : 0), targets + (n > 0 ? toff[0] : 0), plan)) return 1;
-    noPairs_ = false;
     return 0;
 }
 
-// the device's share of setPairs: the pools and the offsets go up as they are, the rest is prepareFlat
-int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& p)
+// the device's share of a streamed set, first half: the pools sized, the offsets on their way up
+int Batch::streamFlatBegin(const FlatPlan& p)
 {
     const size_t n = (size_t)p.n;
     // (pools and offsets that were views into init()'s one block become buffers of their own; the block goes)
@@ -410,12 +425,15 @@ int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& 
     if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(8 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)));
     d_tlut_.alias(d_tabs_.p, 256); d_idToByte_.alias(d_tabs_.p + 256, 256); d_eqtbl_.alias(d_tabs_.p + 512, 256);
     d_presence_.alias(d_flatPrepOut_.p, 8);
-    if (p.qbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_qpool_.p, queries, (size_t)p.qbytes, hipMemcpyHostToDevice, stream_));
-    if (p.tbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_tpool_.p, targets, (size_t)p.tbytes, hipMemcpyHostToDevice, stream_));
-    EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p + p.qbytes, 0, 16, stream_));
-    EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p + p.tbytes, 0, 16, stream_));
     EDLIB_AMD_HIP(hipMemcpyAsync(d_qoff_.p, qoff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
     EDLIB_AMD_HIP(hipMemcpyAsync(d_toff_.p, toff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
+    return 0;
+}
+
+// ... second half, behind the pools: the rest is prepareFlat
+int Batch::streamFlatEnd(const FlatPlan& p)
+{
+    const size_t n = (size_t)p.n;
     // alphabetLength is counted per unit as before: its unit list (0, 1, ...) is written with the layout
     EDLIB_AMD_HIP(d_alphaIdx_.ensure(n)); EDLIB_AMD_HIP(d_alphaOut_.ensure(n));
     if (alphaPin_.n < n * sizeof(int) || !alphaPin_.p) EDLIB_AMD_HIP(alphaPin_.alloc(n * sizeof(int)));
@@ -433,6 +451,112 @@ int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& 
     // algorithmic bytes of a Run whose results stay on the device (startStats): a constant of the set
     algoBase_ = p.lens + 8LL * (tab_.sigmaT + 1) * p.totalBlocks + 20LL * p.n;
     return 0;
+}
+
+// setPairs: the pools go up as they are
+int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& p)
+{
+    if (streamFlatBegin(p)) return 1;
+    if (p.qbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_qpool_.p, queries, (size_t)p.qbytes, hipMemcpyHostToDevice, stream_));
+    if (p.tbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_tpool_.p, targets, (size_t)p.tbytes, hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p + p.qbytes, 0, 16, stream_));
+    EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p + p.tbytes, 0, 16, stream_));
+    return streamFlatEnd(p);
+}
+
+// ------------------------------------------------------------ pairs from a window batch
+
+// edlibAmdBatchPairsSetWindows (DESIGN.md §4b "Pairs from a window batch"): a streamed set whose pairs are (query, strand,
+// window) tuples over a window batch `src` on the same device.  The host's pass over the tuples checks them against the
+// window batch's query offsets and target length and builds the offsets of the two pools by running sums; they go
+// through planFlat like any streamed set.  The pools are gathered on the device from the window batch's resident query
+// pool and 4-bit pack (pairs_gather.hip); the rest is setPairs'.  What is refused leaves the batch as it was.
+int Batch::setWindows(const WindowSource& src, const int* pairQuery, const int* pairStart, const int* pairLength,
+                      const unsigned char* pairStrand, int n)
+{
+    static const char* const fn = "edlibAmdBatchPairsSetWindows";
+    if (n < 0) { set_error("%s: numPairs must be >= 0 (got %d)", fn, n); return 1; }
+    if (n > 0 && (!pairQuery || !pairStart || !pairLength)) {
+        set_error("%s: pairQuery, pairStart and pairLength must not be NULL for %d pairs", fn, n);
+        return 1;
+    }
+    const int mode = (int)cfg_.mode;
+    if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) {
+        set_error("%s: the batch's config.mode (%d) has no flat form: create a new batch", fn, mode);
+        return 1;
+    }
+    std::vector<long long> qnew((size_t)n + 1, 0), tnew((size_t)n + 1, 0);
+    for (int p = 0; p < n; ++p) {
+        const int q = pairQuery[p], start = pairStart[p], len = pairLength[p];
+        if (q < 0 || q >= src.numQueries) {
+            set_error("%s: pair %d names query %d, outside [0, numQueries = %d) of the window batch", fn, p, q, src.numQueries);
+            return 1;
+        }
+        if (start < 0) { set_error("%s: pair %d has a negative pairStart (%d)", fn, p, start); return 1; }
+        if (len < 0) { set_error("%s: pair %d has a negative pairLength (%d)", fn, p, len); return 1; }
+        if ((long long)start + (long long)len > (long long)src.targetLength) {
+            set_error("%s: pair %d ends past the target (pairStart %d + pairLength %d > targetLength %d)", fn, p, start, len,
+                      src.targetLength);
+            return 1;
+        }
+        if (pairStrand && pairStrand[p] > 1) {
+            set_error("%s: pair %d has pairStrand %d (0: the query, 1: its reverse complement)", fn, p, (int)pairStrand[p]);
+            return 1;
+        }
+        qnew[(size_t)p + 1] = qnew[p] + (src.h_qoff[q + 1] - src.h_qoff[q]);
+        tnew[(size_t)p + 1] = tnew[p] + len;
+    }
+    FlatPlan plan;
+    planFlat(qnew.data(), tnew.data(), n, false, plan, nullptr, nullptr);
+    if (plan.why != FlatPlan::kOk) {
+        const int u = plan.who;
+        refuseFlat(fn, plan, qnew[(size_t)u + 1] - qnew[u], tnew[(size_t)u + 1] - tnew[u]);
+        return 1;
+    }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+
+    // ---- from here a device error leaves the batch without pairs
+    noPairs_ = true;
+    if (dropForStreamedSet(plan, qnew, tnew)) return 1;
+    if (gatherFlat(src, pairQuery, pairStart, pairStrand, plan)) {
+        (void)hipStreamSynchronize(stream_);                         // nothing of this batch's reads the window batch behind the call
+        return 1;
+    }
+    noPairs_ = false;
+    return 0;
+}
+
+// the device's share of setWindows: the offsets and the tuples go up, the pools are gathered
+int Batch::gatherFlat(const WindowSource& src, const int* pairQuery, const int* pairStart, const unsigned char* pairStrand,
+                      const FlatPlan& p)
+{
+    if (streamFlatBegin(p)) return 1;
+    if (p.n == 0) {
+        EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p, 0, 16, stream_));
+        EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p, 0, 16, stream_));
+        return streamFlatEnd(p);
+    }
+    const size_t n = (size_t)p.n;
+    EDLIB_AMD_HIP(d_gatherTuples_.ensure(2 * n + (n + 3) / 4));
+    int* const dq = d_gatherTuples_.p; int* const ds = dq + n;
+    uint8_t* const dst = reinterpret_cast<uint8_t*>(ds + n);
+    EDLIB_AMD_HIP(hipMemcpyAsync(dq, pairQuery, n * sizeof(int), hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(ds, pairStart, n * sizeof(int), hipMemcpyHostToDevice, stream_));
+    if (pairStrand) EDLIB_AMD_HIP(hipMemcpyAsync(dst, pairStrand, n, hipMemcpyHostToDevice, stream_));
+    PairsGatherArgs a{};
+    a.numPairs = p.n; a.qoff = d_qoff_.p; a.toff = d_toff_.p; a.qbytes = p.qbytes; a.tbytes = p.tbytes;
+    a.pairQuery = dq; a.pairStart = ds; a.pairStrand = pairStrand ? dst : nullptr;
+    a.qpool = d_qpool_.p; a.tpool = d_tpool_.p;
+    // The gather reads the window batch's query pool, its offsets and the target pack from THIS batch's stream.  They
+    // are written by WindowBatch::prepareUnits and, at Create, by LaneEngine::packHostTargets (synchronous copies, then
+    // packTargets' kernel) only, and both wait for the window batch's stream before they succeed (a Run and a view read
+    // them and wait, too): nothing is in flight on them between the window batch's calls, so no event orders the two
+    // streams.  prepareFlat's wait below ends the reads before this call
+    // returns: the window batch may change or go afterwards.
+    EDLIB_AMD_HIP(launch_pairs_gather(src, a, stream_));
+    return streamFlatEnd(p);
 }
 
 int Batch::noResults(const char* who)

@@ -239,6 +239,12 @@ public:
                  const int* unitLength, const unsigned char* unitStrand, int numUnits);
     int run();
     int view(int what, EdlibAmdWindowView* out);
+    int device() const { return device_; }
+    // What a pair batch gathers its pairs from (edlibAmdBatchPairsSetWindows, `fn` in the messages): the resident query
+    // pool and target pack of a set that was prepared on the device.  1 with the error set where nothing is resident: a
+    // target of more than 16 symbols, a Create that took the host route, a setUnits that failed on the device.  The batch
+    // is not changed.
+    int gatherSource(const char* fn, WindowSource& out) const;
 
 private:
     struct Group : LaneGroup {                    // slots: the (query, strand) entries its units name, unpadded
@@ -274,6 +280,10 @@ private:
                      const int* unitLength, const unsigned char* unitStrand, int nu, const UnitCensus& c);
     int noResults();                              // Run's and the views': the error of a batch without units or without a Run
     bool noUnits_ = false;                        // a setUnits failed on the device after it had begun to change the batch
+    // of the set prepareUnits made last (none: a Create on the host route): the host's copy of the queries' offsets as the
+    // caller gave them (any base: a gathered set is planned from their differences), and whether the pool holds both strands
+    bool onDevice_ = false, stranded_ = false;
+    std::vector<long long> h_qoff_;
     int nu_ = 0, targetLength_ = 0;
     std::unique_ptr<Group> groupOf_[kCrossMaxQueryWords + 1];  // the group of every word count, kept for its buffers
     std::vector<Group*> groups_;                  // those that have units

@@ -191,6 +191,9 @@ int WindowBatch::prepareUnits(const char* queries, const long long* qoff, int nq
     haveRun_ = false;
     stats = EdlibAmdBatchStats{};
     stats.cells = c.cells;
+    // (what a pair batch plans a gathered set from: gatherSource)
+    onDevice_ = true; stranded_ = st;
+    if (nq > 0) h_qoff_.assign(qoff, qoff + nq + 1); else h_qoff_.assign(1, 0);
     EDLIB_AMD_HIP(d_units_.ensure(3 * (size_t)std::max(nu, 1))); EDLIB_AMD_HIP(d_uq_.ensure((size_t)std::max(nu, 1)));
     EDLIB_AMD_HIP(d_best_.ensure(3 * (size_t)std::max(nq, 1))); EDLIB_AMD_HIP(d_bkey_.ensure(2 * (size_t)std::max(nq, 1)));
 
@@ -308,6 +311,34 @@ int WindowBatch::setUnits(const char* queries, const long long* qoff, int nq, co
     noUnits_ = true;
     if (prepareUnits(queries, qoff, nq, unitQuery, unitStart, unitLength, unitStrand, nu, census)) return 1;
     noUnits_ = false;
+    return 0;
+}
+
+int WindowBatch::gatherSource(const char* fn, WindowSource& out) const
+{
+    if (tab_.sigmaT > kCrossMaxSyms) {
+        set_error("%s: the window batch's target holds %d distinct symbols, the limit for a batch to gather pairs from is %d "
+                  "(its target is not resident as a 4-bit pack): materialise the pairs and use edlibAmdBatchPairsSetPairs", fn,
+                  tab_.sigmaT, kCrossMaxSyms);
+        return 1;
+    }
+    if (noUnits_) {
+        set_error("%s: the window batch has no units (edlibAmdBatchWindowsSetUnits failed on the device): set them again", fn);
+        return 1;
+    }
+    if (!onDevice_) {
+        set_error("%s: the window batch was created over a unit outside the window kernel's envelope (a query above %d bases "
+                  "or a window above %s columns) and took the host route: its queries are not resident to gather from; give "
+                  "it a set with edlibAmdBatchWindowsSetUnits, or materialise the pairs and use edlibAmdBatchPairsSetPairs", fn,
+                  32 * kCrossMaxQueryWords, with_commas(kCrossMaxTarget).c_str());
+        return 1;
+    }
+    out = WindowSource{};
+    out.numQueries = nq_; out.targetLength = targetLength_;
+    out.h_qoff = h_qoff_.data();
+    out.d_qpool = d_qpool_.p; out.qpoolBytes = d_qpool_.n; out.d_qoff = d_qoff_.p; out.stranded = stranded_;
+    out.d_pack = d_tpk_.p; out.packDwords = ((long long)targetLength_ + 7) / 8;
+    memcpy(out.idToByte, tab_.idToByte, 16);
     return 0;
 }
 

@@ -1,0 +1,114 @@
+// pairs_gather.hip -- the pools of a flat pair set gathered on the device from a window batch's resident query pool and
+// 4-bit target pack (edlibAmdBatchPairsSetWindows; DESIGN.md §4b "Pairs from a window batch").  Pure data movement: a
+// thread owns 16 aligned destination bytes (pairs_gather_core.hpp) and a wave stores 1 KiB of consecutive bytes per
+// instruction.  A block first narrows the offsets to the pairs its 4 KiB touch -- every wave searches the same two
+// positions, 64 probes a step -- so that a thread's own binary search runs over a handful of pairs.
+#include "pairs_gather.hpp"
+#include "pairs_gather_core.hpp"
+#include "strands.hpp"
+
+namespace edlib_amd {
+
+using namespace pairs_gather;
+
+struct IdToByte { uint8_t b[16]; };
+
+// The largest p in [lo, hi] with off[p] <= pos, by a whole wave (every lane with the same arguments): a lane a probe, the
+// ballot counts the probes at or below pos
+__device__ __forceinline__ int find_pair_wave(const long long* __restrict__ off, int lo, int hi, long long pos)
+{
+    const int lane = threadIdx.x & 63;
+    while (lo < hi) {
+        const long long at = probe_at(lo, hi, lane);
+        const bool below = at <= hi && off[at] <= pos;
+        narrow(lo, hi, __popcll(__ballot(below)));
+    }
+    return lo;
+}
+
+// the pairs [lo, hi] that hold the bytes of this block (called by whole waves)
+__device__ __forceinline__ void block_pairs(const long long* __restrict__ off, int n, long long total, int& lo, int& hi)
+{
+    lo = find_pair_wave(off, 0, n - 1, block_first(total, blockIdx.x));
+    hi = find_pair_wave(off, lo, block_far(lo, n), block_last(total, blockIdx.x));
+}
+
+// the run of thread `d0 / 16`: 16 bytes where the pool (total + 16 bytes) has them, the pool's last bytes one by one
+__device__ __forceinline__ void store_run(uint8_t* __restrict__ pool, long long d0, long long total, const Run& r)
+{
+    const long long left = total + 16 - d0;
+    if (left >= kRun) {
+        uint4 v;
+        v.x = (u32)r.w[0]; v.y = (u32)(r.w[0] >> 32); v.z = (u32)r.w[1]; v.w = (u32)(r.w[1] >> 32);
+        *reinterpret_cast<uint4*>(pool + d0) = v;
+    } else {
+        for (int j = 0; j < (int)left; ++j) pool[d0 + j] = (uint8_t)(r.w[j >> 3] >> (8 * (j & 7)));
+    }
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+gather_targets_kernel(const long long* __restrict__ toff, int n, long long total, TargetSource src, IdToByte ids,
+                      uint8_t* __restrict__ tpool)
+{
+    __shared__ uint16_t s_tab2[256];
+    s_tab2[threadIdx.x] = (uint16_t)(ids.b[threadIdx.x & 15] | ids.b[threadIdx.x >> 4] << 8);
+    __syncthreads();
+    int lo, hi;
+    block_pairs(toff, n, total, lo, hi);                         // (every lane of every wave: before any of them leaves)
+    const long long d0 = ((long long)blockIdx.x * kBlockThreads + threadIdx.x) * kRun;
+    if (d0 >= total + 16) return;
+    Run r; r.w[0] = 0; r.w[1] = 0;
+    if (d0 < total) {
+        r = target_run(d0, total, find_pair(toff, lo, hi, d0), toff, src, s_tab2);
+    }
+    store_run(tpool, d0, total, r);
+}
+
+__global__ void __launch_bounds__(kBlockThreads)
+gather_queries_kernel(const long long* __restrict__ qoff, int n, long long total, QuerySource src, uint8_t* __restrict__ qpool)
+{
+    __shared__ uint8_t s_comp[256];
+    s_comp[threadIdx.x] = complement_byte((uint8_t)threadIdx.x);
+    __syncthreads();
+    int lo, hi;
+    block_pairs(qoff, n, total, lo, hi);                         // (every lane of every wave: before any of them leaves)
+    const long long d0 = ((long long)blockIdx.x * kBlockThreads + threadIdx.x) * kRun;
+    if (d0 >= total + 16) return;
+    Run r; r.w[0] = 0; r.w[1] = 0;
+    if (d0 < total) {
+        r = query_run(d0, total, find_pair(qoff, lo, hi, d0), qoff, src, s_comp);
+    }
+    store_run(qpool, d0, total, r);
+}
+
+hipError_t launch_pairs_gather(const WindowSource& w, const PairsGatherArgs& a, hipStream_t stream)
+{
+    static_assert(kBlockThreads == 256, "a block fills its 256-entry tables with one entry per thread");
+    static_assert(kProbes == 64, "a probe per lane of a wave");
+    if (a.numPairs < 1 || a.qbytes < 1 || a.tbytes < 1) return hipErrorInvalidValue;
+    // the wide accesses: dwords of the sources, 128-bit stores into the pools
+    if ((reinterpret_cast<uintptr_t>(w.d_qpool) & 3) || (reinterpret_cast<uintptr_t>(w.d_pack) & 3) ||
+        (reinterpret_cast<uintptr_t>(a.qpool) & 15) || (reinterpret_cast<uintptr_t>(a.tpool) & 15)) return hipErrorInvalidValue;
+    const auto blocks = [](long long bytes) { return (unsigned)((bytes + 16 + kBlockBytes - 1) / kBlockBytes); };
+    if ((a.qbytes + 16 + kBlockBytes - 1) / kBlockBytes > 0x7fffffffLL || (a.tbytes + 16 + kBlockBytes - 1) / kBlockBytes > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+
+    TargetSource ts{};
+    ts.pack = w.d_pack; ts.ndw = w.packDwords; ts.pairStart = a.pairStart;
+    IdToByte ids;
+    for (int i = 0; i < 16; ++i) ids.b[i] = w.idToByte[i];
+    hipLaunchKernelGGL(gather_targets_kernel, dim3(blocks(a.tbytes)), dim3(kBlockThreads), 0, stream,
+                       a.toff, a.numPairs, a.tbytes, ts, ids, a.tpool);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    QuerySource qs{};
+    qs.pool = reinterpret_cast<const u32*>(w.d_qpool); qs.ndw = (long long)(w.qpoolBytes / 4);
+    qs.off = w.d_qoff; qs.stranded = w.stranded ? 1 : 0;
+    qs.pairQuery = a.pairQuery; qs.pairStrand = a.pairStrand;
+    hipLaunchKernelGGL(gather_queries_kernel, dim3(blocks(a.qbytes)), dim3(kBlockThreads), 0, stream,
+                       a.qoff, a.numPairs, a.qbytes, qs, a.qpool);
+    return hipGetLastError();
+}
+
+}  // namespace edlib_amd

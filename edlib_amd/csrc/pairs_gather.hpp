@@ -1,0 +1,33 @@
+// pairs_gather.hpp -- launch interface of the gather that fills the pools of a flat pair set from a window batch
+// (edlibAmdBatchPairsSetWindows; pairs_gather_core.hpp: what a thread does).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace edlib_amd {
+
+// What a window batch lends to the gather: device pointers that stay valid, and unwritten, while the window batch is not
+// given new units or destroyed; and the host's copy of what the set is planned from.
+struct WindowSource {
+    int numQueries = 0, targetLength = 0;
+    const long long* h_qoff = nullptr;            // host: [numQueries + 1] offsets of the queries as the caller gave them, from any base
+    const uint8_t* d_qpool = nullptr; size_t qpoolBytes = 0;       // the query pool (both strands of every query where stranded)
+    const long long* d_qoff = nullptr;            // offsets of its entries: entry q, or 2 q + strand where stranded
+    bool stranded = false;
+    const uint32_t* d_pack = nullptr; long long packDwords = 0;    // the target, 4-bit codes, 8 columns per dword from dword 0
+    uint8_t idToByte[16] = {};                    // code -> byte
+};
+
+struct PairsGatherArgs {
+    int numPairs;                                 // >= 1
+    const long long* qoff; const long long* toff; // device: [numPairs + 1] offsets of the destination pools, from 0
+    long long qbytes, tbytes;                     // qoff[numPairs], toff[numPairs]
+    const int* pairQuery; const int* pairStart; const uint8_t* pairStrand;    // device; pairStrand null: all forward
+    uint8_t* qpool; uint8_t* tpool;               // device: qbytes + 16 and tbytes + 16 bytes, 16-byte aligned
+};
+
+// Writes both pools with their 16 trailing zero bytes on `stream`.  Every tuple has been checked against the source by
+// the caller: the kernel checks none.
+hipError_t launch_pairs_gather(const WindowSource& src, const PairsGatherArgs& a, hipStream_t stream);
+
+}  // namespace edlib_amd

@@ -565,6 +565,40 @@ EDLIB_API int edlibAmdBatchPairsSetPairs(EdlibAmdBatch* batch,
     const char* queries, const long long* queryOffsets,
     const char* targets, const long long* targetOffsets, int numPairs);
 
+/* Replace the pairs of a resident pair batch by pairs named over a window batch and gathered on the device (a mapper's
+ * winners of edlibAmdBatchWindowView, without the slices leaving the device): the query of pair i is query pairQuery[i]
+ * of `windows` -- its edlibAmdReverseComplement where pairStrand[i] == 1 -- and its target is
+ * target[pairStart[i] .. pairStart[i] + pairLength[i]) of the target of `windows`.  Afterwards `pairs` is exactly the
+ * batch edlibAmdBatchPairsSetPairs would have made over these pairs materialised: everything that call keeps and resets
+ * this one keeps and resets, and Run, Results, ResultsFlat, ResultsView, CigarView and Stats follow as there.  Returns 0,
+ * or non-zero with edlibAmdLastError().  The tuples are the caller's own, not unit indices of `windows`: a padded window
+ * around a verified one, a second-best unit, any strand.
+ * The bytes are copied: when the call returns `pairs` depends on nothing in `windows`, which may be given new units, run
+ * or destroyed.  `windows` is not changed in any way a caller can observe: the views of its last Run, its next Run and
+ * its Stats stay as they were.
+ * `pairs` is a batch of edlibAmdBatchCreatePairs in any state SetPairs accepts.  `windows` is a window batch whose current
+ * set was prepared on the device -- by a Create whose units all lie inside the window kernel's envelope, or by any
+ * successful edlibAmdBatchWindowsSetUnits; then its query pool (both strands where a unit named one) and the 4-bit pack
+ * of its target are resident.  Any number of Runs may have happened, none included.
+ * Refused, with this function and the reason named: a NULL handle; another kind of batch on either side (the kind is
+ * named as SetPairs names it); batches on different devices; a `windows` over a target with more than 16 distinct symbols;
+ * a `windows` whose Create took the host route (a unit outside the envelope: nothing is resident to gather from); a
+ * `windows` left without units by a SetUnits that failed on the device; numPairs < 0; a NULL pairQuery, pairStart or
+ * pairLength with a positive count (a NULL pairStrand is all forward).  Per pair, the first offender named with its
+ * values: pairQuery outside [0, numQueries) of `windows`, a negative pairStart or pairLength,
+ * pairStart + pairLength > targetLength, pairStrand > 1.  Then the flat envelope of SetPairs with its messages ("... create
+ * a new batch"): an empty query or an empty window, and under EDLIB_TASK_PATH the limits named there.  numPairs == 0 is
+ * valid.
+ * Every refusal is decided on the host from the lengths alone, before either batch changes, and leaves `pairs` as it
+ * was: its previous pairs, the views the caller still holds, the results of its next Run.  Behind that point only a device
+ * error can fail the call; it leaves `pairs` without pairs, as a failed SetPairs does.
+ * The config of `pairs` and its additionalEqualities are its own and need not match those of `windows`; its alphabet is
+ * the census of the gathered target bytes, as for any streamed set.
+ * What crosses the link is the offsets and the tuples (about 25 bytes a pair); the host reads no byte of a sequence. */
+EDLIB_API int edlibAmdBatchPairsSetWindows(EdlibAmdBatch* pairs, EdlibAmdBatch* windows,
+    const int* pairQuery, const int* pairStart, const int* pairLength,
+    const unsigned char* pairStrand /* NULL: all forward */, int numPairs);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
