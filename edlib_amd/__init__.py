@@ -194,6 +194,9 @@ def lib():
         if hasattr(L, "edlibAmdBatchPairsSetWindows"):
             L.edlibAmdBatchPairsSetWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_int]
+        if hasattr(L, "edlibAmdBatchPairsSetSharedWindows"):
+            L.edlibAmdBatchPairsSetSharedWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_int]
         if hasattr(L, "edlibAmdBatchCreateSelf"):
             L.edlibAmdBatchCreateSelf.restype = C.c_void_p
             L.edlibAmdBatchCreateSelf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -621,7 +624,12 @@ class PairBatch(_Batch):
     set_windows(window_batch, unit_query, unit_start, unit_length, unit_strand=None) (edlibAmdBatchPairsSetWindows) makes
     the same streamed set from (query, strand, window) tuples over a WindowBatch on the same device: the sequences are
     gathered on the device from its resident query pool and packed target, only the tuples cross the link, and the
-    window batch stays as it was -- the mapper loop set_units, run, best(), set_windows, run, cigars()."""
+    window batch stays as it was -- the mapper loop set_units, run, best(), set_windows, run, cigars().
+    set_shared_windows(batch, pair_query, pair_start, pair_length, pair_strand=None)
+    (edlibAmdBatchPairsSetSharedWindows) makes it from (read, strand, window) tuples over a SharedBatch or a
+    BothStrandsBatch: the reads and the target windows are gathered from the read batch's resident pools, so a distance
+    run, first_hit_windows(), set_shared_windows, run gives start locations and CIGARs of the first hit of every read
+    that mapped, equal to the whole-target HW path answer."""
 
     def __init__(self, queries, targets, mode="NW", task="distance", k=-1, additionalEqualities=None, device=0):
         qd, qo = _pack(queries)
@@ -658,6 +666,47 @@ class PairBatch(_Batch):
                                               None if st is None else st.ctypes.data, n) != 0:
             raise RuntimeError("edlib_amd: set_windows failed: " + last_error())
         self.n = n
+
+    def set_shared_windows(self, batch, pair_query, pair_start, pair_length, pair_strand=None):
+        """Replace the pairs by pairs gathered on the device from a read batch -- a SharedBatch (hits=True included) or a
+        BothStrandsBatch on the same device (edlibAmdBatchPairsSetSharedWindows): pair i is read pair_query[i] of batch --
+        its reverse complement where pair_strand[i] == 1 -- against target[pair_start[i] : pair_start[i] + pair_length[i]]
+        of its target.  The batch is then what set_pairs over the materialised pairs would have made; the bytes are
+        copied, so the read batch may run or close afterwards, and it is itself left as it was, whether it has run or not.
+        first_hit_windows() makes the tuples of the first hit of every read from the read batch's results_flat().  Raises
+        RuntimeError with last_error() on a refusal, which leaves the batch as it was.  run() before the next results."""
+        pad, st, n = WindowBatch._units(pair_query, pair_start, pair_length, pair_strand)
+        if lib().edlibAmdBatchPairsSetSharedWindows(self._h, getattr(batch, "_h", None), pad[0].ctypes.data,
+                                                    pad[1].ctypes.data, pad[2].ctypes.data,
+                                                    None if st is None else st.ctypes.data, n) != 0:
+            raise RuntimeError("edlib_amd: set_shared_windows failed: " + last_error())
+        self.n = n
+
+
+def first_hit_windows(flat, read_lengths, strand=None):
+    """The tuples PairBatch.set_shared_windows takes for the first hit of every read of a HW read batch (numpy only):
+    flat is its results_flat(), read_lengths the length m of every read, strand the first array of strands() of a
+    both-strand batch (None: all forward).  Returns (read, start, length, strand): int32 / int32 / int32 / uint8 arrays
+    over the reads with editDistance d >= 0 and first end location e >= 0, in read order, with
+    start = max(0, e - m - d + 1) and length = e + 1 - start; strand is None where none was given.  Over that window
+    the HW path answer -- distance, first end, first start, alignment -- is the whole target's, shifted by start.
+    Left out: reads with nothing within k (editDistance -1), and reads whose first end location is the -1 of the padded
+    last block (the whole read matches the empty prefix at cost d = m: a streamed pair set has no empty window)."""
+    ed = np.asarray(flat["editDistance"], dtype=np.int64)
+    m = np.asarray(read_lengths, dtype=np.int64)
+    if len(m) != len(ed):
+        raise ValueError("read_lengths and the results differ in count")
+    loc = np.asarray(flat["locOff"], dtype=np.int64)
+    ends = np.asarray(flat["ends"], dtype=np.int64)
+    has = (ed >= 0) & (loc[1:] > loc[:-1])
+    e = np.full(len(ed), -1, dtype=np.int64)
+    e[has] = ends[loc[:-1][has]]
+    keep = has & (e >= 0)
+    read = np.flatnonzero(keep)
+    e, m, ed = e[read], m[read], ed[read]
+    start = np.maximum(0, e - m - ed + 1)
+    st = None if strand is None else np.ascontiguousarray(np.asarray(strand, dtype=np.uint8)[read])
+    return read.astype(np.int32), start.astype(np.int32), (e + 1 - start).astype(np.int32), st
 
 
 class CrossBatch(_Batch):

@@ -436,7 +436,40 @@ EDLIB_API int edlibAmdBatchPairsSetWindows(EdlibAmdBatch* pairs, EdlibAmdBatch* 
     return guarded(fn, 1, [&] {
                WindowSource src;
                if (windows->windows->gatherSource(fn, src)) return 1;
-               return pairs->impl.setWindows(src, pairQuery, pairStart, pairLength, pairStrand, numPairs);
+               return pairs->impl.setWindows(fn, src, pairQuery, pairStart, pairLength, pairStrand, numPairs);
+           }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+EDLIB_API int edlibAmdBatchPairsSetSharedWindows(EdlibAmdBatch* pairs, EdlibAmdBatch* reads, const int* pairQuery,
+                                                 const int* pairStart, const int* pairLength,
+                                                 const unsigned char* pairStrand, int numPairs) {
+    static const char* const fn = "edlibAmdBatchPairsSetSharedWindows";
+    if (!pairs || !reads) {                       // (both handles before either is read)
+        set_error("%s: %s%s%s", fn, pairs ? "" : "null pair batch", !pairs && !reads ? " and " : "",
+                  reads ? "" : "null read batch");
+        return EDLIB_STATUS_ERROR;
+    }
+    if (pairs->windows || pairs->cross || !pairs->impl.isPairs()) {
+        set_error("%s: not available on %s (only the pairs of a batch made by edlibAmdBatchCreatePairs can be replaced)", fn,
+                  kind_of(pairs));
+        return EDLIB_STATUS_ERROR;
+    }
+    if (reads->windows || reads->cross || reads->impl.isPairs()) {
+        set_error("%s: the pairs cannot be gathered from %s (only from a read batch: edlibAmdBatchCreateShared, "
+                  "...SharedBothStrands or ...SharedHits; a window batch has edlibAmdBatchPairsSetWindows)", fn, kind_of(reads));
+        return EDLIB_STATUS_ERROR;
+    }
+    if (pairs->impl.device() != reads->impl.device()) {
+        set_error("%s: the pair batch is on device %d and the read batch on device %d: the gather does not cross devices", fn,
+                  pairs->impl.device(), reads->impl.device());
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded(fn, 1, [&] {
+               // (gatherSource waits for the read batch's stream -- its Create uploads asynchronously -- and changes nothing
+               // a caller can observe; the tuples and the envelope are then judged before the pair batch changes)
+               WindowSource src;
+               if (reads->impl.gatherSource(fn, src)) return 1;
+               return pairs->impl.setWindows(fn, src, pairQuery, pairStart, pairLength, pairStrand, numPairs);
            }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 

@@ -179,8 +179,12 @@ public:
     int setPairs(const char* queries, const long long* qoff, const char* targets, const long long* toff, int n);
     // the same with the pairs named as (query, strand, window) tuples over a window batch and gathered from its resident
     // pools on the device (edlibAmdBatchPairsSetWindows; engine_flat.hip "pairs from a window batch")
-    int setWindows(const WindowSource& src, const int* pairQuery, const int* pairStart, const int* pairLength,
+    // (fn: the caller's name in the messages -- edlibAmdBatchPairsSetSharedWindows gathers from a read batch the same way)
+    int setWindows(const char* fn, const WindowSource& src, const int* pairQuery, const int* pairStart, const int* pairLength,
                    const unsigned char* pairStrand, int n);
+    // what a read batch (not a pair batch) lends to that gather: its query pool and its raw target, behind a wait for
+    // init's upload (engine_flat.hip "pairs from a window batch")
+    int gatherSource(const char* fn, WindowSource& out);
     bool isPairs() const { return pairsKind_; }
     int device() const { return device_; }
     bool isBothStrands() const { return strands_; }
@@ -457,6 +461,7 @@ private:
     int gatherFlat(const WindowSource& src, const int* pairQuery, const int* pairStart, const unsigned char* pairStrand,
                    const FlatPlan& plan);
     DevBuf<int> d_gatherTuples_;                             // setWindows: pairQuery [n], pairStart [n], pairStrand (bytes)
+    std::vector<long long> gatherQoff_;                      // gatherSource of a both-strand batch: the reads' n + 1 offsets
     DevBuf<long long> d_flatPrep_; DevBuf<uint8_t> d_flatPrepTmp_; DevBuf<int> d_flatCuts_;
     DevBuf<uint8_t> d_flatPrepOut_; PinBuf h_flatPrepOut_;   // presence [8] and word-steps [2] of the prepared set
     DevBuf<uint8_t> d_tabs_; PinBuf h_tabs_;                 // tlut, idToByte, eqtbl of a streamed set

@@ -471,10 +471,11 @@ int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& 
 // window batch's query offsets and target length and builds the offsets of the two pools by running sums; they go
 // through planFlat like any streamed set.  The pools are gathered on the device from the window batch's resident query
 // pool and 4-bit pack (pairs_gather.hip); the rest is setPairs'.  What is refused leaves the batch as it was.
-int Batch::setWindows(const WindowSource& src, const int* pairQuery, const int* pairStart, const int* pairLength,
-                      const unsigned char* pairStrand, int n)
+// edlibAmdBatchPairsSetSharedWindows ("Pairs from a read batch") is the same call over what a read batch lends
+// (gatherSource below: its query pool and its raw target); `fn` is the caller's name in the messages.
+int Batch::setWindows(const char* fn, const WindowSource& src, const int* pairQuery, const int* pairStart,
+                      const int* pairLength, const unsigned char* pairStrand, int n)
 {
-    static const char* const fn = "edlibAmdBatchPairsSetWindows";
     if (n < 0) { set_error("%s: numPairs must be >= 0 (got %d)", fn, n); return 1; }
     if (n > 0 && (!pairQuery || !pairStart || !pairLength)) {
         set_error("%s: pairQuery, pairStart and pairLength must not be NULL for %d pairs", fn, n);
@@ -489,7 +490,7 @@ int Batch::setWindows(const WindowSource& src, const int* pairQuery, const int* 
     for (int p = 0; p < n; ++p) {
         const int q = pairQuery[p], start = pairStart[p], len = pairLength[p];
         if (q < 0 || q >= src.numQueries) {
-            set_error("%s: pair %d names query %d, outside [0, numQueries = %d) of the window batch", fn, p, q, src.numQueries);
+            set_error("%s: pair %d names query %d, outside [0, numQueries = %d) of %s", fn, p, q, src.numQueries, src.what);
             return 1;
         }
         if (start < 0) { set_error("%s: pair %d has a negative pairStart (%d)", fn, p, start); return 1; }
@@ -521,7 +522,7 @@ int Batch::setWindows(const WindowSource& src, const int* pairQuery, const int* 
     noPairs_ = true;
     if (dropForStreamedSet(plan, qnew, tnew)) return 1;
     if (gatherFlat(src, pairQuery, pairStart, pairStrand, plan)) {
-        (void)hipStreamSynchronize(stream_);                         // nothing of this batch's reads the window batch behind the call
+        (void)hipStreamSynchronize(stream_);                         // nothing of this batch's reads the source batch behind the call
         return 1;
     }
     noPairs_ = false;
@@ -553,10 +554,44 @@ int Batch::gatherFlat(const WindowSource& src, const int* pairQuery, const int* 
     // are written by WindowBatch::prepareUnits and, at Create, by LaneEngine::packHostTargets (synchronous copies, then
     // packTargets' kernel) only, and both wait for the window batch's stream before they succeed (a Run and a view read
     // them and wait, too): nothing is in flight on them between the window batch's calls, so no event orders the two
-    // streams.  prepareFlat's wait below ends the reads before this call
-    // returns: the window batch may change or go afterwards.
+    // streams.  A read batch's pools are written by its init alone, and its gatherSource has waited for that upload.
+    // prepareFlat's wait below ends the reads before this call returns: the source batch may change or go afterwards.
     EDLIB_AMD_HIP(launch_pairs_gather(src, a, stream_));
     return streamFlatEnd(p);
+}
+
+// What a pair batch gathers its pairs from where the source is a read batch (edlibAmdBatchPairsSetSharedWindows, `fn` in
+// the messages): the query pool -- entry q, or 2 q + strand of a both-strand batch, whose mates init wrote -- and the raw
+// target.  d_qpool_, d_qoff_ and d_tpool_ of a read batch are written by init alone (synchronous copies, the one
+// asynchronous upload of d_in_ and, both strands, the memset and launch_strand_pool behind which init waits); a Run, a
+// view and a path only read them.  init ends without a wait on that upload, and the gather runs on another batch's
+// stream: the wait here orders the two.  The batch is not changed: the offsets of a both-strand batch's reads, which the
+// set is planned from, are a copy made at the first call.
+int Batch::gatherSource(const char* fn, WindowSource& out)
+{
+    if (!shared_ || pairsKind_) { set_error("%s: the pairs cannot be gathered from a pair batch", fn); return 1; }
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    const int numReads = strands_ ? n_ / 2 : n_;
+    if (strands_ && gatherQoff_.size() != (size_t)numReads + 1) {
+        gatherQoff_.resize((size_t)numReads + 1);
+        for (int i = 0; i < numReads; ++i) gatherQoff_[i] = qoff_[2 * (size_t)i] / 2;
+        gatherQoff_[numReads] = qoff_[n_] / 2;
+    }
+    out = WindowSource{};
+    out.what = "the read batch";
+    out.numQueries = numReads; out.targetLength = tlen(0);
+    out.h_qoff = strands_ ? gatherQoff_.data() : qoff_.data();
+    out.d_qpool = d_qpool_.p; out.qpoolBytes = d_qpool_.n; out.d_qoff = d_qoff_.p; out.stranded = strands_;
+    out.d_tbytes = d_tpool_.p; out.tbytesAlloc = d_tpool_.n;
+    // (the gather's dword loads: launch_pairs_gather refuses the rest)
+    if (!out.d_qpool || !out.d_qoff || !out.d_tbytes || (reinterpret_cast<uintptr_t>(out.d_qpool) & 3) ||
+        (reinterpret_cast<uintptr_t>(out.d_tbytes) & 3)) {
+        set_error("%s: the read batch's pools are not resident at a 4-byte boundary", fn);
+        return 1;
+    }
+    return 0;
 }
 
 int Batch::noResults(const char* who)

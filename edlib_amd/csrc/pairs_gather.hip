@@ -1,5 +1,6 @@
 // pairs_gather.hip -- the pools of a flat pair set gathered on the device from a window batch's resident query pool and
-// 4-bit target pack (edlibAmdBatchPairsSetWindows; DESIGN.md §4b "Pairs from a window batch").  Pure data movement: a
+// 4-bit target pack (edlibAmdBatchPairsSetWindows; DESIGN.md §4b "Pairs from a window batch"), or from a read batch's
+// query pool and raw target (edlibAmdBatchPairsSetSharedWindows; "Pairs from a read batch").  Pure data movement: a
 // thread owns 16 aligned destination bytes (pairs_gather_core.hpp) and a wave stores 1 KiB of consecutive bytes per
 // instruction.  A block first narrows the offsets to the pairs its 4 KiB touch -- every wave searches the same two
 // positions, 64 probes a step -- so that a thread's own binary search runs over a handful of pairs.
@@ -64,6 +65,37 @@ gather_targets_kernel(const long long* __restrict__ toff, int n, long long total
     store_run(tpool, d0, total, r);
 }
 
+// store_run with the run's two words named, not indexed: the run stays in registers (an indexed `r.w[j >> 3]` makes the
+// compiler keep every thread's run in LDS, 4 KiB a block, on the full-store path too)
+__device__ __forceinline__ void store_run_words(uint8_t* __restrict__ pool, long long d0, long long total, u64 w0, u64 w1)
+{
+    const long long left = total + 16 - d0;
+    if (left >= kRun) {
+        uint4 v;
+        v.x = (u32)w0; v.y = (u32)(w0 >> 32); v.z = (u32)w1; v.w = (u32)(w1 >> 32);
+        *reinterpret_cast<uint4*>(pool + d0) = v;
+    } else {
+        for (int j = 0; j < (int)left; ++j) pool[d0 + j] = (uint8_t)((j < 8 ? w0 : w1) >> (8 * (j & 7)));
+    }
+}
+
+// the same from a target that is resident as bytes (a read batch's target pool): no table, a run inside one pair is five
+// dwords funnel-shifted
+__global__ void __launch_bounds__(kBlockThreads)
+gather_targets_bytes_kernel(const long long* __restrict__ toff, int n, long long total, TargetBytesSource src,
+                            uint8_t* __restrict__ tpool)
+{
+    int lo, hi;
+    block_pairs(toff, n, total, lo, hi);                         // (every lane of every wave: before any of them leaves)
+    const long long d0 = ((long long)blockIdx.x * kBlockThreads + threadIdx.x) * kRun;
+    if (d0 >= total + 16) return;
+    Run r; r.w[0] = 0; r.w[1] = 0;
+    if (d0 < total) {
+        r = target_run_bytes(d0, total, find_pair(toff, lo, hi, d0), toff, src);
+    }
+    store_run_words(tpool, d0, total, r.w[0], r.w[1]);
+}
+
 __global__ void __launch_bounds__(kBlockThreads)
 gather_queries_kernel(const long long* __restrict__ qoff, int n, long long total, QuerySource src, uint8_t* __restrict__ qpool)
 {
@@ -88,17 +120,28 @@ hipError_t launch_pairs_gather(const WindowSource& w, const PairsGatherArgs& a, 
     if (a.numPairs < 1 || a.qbytes < 1 || a.tbytes < 1) return hipErrorInvalidValue;
     // the wide accesses: dwords of the sources, 128-bit stores into the pools
     if ((reinterpret_cast<uintptr_t>(w.d_qpool) & 3) || (reinterpret_cast<uintptr_t>(w.d_pack) & 3) ||
+        (reinterpret_cast<uintptr_t>(w.d_tbytes) & 3) ||
         (reinterpret_cast<uintptr_t>(a.qpool) & 15) || (reinterpret_cast<uintptr_t>(a.tpool) & 15)) return hipErrorInvalidValue;
+    // (the target: a pack or bytes, one of the two; every window lies inside what is allocated, whose dwords bound the loads)
+    if ((w.d_pack != nullptr) == (w.d_tbytes != nullptr)) return hipErrorInvalidValue;
+    if (w.d_tbytes && (long long)(w.tbytesAlloc / 4) * 4 < (long long)w.targetLength) return hipErrorInvalidValue;
     const auto blocks = [](long long bytes) { return (unsigned)((bytes + 16 + kBlockBytes - 1) / kBlockBytes); };
     if ((a.qbytes + 16 + kBlockBytes - 1) / kBlockBytes > 0x7fffffffLL || (a.tbytes + 16 + kBlockBytes - 1) / kBlockBytes > 0x7fffffffLL)
         return hipErrorInvalidValue;
 
-    TargetSource ts{};
-    ts.pack = w.d_pack; ts.ndw = w.packDwords; ts.pairStart = a.pairStart;
-    IdToByte ids;
-    for (int i = 0; i < 16; ++i) ids.b[i] = w.idToByte[i];
-    hipLaunchKernelGGL(gather_targets_kernel, dim3(blocks(a.tbytes)), dim3(kBlockThreads), 0, stream,
-                       a.toff, a.numPairs, a.tbytes, ts, ids, a.tpool);
+    if (w.d_tbytes) {
+        TargetBytesSource tb{};
+        tb.bytes = reinterpret_cast<const u32*>(w.d_tbytes); tb.ndw = (long long)(w.tbytesAlloc / 4); tb.pairStart = a.pairStart;
+        hipLaunchKernelGGL(gather_targets_bytes_kernel, dim3(blocks(a.tbytes)), dim3(kBlockThreads), 0, stream,
+                           a.toff, a.numPairs, a.tbytes, tb, a.tpool);
+    } else {
+        TargetSource ts{};
+        ts.pack = w.d_pack; ts.ndw = w.packDwords; ts.pairStart = a.pairStart;
+        IdToByte ids;
+        for (int i = 0; i < 16; ++i) ids.b[i] = w.idToByte[i];
+        hipLaunchKernelGGL(gather_targets_kernel, dim3(blocks(a.tbytes)), dim3(kBlockThreads), 0, stream,
+                           a.toff, a.numPairs, a.tbytes, ts, ids, a.tpool);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
 

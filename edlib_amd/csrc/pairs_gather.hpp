@@ -7,7 +7,8 @@
 namespace edlib_amd {
 
 // What a window batch lends to the gather: device pointers that stay valid, and unwritten, while the window batch is not
-// given new units or destroyed; and the host's copy of what the set is planned from.
+// given new units or destroyed; and the host's copy of what the set is planned from.  A read batch (Batch::gatherSource)
+// lends the same with its raw target in place of the pack; its pointers hold until it is destroyed.
 struct WindowSource {
     int numQueries = 0, targetLength = 0;
     const long long* h_qoff = nullptr;            // host: [numQueries + 1] offsets of the queries as the caller gave them, from any base
@@ -16,6 +17,10 @@ struct WindowSource {
     bool stranded = false;
     const uint32_t* d_pack = nullptr; long long packDwords = 0;    // the target, 4-bit codes, 8 columns per dword from dword 0
     uint8_t idToByte[16] = {};                    // code -> byte
+    // ... or, in place of the pack, the target as its bytes (a read batch: edlibAmdBatchPairsSetSharedWindows): 4-byte
+    // aligned, tbytesAlloc bytes allocated (>= targetLength)
+    const uint8_t* d_tbytes = nullptr; size_t tbytesAlloc = 0;
+    const char* what = "the window batch";        // the source in a refusal
 };
 
 struct PairsGatherArgs {

@@ -14,6 +14,8 @@
 //     it funnel-shifted by the byte phase (bytes8).  Strand 1 of a pair reads the reverse-complement entry of a stranded
 //     pool as it is; from a plain pool it reads the same bytes from the far end, byte-swapped and complemented through a
 //     256-entry table (revcomp8).
+//   target pool from a read batch (edlibAmdBatchPairsSetSharedWindows, "Pairs from a read batch"): the source is the raw
+//     target.  Sixteen bytes at any byte position are five dwords funnel-shifted (bytes16); at a pair boundary, bytes8.
 //
 // This header compiles for the device (pairs_gather.hip) AND for the host (tests/pairs_gather_host.cpp: the same code, the
 // runs walked one by one, checked against numpy slicing: tests/test_pairs_gather_model.py).
@@ -183,6 +185,50 @@ PG_FN Run query_run(long long d0, long long total, int p, const long long* qoff,
             else e = revcomp8(bytes8(src.pool, src.ndw, from + (next - first) - a - cnt), cnt, comp);
             put(r, (int)(pos - d0), e, cnt);
             pos += cnt;
+        }
+        ++p;
+    }
+    return r;
+}
+
+// ---- a target that is resident as its raw bytes (edlibAmdBatchPairsSetSharedWindows: the target pool of a read batch)
+
+// The source of the target pool where the target is bytes: the pool as dwords (ndw of them: what is allocated, reads
+// behind them are zero) and per pair the first column of its window
+struct TargetBytesSource {
+    const u32* bytes; long long ndw;
+    const int* pairStart;
+};
+
+// the sixteen bytes from byte position s on: the five dwords around them funnel-shifted by the byte phase (two bytes8
+// would load six)
+PG_FN Run bytes16(const u32* pool, long long ndw, long long s)
+{
+    const long long i = s >> 2;
+    const int sh = 8 * (int)(s & 3);
+    const u32 d0 = dword_at(pool, ndw, i), d1 = dword_at(pool, ndw, i + 1), d2 = dword_at(pool, ndw, i + 2),
+              d3 = dword_at(pool, ndw, i + 3), d4 = dword_at(pool, ndw, i + 4);
+    Run r;
+    r.w[0] = (u64)funnel(d0, d1, sh) | (u64)funnel(d1, d2, sh) << 32;
+    r.w[1] = (u64)funnel(d2, d3, sh) | (u64)funnel(d3, d4, sh) << 32;
+    return r;
+}
+
+// The run [d0, d0 + 16) of the target pool from a byte target; total = toff[n], p = the pair of byte d0 (d0 < total).  A
+// run inside one pair is one bytes16; a run that meets a pair boundary (or the pool's end) is composed of bytes8 pieces
+PG_FN Run target_run_bytes(long long d0, long long total, int p, const long long* toff, const TargetBytesSource& src)
+{
+    if (toff[p + 1] >= d0 + kRun) return bytes16(src.bytes, src.ndw, (long long)src.pairStart[p] + (d0 - toff[p]));
+    Run r; r.w[0] = 0; r.w[1] = 0;
+    const long long end = d0 + kRun < total ? d0 + kRun : total;
+    long long pos = d0;
+    while (pos < end) {
+        const long long first = toff[p], next = toff[p + 1], stop = next < end ? next : end;
+        long long s = (long long)src.pairStart[p] + (pos - first);
+        while (pos < stop) {
+            const int cnt = stop - pos < 8 ? (int)(stop - pos) : 8;
+            put(r, (int)(pos - d0), bytes8(src.bytes, src.ndw, s), cnt);
+            pos += cnt; s += cnt;
         }
         ++p;
     }

@@ -599,6 +599,35 @@ EDLIB_API int edlibAmdBatchPairsSetWindows(EdlibAmdBatch* pairs, EdlibAmdBatch* 
     const int* pairQuery, const int* pairStart, const int* pairLength,
     const unsigned char* pairStrand /* NULL: all forward */, int numPairs);
 
+/* The same from a READ batch (start locations and CIGARs for the reads a distance Run mapped, without the windows or the
+ * reverse complements being made on the host): the query of pair i is read pairQuery[i] of `reads` -- its
+ * edlibAmdReverseComplement where pairStrand[i] == 1 -- and its target is target[pairStart[i] .. pairStart[i] +
+ * pairLength[i]) of the target of `reads`.  Afterwards `pairs` is exactly the batch edlibAmdBatchPairsSetPairs would have
+ * made over these pairs materialised: everything that call keeps and resets this one keeps and resets, and Run, Results,
+ * ResultsFlat, ResultsView, CigarView and Stats follow as there.  Returns 0, or non-zero with edlibAmdLastError().
+ * The tuples are the caller's own: the first hit of a read, any other end location, a run of a hit-list batch, a padded
+ * window.  For a read of m bases with HW distance d and first end location e >= 0, the window
+ * [max(0, e - m - d + 1), e] gives the first start, the first end and the alignment of the whole-target HW / PATH answer,
+ * shifted by the window's start (DESIGN.md 4b "Pairs from a read batch").
+ * The bytes are copied: when the call returns `pairs` depends on nothing in `reads`, which may be run or destroyed.
+ * `reads` is not changed in any way a caller can observe.
+ * `pairs` is a batch of edlibAmdBatchCreatePairs in any state SetPairs accepts.  `reads` is a batch of
+ * edlibAmdBatchCreateShared, ...SharedBothStrands or ...SharedHits in any state after Create (any number of Runs, none
+ * included), with reads of any length and route, over any alphabet and mode: the source is the raw bytes of its target and
+ * its query pool, so the 16-symbol limit of SetWindows does not apply.  Strand 1 of a both-strand batch reads the reverse
+ * complement the batch made at Create; from the other two kinds it is reversed and complemented on the fly.
+ * Refused, with this function and the reason named: a NULL handle; another kind of batch on either side (for `reads`: a
+ * pair batch and a cross, self, occurrence or window batch); batches on different devices; numPairs < 0; a NULL
+ * pairQuery, pairStart or pairLength with a positive count (a NULL pairStrand is all forward).  Per pair, the first
+ * offender named with its values: pairQuery outside [0, numQueries) of `reads`, a negative pairStart or pairLength,
+ * pairStart + pairLength > targetLength, pairStrand > 1.  Then the flat envelope of SetPairs with its messages: an empty
+ * query or window, a query above 1,024 bases, a window above 65,536, and under EDLIB_TASK_PATH the limits named there.
+ * numPairs == 0 is valid.  Every refusal is decided on the host from the lengths alone and leaves `pairs` as it was.
+ * Behind that point only a device error can fail the call; it leaves `pairs` without pairs, as a failed SetPairs does. */
+EDLIB_API int edlibAmdBatchPairsSetSharedWindows(EdlibAmdBatch* pairs, EdlibAmdBatch* reads,
+    const int* pairQuery, const int* pairStart, const int* pairLength,
+    const unsigned char* pairStrand /* NULL: all forward */, int numPairs);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
