@@ -151,7 +151,7 @@ struct UnitResult {
 };
 
 struct Lap;                        // (below)
-struct ViewLayout;                 // engine_flat.hip
+struct ViewLayout; struct ViewVar; // engine_flat.hip
 
 // The host's one pass over the offsets of a pair set (engine_flat.hip: planFlat): whether the set lies inside the flat
 // envelope -- if not, the first pair outside it and why -- and the reductions its layout needs.  No sequence byte is read.
@@ -159,7 +159,7 @@ struct FlatPlan {
     enum Why { kOk = 0, kBadQueryOffsets, kBadTargetOffsets, kEmptyQuery, kEmptyTarget, kLongQuery, kLongTarget, kPathBlocks,
                kHirschberg, kStoreCap, kOpsCap };
     Why why = kOk; int who = -1;                  // the first offending pair
-    int n = 0, maxBlocks = 0, maxT = 0, maxWords = 0;
+    int n = 0, maxBlocks = 0, maxWords = 0;
     long long qbytes = 0, tbytes = 0, cells = 0, lens = 0, totalBlocks = 0;
     long long opBytes = 0, store4 = 0, store32 = 0;   // PATH: op slots; entries of the 4-lane ring stores, of the ring32 stores
     long long chunkMax32 = 0;                         // ... and of the largest chunk of the ring32 NW store
@@ -438,66 +438,89 @@ private:
     int prepareLaneLevel(const std::vector<UnitSpec>& units);
     int runLaneLevel(const std::vector<UnitSpec>& units, double rate, int kcap, int W);
     std::vector<OpsOut> fusedOps_;
-    // ---- flat pair path (TASK_DISTANCE, every unit a pair of at most 16 blocks): descriptors built once and resident, a
-    // run is Peq build + ONE ring scan + an overflow census, results stay in HBM until results() (like the reads path)
-    bool flatPairs_ = false, pairsCollected_ = true, lastRunFlat_ = false;
-    int flatRing_ = 0;
-    long long flatWordSteps_ = 0;               // word-steps inside the bands of one run over the flat descriptors
-    DevBuf<PairDesc> d_flatDescs_;
-    DevBuf<int> d_flatOut3_, d_flatPos_, d_flatCensus_;
-    PinBuf h_flatCensus_;
-    std::vector<int> flatOvfUnit_; std::vector<long long> flatOvfOff_; std::vector<int> flatOvfPos_;   // exact lists of the last run's overflowing units
-    FlatShape flatShape() const;
-    void planFlat(const long long* qoff, const long long* toff, int n, bool sharedTarget, FlatPlan& plan,
-                  std::vector<long long>* qout, std::vector<long long>* tout) const;
-    int prepareFlat(const FlatPlan& plan, bool census);      // the set's layout, made on the device: Create and setPairs
-    // a streamed set (setPairs, setWindows): the refusal of a plan that failed; what the batch drops before the set
-    // changes; the device's share in two halves with the filling of the pools between them
-    void refuseFlat(const char* fn, const FlatPlan& plan, long long m, long long T) const;
-    int dropForStreamedSet(const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew);
-    int streamFlatBegin(const FlatPlan& plan);
-    int streamFlatEnd(const FlatPlan& plan);
-    int streamFlat(const char* queries, const char* targets, const FlatPlan& plan);
-    int gatherFlat(const WindowSource& src, const int* pairQuery, const int* pairStart, const unsigned char* pairStrand,
-                   const FlatPlan& plan);
-    DevBuf<int> d_gatherTuples_;                             // setWindows: pairQuery [n], pairStart [n], pairStrand (bytes)
-    std::vector<long long> gatherQoff_;                      // gatherSource of a both-strand batch: the reads' n + 1 offsets
-    DevBuf<long long> d_flatPrep_; DevBuf<uint8_t> d_flatPrepTmp_; DevBuf<int> d_flatCuts_;
-    DevBuf<uint8_t> d_flatPrepOut_; PinBuf h_flatPrepOut_;   // presence [8] and word-steps [2] of the prepared set
-    DevBuf<uint8_t> d_tabs_; PinBuf h_tabs_;                 // tlut, idToByte, eqtbl of a streamed set
-    int initFlatPairs();
-    int runPairsFlat(bool& fellBack);
+    // ---- flat pair path (every unit a pair of at most 16 blocks): descriptors built once and resident, a run is Peq
+    // build + ONE ring scan + an overflow census, results stay in HBM until results() (like the reads path).
     // flat LOC / PATH (round 4): start locations and paths of a flat batch are found and kept on the device as well.
     // HW starts: one reverse prefix scan per end location, descriptors written by a kernel from the phase-1 results;
     // paths: one storing scan per unit over its window + the traceback into resident op slots.  What the fixed layouts
     // cannot hold (more than 16 end locations, a band level that fails) makes the run fall back to the general path.
-    bool flatStarts_ = false, flatPaths_ = false, flatNwStore_ = false;
-    int flatMaxBlocks_ = 0;
-    size_t flatStartCap_ = 0;
-    long long flatRevPeqBase_ = 0, flatOpsTotal_ = 0;
+    bool flatPairs_ = false, pairsCollected_ = true, lastRunFlat_ = false;
+    // What prepareFlat decided about the resident set, on the host; a default-constructed value is "no flat set"
+    struct FlatSet {
+        int scanMode = EDLIB_MODE_NW;           // of the config (flatScanMode)
+        int ring = 0;                           // lanes of the phase-1 ring
+        bool ring32 = false;                    // storing scans and walks on rings of 32-row words (ring32_kernels.hip)
+        int maxBlocks = 0, maxWords = 0;
+        bool starts = false, paths = false, nwStore = false;
+        std::vector<int> chunkStart;            // ring32 NW store: unit ranges whose store fits 32-bit offsets (one range = the usual case)
+        long long wordSteps = 0;                // word-steps inside the bands of one run over the flat descriptors
+        long long revPeqBase = 0, opsTotal = 0;
+        size_t startCap = 0;
+    } flat_;
+    // exact lists of the last run's overflowing units (the lists themselves, and d_flatOvfAt_ / d_flatOvfOff_, are on the
+    // device: the collection reads them there while `unit` is not empty)
+    struct FlatOverflow {
+        std::vector<int> unit; std::vector<long long> off{0};
+        void clear() { unit.clear(); off.assign(1, 0); }
+    } flatOvf_;
+    void dropFlatSet() { flatPairs_ = false; flat_ = FlatSet{}; flatOvf_.clear(); }
+    int flatG32_ = 8;                          // lanes of the rings of 32-row words
+    // the config's mode as the kernels number it (NW, SHW or HW); -1: it has no flat form
+    int flatScanMode() const {
+        const int mode = (int)cfg_.mode;
+        return (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : (mode == EDLIB_MODE_NW ? mode : -1);
+    }
+    FlatShape flatShape() const;
+    DevBuf<PairDesc> d_flatDescs_;
+    DevBuf<int> d_flatOut3_, d_flatPos_, d_flatCensus_;
+    PinBuf h_flatCensus_;
+    int flatCensus() const { return *reinterpret_cast<const int*>(h_flatCensus_.p); }   // behind the wait that follows enqueueFlatCensus
+    DevBuf<int> d_flatOvfAt_, d_flatOvfPool_; DevBuf<long long> d_flatOvfOff_;
     DevBuf<PairDesc> d_flatRevDescs_, d_flatStartDescs_, d_flatPathDescs_;
     DevBuf<int> d_flatSlotOf_, d_flatStartOut3_, d_flatStartsOut_, d_flatPathOut3_, d_flatOpsLen_;
     DevBuf<long long> d_flatOpsOff_, d_flatStoreBase_;
-    DevBuf<uint8_t> d_flatOps_;
-    int runFlatStartsAndPaths(bool& fellBack);
+    DevBuf<uint8_t> d_flatOps_, d_tsym_;
+    void planFlat(const long long* qoff, const long long* toff, int n, bool sharedTarget, FlatPlan& plan,
+                  std::vector<long long>* qout, std::vector<long long>* tout) const;
+    int initFlatPairs();
+    int prepareFlat(const FlatPlan& plan, bool census);      // the set's layout, made on the device: Create and a streamed set
+    DevBuf<long long> d_flatPrep_; DevBuf<uint8_t> d_flatPrepTmp_; DevBuf<int> d_flatCuts_;
+    struct FlatPrepOut { uint32_t presence[8]; unsigned long long steps[2]; };      // what prepareFlat brings back
+    DevBuf<FlatPrepOut> d_flatPrepOut_; PinBuf h_flatPrepOut_;
+    // a streamed set (setPairs, setWindows) takes the place of the batch's (replaceFlatSet): the refusal of a plan that
+    // failed, what the batch drops before the set changes, the device's share with `fill` -- the pairs' bytes into the two
+    // pools, on the stream -- in its middle
+    enum { kSetRefused = 1, kSetLost = 2 };                  // replaceFlatSet: the batch is as it was; it has no pairs
+    int replaceFlatSet(const char* fn, const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew,
+                       const std::function<int()>& fill);
+    void refuseFlat(const char* fn, const FlatPlan& plan, long long m, long long T) const;
+    int dropForStreamedSet(const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew);
+    int loadFlatSet(const FlatPlan& plan, const std::function<int()>& fill);
+    DevBuf<int> d_gatherTuples_;                             // setWindows: pairQuery [n], pairStart [n], pairStrand (bytes)
+    std::vector<long long> gatherQoff_;                      // gatherSource of a both-strand batch: the reads' n + 1 offsets
+    DevBuf<uint8_t> d_tabs_; PinBuf h_tabs_;                 // tlut, idToByte, eqtbl of a streamed set
+    // a Run (runPairsFlat) and its phases; every scan takes its arguments from flatScanArgs
+    int runPairsFlat(bool& fellBack);
+    PairScanArgs flatScanArgs(const PairDesc* descs, int count, int* out3, size_t out3Stride) const;
+    int flatStoreAndWalk(const PairDesc* descs, int* out3, int u0, int count);
+    template <class Count> int enqueueFlatCensus(Count count);
+    int runFlatNwPaths(bool& fellBack);
+    int runFlatOverflowPass(const PairScanArgs& phase1);
+    int runFlatStarts(bool& fellBack);
+    int runFlatPaths();
     int collectPairsFlat(std::vector<UnitResult>& res);
     bool readsViewOnDevice() const;               // a DISTANCE run over read groups only: its view is made by flat_results.hip
     int buildReadsView();
-    // rings of 32-row words for the storing scans and walks of a flat PATH batch (ring32_kernels.hip)
-    bool flatRing32_ = false; int flatG32_ = 8, flatMaxWords_ = 0;
     bool deferReadsReset_ = false;                // this run blanks the recycled records of reads-path units where it fills them (collectGroup)
     bool deferReset_ = false;                     // ... and of pair units where it fills them (runPairPhase)
-    std::vector<int> flatChunkStart_;             // ring32 NW store: unit ranges whose store fits 32-bit offsets (one range = the usual case)
-    DevBuf<uint8_t> d_tsym_;
     // the caller-facing arrays of the last run: made on the device for a flat batch (buildFlatView), from the records otherwise
     DevBuf<uint8_t> d_view_; PinBuf h_view_, h_viewVar_; bool viewReady_ = false;     // host: per-unit fields + offsets / locations + op bytes
     EdlibAmdResultsView view_{};
     const uint8_t* viewAlnDev_ = nullptr; const long long* viewAlnOffDev_ = nullptr;     // the dense op bytes on the device (CIGARs)
     std::vector<int> viewInts_; std::vector<long long> viewOffs_; std::vector<uint8_t> viewOps_;   // host-made view of a general batch
-    DevBuf<int> d_flatOvfAt_, d_flatOvfPool_; DevBuf<long long> d_flatOvfOff_;
     int buildFlatView();
     int buildHostView();
-    int fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln, const char* who, long long& nloc, long long& naln);
+    int fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln, const char* who, ViewVar& var);
     // CIGAR strings of the last run (edlibAlignmentToCigar, edlib.cpp:303-350, over the batch): [0] extended, [1] standard
     struct CigarOut { bool ready = false; PinBuf chars, offs; std::vector<char> hostChars; std::vector<long long> hostOffs; const char* p = nullptr; const long long* off = nullptr; };
     CigarOut cigar_[2];

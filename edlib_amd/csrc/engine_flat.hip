@@ -114,10 +114,9 @@ flat_path_descs_kernel(const PairDesc* __restrict__ descs, const int* __restrict
 // and the results stay in HBM until results() asks for them -- the lazy form the reads path has had since round 1.
 FlatShape Batch::flatShape() const
 {
-    const int mode = (int)cfg_.mode;
     FlatShape s{};
-    s.scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
-    s.k = cfg_.k; s.ring = flatRing_; s.g32 = flatG32_; s.nwStore = flatNwStore_ ? 1 : 0; s.ring32 = flatRing32_ ? 1 : 0;
+    s.scanMode = flat_.scanMode; s.k = cfg_.k; s.ring = flat_.ring; s.g32 = flatG32_;
+    s.nwStore = flat_.nwStore ? 1 : 0; s.ring32 = flat_.ring32 ? 1 : 0;
     return s;
 }
 
@@ -128,8 +127,7 @@ FlatShape Batch::flatShape() const
 void Batch::planFlat(const long long* qoff, const long long* toff, int n, bool sharedTarget, FlatPlan& p,
                      std::vector<long long>* qout, std::vector<long long>* tout) const
 {
-    const int mode = (int)cfg_.mode;
-    const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
+    const int scanMode = flatScanMode();
     const bool paths = cfg_.task == EDLIB_TASK_PATH, nwStore = paths && scanMode == EDLIB_MODE_NW;
     const long long chunkCap = 0xE0000000LL / 8;                      // 8-byte entries a ring32 launch can address
     p = FlatPlan{};
@@ -150,7 +148,7 @@ void Batch::planFlat(const long long* qoff, const long long* toff, int n, bool s
         // (long targets: the general path cuts HW targets into segments when the batch alone does not fill the chip)
         if (tl > kFlatMaxTarget) { p.why = FlatPlan::kLongTarget; return; }
         const int m = (int)ml, T = (int)tl, w = flat_window(scanMode, m, T), blocks = (m + 63) / 64;
-        p.maxBlocks = std::max(p.maxBlocks, blocks); p.maxT = std::max(p.maxT, T); p.maxWords = std::max(p.maxWords, (m + 31) / 32);
+        p.maxBlocks = std::max(p.maxBlocks, blocks); p.maxWords = std::max(p.maxWords, (m + 31) / 32);
         p.totalBlocks += blocks; p.cells += (long long)m * T; p.lens += m + T;
         if (!paths) continue;
         // paths stay flat when every unit's store fits a 4-lane ring: SHW / HW queries of at most 4 blocks (whole matrix of
@@ -180,14 +178,11 @@ void Batch::planFlat(const long long* qoff, const long long* toff, int n, bool s
 
 int Batch::initFlatPairs()
 {
-    flatPairs_ = false;
-    flatStarts_ = flatPaths_ = flatNwStore_ = flatRing32_ = false;
-    flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0);
+    dropFlatSet();
     if (!emptyUnits_.empty() || !groups_.empty() || !longUnits_.empty()) return 0;
     if (strands_) return 0;                                         // both strands resolve from the general path's records
     if ((int)pairUnits_.size() != n_ || n_ < 1024) return 0;       // (a handful of units: the zero-copy path of solveChunk)
-    const int mode = (int)cfg_.mode;
-    if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) return 0;
+    if (flatScanMode() < 0) return 0;
     FlatPlan plan;
     planFlat(qoff_.data(), toff_.data(), n_, shared_, plan, nullptr, nullptr);
     if (plan.why != FlatPlan::kOk) return 0;
@@ -199,104 +194,98 @@ int Batch::initFlatPairs()
 // are init()'s.  Every buffer grows only.
 int Batch::prepareFlat(const FlatPlan& p, bool census)
 {
-    const int mode = (int)cfg_.mode;
-    const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
     const size_t n = (size_t)p.n;
-    flatPairs_ = false;
-    flatPaths_ = cfg_.task == EDLIB_TASK_PATH;
-    flatNwStore_ = flatPaths_ && scanMode == EDLIB_MODE_NW;
-    flatStarts_ = cfg_.task != EDLIB_TASK_DISTANCE && mode == EDLIB_MODE_HW;
-    flatMaxBlocks_ = p.maxBlocks; flatMaxWords_ = p.maxWords;
-    // (the smallest ring that holds every query whole; storing scans: 4 lanes)
-    flatRing_ = (flatPaths_ || p.maxBlocks <= 4) ? 4 : (p.maxBlocks <= 8 ? 8 : 16);
-    flatRing32_ = false;                                            // (decided below, with the alphabet)
-    flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0); flatOvfPos_.clear();
-    flatChunkStart_ = p.cuts;
-    if (flatChunkStart_.size() < 2) { flatChunkStart_.assign(1, 0); flatChunkStart_.push_back(p.n); }
+    dropFlatSet();
+    FlatSet& f = flat_;
+    f.scanMode = flatScanMode();
+    f.paths = cfg_.task == EDLIB_TASK_PATH;
+    f.nwStore = f.paths && f.scanMode == EDLIB_MODE_NW;
+    f.starts = cfg_.task != EDLIB_TASK_DISTANCE && f.scanMode == EDLIB_MODE_HW;
+    f.maxBlocks = p.maxBlocks; f.maxWords = p.maxWords;
+    // (the smallest ring that holds every query whole; storing scans: 4 lanes.  ring32 is decided below, with the alphabet)
+    f.ring = (f.paths || p.maxBlocks <= 4) ? 4 : (p.maxBlocks <= 8 ? 8 : 16);
+    f.chunkStart = p.cuts;
+    if (f.chunkStart.size() < 2) { f.chunkStart.assign(1, 0); f.chunkStart.push_back(p.n); }
 
     EDLIB_AMD_HIP(d_flatDescs_.ensure(n));
     EDLIB_AMD_HIP(d_flatOut3_.ensure(3 * n));
-    EDLIB_AMD_HIP(d_flatPos_.ensure(scanMode == EDLIB_MODE_NW ? 1 : n * kFlatPosCap));
+    EDLIB_AMD_HIP(d_flatPos_.ensure(f.scanMode == EDLIB_MODE_NW ? 1 : n * kFlatPosCap));
     EDLIB_AMD_HIP(d_flatCensus_.ensure(2));
     if (!h_flatCensus_.p) EDLIB_AMD_HIP(h_flatCensus_.alloc(2 * sizeof(int)));
-    if (flatStarts_) {
+    if (f.starts) {
         EDLIB_AMD_HIP(d_flatRevDescs_.ensure(n));
-        flatStartCap_ = 2 * n + 1024;
-        EDLIB_AMD_HIP(d_flatStartDescs_.ensure(flatStartCap_));
-        EDLIB_AMD_HIP(d_flatStartOut3_.ensure(3 * flatStartCap_));
+        f.startCap = 2 * n + 1024;
+        EDLIB_AMD_HIP(d_flatStartDescs_.ensure(f.startCap));
+        EDLIB_AMD_HIP(d_flatStartOut3_.ensure(3 * f.startCap));
         EDLIB_AMD_HIP(d_flatSlotOf_.ensure(n * kFlatPosCap));
         EDLIB_AMD_HIP(d_flatStartsOut_.ensure(n * kFlatPosCap));
     }
-    if (flatPaths_) {
+    if (f.paths) {
         // op slots (m + window + 8 bytes per unit, filled from the back) and store ranges: upper bounds that depend on the
         // set only, laid out once
-        flatOpsTotal_ = p.opBytes;
+        f.opsTotal = p.opBytes;
         EDLIB_AMD_HIP(d_flatOpsOff_.ensure(n + 1)); EDLIB_AMD_HIP(d_flatStoreBase_.ensure(n));
-        EDLIB_AMD_HIP(d_flatOps_.ensure((size_t)flatOpsTotal_)); EDLIB_AMD_HIP(d_flatOpsLen_.ensure(n));
-        if (!flatNwStore_) { EDLIB_AMD_HIP(d_flatPathDescs_.ensure(n)); EDLIB_AMD_HIP(d_flatPathOut3_.ensure(3 * n)); }
+        EDLIB_AMD_HIP(d_flatOps_.ensure((size_t)f.opsTotal)); EDLIB_AMD_HIP(d_flatOpsLen_.ensure(n));
+        if (!f.nwStore) { EDLIB_AMD_HIP(d_flatPathDescs_.ensure(n)); EDLIB_AMD_HIP(d_flatPathOut3_.ensure(3 * n)); }
     }
     size_t tmpBytes = 0;
     EDLIB_AMD_HIP(flat_prepare_tmp_bytes(p.n, &tmpBytes));
     EDLIB_AMD_HIP(d_flatPrepTmp_.ensure(tmpBytes + 16));
     EDLIB_AMD_HIP(d_flatPrep_.ensure(5 * (n + 1)));
-    EDLIB_AMD_HIP(d_flatCuts_.ensure(flatChunkStart_.size()));
-    const size_t outBytes = 8 * sizeof(uint32_t) + 2 * sizeof(unsigned long long);
-    if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(outBytes));
-    if (!h_flatPrepOut_.p) EDLIB_AMD_HIP(h_flatPrepOut_.alloc(outBytes));
+    EDLIB_AMD_HIP(d_flatCuts_.ensure(f.chunkStart.size()));
+    if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(1));
+    if (!h_flatPrepOut_.p) EDLIB_AMD_HIP(h_flatPrepOut_.alloc(sizeof(FlatPrepOut)));
     // (the cut points are a member: the copy may still be on its way when this function returns on an error)
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_flatCuts_.p, flatChunkStart_.data(), flatChunkStart_.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_flatCuts_.p, f.chunkStart.data(), f.chunkStart.size() * sizeof(int), hipMemcpyHostToDevice, stream_));
 
     FlatPrepareArgs a{};
-    a.n = p.n; a.shape = flatShape(); a.paths = flatPaths_ ? 1 : 0; a.starts = flatStarts_ ? 1 : 0;
+    a.n = p.n; a.shape = flatShape(); a.paths = f.paths ? 1 : 0; a.starts = f.starts ? 1 : 0;
     a.maxWords = p.maxWords; a.store32Bytes = 8 * p.store32;
     a.tpool = census ? d_tpool_.p : nullptr; a.tbytes = p.tbytes;
     a.qoff = d_qoff_.p; a.toff = d_toff_.p; a.sharedTarget = shared_ ? 1 : 0;
-    a.presence = census ? reinterpret_cast<uint32_t*>(d_flatPrepOut_.p) : d_presence_.p;
-    a.cuts = d_flatCuts_.p; a.ncuts = (int)flatChunkStart_.size();
+    a.presence = census ? d_flatPrepOut_.p->presence : d_presence_.p;
+    a.cuts = d_flatCuts_.p; a.ncuts = (int)f.chunkStart.size();
     a.sizes = d_flatPrep_.p; a.peqOff = d_flatPrep_.p + 3 * (n + 1); a.storeCum = d_flatPrep_.p + 4 * (n + 1);
     a.opsOff = d_flatOpsOff_.p; a.storeBase = d_flatStoreBase_.p;
     a.descs = d_flatDescs_.p; a.revDescs = d_flatRevDescs_.p;
     a.iota = census ? d_alphaIdx_.p : nullptr;
-    a.steps = reinterpret_cast<unsigned long long*>(d_flatPrepOut_.p + 8 * sizeof(uint32_t));
+    a.steps = d_flatPrepOut_.p->steps;
     a.tmp = d_flatPrepTmp_.p; a.tmpBytes = tmpBytes;
     EDLIB_AMD_HIP(launch_flat_prepare(a, stream_));
-    EDLIB_AMD_HIP(hipMemcpyAsync(h_flatPrepOut_.p, d_flatPrepOut_.p, outBytes, hipMemcpyDeviceToHost, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(h_flatPrepOut_.p, d_flatPrepOut_.p, sizeof(FlatPrepOut), hipMemcpyDeviceToHost, stream_));
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));                // the call's one wait: the caller's memory is free behind it
+    const FlatPrepOut& out = *reinterpret_cast<const FlatPrepOut*>(h_flatPrepOut_.p);
 
     if (census) {
         // the tables of the set, over the bytes the census found, in ascending order (nothing a pair batch reports depends
-        // on symbol ids); they follow on the stream from a pinned block of the batch's own
-        const uint32_t* pres = reinterpret_cast<const uint32_t*>(h_flatPrepOut_.p);
+        // on symbol ids); they follow on the stream from a pinned block of the batch's own, into the block loadFlatSet
+        // made the batch's tables views of
         uint8_t present[256]; int count = 0;
-        for (int b = 0; b < 256; ++b) if ((pres[b >> 5] >> (b & 31)) & 1u) present[count++] = (uint8_t)b;
+        for (int b = 0; b < 256; ++b) if ((out.presence[b >> 5] >> (b & 31)) & 1u) present[count++] = (uint8_t)b;
         build_tables(tab_, present, count, eqs_.data(), (int)eqs_.size());
-        if (!d_tabs_.p) EDLIB_AMD_HIP(d_tabs_.alloc(1024));
         if (!h_tabs_.p) EDLIB_AMD_HIP(h_tabs_.alloc(1024));
         memcpy(h_tabs_.p, tab_.tlut, 256); memcpy(h_tabs_.p + 256, tab_.idToByte, 256); memcpy(h_tabs_.p + 512, tab_.eqtbl, 512);
         EDLIB_AMD_HIP(hipMemcpyAsync(d_tabs_.p, h_tabs_.p, 1024, hipMemcpyHostToDevice, stream_));
-        d_tlut_.alias(d_tabs_.p, 256); d_idToByte_.alias(d_tabs_.p + 256, 256); d_eqtbl_.alias(d_tabs_.p + 512, 256);
-        d_presence_.alias(d_flatPrepOut_.p, 8);
         syms_ = peq_syms(tab_.sigmaT);
     }
     // Storing scans and walks on rings of 32-row words (ring32_kernels.hip) whenever the set allows it (flat_uses_ring32: the
     // kernels decided the same from the same census).  SHW / HW paths: queries of at most 4 blocks = 8 words, whole on an
     // 8-lane ring.
-    flatRing32_ = flat_uses_ring32(flatPaths_, flatNwStore_, 8 * p.store32, flatG32_, tab_.sigmaT, p.maxWords);
-    const bool chunked32 = flatRing32_ && flatNwStore_;
-    if (!chunked32) { flatChunkStart_.assign(1, 0); flatChunkStart_.push_back(p.n); }
+    f.ring32 = flat_uses_ring32(f.paths, f.nwStore, 8 * p.store32, flatG32_, tab_.sigmaT, p.maxWords);
+    const bool chunked32 = f.ring32 && f.nwStore;
+    if (!chunked32) { f.chunkStart.assign(1, 0); f.chunkStart.push_back(p.n); }
     const long long peqWords = p.totalBlocks * tab_.sigmaT;
     // reversed-query Peq rows (same layout as the forward ones, behind them)
-    flatRevPeqBase_ = peqWords;
-    EDLIB_AMD_HIP(d_peq64_.ensure((size_t)(flatStarts_ ? 2 * peqWords : peqWords)));
-    if (flatPaths_) {
-        const long long entries = chunked32 ? p.chunkMax32 : (flatRing32_ ? p.store32 : p.store4);
-        EDLIB_AMD_HIP(d_store_.ensure(flatRing32_ ? (size_t)(entries + 1) / 2 : (size_t)entries));      // (ring32: 8-byte entries)
-        if (flatRing32_) EDLIB_AMD_HIP(d_tsym_.ensure(d_tpool_.n));
+    f.revPeqBase = peqWords;
+    EDLIB_AMD_HIP(d_peq64_.ensure((size_t)(f.starts ? 2 * peqWords : peqWords)));
+    if (f.paths) {
+        const long long entries = chunked32 ? p.chunkMax32 : (f.ring32 ? p.store32 : p.store4);
+        EDLIB_AMD_HIP(d_store_.ensure(f.ring32 ? (size_t)(entries + 1) / 2 : (size_t)entries));      // (ring32: 8-byte entries)
+        if (f.ring32) EDLIB_AMD_HIP(d_tsym_.ensure(d_tpool_.n));
     }
     // the word-steps of a run over the resident descriptors never change (phase 1 of a ring32 NW batch runs on the rings of
     // 32-row words)
-    const unsigned long long* steps = reinterpret_cast<const unsigned long long*>(h_flatPrepOut_.p + 8 * sizeof(uint32_t));
-    flatWordSteps_ = (long long)steps[chunked32 ? 1 : 0];
+    f.wordSteps = (long long)out.steps[chunked32 ? 1 : 0];
     ringStepsUsed_ = false;
     flatPairs_ = true;
     return 0;
@@ -304,6 +293,8 @@ int Batch::prepareFlat(const FlatPlan& p, bool census)
 
 
 // ------------------------------------------------------------ streamed pairs
+
+static const char* const kNoFlatForm = "%s: the batch's config.mode (%d) has no flat form: create a new batch";
 
 // edlibAmdBatchPairsSetPairs: another pair set through a resident pair batch (DESIGN.md §4b "Streamed pairs").  A streamed
 // set is a flat set of any count; the host walks the two offset arrays once and reads no sequence byte, everything
@@ -316,27 +307,37 @@ int Batch::setPairs(const char* queries, const long long* qoff, const char* targ
         set_error("%s: queries, queryOffsets, targets and targetOffsets must not be NULL for %d pairs", fn, n);
         return 1;
     }
-    const int mode = (int)cfg_.mode;
-    if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) {
-        set_error("%s: the batch's config.mode (%d) has no flat form: create a new batch", fn, mode);
-        return 1;
-    }
+    if (flatScanMode() < 0) { set_error(kNoFlatForm, fn, (int)cfg_.mode); return 1; }
     FlatPlan plan;
     std::vector<long long> qnew, tnew;
     planFlat(qoff, toff, n, false, plan, &qnew, &tnew);
+    // the pools go up as they are, 16 zero bytes behind each
+    return replaceFlatSet(fn, plan, qnew, tnew, [&]() -> int {
+        if (plan.qbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_qpool_.p, queries + qoff[0], (size_t)plan.qbytes, hipMemcpyHostToDevice, stream_));
+        if (plan.tbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_tpool_.p, targets + toff[0], (size_t)plan.tbytes, hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p + plan.qbytes, 0, 16, stream_));
+        EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p + plan.tbytes, 0, 16, stream_));
+        return 0;
+    }) ? 1 : 0;
+}
+
+// A streamed set takes the place of the batch's: `plan` is planFlat's over the set's offsets, qnew / tnew their rebased
+// copies, `fill` puts the bytes of its (one or more) pairs into the two pools on the stream (loadFlatSet).  kSetRefused: the
+// first pair outside the flat envelope is named and the batch is as it was; kSetLost: an error on the device, which leaves
+// the batch without pairs.
+int Batch::replaceFlatSet(const char* fn, const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew,
+                          const std::function<int()>& fill)
+{
     if (plan.why != FlatPlan::kOk) {
-        const int u = plan.who;
-        refuseFlat(fn, plan, qoff[u + 1] - qoff[u], toff[u + 1] - toff[u]);
-        return 1;
+        const size_t u = (size_t)plan.who;
+        refuseFlat(fn, plan, qnew[u + 1] - qnew[u], tnew[u + 1] - tnew[u]);
+        return kSetRefused;
     }
     pool_quarantine(false);
     DeviceGuard guard(device_);
-    EDLIB_AMD_HIP(guard.status);
-
-    // ---- from here a device error leaves the batch without pairs
+    EDLIB_AMD_HIP(guard.status);                                     // (1: kSetRefused)
     noPairs_ = true;
-    if (dropForStreamedSet(plan, qnew, tnew)) return 1;
-    if (streamFlat(queries + (n > 0 ? qoff[0] : 0), targets + (n > 0 ? toff[0] : 0), plan)) return 1;
+    if (dropForStreamedSet(plan, qnew, tnew) || loadFlatSet(plan, fill)) return kSetLost;
     noPairs_ = false;
     return 0;
 }
@@ -414,54 +415,40 @@ int Batch::dropForStreamedSet(const FlatPlan& plan, std::vector<long long>& qnew
     return 0;
 }
 
-// the device's share of a streamed set, first half: the pools sized, the offsets on their way up
-int Batch::streamFlatBegin(const FlatPlan& p)
+// The device's share of a streamed set: the pools sized and the offsets on their way up; `fill`; behind the pools, the
+// rest is prepareFlat.
+int Batch::loadFlatSet(const FlatPlan& p, const std::function<int()>& fill)
 {
     const size_t n = (size_t)p.n;
     // (pools and offsets that were views into init()'s one block become buffers of their own; the block goes)
     EDLIB_AMD_HIP(d_qpool_.resize((size_t)p.qbytes + 16)); EDLIB_AMD_HIP(d_tpool_.resize((size_t)p.tbytes + 16));
     EDLIB_AMD_HIP(d_qoff_.resize(n + 1)); EDLIB_AMD_HIP(d_toff_.resize(n + 1));
+    // (the tables of a streamed set are views, too: into the block prepareFlat's census fills, and into its output)
     if (!d_tabs_.p) EDLIB_AMD_HIP(d_tabs_.alloc(1024));
-    if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(8 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)));
+    if (!d_flatPrepOut_.p) EDLIB_AMD_HIP(d_flatPrepOut_.alloc(1));
     d_tlut_.alias(d_tabs_.p, 256); d_idToByte_.alias(d_tabs_.p + 256, 256); d_eqtbl_.alias(d_tabs_.p + 512, 256);
-    d_presence_.alias(d_flatPrepOut_.p, 8);
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_qoff_.p, qoff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
-    EDLIB_AMD_HIP(hipMemcpyAsync(d_toff_.p, toff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
-    return 0;
-}
-
-// ... second half, behind the pools: the rest is prepareFlat
-int Batch::streamFlatEnd(const FlatPlan& p)
-{
-    const size_t n = (size_t)p.n;
+    d_presence_.alias(d_flatPrepOut_.p->presence, 8);
     // alphabetLength is counted per unit as before: its unit list (0, 1, ...) is written with the layout
     EDLIB_AMD_HIP(d_alphaIdx_.ensure(n)); EDLIB_AMD_HIP(d_alphaOut_.ensure(n));
     if (alphaPin_.n < n * sizeof(int) || !alphaPin_.p) EDLIB_AMD_HIP(alphaPin_.alloc(n * sizeof(int)));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_qoff_.p, qoff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
+    EDLIB_AMD_HIP(hipMemcpyAsync(d_toff_.p, toff_.data(), (n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream_));
     if (p.n == 0) {
-        // no pairs: nothing to lay out; Run and the views are those of a batch created over zero pairs
+        // no pairs: 16 zero bytes behind each (empty) pool and nothing to lay out; Run and the views are those of a batch
+        // created over zero pairs
+        EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p, 0, 16, stream_));
+        EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p, 0, 16, stream_));
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
         d_in_.release(); h_in_.release();
         build_tables(tab_, nullptr, 0, eqs_.data(), (int)eqs_.size());
-        flatStarts_ = flatPaths_ = flatNwStore_ = flatRing32_ = false;
-        flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0); flatOvfPos_.clear();
+        dropFlatSet();
         return 0;
     }
-    if (prepareFlat(p, true)) return 1;
+    if (fill() || prepareFlat(p, true)) return 1;
     d_in_.release(); h_in_.release();                            // (behind the wait: init()'s upload came from it)
     // algorithmic bytes of a Run whose results stay on the device (startStats): a constant of the set
     algoBase_ = p.lens + 8LL * (tab_.sigmaT + 1) * p.totalBlocks + 20LL * p.n;
     return 0;
-}
-
-// setPairs: the pools go up as they are
-int Batch::streamFlat(const char* queries, const char* targets, const FlatPlan& p)
-{
-    if (streamFlatBegin(p)) return 1;
-    if (p.qbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_qpool_.p, queries, (size_t)p.qbytes, hipMemcpyHostToDevice, stream_));
-    if (p.tbytes) EDLIB_AMD_HIP(hipMemcpyAsync(d_tpool_.p, targets, (size_t)p.tbytes, hipMemcpyHostToDevice, stream_));
-    EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p + p.qbytes, 0, 16, stream_));
-    EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p + p.tbytes, 0, 16, stream_));
-    return streamFlatEnd(p);
 }
 
 // ------------------------------------------------------------ pairs from a window batch
@@ -481,11 +468,7 @@ int Batch::setWindows(const char* fn, const WindowSource& src, const int* pairQu
         set_error("%s: pairQuery, pairStart and pairLength must not be NULL for %d pairs", fn, n);
         return 1;
     }
-    const int mode = (int)cfg_.mode;
-    if (mode != EDLIB_MODE_NW && mode != EDLIB_MODE_SHW && mode != EDLIB_MODE_HW) {
-        set_error("%s: the batch's config.mode (%d) has no flat form: create a new batch", fn, mode);
-        return 1;
-    }
+    if (flatScanMode() < 0) { set_error(kNoFlatForm, fn, (int)cfg_.mode); return 1; }
     std::vector<long long> qnew((size_t)n + 1, 0), tnew((size_t)n + 1, 0);
     for (int p = 0; p < n; ++p) {
         const int q = pairQuery[p], start = pairStart[p], len = pairLength[p];
@@ -509,55 +492,30 @@ int Batch::setWindows(const char* fn, const WindowSource& src, const int* pairQu
     }
     FlatPlan plan;
     planFlat(qnew.data(), tnew.data(), n, false, plan, nullptr, nullptr);
-    if (plan.why != FlatPlan::kOk) {
-        const int u = plan.who;
-        refuseFlat(fn, plan, qnew[(size_t)u + 1] - qnew[u], tnew[(size_t)u + 1] - tnew[u]);
-        return 1;
-    }
-    pool_quarantine(false);
-    DeviceGuard guard(device_);
-    EDLIB_AMD_HIP(guard.status);
-
-    // ---- from here a device error leaves the batch without pairs
-    noPairs_ = true;
-    if (dropForStreamedSet(plan, qnew, tnew)) return 1;
-    if (gatherFlat(src, pairQuery, pairStart, pairStrand, plan)) {
-        (void)hipStreamSynchronize(stream_);                         // nothing of this batch's reads the source batch behind the call
-        return 1;
-    }
-    noPairs_ = false;
-    return 0;
-}
-
-// the device's share of setWindows: the offsets and the tuples go up, the pools are gathered
-int Batch::gatherFlat(const WindowSource& src, const int* pairQuery, const int* pairStart, const unsigned char* pairStrand,
-                      const FlatPlan& p)
-{
-    if (streamFlatBegin(p)) return 1;
-    if (p.n == 0) {
-        EDLIB_AMD_HIP(hipMemsetAsync(d_qpool_.p, 0, 16, stream_));
-        EDLIB_AMD_HIP(hipMemsetAsync(d_tpool_.p, 0, 16, stream_));
-        return streamFlatEnd(p);
-    }
-    const size_t n = (size_t)p.n;
-    EDLIB_AMD_HIP(d_gatherTuples_.ensure(2 * n + (n + 3) / 4));
-    int* const dq = d_gatherTuples_.p; int* const ds = dq + n;
-    uint8_t* const dst = reinterpret_cast<uint8_t*>(ds + n);
-    EDLIB_AMD_HIP(hipMemcpyAsync(dq, pairQuery, n * sizeof(int), hipMemcpyHostToDevice, stream_));
-    EDLIB_AMD_HIP(hipMemcpyAsync(ds, pairStart, n * sizeof(int), hipMemcpyHostToDevice, stream_));
-    if (pairStrand) EDLIB_AMD_HIP(hipMemcpyAsync(dst, pairStrand, n, hipMemcpyHostToDevice, stream_));
-    PairsGatherArgs a{};
-    a.numPairs = p.n; a.qoff = d_qoff_.p; a.toff = d_toff_.p; a.qbytes = p.qbytes; a.tbytes = p.tbytes;
-    a.pairQuery = dq; a.pairStart = ds; a.pairStrand = pairStrand ? dst : nullptr;
-    a.qpool = d_qpool_.p; a.tpool = d_tpool_.p;
-    // The gather reads the window batch's query pool, its offsets and the target pack from THIS batch's stream.  They
-    // are written by WindowBatch::prepareUnits and, at Create, by LaneEngine::packHostTargets (synchronous copies, then
-    // packTargets' kernel) only, and both wait for the window batch's stream before they succeed (a Run and a view read
-    // them and wait, too): nothing is in flight on them between the window batch's calls, so no event orders the two
-    // streams.  A read batch's pools are written by its init alone, and its gatherSource has waited for that upload.
-    // prepareFlat's wait below ends the reads before this call returns: the source batch may change or go afterwards.
-    EDLIB_AMD_HIP(launch_pairs_gather(src, a, stream_));
-    return streamFlatEnd(p);
+    // the tuples go up, the pools are gathered
+    const int failed = replaceFlatSet(fn, plan, qnew, tnew, [&]() -> int {
+        const size_t np = (size_t)n;
+        EDLIB_AMD_HIP(d_gatherTuples_.ensure(2 * np + (np + 3) / 4));
+        int* const dq = d_gatherTuples_.p; int* const ds = dq + np;
+        uint8_t* const dst = reinterpret_cast<uint8_t*>(ds + np);
+        EDLIB_AMD_HIP(hipMemcpyAsync(dq, pairQuery, np * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(ds, pairStart, np * sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (pairStrand) EDLIB_AMD_HIP(hipMemcpyAsync(dst, pairStrand, np, hipMemcpyHostToDevice, stream_));
+        PairsGatherArgs a{};
+        a.numPairs = n; a.qoff = d_qoff_.p; a.toff = d_toff_.p; a.qbytes = plan.qbytes; a.tbytes = plan.tbytes;
+        a.pairQuery = dq; a.pairStart = ds; a.pairStrand = pairStrand ? dst : nullptr;
+        a.qpool = d_qpool_.p; a.tpool = d_tpool_.p;
+        // The gather reads the window batch's query pool, its offsets and the target pack from THIS batch's stream.  They
+        // are written by WindowBatch::prepareUnits and, at Create, by LaneEngine::packHostTargets (synchronous copies, then
+        // packTargets' kernel) only, and both wait for the window batch's stream before they succeed (a Run and a view read
+        // them and wait, too): nothing is in flight on them between the window batch's calls, so no event orders the two
+        // streams.  A read batch's pools are written by its init alone, and its gatherSource has waited for that upload.
+        // prepareFlat's wait (loadFlatSet) ends the reads before this call returns: the source batch may change or go afterwards.
+        EDLIB_AMD_HIP(launch_pairs_gather(src, a, stream_));
+        return 0;
+    });
+    if (failed == kSetLost) (void)hipStreamSynchronize(stream_);     // nothing of this batch's reads the source batch behind the call
+    return failed ? 1 : 0;
 }
 
 // What a pair batch gathers its pairs from where the source is a read batch (edlibAmdBatchPairsSetSharedWindows, `fn` in
@@ -601,170 +559,174 @@ int Batch::noResults(const char* who)
     return 1;
 }
 
-int Batch::runPairsFlat(bool& fellBack)
+// ------------------------------------------------------------ a Run of a flat set
+
+// What every flat scan shares -- the resident pools, tables and Peq rows, the end-location lists, the targets as symbol
+// ids (ring32 scans) -- for `count` descriptors whose scores, counts and last columns go to out3, out3Stride apart
+PairScanArgs Batch::flatScanArgs(const PairDesc* descs, int count, int* out3, size_t out3Stride) const
 {
-    fellBack = false;
-    const int mode = (int)cfg_.mode;
-    const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
-    stats.path |= 2;
-    EDLIB_AMD_HIP(uploadEq8());
-    EDLIB_AMD_HIP(launch_build_peq_pairs(d_flatDescs_.p, n_, d_qpool_.p, d_eq8_.p, d_idToByte_.p, tab_.sigmaT, d_peq64_.p, stream_));
     PairScanArgs a{};
-    a.descs = d_flatDescs_.p; a.numUnits = n_; a.qpool = d_qpool_.p; a.tpool = d_tpool_.p;
-    a.tlut = d_tlut_.p; a.sigmaT = tab_.sigmaT; a.peq = d_peq64_.p; a.aux = nullptr;
-    a.peqRowStride = peq_row_stride(std::max(flatRing_, flatMaxBlocks_));
+    a.descs = descs; a.numUnits = count; a.qpool = d_qpool_.p; a.tpool = d_tpool_.p;
+    a.tlut = d_tlut_.p; a.sigmaT = tab_.sigmaT; a.peq = d_peq64_.p;
+    a.peqRowStride = peq_row_stride(std::max(flat_.ring, flat_.maxBlocks));
     a.peqFullStride = (int)std::min<long long>((long long)a.peqRowStride * tab_.sigmaT, 1 << 20);
-    a.store = flatNwStore_ ? d_store_.p : nullptr;
-    a.outScore = d_flatOut3_.p; a.outCount = d_flatOut3_.p + n_; a.outLast = d_flatOut3_.p + 2 * (size_t)n_; a.posPool = d_flatPos_.p;
-    a.wordSteps = nullptr;
-    stats.word_steps += flatWordSteps_;
-    const bool ring32 = flatRing32_ && flatNwStore_;
-    if (flatRing32_) {                                   // the targets as symbol ids, once per run (the refills of the ring32 scans read them)
-        EDLIB_AMD_HIP(launch_target_symbols(d_tpool_.p, d_tlut_.p, (long long)d_tpool_.n, d_tsym_.p, stream_));
-        a.tsym = d_tsym_.p;
-    }
-    const bool chunked = ring32 && flatChunkStart_.size() > 2;
-    if (!chunked) {
-        scanTimerStart();
-        if (ring32) EDLIB_AMD_HIP(launch_scan_pairs_ring32(flatG32_, true, a, flatMaxWords_, stream_));
-        else EDLIB_AMD_HIP(launch_scan_pairs_ring(flatRing_, scanMode, flatNwStore_, a, stream_));
-        scanTimerStop();
-    }
-    if (flatNwStore_) {
-        // NW paths: the distance scan was the storing scan (one band level); walk it, and see whether every unit got its answer
-        TracebackArgs tb{};
-        tb.descs = d_flatDescs_.p; tb.numUnits = n_; tb.score = d_flatOut3_.p; tb.store = d_store_.p;
-        tb.ops = d_flatOps_.p; tb.opsOff = d_flatOpsOff_.p; tb.opsLen = d_flatOpsLen_.p;
-        if (chunked) {
-            // a store beyond the 32-bit offsets of the ring32 kernels: chunk by chunk, each scanned and walked before the next
-            // reuses the store (store offsets are relative to the chunk: initFlatPairs)
-            for (size_t c = 0; c + 1 < flatChunkStart_.size(); ++c) {
-                const int u0 = flatChunkStart_[c], nu = flatChunkStart_[c + 1] - u0;
-                PairScanArgs ac = a;
-                ac.descs = a.descs + u0; ac.numUnits = nu;
-                ac.outScore = a.outScore + u0; ac.outCount = a.outCount + u0; ac.outLast = a.outLast + u0;
-                scanTimerStart();
-                EDLIB_AMD_HIP(launch_scan_pairs_ring32(flatG32_, true, ac, flatMaxWords_, stream_));
-                scanTimerStop();
-                TracebackArgs tc = tb;
-                tc.descs = tb.descs + u0; tc.numUnits = nu; tc.score = tb.score + u0; tc.opsOff = tb.opsOff + u0; tc.opsLen = tb.opsLen + u0;
-                EDLIB_AMD_HIP(launch_traceback32(tc, flatG32_, stream_));
-            }
-        } else
-        if (ring32) EDLIB_AMD_HIP(launch_traceback32(tb, flatG32_, stream_));
-        else EDLIB_AMD_HIP(launch_traceback(tb, stream_));
-        EDLIB_AMD_HIP(hipMemsetAsync(d_flatCensus_.p, 0, 2 * sizeof(int), stream_));
-        hipLaunchKernelGGL(count_failed_levels_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatDescs_.p, d_flatOut3_.p, n_,
-                           cfg_.k >= 0 ? cfg_.k : 0x3fffffff, d_flatCensus_.p);
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_flatCensus_.p, d_flatCensus_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        if (*reinterpret_cast<const int*>(h_flatCensus_.p) > 0) { fellBack = true; return 0; }     // some unit needs the next level: the general path has them
-        return 0;
-    }
-    if (scanMode != EDLIB_MODE_NW) {
-        EDLIB_AMD_HIP(hipMemsetAsync(d_flatCensus_.p, 0, sizeof(int), stream_));
-        hipLaunchKernelGGL(count_over_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatOut3_.p + n_, n_, kFlatPosCap, d_flatCensus_.p);
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_flatCensus_.p, d_flatCensus_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        const int novf = *reinterpret_cast<const int*>(h_flatCensus_.p);
-        flatOvfUnit_.clear(); flatOvfOff_.assign(1, 0); flatOvfPos_.clear();
-        if (novf > 0) {
-            // exact second pass for the (rare) units with more end locations than a list keeps: their best score is already
-            // exact, so a scan with threshold = best and a list of the right size finds every location (strip kernel)
-            const size_t n = (size_t)n_;
-            PinBuf sc; EDLIB_AMD_HIP(sc.alloc(2 * n * sizeof(int)));
-            EDLIB_AMD_HIP(hipMemcpyAsync(sc.p, d_flatOut3_.p, 2 * n * sizeof(int), hipMemcpyDeviceToHost, stream_));
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-            const int* score = reinterpret_cast<const int*>(sc.p); const int* count = score + n;
-            std::vector<PairDesc> d2;
-            const FlatShape shape = flatShape();
-            long long peqOff = 0;                                    // (the scan of flat_pairs_prepare.hip, recomputed on the way)
-            for (int u = 0; u < n_; peqOff += (long long)((qlen(u) + 63) / 64) * tab_.sigmaT, ++u)
-                if (count[u] > kFlatPosCap) {
-                    PairDesc x = flat_desc(shape, u, qoff_[u], qlen(u), tbase(u), tlen(u), peqOff);
-                    x.kinit = score[u]; x.posCap = count[u]; x.posOff = flatOvfOff_.back(); x.ring = 0;
-                    d2.push_back(x); flatOvfUnit_.push_back(u); flatOvfOff_.push_back(flatOvfOff_.back() + count[u]);
-                }
-            DevBuf<PairDesc> dd; DevBuf<int> s2;
-            DevBuf<int>& pool2 = d_flatOvfPool_;                     // (the lists stay on the device: the collection reads them there)
-            EDLIB_AMD_HIP(dd.alloc(d2.size())); EDLIB_AMD_HIP(pool2.ensure((size_t)flatOvfOff_.back())); EDLIB_AMD_HIP(s2.alloc(3 * d2.size()));
-            EDLIB_AMD_HIP(hipMemcpyAsync(dd.p, d2.data(), d2.size() * sizeof(PairDesc), hipMemcpyHostToDevice, stream_));
-            PairScanArgs a2 = a;
-            a2.descs = dd.p; a2.numUnits = (int)d2.size(); a2.posPool = pool2.p;
-            a2.outScore = s2.p; a2.outCount = s2.p + d2.size(); a2.outLast = s2.p + 2 * d2.size();
-            scanTimerStart();
-            EDLIB_AMD_HIP(launch_scan_pairs(scanMode, false, a2, stream_));
-            scanTimerStop();
-            // which list belongs to which unit, for the device-side collection
-            {
-                std::vector<int> at((size_t)n_, -1);
-                for (size_t j = 0; j < flatOvfUnit_.size(); ++j) at[(size_t)flatOvfUnit_[j]] = (int)j;
-                EDLIB_AMD_HIP(d_flatOvfAt_.ensure((size_t)n_)); EDLIB_AMD_HIP(d_flatOvfOff_.ensure(flatOvfOff_.size()));
-                EDLIB_AMD_HIP(hipMemcpyAsync(d_flatOvfAt_.p, at.data(), (size_t)n_ * sizeof(int), hipMemcpyHostToDevice, stream_));
-                EDLIB_AMD_HIP(hipMemcpyAsync(d_flatOvfOff_.p, flatOvfOff_.data(), flatOvfOff_.size() * sizeof(long long), hipMemcpyHostToDevice, stream_));
-            }
-            EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-            stats.overflow_units += (int)d2.size();
-            for (const PairDesc& x : d2) stats.word_steps += 2LL * ((x.qlen + 63) / 64) * x.tlen;
-        }
-    }
-    if (flatStarts_ || flatPaths_) return runFlatStartsAndPaths(fellBack);
+    a.outScore = out3; a.outCount = out3 + out3Stride; a.outLast = out3 + 2 * out3Stride; a.posPool = d_flatPos_.p;
+    a.tsym = flat_.ring32 ? d_tsym_.p : nullptr;
+    return a;
+}
+
+// The storing NW scan of units [u0, u0 + count) of descs (results in out3, n_ apart) and its walk into their resident op
+// slots, on rings of 32-row words or on the ring of 64-row blocks.  The store and the op bytes are addressed by what the
+// descriptors and opsOff hold: they take no offset.
+int Batch::flatStoreAndWalk(const PairDesc* descs, int* out3, int u0, int count)
+{
+    PairScanArgs a = flatScanArgs(descs + u0, count, out3 + u0, (size_t)n_);
+    a.store = d_store_.p;
+    scanTimerStart();
+    if (flat_.ring32) EDLIB_AMD_HIP(launch_scan_pairs_ring32(flatG32_, true, a, flat_.maxWords, stream_));
+    else EDLIB_AMD_HIP(launch_scan_pairs_ring(flat_.ring, EDLIB_MODE_NW, true, a, stream_));
+    scanTimerStop();
+    TracebackArgs tb{};
+    tb.descs = descs + u0; tb.numUnits = count; tb.score = out3 + u0; tb.store = d_store_.p;
+    tb.ops = d_flatOps_.p; tb.opsOff = d_flatOpsOff_.p + u0; tb.opsLen = d_flatOpsLen_.p + u0;
+    if (flat_.ring32) EDLIB_AMD_HIP(launch_traceback32(tb, flatG32_, stream_));
+    else EDLIB_AMD_HIP(launch_traceback(tb, stream_));
     return 0;
 }
 
-// Phases 2 and 3 of a flat SHW / HW batch (reference edlib.cpp:228-289), everything on the device: descriptors of the
-// reverse prefix scans written by a kernel from the phase-1 results (HW), one ring scan over them, the starts; then one
-// storing NW scan per unit over its first location's window + the traceback into the resident op slots.
-int Batch::runFlatStartsAndPaths(bool& fellBack)
+// One count made on the device: the counter zeroed, count(counter) launches the kernel that adds to it, the value on its
+// way to pinned memory.  Enqueued only: it is flatCensus() behind the caller's wait for the stream.
+template <class Count>
+int Batch::enqueueFlatCensus(Count count)
 {
-    const int mode = (int)cfg_.mode;
-    const int* score = d_flatOut3_.p; const int* count = d_flatOut3_.p + n_;
-    PairScanArgs a{};
-    a.qpool = d_qpool_.p; a.tpool = d_tpool_.p; a.tlut = d_tlut_.p; a.sigmaT = tab_.sigmaT; a.peq = d_peq64_.p; a.aux = nullptr;
-    a.peqRowStride = peq_row_stride(std::max(flatRing_, flatMaxBlocks_));
-    a.peqFullStride = (int)std::min<long long>((long long)a.peqRowStride * tab_.sigmaT, 1 << 20);
-    a.posPool = d_flatPos_.p; a.wordSteps = nullptr;
-    if (flatStarts_) {
-        EDLIB_AMD_HIP(hipMemsetAsync(d_flatCensus_.p, 0, 2 * sizeof(int), stream_));
-        hipLaunchKernelGGL(flat_start_descs_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatDescs_.p, score, count, d_flatPos_.p,
-                           n_, kFlatPosCap, flatRevPeqBase_, flatRing_, d_flatStartDescs_.p, d_flatSlotOf_.p, d_flatCensus_.p, (int)flatStartCap_);
-        EDLIB_AMD_HIP(hipMemcpyAsync(h_flatCensus_.p, d_flatCensus_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
-        // (the reversed queries' Peq rows do not depend on the count: built while it travels)
-        EDLIB_AMD_HIP(launch_build_peq_pairs(d_flatRevDescs_.p, n_, d_qpool_.p, d_eq8_.p, d_idToByte_.p, tab_.sigmaT, d_peq64_.p, stream_));
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        const int nscan = *reinterpret_cast<const int*>(h_flatCensus_.p);
-        if ((size_t)nscan > flatStartCap_) { fellBack = true; return 0; }
-        if (nscan > 0) {
-            PairScanArgs b = a;
-            b.descs = d_flatStartDescs_.p; b.numUnits = nscan; b.store = nullptr;
-            b.outScore = d_flatStartOut3_.p; b.outCount = d_flatStartOut3_.p + flatStartCap_; b.outLast = d_flatStartOut3_.p + 2 * flatStartCap_;
-            scanTimerStart();
-            EDLIB_AMD_HIP(launch_scan_pairs_ring(flatRing_, EDLIB_MODE_SHW, false, b, stream_));
-            scanTimerStop();
-        }
-        const long long total = (long long)n_ * kFlatPosCap;
-        hipLaunchKernelGGL(flat_starts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream_, d_flatSlotOf_.p, d_flatPos_.p,
-                           d_flatStartOut3_.p + 2 * flatStartCap_, total, d_flatStartsOut_.p);
-        EDLIB_AMD_HIP(hipGetLastError());
-    }
-    if (flatPaths_ && !flatNwStore_) {
-        hipLaunchKernelGGL(flat_path_descs_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatDescs_.p, score, count, d_flatPos_.p,
-                           mode == EDLIB_MODE_HW ? d_flatStartsOut_.p : nullptr, n_, kFlatPosCap, d_flatStoreBase_.p, flatRing_, d_flatPathDescs_.p);
-        PairScanArgs b = a;
-        b.descs = d_flatPathDescs_.p; b.numUnits = n_; b.store = d_store_.p;
-        b.outScore = d_flatPathOut3_.p; b.outCount = d_flatPathOut3_.p + n_; b.outLast = d_flatPathOut3_.p + 2 * (size_t)n_;
-        b.tsym = flatRing32_ ? d_tsym_.p : nullptr;
-        scanTimerStart();
-        if (flatRing32_) EDLIB_AMD_HIP(launch_scan_pairs_ring32(flatG32_, true, b, flatMaxWords_, stream_));
-        else EDLIB_AMD_HIP(launch_scan_pairs_ring(flatRing_, EDLIB_MODE_NW, true, b, stream_));
-        scanTimerStop();
-        TracebackArgs tb{};
-        tb.descs = d_flatPathDescs_.p; tb.numUnits = n_; tb.score = d_flatPathOut3_.p; tb.store = d_store_.p;
-        tb.ops = d_flatOps_.p; tb.opsOff = d_flatOpsOff_.p; tb.opsLen = d_flatOpsLen_.p;
-        if (flatRing32_) EDLIB_AMD_HIP(launch_traceback32(tb, flatG32_, stream_));
-        else EDLIB_AMD_HIP(launch_traceback(tb, stream_));
-    }
+    EDLIB_AMD_HIP(hipMemsetAsync(d_flatCensus_.p, 0, sizeof(int), stream_));
+    count(d_flatCensus_.p);
+    EDLIB_AMD_HIP(hipMemcpyAsync(h_flatCensus_.p, d_flatCensus_.p, sizeof(int), hipMemcpyDeviceToHost, stream_));
     return 0;
+}
+
+// Peq rows, the phase-1 scan, what the mode and the task add to it (reference edlib.cpp:146-301 for a batch whose every
+// phase stays on the device).  fellBack: the fixed layouts do not hold this run's answer, the general path takes it.
+int Batch::runPairsFlat(bool& fellBack)
+{
+    fellBack = false;
+    stats.path |= 2;
+    stats.word_steps += flat_.wordSteps;
+    EDLIB_AMD_HIP(uploadEq8());
+    EDLIB_AMD_HIP(launch_build_peq_pairs(d_flatDescs_.p, n_, d_qpool_.p, d_eq8_.p, d_idToByte_.p, tab_.sigmaT, d_peq64_.p, stream_));
+    // the targets as symbol ids, once per run (the refills of the ring32 scans read them)
+    if (flat_.ring32) EDLIB_AMD_HIP(launch_target_symbols(d_tpool_.p, d_tlut_.p, (long long)d_tpool_.n, d_tsym_.p, stream_));
+    if (flat_.nwStore) return runFlatNwPaths(fellBack);       // (the phase-1 scan IS the storing scan)
+    const PairScanArgs a = flatScanArgs(d_flatDescs_.p, n_, d_flatOut3_.p, (size_t)n_);
+    scanTimerStart();
+    EDLIB_AMD_HIP(launch_scan_pairs_ring(flat_.ring, flat_.scanMode, false, a, stream_));
+    scanTimerStop();
+    if (flat_.scanMode != EDLIB_MODE_NW && runFlatOverflowPass(a)) return 1;
+    if (flat_.starts && runFlatStarts(fellBack)) return 1;
+    if (flat_.paths && !fellBack && runFlatPaths()) return 1;
+    return 0;
+}
+
+// NW paths: one band level with the column store, walked; then, whether every unit got its answer from it.  A store beyond
+// the 32-bit offsets of the ring32 kernels goes chunk by chunk, each scanned and walked before the next reuses the store
+// (store offsets are relative to the chunk: flat_pairs_prepare.hip); every other set is one chunk.
+int Batch::runFlatNwPaths(bool& fellBack)
+{
+    for (size_t c = 0; c + 1 < flat_.chunkStart.size(); ++c)
+        if (flatStoreAndWalk(d_flatDescs_.p, d_flatOut3_.p, flat_.chunkStart[c], flat_.chunkStart[c + 1] - flat_.chunkStart[c])) return 1;
+    if (enqueueFlatCensus([&](int* counter) {
+            hipLaunchKernelGGL(count_failed_levels_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatDescs_.p, d_flatOut3_.p, n_,
+                               cfg_.k >= 0 ? cfg_.k : 0x3fffffff, counter);
+        })) return 1;
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    fellBack = flatCensus() > 0;                               // some unit needs the next level: the general path has them
+    return 0;
+}
+
+// SHW / HW: the census of overflowing end-location lists and, for the (rare) units with more end locations than a list
+// keeps, the exact second pass: their best score is already exact, so a scan with threshold = best and a list of the
+// right size finds every location (strip kernel).  a: the arguments of the phase-1 scan.
+int Batch::runFlatOverflowPass(const PairScanArgs& a)
+{
+    if (enqueueFlatCensus([&](int* counter) {
+            hipLaunchKernelGGL(count_over_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatOut3_.p + n_, n_, kFlatPosCap, counter);
+        })) return 1;
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    flatOvf_.clear();
+    if (flatCensus() == 0) return 0;
+    const size_t n = (size_t)n_;
+    PinBuf sc; EDLIB_AMD_HIP(sc.alloc(2 * n * sizeof(int)));
+    EDLIB_AMD_HIP(hipMemcpyAsync(sc.p, d_flatOut3_.p, 2 * n * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    const int* score = reinterpret_cast<const int*>(sc.p); const int* count = score + n;
+    std::vector<PairDesc> d2;
+    const FlatShape shape = flatShape();
+    long long peqOff = 0;                                    // (the scan of flat_pairs_prepare.hip, recomputed on the way)
+    for (int u = 0; u < n_; peqOff += (long long)((qlen(u) + 63) / 64) * tab_.sigmaT, ++u)
+        if (count[u] > kFlatPosCap) {
+            PairDesc x = flat_desc(shape, u, qoff_[u], qlen(u), tbase(u), tlen(u), peqOff);
+            x.kinit = score[u]; x.posCap = count[u]; x.posOff = flatOvf_.off.back(); x.ring = 0;
+            d2.push_back(x); flatOvf_.unit.push_back(u); flatOvf_.off.push_back(flatOvf_.off.back() + count[u]);
+        }
+    DevBuf<PairDesc> dd; DevBuf<int> s2;
+    DevBuf<int>& pool2 = d_flatOvfPool_;                     // (the lists stay on the device: the collection reads them there)
+    EDLIB_AMD_HIP(dd.alloc(d2.size())); EDLIB_AMD_HIP(pool2.ensure((size_t)flatOvf_.off.back())); EDLIB_AMD_HIP(s2.alloc(3 * d2.size()));
+    EDLIB_AMD_HIP(hipMemcpyAsync(dd.p, d2.data(), d2.size() * sizeof(PairDesc), hipMemcpyHostToDevice, stream_));
+    PairScanArgs a2 = a;
+    a2.descs = dd.p; a2.numUnits = (int)d2.size(); a2.posPool = pool2.p;
+    a2.outScore = s2.p; a2.outCount = s2.p + d2.size(); a2.outLast = s2.p + 2 * d2.size();
+    scanTimerStart();
+    EDLIB_AMD_HIP(launch_scan_pairs(flat_.scanMode, false, a2, stream_));
+    scanTimerStop();
+    // which list belongs to which unit, for the device-side collection
+    {
+        std::vector<int> at((size_t)n_, -1);
+        for (size_t j = 0; j < flatOvf_.unit.size(); ++j) at[(size_t)flatOvf_.unit[j]] = (int)j;
+        EDLIB_AMD_HIP(d_flatOvfAt_.ensure((size_t)n_)); EDLIB_AMD_HIP(d_flatOvfOff_.ensure(flatOvf_.off.size()));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_flatOvfAt_.p, at.data(), (size_t)n_ * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(d_flatOvfOff_.p, flatOvf_.off.data(), flatOvf_.off.size() * sizeof(long long), hipMemcpyHostToDevice, stream_));
+    }
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    stats.overflow_units += (int)d2.size();
+    for (const PairDesc& x : d2) stats.word_steps += 2LL * ((x.qlen + 63) / 64) * x.tlen;
+    return 0;
+}
+
+// HW start locations (reference edlib.cpp:228-266), everything on the device: descriptors of the reverse prefix scans
+// written by a kernel from the phase-1 results, one ring scan over them, the starts
+int Batch::runFlatStarts(bool& fellBack)
+{
+    const int* score = d_flatOut3_.p; const int* count = d_flatOut3_.p + n_;
+    int* const startOut3 = d_flatStartOut3_.p;
+    if (enqueueFlatCensus([&](int* counter) {
+            hipLaunchKernelGGL(flat_start_descs_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatDescs_.p, score, count, d_flatPos_.p,
+                               n_, kFlatPosCap, flat_.revPeqBase, flat_.ring, d_flatStartDescs_.p, d_flatSlotOf_.p, counter, (int)flat_.startCap);
+        })) return 1;
+    // (the reversed queries' Peq rows do not depend on the count: built while it travels)
+    EDLIB_AMD_HIP(launch_build_peq_pairs(d_flatRevDescs_.p, n_, d_qpool_.p, d_eq8_.p, d_idToByte_.p, tab_.sigmaT, d_peq64_.p, stream_));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    const int nscan = flatCensus();
+    if ((size_t)nscan > flat_.startCap) { fellBack = true; return 0; }
+    if (nscan > 0) {
+        const PairScanArgs b = flatScanArgs(d_flatStartDescs_.p, nscan, startOut3, flat_.startCap);
+        scanTimerStart();
+        EDLIB_AMD_HIP(launch_scan_pairs_ring(flat_.ring, EDLIB_MODE_SHW, false, b, stream_));
+        scanTimerStop();
+    }
+    const long long total = (long long)n_ * kFlatPosCap;
+    hipLaunchKernelGGL(flat_starts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream_, d_flatSlotOf_.p, d_flatPos_.p,
+                       startOut3 + 2 * flat_.startCap, total, d_flatStartsOut_.p);
+    EDLIB_AMD_HIP(hipGetLastError());
+    return 0;
+}
+
+// TASK_PATH of SHW / HW units (reference edlib.cpp:276-289): one storing NW scan per unit over its first location's
+// window + the traceback into the resident op slots
+int Batch::runFlatPaths()
+{
+    hipLaunchKernelGGL(flat_path_descs_kernel, dim3((n_ + 255) / 256), dim3(256), 0, stream_, d_flatDescs_.p, d_flatOut3_.p, d_flatOut3_.p + n_,
+                       d_flatPos_.p, flat_.scanMode == EDLIB_MODE_HW ? d_flatStartsOut_.p : nullptr, n_, kFlatPosCap, d_flatStoreBase_.p, flat_.ring, d_flatPathDescs_.p);
+    return flatStoreAndWalk(d_flatPathDescs_.p, d_flatPathOut3_.p, 0, n_);
 }
 
 // ---------------------------------------------------------------- collection
@@ -825,17 +787,20 @@ struct ViewLayout {
     }
 };
 
+// the variable part of a view in its pinned host block: the totals, and where the start locations and the op bytes begin
+struct ViewVar { long long nloc = 0, naln = 0; size_t oStarts = 0, oAln = 0; };
+
 // ---- the fixed part (per-unit fields, offsets, totals): waited for, checked, published; then the variable part's block
-int Batch::fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln, const char* who, long long& nloc, long long& naln)
+int Batch::fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln, const char* who, ViewVar& var)
 {
     uint8_t* const hv = h_view_.p;
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));        // (the caller queued the head copy, and what rides the same wait)
     const long long* totals = reinterpret_cast<const long long*>(hv + L.oTotals);
-    nloc = totals[0]; naln = totals[1];
+    const long long nloc = var.nloc = totals[0], naln = var.naln = totals[1];
     if (nloc < 0 || nloc > capLoc || naln < 0 || naln > capAln) { set_error("%s: totals out of range", who); return 1; }
     // the variable part in a pinned block of its own, sized by what there is (a block for everything a batch COULD have --
     // 146 MB of op slots for 262,144 x 150 bp HW paths that come to 39 MB -- cost its pinning on the first collection)
-    const size_t vStarts = ((size_t)nloc * 4 + 63) & ~(size_t)63, vAln = vStarts + (L.oStarts ? vStarts : 0);
+    const size_t vStarts = var.oStarts = ((size_t)nloc * 4 + 63) & ~(size_t)63, vAln = var.oAln = vStarts + (L.oStarts ? vStarts : 0);
     const size_t varBytes = vAln + (size_t)naln + 64;
     if (h_viewVar_.n < varBytes) EDLIB_AMD_HIP(h_viewVar_.alloc(varBytes + varBytes / 8));
     uint8_t* const hvar = h_viewVar_.p;
@@ -857,12 +822,11 @@ int Batch::fetchViewHead(const ViewLayout& L, long long capLoc, long long capAln
 int Batch::buildFlatView()
 {
     if (viewReady_) return 0;
-    const int mode = (int)cfg_.mode;
-    const int scanMode = (mode == EDLIB_MODE_HW || mode == EDLIB_MODE_SHW) ? mode : EDLIB_MODE_NW;
+    const int scanMode = flat_.scanMode;
     const size_t n = (size_t)n_;
-    const bool wantStarts = cfg_.task != EDLIB_TASK_DISTANCE, wantPath = flatPaths_;
-    const long long capLoc = (scanMode == EDLIB_MODE_NW ? (long long)n : (long long)n * (kFlatPosCap + 1)) + (flatOvfOff_.empty() ? 0 : flatOvfOff_.back());
-    const long long capAln = wantPath ? flatOpsTotal_ : 0;
+    const bool wantStarts = cfg_.task != EDLIB_TASK_DISTANCE, wantPath = flat_.paths;
+    const long long capLoc = (scanMode == EDLIB_MODE_NW ? (long long)n : (long long)n * (kFlatPosCap + 1)) + flatOvf_.off.back();
+    const long long capAln = wantPath ? flat_.opsTotal : 0;
     ViewLayout L{n};
     // (device: room for every location / op byte the batch could have; host: the fixed part now, the rest once the totals are known)
     L.oEnds = L.take((size_t)capLoc * 4); L.oStarts = wantStarts ? L.take((size_t)capLoc * 4) : 0; L.oAln = L.take((size_t)capAln + 16);
@@ -872,8 +836,8 @@ int Batch::buildFlatView()
     FlatResultArgs a{};
     a.descs = d_flatDescs_.p; a.n = n_; a.mode = scanMode; a.k = cfg_.k; a.wantPath = wantPath ? 1 : 0; a.posCap = kFlatPosCap;
     a.score = d_flatOut3_.p; a.count = d_flatOut3_.p + n; a.pos = d_flatPos_.p;
-    a.devStarts = flatStarts_ ? d_flatStartsOut_.p : nullptr;
-    if (!flatOvfUnit_.empty()) { a.ovfAt = d_flatOvfAt_.p; a.ovfOff = d_flatOvfOff_.p; a.ovfPos = d_flatOvfPool_.p; }
+    a.devStarts = flat_.starts ? d_flatStartsOut_.p : nullptr;
+    if (!flatOvf_.unit.empty()) { a.ovfAt = d_flatOvfAt_.p; a.ovfOff = d_flatOvfOff_.p; a.ovfPos = d_flatOvfPool_.p; }
     // alphabetLength comes from the side stream's kernel (or, for a handful of short sequences, from the host below)
     const bool alphaOnDevice = alphaPending_ && !alphaOnHost_ && alphaUnits_.size() == n;
     if (alphaOnDevice) { EDLIB_AMD_HIP(hipStreamWaitEvent(stream_, evB_.e, 0)); a.alphabet = d_alphaOut_.p; }
@@ -901,9 +865,10 @@ int Batch::buildFlatView()
             }
     }
     EDLIB_AMD_HIP(hipMemcpyAsync(hv, dv, L.headBytes, hipMemcpyDeviceToHost, stream_));
-    long long nloc, naln;
-    if (fetchViewHead(L, capLoc, capAln, "flat results", nloc, naln)) return 1;
-    const size_t vStarts = ((size_t)nloc * 4 + 63) & ~(size_t)63, vAln = vStarts + (wantStarts ? vStarts : 0);
+    ViewVar var;
+    if (fetchViewHead(L, capLoc, capAln, "flat results", var)) return 1;
+    const long long nloc = var.nloc, naln = var.naln;
+    const size_t vStarts = var.oStarts, vAln = var.oAln;
     uint8_t* const hvar = h_viewVar_.p;
     if (nloc) EDLIB_AMD_HIP(hipMemcpyAsync(hvar, dv + L.oEnds, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
     if (nloc && wantStarts) EDLIB_AMD_HIP(hipMemcpyAsync(hvar + vStarts, dv + L.oStarts, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
@@ -932,10 +897,10 @@ int Batch::buildFlatView()
         }
     }
     // start locations beyond the 16 a unit's flat list keeps (a unit of the exact second pass, HW): their reverse scans run now
-    if (flatStarts_ && !flatOvfUnit_.empty()) {
+    if (flat_.starts && !flatOvf_.unit.empty()) {
         int* starts = reinterpret_cast<int*>(hvar + vStarts);
         std::vector<UnitSpec> late; std::vector<long long> where;
-        for (int u : flatOvfUnit_) {
+        for (int u : flatOvf_.unit) {
             const int ed = view_.editDistance[u], m = qlen(u);
             if (ed < 0) continue;
             const long long lo = view_.locOffsets[u]; const int cnt = view_.numLocations[u];
@@ -1097,8 +1062,9 @@ int Batch::buildReadsView()
     EDLIB_AMD_HIP(launch_flat_results(a, reinterpret_cast<long long*>(dv + L.oTotals), stream_));
     EDLIB_AMD_HIP(hipMemcpyAsync(h_view_.p, dv, L.headBytes, hipMemcpyDeviceToHost, stream_));
     if (strands_ && n) EDLIB_AMD_HIP(hipMemcpyAsync(h_strand_.p, dv + oUStrand, 2 * n, hipMemcpyDeviceToHost, stream_));
-    long long nloc, naln;
-    if (fetchViewHead(L, capLoc, 0, "reads view", nloc, naln)) return 1;
+    ViewVar var;
+    if (fetchViewHead(L, capLoc, 0, "reads view", var)) return 1;
+    const long long nloc = var.nloc;
     if (nloc) EDLIB_AMD_HIP(hipMemcpyAsync(h_viewVar_.p, dv + L.oEnds, (size_t)nloc * 4, hipMemcpyDeviceToHost, stream_));
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     viewReady_ = true;

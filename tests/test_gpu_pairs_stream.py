@@ -9,15 +9,12 @@ import pytest
 
 import edlib_amd
 from edlib_amd import synth
+from pairs_set_cases import IUPAC, STATS, check as _check, fresh as _fresh, same as _same, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 
-STATS = ("cells", "word_steps", "path", "scan_launches")
-FIELDS = ("status", "editDistance", "endLocations", "startLocations", "numLocations", "alignment", "alignmentLength",
-          "alphabetLength")
 ACGT = b"ACGT"
 AMINO = b"ACDEFGHIKLMNPQRSTVWY"
-IUPAC = [("R", "A"), ("R", "G"), ("Y", "C"), ("Y", "T"), ("N", "A"), ("N", "C"), ("N", "G"), ("N", "T")]
 
 
 def _pair(rng, m, mode, alphabet=ACGT, qalphabet=None, sub=0.03, T=None):
@@ -43,46 +40,6 @@ def _pair(rng, m, mode, alphabet=ACGT, qalphabet=None, sub=0.03, T=None):
 def _pairs(rng, n, mode, lo=30, hi=300, **kw):
     out = [_pair(rng, int(m), mode, **kw) for m in rng.integers(lo, hi + 1, size=n)]
     return [q for q, _ in out], [t for _, t in out]
-
-
-def _snapshot(b):
-    """everything a caller can read after a run: results_flat() and both CIGAR forms"""
-    out = dict(b.results_flat())
-    for ext in (True, False):
-        chars, off = b.cigars(extended=ext)
-        out["cigar%d.chars" % ext], out["cigar%d.off" % ext] = chars, off
-    return out
-
-
-def _same(got, want, what=""):
-    assert sorted(got) == sorted(want), what
-    for f in want:
-        if want[f] is None or got[f] is None:
-            assert got[f] is None and want[f] is None, (what, f)
-            continue
-        assert got[f].shape == want[f].shape and got[f].dtype == want[f].dtype, (what, f, got[f].shape, want[f].shape)
-        assert np.array_equal(got[f], want[f]), (what, f, np.argwhere(got[f] != want[f])[:5].tolist())
-
-
-def _fresh(engine, qs, ts, mode, task, k, eqs=None):
-    b = engine.PairBatch(qs, ts, mode=mode, task=task, k=k, additionalEqualities=eqs)
-    try:
-        stats = b.run()
-        return _snapshot(b), stats
-    finally:
-        b.close()
-
-
-def _check(b, checker, qs, ts, mode, task, k, eqs=None, sel=None, what=""):
-    """results() of the units `sel` (all: None) against the checker, every field"""
-    got = b.results(raw=True)
-    assert len(got) == len(qs)
-    bad = []
-    for i in (range(len(qs)) if sel is None else sel):
-        want = checker.align(qs[i], ts[i], mode, task, k, eq_pairs=eqs)
-        if any(got[i][f] != want[f] for f in FIELDS):
-            bad.append((i, len(qs[i]), len(ts[i]), {f: (got[i][f], want[f]) for f in FIELDS if got[i][f] != want[f]}))
-    assert not bad, (what, mode, task, k, bad[:3])
 
 
 def _stream_and_compare(engine, checker, b, qs, ts, mode, task, k, eqs=None, everything=False, stats_equal=True, what=""):

@@ -2,165 +2,38 @@
 a resident pair batch must be exactly a fresh PairBatch created over the same pairs materialised on the host -- every
 array of results_flat(), both CIGAR forms and the statistics that describe the work -- and a strided sample (or all) of
 its units must equal the checker; the window batch must be left as it was; a refused call must leave the pair batch as
-it was.  The yardstick and its helpers are those of tests/test_gpu_pairs_stream.py.
+it was.  The yardstick and its helpers are in tests/pairs_set_cases.py.
 Two refusals of the contract have no case here: a window batch left without units by a SetUnits that failed on the device
 (only a device error, out of memory, gets there, and no test provokes one), and batches on different devices (checked
 where the machine has a second device, a branch a one-device machine does not take)."""
+import functools
+
 import numpy as np
 import pytest
 
 import edlib_amd
 from edlib_amd import synth
+import pairs_set_cases as PS
+from pairs_set_cases import (IUPAC, STATS, Tuples, check as _check, fresh as _fresh, mapper_tuples as _mapper_tuples,
+                             reads as _reads, same as _same, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 
 NAME = "edlibAmdBatchPairsSetWindows"
-STATS = ("cells", "word_steps", "path", "scan_launches")
-FIELDS = ("status", "editDistance", "endLocations", "startLocations", "numLocations", "alignment", "alignmentLength",
-          "alphabetLength")
-IUPAC = [("R", "A"), ("R", "G"), ("Y", "C"), ("Y", "T"), ("N", "A"), ("N", "C"), ("N", "G"), ("N", "T")]
-WINDOW_LENGTHS = (1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 32, 33, 400)
 QUERY_LENGTHS = (1, 2, 3, 4, 5, 31, 32, 33, 150, 255, 256)
 
+# ---- the yardstick and the tuples of tests/pairs_set_cases.py, over a window batch
 
-# ---- the yardstick of tests/test_gpu_pairs_stream.py
-
-def _snapshot(b):
-    """everything a caller can read after a run: results_flat() and both CIGAR forms"""
-    out = dict(b.results_flat())
-    for ext in (True, False):
-        chars, off = b.cigars(extended=ext)
-        out["cigar%d.chars" % ext], out["cigar%d.off" % ext] = chars, off
-    return out
-
-
-def _same(got, want, what=""):
-    assert sorted(got) == sorted(want), what
-    for f in want:
-        if want[f] is None or got[f] is None:
-            assert got[f] is None and want[f] is None, (what, f)
-            continue
-        assert got[f].shape == want[f].shape and got[f].dtype == want[f].dtype, (what, f, got[f].shape, want[f].shape)
-        assert np.array_equal(got[f], want[f]), (what, f, np.argwhere(got[f] != want[f])[:5].tolist())
-
-
-def _fresh(engine, qs, ts, mode, task, k, eqs=None):
-    b = engine.PairBatch(qs, ts, mode=mode, task=task, k=k, additionalEqualities=eqs)
-    try:
-        stats = b.run()
-        return _snapshot(b), stats
-    finally:
-        b.close()
-
-
-def _check(b, checker, qs, ts, mode, task, k, eqs=None, sel=None, what=""):
-    got = b.results(raw=True)
-    assert len(got) == len(qs)
-    bad = []
-    for i in (range(len(qs)) if sel is None else sel):
-        want = checker.align(qs[i], ts[i], mode, task, k, eq_pairs=eqs)
-        if any(got[i][f] != want[f] for f in FIELDS):
-            bad.append((i, len(qs[i]), len(ts[i]), {f: (got[i][f], want[f]) for f in FIELDS if got[i][f] != want[f]}))
-    assert not bad, (what, mode, task, k, bad[:3])
-
-
-# ---- sets over a window batch
-
-class Tuples:
-    """(query, start, length, strand) per pair, as set_windows takes them"""
-
-    def __init__(self, q, s, n, st=None):
-        self.q, self.s, self.n = (np.asarray(a, dtype=np.int32) for a in (q, s, n))
-        self.st = None if st is None else np.asarray(st, dtype=np.uint8)
-
-    def __len__(self):
-        return len(self.q)
-
-    def args(self):
-        return self.q, self.s, self.n, self.st
-
-    def materialise(self, queries, target):
-        """the pairs on the host: slices of the target, reverse complements of the queries of strand 1"""
-        t = bytes(target)
-        qs = [bytes(queries[q]) if (self.st is None or not self.st[i]) else edlib_amd.reverse_complement(bytes(queries[q]))
-              for i, q in enumerate(self.q)]
-        return qs, [t[s:s + n] for s, n in zip(self.s, self.n)]
-
-
-def _reads(rng, target, count, lo=30, hi=256, sub=0.03):
-    """reads cut from the target with a few substitutions and now and then an indel, every other one from the reverse
-    strand; where each came from"""
-    t = np.frombuffer(bytes(target), dtype=np.uint8)
-    A = np.frombuffer(b"ACGT", dtype=np.uint8)
-    reads, origin, strand = [], [], []
-    for i, m in enumerate(rng.integers(lo, hi + 1, size=count)):
-        m = int(m)
-        s = int(rng.integers(0, len(t) - m + 1))
-        q = t[s:s + m].copy()
-        at = rng.integers(0, m, size=rng.binomial(m, sub))
-        q[at] = A[rng.integers(0, 4, size=len(at))]
-        if m > 4 and rng.random() < 0.3:
-            p = int(rng.integers(1, m - 1))
-            q = np.concatenate([q[:p], q[p + 1:], A[rng.integers(0, 4, size=1)]])
-        st = i & 1
-        reads.append(edlib_amd.reverse_complement(q.tobytes()) if st else q.tobytes())
-        origin.append(s)
-        strand.append(st)
-    return reads, np.array(origin), np.array(strand)
-
-
-def _mapper_tuples(rng, reads, origin, strand, target_length, n, mode):
-    """n pairs in no order: a read in the strand it maps on (now and then the other one), its window around where it came
-    from -- NW: about the read's span, SHW: from its first column on, HW: padded on both sides up to about 3 m; windows of
-    reads from nearby loci overlap"""
-    q = rng.integers(0, len(reads), size=n)
-    m = np.array([len(reads[i]) for i in q], dtype=np.int64)
-    st = np.where(rng.random(n) < 0.9, strand[q], 1 - strand[q])
-    if mode == "NW":
-        lead, trail = rng.integers(0, 3, size=n), rng.integers(0, 3, size=n)
-    elif mode == "SHW":
-        lead, trail = np.zeros(n, dtype=np.int64), rng.integers(0, 2 * m + 1)
-    else:
-        lead, trail = rng.integers(0, m + 1), rng.integers(0, m + 1)
-    s = np.maximum(origin[q] - lead, 0)
-    e = np.minimum(origin[q] + m + trail, target_length)
-    return Tuples(q, s, e - s, st)
-
-
-def _set_and_compare(engine, checker, pb, wb, queries, target, tup, mode, task, k, eqs=None, everything=False, what=""):
-    """set_windows + run on pb against a fresh batch over the materialised pairs, and about 100 units (or all) against
-    the checker"""
-    pb.set_windows(wb, *tup.args())
-    assert pb.n == len(tup)
-    stats = pb.run()
-    got = _snapshot(pb)
-    qs, ts = tup.materialise(queries, target)
-    want, wstats = _fresh(engine, qs, ts, mode, task, k, eqs)
-    _same(got, want, what)
-    # (a fresh batch of fewer than 1,024 pairs takes the general path, whose word_steps and launches are another count:
-    # there the statistics are those of the batch set_pairs makes)
-    if len(tup) < 1024:
-        other = engine.PairBatch([], [], mode=mode, task=task, k=k, additionalEqualities=eqs)
-        try:
-            other.set_pairs(qs, ts)
-            wstats = other.run()
-            _same(got, _snapshot(other), ("set_pairs", what))
-        finally:
-            other.close()
-    assert {f: stats[f] for f in STATS} == {f: wstats[f] for f in STATS}, what
-    assert stats["cells"] == sum(len(q) * len(t) for q, t in zip(qs, ts)), what
-    n = len(qs)
-    _check(pb, checker, qs, ts, mode, task, k, eqs, None if everything else range(0, n, max(1, n // 100)), what)
-    return got, stats
+_set_and_compare = functools.partial(PS.set_and_compare, "set_windows")
+_refused = functools.partial(PS.refused, NAME)
+# the grid of tests/test_pairs_gather_model.py: every nibble phase x every window length
+_grid = functools.partial(PS.grid, phases=8)
 
 
 @pytest.fixture(scope="module")
 def genome():
     """a 20,000-base ACGT target, 400 reads of 30 to 256 bases from both of its strands, and a window batch over them"""
-    rng = np.random.default_rng(2024)
-    target = synth.random_dna(11, 20000).tobytes()
-    reads, origin, strand = _reads(rng, target, 400)
-    return {"target": target, "reads": reads, "origin": origin, "strand": strand}
+    return PS.genome(2024, 11)
 
 
 def _window_batch(engine, genome, stranded, mode="HW", k=-1):
@@ -197,25 +70,6 @@ def test_set_windows_equals_fresh_batch(engine, checker, genome, mode, task, k):
 
 
 # ---- 2. the shapes the gather can get wrong
-
-def _grid(rng, target_length, num_queries):
-    """the grid of tests/test_pairs_gather_model.py: every nibble phase x every window length, consecutive odd lengths
-    (every alignment of the next pair), windows at column 0 and up to the last column, both strands"""
-    ps, pl = [], []
-    for phase in range(8):
-        for n in WINDOW_LENGTHS:
-            ps.append(8 * int(rng.integers(0, (target_length - 400) // 8 - 1)) + phase)
-            pl.append(n)
-    for n in range(1, 35, 2):
-        ps.append(int(rng.integers(0, target_length - 40)))
-        pl.append(n)
-    for n in WINDOW_LENGTHS:
-        ps += [0, target_length - n]
-        pl += [n, n]
-    pq = [i % num_queries for i in range(len(ps))]
-    st = [(i // num_queries) & 1 for i in range(len(ps))]
-    return Tuples(pq, ps, pl, st)
-
 
 @pytest.mark.parametrize("alphabet", [b"ACGT", b"ACGTNacgtn", b"ACGTRYKMBDHVNSWU", b"A"])
 @pytest.mark.parametrize("stranded", [False, True])
@@ -471,23 +325,6 @@ def test_the_pair_batch_keeps_its_own_equalities(engine, checker, mode, task):
 
 
 # ---- 5. refusals leave the pair batch as it was
-
-def _refused(engine, pb, before, call, *words):
-    """the call fails with a message that names the function and carries `words`; the views held across it, the views
-    fetched after it and the next Run are those of `before`"""
-    held = pb.results_flat(copy=False)                    # views of the batch's own memory, held across the refusal
-    cig = pb.cigars(copy=False)
-    assert call() != 0
-    msg = engine.last_error()
-    assert NAME in msg and all(w in msg for w in words), msg
-    for f, v in held.items():
-        assert v is None or np.array_equal(v, before[f]), (msg, f)
-    assert np.array_equal(cig[0], before["cigar1.chars"]) and np.array_equal(cig[1], before["cigar1.off"]), msg
-    _same(_snapshot(pb), before, msg)
-    del held, cig
-    pb.run()                                              # ... and the next Run reproduces them
-    _same(_snapshot(pb), before, ("the next run", msg))
-
 
 @pytest.mark.parametrize("mode", ["HW", "NW"])
 def test_refusals_leave_the_pair_batch_as_it_was(engine, checker, genome, mode):
