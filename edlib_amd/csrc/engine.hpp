@@ -323,7 +323,8 @@ private:
                   int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                   const long long* posOff, const int* posCap, bool unbanded = false,
                   unsigned long long* wordSteps = nullptr, const uint32_t* peqDense = nullptr,
-                  const int* qlenDense = nullptr, int peqBottom = 0, int* liveBest = nullptr);
+                  const int* qlenDense = nullptr, int peqBottom = 0, int* liveBest = nullptr,
+                  const Segment* segTable = nullptr, long long tableCols = 0);   // segTable: its segments (with numSegments), tableCols: columns a lane walks
 
     // ---- block-per-lane path
     DevBuf<PairDesc> d_descs_;

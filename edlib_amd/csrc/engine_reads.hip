@@ -28,7 +28,8 @@ seed_thresholds_kernel(int* __restrict__ kinit, const int* __restrict__ best, co
 int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, int kcap, const int* d_kinit,
                      int numSegments, int segLen, int warm, int* segBest, int* segCnt, int* segPos, int cap,
                      const long long* posOff, const int* posCap, bool unbanded, unsigned long long* wordSteps,
-                     const uint32_t* peqDense, const int* qlenDense, int peqBottom, int* liveBest)
+                     const uint32_t* peqDense, const int* qlenDense, int peqBottom, int* liveBest,
+                     const Segment* segTable, long long tableCols)
 {
     ReadScanArgs a{};
     // peqDense / qlenDense (+ d_kinit): rows rebuilt for exactly the lanes of this launch, in lane order (pass 2)
@@ -43,6 +44,7 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     a.kcap = kcap; a.wordSteps = wordSteps ? wordSteps : d_wordSteps_.p;
     a.filter = filterScan_ ? 1 : 0;
     a.liveBest = liveBest;
+    a.segTable = segTable;                            // (scan_reads_kernel only: the other launchers refuse one)
     a.bottomAligned = peqBottom;                      // (only scan_reads_kernel reads such rows: launch_scan_reads below)
     a.chainIn = chain_.in; a.chainOut = chain_.out; a.chainSrc = chain_.src; a.chainInLanes = chain_.inLanes;
     a.chainBlocks = chain_.blocks; a.rowBase = chain_.rowBase;
@@ -61,7 +63,22 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     // long word groups
     const bool longGroup = g.nwords > kMaxReadWords;                  // no plain kernel for 12 / 16 words
     // columns a lane walks: the segments' own columns (a launch may cover a prefix of the target only) and their warm-ups
-    const long long colsScanned = std::min<long long>(a.targetLength, (long long)numSegments * segLen) + (long long)(numSegments - 1) * warm;
+    // (a table of segments comes with its own sum)
+    const long long colsScanned = segTable ? tableCols
+        : std::min<long long>(a.targetLength, (long long)numSegments * segLen) + (long long)(numSegments - 1) * warm;
+#ifdef EDLIB_AMD_DRAIN_DIAG
+    // diagnostic build (-DEDLIB_AMD_DRAIN_DIAG, never the library that ships): the clocks of every wave of the last level's
+    // main launch go to edlib_amd_drain.bin in the working directory (tools/drain_model.py reads it): gridX, gridY, then the
+    // entry and the exit clocks.  With -DEDLIB_AMD_DRAIN_UNIFORM as well the launch keeps the uniform plan.
+    const char* drainOut = (peqBottom && liveBest) ? "edlib_amd_drain.bin" : nullptr;
+    DevBuf<unsigned long long> d_clk;
+    const size_t drainGX = ((size_t)(nlanes + 63) / 64 + 3) / 4, drainWaves = drainGX * numSegments * 4;
+    if (drainOut) {
+        EDLIB_AMD_HIP(d_clk.alloc(2 * drainWaves));
+        EDLIB_AMD_HIP(hipMemsetAsync(d_clk.p, 0, 2 * drainWaves * sizeof(unsigned long long), stream_));
+        a.waveClock = d_clk.p;
+    }
+#endif
     const bool fullHeight = banded_ && mode == EDLIB_MODE_HW && unbanded && (chained || syms_ > 4 || longGroup);
     const bool bandedKernel = !fullHeight && banded_ && mode == EDLIB_MODE_HW && (!unbanded || syms_ > 4 || longGroup);
     if (peqBottom && (fullHeight || bandedKernel)) EDLIB_AMD_HIP(hipErrorInvalidValue);   // rows only scan_reads_kernel reads
@@ -74,6 +91,17 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
         stats.word_steps += (long long)((nlanes + 63) / 64 * 64) * g.nwords * colsScanned;
     }
     scanTimerStop();
+#ifdef EDLIB_AMD_DRAIN_DIAG
+    if (drainOut) {
+        std::vector<unsigned long long> clk(2 * drainWaves);
+        EDLIB_AMD_HIP(hipMemcpyAsync(clk.data(), d_clk.p, clk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        if (FILE* f = fopen(drainOut, "wb")) {
+            const unsigned long long head[2] = {drainGX, (unsigned long long)numSegments};
+            fwrite(head, sizeof head, 1, f); fwrite(clk.data(), sizeof(unsigned long long), clk.size(), f); fclose(f);
+        }
+    }
+#endif
     if (dbg) {
         EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
         fprintf(stderr, "[edlib_amd] scanGroup done\n");
@@ -85,15 +113,7 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
 void plan_segments(int nlanes, int T, int mode, int warmFull, long long wantWaves,
                           int& S, int& segLen, int& warm, int minSegCols)
 {
-    S = 1; segLen = roundup(T, 16); warm = 0;
-    if (mode != EDLIB_MODE_HW) return;
-    const long long nrblk = ((long long)nlanes + 63) / 64;
-    long long want = (wantWaves + nrblk - 1) / nrblk;
-    want = std::max(1LL, std::min<long long>(want, std::min(65535, std::max(1, T / minSegCols))));   // gridDim.y limit
-    if (warmFull > 0) want = std::max(1LL, std::min<long long>(want, std::max<long long>(1, T / (4LL * warmFull))));   // >= four warm-ups per segment
-    segLen = roundup((int)((T + want - 1) / want), 16);
-    S = (T + segLen - 1) / segLen;
-    warm = warmFull;
+    plan_segments_uniform(nlanes, T, mode == EDLIB_MODE_HW, warmFull, wantWaves, minSegCols, S, segLen, warm);   // segment_plan.hpp
 }
 
 int Batch::runReads()
@@ -275,15 +295,14 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             const size_t no = todo.size();
             int S2, segLen2, warm2;
             plan_segments((int)no, T, mode, g.warm, 65536, S2, segLen2, warm2);
-            const size_t items = no * (size_t)S2;
             // The segment records of a level are the group's: they are reused from run to run (at 1M reads the positions
             // are a block the allocator's pool does not keep), and those of the last level outlive the loop -- the exact
             // pass gathers from them the lists that only overflowed the 16 positions of a slot.  The last level keeps 16
             // positions per segment instead of 8, so that a segment alone rarely overflows.
             const int capL = last ? kLastLevelCap : 8;
-            EDLIB_AMD_HIP(g.d_lvMap.ensure(no)); EDLIB_AMD_HIP(g.d_lvBest.ensure(items)); EDLIB_AMD_HIP(g.d_lvCnt.ensure(items));
-            EDLIB_AMD_HIP(g.d_lvPos.ensure(items * capL));
-            int *d_map = g.d_lvMap.p, *d_sb = g.d_lvBest.p, *d_sc = g.d_lvCnt.p, *d_sp = g.d_lvPos.p;
+            // (sized below, once the launch's segments are known)
+            EDLIB_AMD_HIP(g.d_lvMap.ensure(no));
+            int* d_map = g.d_lvMap.p;
             EDLIB_AMD_HIP(hipMemcpyAsync(d_map, todo.data(), no * sizeof(int), hipMemcpyHostToDevice, stream_));
             // What the last level leaves over is usually unrelated sequence whose band is the whole query; there the
             // plain full-height kernel (register-resident Peq rows, no band bookkeeping) is ~12 % faster per
@@ -323,6 +342,30 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             const bool bottomOk = plain && mode == EDLIB_MODE_HW && syms_ == 4 && g.nwords <= kMaxReadWords &&
                                   chain_.in == nullptr && chain_.out == nullptr;
             const int bottom = !bottomOk ? 0 : (delay_rows_fit(g.nwords, g.mMax) ? 1 + kDelayRows : 1);
+            // The main launch over the leftovers is eight rounds of resident workgroups at 1M reads, and with uniform segments
+            // its end is ragged: for the time of up to one segment every workgroup that finishes leaves its slot empty.
+            // Its segments taper instead (plan_segments_tapered): the uniform length while much is left, then ever shorter
+            // ones towards the target's end, so that the workgroups still running at the end are short ones.  The records
+            // stay [lane][segment]; every column belongs to exactly one segment and positions are absolute, so the merge, the
+            // gather of the exact pass and the reuse of these records (lvS) only see another segment count.
+            std::vector<Segment> table;                              // (live until the synchronisation below)
+            DevBuf<Segment> d_segTable; long long tableCols = 0;
+            if (bottom && S2 > 1 && no >= 4096) {
+                int resident = 0;
+                EDLIB_AMD_HIP(scan_reads_resident_workgroups(g.nwords, bottom, &resident));
+#ifdef EDLIB_AMD_DRAIN_UNIFORM
+                resident = 0;                                        // diagnostic build: the uniform plan, as a table
+#endif
+                table = plan_segments_tapered(T, (int)(((no + 63) / 64 + 3) / 4), resident, warm2, segLen2);
+                S2 = (int)table.size();
+                for (const Segment& sg : table) tableCols += sg.cols + std::min(warm2, sg.start);
+                EDLIB_AMD_HIP(d_segTable.alloc(table.size()));
+                EDLIB_AMD_HIP(hipMemcpyAsync(d_segTable.p, table.data(), table.size() * sizeof(Segment), hipMemcpyHostToDevice, stream_));
+            }
+            const size_t items = no * (size_t)S2;
+            EDLIB_AMD_HIP(g.d_lvBest.ensure(items)); EDLIB_AMD_HIP(g.d_lvCnt.ensure(items));
+            EDLIB_AMD_HIP(g.d_lvPos.ensure(items * capL));
+            int *d_sb = g.d_lvBest.p, *d_sc = g.d_lvCnt.p, *d_sp = g.d_lvPos.p;
             const size_t no64 = (no + 63) / 64 * 64;
             std::vector<int> perm2(no64, -1);
             for (size_t i = 0; i < no; ++i) perm2[i] = g.perm[todo[i]];
@@ -357,7 +400,8 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
                 EDLIB_AMD_HIP(hipMemcpyAsync(d_live2.p, d_kinit2.p, no64 * sizeof(int), hipMemcpyDeviceToDevice, stream_));
             }
             if (scanGroup(g, mode, nullptr, (int)no, kcapL, d_kinit2.p, S2, segLen2, warm2,
-                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p, bottom, d_live2.p)) return 1;
+                          d_sb, d_sc, d_sp, capL, nullptr, nullptr, plain, nullptr, d_peq2.p, d_qlen2.p, bottom, d_live2.p,
+                          d_segTable.p, tableCols)) return 1;
             EDLIB_AMD_HIP(launch_merge_segments(d_sb, d_sc, d_sp, S2, capL, (int)no, d_map, 16,
                                                 g.d_best.p, g.d_total.p, g.d_pos.p, g.d_flags.p, stream_,
                                                 last ? kOvfGatherLevel : kOvfRescan));

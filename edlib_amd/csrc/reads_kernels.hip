@@ -285,6 +285,12 @@ scan_reads_kernel(const ReadScanArgs a)
     if (rblk * 64 >= a.nlanes) return;                             // whole wave out of range
     const bool live = idx < a.nlanes;
     const int slot = live ? (a.slotmap ? a.slotmap[idx] : idx) : 0;
+#ifdef EDLIB_AMD_DRAIN_DIAG
+    // diagnostic build only (tools/drain_model.py): when every wave of the launch came and went.  (The wave's index is worked
+    // out again at the exit from what the loop keeps anyway: a register held across the scan would cost the kernel a wave.)
+    if (BOTTOM && a.waveClock && lane == 0)
+        a.waveClock[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)] = wall_clock64();
+#endif
 
     u32 E0[NWD], E1[NWD], E2[NWD], E3[NWD], Pv[NWD], Mv[NWD];
     {
@@ -343,8 +349,9 @@ scan_reads_kernel(const ReadScanArgs a)
 #define EDLIB_AMD_LIVE_LOAD() (live ? __hip_atomic_load(livep + lidx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : kNoImport)
 
     const int T = a.targetLength;
-    const int c0 = seg * a.segLen;                                 // multiple of 16
-    int c1 = c0 + a.segLen; if (c1 > T) c1 = T;
+    int c0 = seg * a.segLen, c1 = c0 + a.segLen;                   // c0: multiple of 16
+    if (a.segTable) { const Segment sg = a.segTable[seg]; c0 = sg.start; c1 = c0 + sg.cols; }   // (one scalar load per wave)
+    if (c1 > T) c1 = T;
     int cw = c0 - a.warm; if (cw < 0) cw = 0;
     cw &= ~15;
 
@@ -470,6 +477,12 @@ scan_reads_kernel(const ReadScanArgs a)
         a.segBest[o] = (MODE == 0) ? score : best;                 // NW: D[m][T] (edlib.cpp:914-917)
         a.segCnt[o] = (MODE == 0) ? 1 : cnt;
     }
+#ifdef EDLIB_AMD_DRAIN_DIAG
+    if (BOTTOM && a.waveClock && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0) {
+        const int rb = lidx >> 6;                                  // = rblk
+        a.waveClock[((size_t)gridDim.y + blockIdx.y) * gridDim.x * 4 + rb] = wall_clock64();
+    }
+#endif
 }
 
 template <int NWD>
@@ -502,6 +515,29 @@ hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStr
     return hipErrorInvalidValue;
 }
 
+template <int NWD>
+static hipError_t resident_bottom(int bottomAligned, int* perCU)
+{
+    if (bottomAligned == 1 + kDelayRows) return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, scan_reads_kernel<NWD, 2, true, true>, 256, 0);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, scan_reads_kernel<NWD, 2, true>, 256, 0);
+}
+
+hipError_t scan_reads_resident_workgroups(int nwords, int bottomAligned, int* resident)
+{
+    int dev = 0, cus = 0, perCU = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    switch (nwords) {
+#define CASE(N) case N: e = resident_bottom<N>(bottomAligned, &perCU); break;
+        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+        default: return hipErrorInvalidValue;
+    }
+    *resident = perCU * cus;
+    return e;
+}
+
 // ------------------------------------------------------------- launchers (groups of up to 8 words; longer: reads_kernels_long.hip)
 
 hipError_t launch_scan_reads_full_long(int nwords, int syms, const ReadScanArgs& a, hipStream_t stream);
@@ -524,6 +560,7 @@ static hipError_t launch_scan_reads_full_s(int nwords, const ReadScanArgs& a, hi
 hipError_t launch_scan_reads_full(int nwords, int syms, const ReadScanArgs& a, hipStream_t stream)
 {
     if (a.nlanes == 0) return hipSuccess;
+    if (a.segTable) return hipErrorInvalidValue;                        // only scan_reads_kernel reads a table
     if (nwords > kMaxReadWords) return launch_scan_reads_full_long(nwords, syms, a, stream);
     const bool chain = a.chainIn != nullptr || a.chainOut != nullptr;
     switch (syms) {
@@ -554,6 +591,7 @@ static hipError_t launch_scan_reads_banded_s(int nwords, const ReadScanArgs& a, 
 hipError_t launch_scan_reads_banded(int nwords, int syms, const ReadScanArgs& a, hipStream_t stream)
 {
     if (a.nlanes == 0) return hipSuccess;
+    if (a.segTable) return hipErrorInvalidValue;
     if (nwords > kMaxReadWords) return a.filter ? hipErrorInvalidValue : launch_scan_reads_banded_long(nwords, syms, a, stream);
     switch (syms) {
         case 4: return launch_scan_reads_banded_s<4>(nwords, a, stream);

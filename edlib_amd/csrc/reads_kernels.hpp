@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "hit_list.hpp"
+#include "segment_plan.hpp"
 
 namespace edlib_amd {
 
@@ -66,11 +67,18 @@ struct ReadScanArgs {
                               // segments, set to the lane's threshold before the launch (no slotmap).  The segments start
                               // from it, publish what they find and pick it up again every kLivePeriod columns.  Null: every
                               // (lane, segment) keeps a best of its own, from kinit
+    const Segment* segTable;  // scan_reads_kernel only: optional [numSegments] columns of every segment, ascending, starts
+                              // multiples of 16 (plan_segments_tapered).  Null: segment s is [s segLen, (s + 1) segLen)
+#ifdef EDLIB_AMD_DRAIN_DIAG
+    unsigned long long* waveClock;   // diagnostic build: optional [2][waves of the launch] s_memrealtime at entry / exit
+#endif
 };
 constexpr int kLivePeriod = 1024;     // columns between two looks at liveBest (a multiple of 16)
 
 // mode: 0 NW, 1 SHW, 2 HW (values of EdlibAlignMode).  Returns hipSuccess or the launch error.
 hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStream_t stream);
+// workgroups of the bottom-aligned HW scan_reads_kernel that the current device holds at once (occupancy x CUs)
+hipError_t scan_reads_resident_workgroups(int nwords, int bottomAligned, int* resident);
 
 // HW only: Ukkonen-banded variant with k-doubling (see reads_kernels.hip); same Peq layout.  syms = Peq rows per word:
 // 4, 8 or 16 (target symbols rounded up); launch_scan_reads only knows 4.
