@@ -77,23 +77,81 @@ def test_wide_alphabet_pairs(engine):
 _ALL = ("status", "editDistance", "numLocations", "alphabetLength", "locOff", "ends", "starts", "alnOff", "alignment")
 
 
-def _check_task(engine, qs, ts, mode, task, k=-1, what=""):
-    b = engine.PairBatch(qs, ts, mode=mode, task=task, k=k)
-    try:
-        b.run(); b.run()
-        got = b.results_flat()
-        again = b.results_flat()
-    finally:
-        b.close()
+def _reference(qs, ts, mode, task, k=-1, select=None):
+    """the reference pool over the pairs (the units `select`: all), with its CIGAR strings when the task makes paths"""
     qoff = np.zeros(len(qs) + 1, dtype=np.int64); qoff[1:] = np.cumsum([len(q) for q in qs])
     toff = np.zeros(len(ts) + 1, dtype=np.int64); toff[1:] = np.cumsum([len(t) for t in ts])
-    ref = O.pool_align(np.concatenate(qs), qoff, np.concatenate(ts), toff, False, mode, task, k)
+    return O.pool_align(np.concatenate(qs), qoff, np.concatenate(ts), toff, False, mode, task, k, select=select,
+                        want_cigar=task == "path")
+
+
+def _ref_cigars(ref, extended):
+    """the reference's CIGARs in the form cigars() hands out.  ref_pool.cpp packs the strings of edlibAlignmentToCigar
+    back to back WITHOUT their NULs (its offsets add std::string::size(); a unit without an alignment adds nothing),
+    cigars() keeps the NUL of every string, the empty one's included: string u starts u characters later."""
+    roff = ref["cigExtOff" if extended else "cigStdOff"]
+    raw = np.frombuffer(ref["cigExt" if extended else "cigStd"], dtype=np.uint8)
+    off = roff + np.arange(len(roff), dtype=np.int64)
+    chars = np.zeros(int(off[-1]), dtype=np.uint8)
+    text = np.ones(len(chars), dtype=bool)
+    text[off[1:] - 1] = False
+    assert int(text.sum()) == len(raw) and not (raw == 0).any()
+    chars[text] = raw
+    return chars, off
+
+
+def _collect(b, task):
+    """everything a caller reads after a run: the flat results and, for paths, both CIGAR forms"""
+    out = dict(b.results_flat())
+    if task == "path":
+        for extended in (True, False):
+            out["cigar", extended] = b.cigars(extended=extended)
+    return out
+
+
+def _compare(got, ref, task, tag):
+    """every field of every unit; for paths the CIGARs of both forms offset by offset and string by string (equal offsets
+    and equal characters, NULs included, are equal strings: the first unit that differs is named)"""
     z = np.zeros(0, dtype=np.int32)
+    for f in _ALL:
+        a = got[f] if got[f] is not None else z
+        r = ref[f] if ref[f] is not None else z
+        assert np.array_equal(a, r), (f,) + tuple(tag)
+    if task != "path":
+        return
+    for extended in (True, False):
+        chars, off = got["cigar", extended]
+        wchars, woff = _ref_cigars(ref, extended)
+        assert off.shape == woff.shape, ("cigar offsets", extended) + tuple(tag)
+        if not np.array_equal(off, woff) or not np.array_equal(chars, wchars):
+            u = int(np.argmax(off[1:] != woff[1:])) if not np.array_equal(off, woff) else \
+                int(np.searchsorted(woff, int(np.argmax(chars != wchars)), side="right") - 1)
+            have = chars[int(off[u]):int(off[u + 1])].tobytes(); want = wchars[int(woff[u]):int(woff[u + 1])].tobytes()
+            raise AssertionError(("cigar", extended, "unit", u, int(off[u]), int(woff[u]), have[:80], want[:80]) + tuple(tag))
+
+
+def _flat_launches(mode, task, chunks=1):
+    """scan_launches of a run that stays on the flat path and has no overflowing list (engine_flat.hip: runPairsFlat): the
+    phase-1 scan -- for NW paths the storing scan of every chunk --, the start scans of HW, the storing scan of SHW / HW
+    paths.  A run that falls back to the general path has scanned by then and scans again: it counts more."""
+    if mode == "NW":
+        return chunks if task == "path" else 1
+    return 1 + (mode == "HW" and task != "distance") + (task == "path")
+
+
+def _check_task(engine, qs, ts, mode, task, k=-1, what="", ref=None):
+    b = engine.PairBatch(qs, ts, mode=mode, task=task, k=k)
+    try:
+        b.run(); st = b.run()
+        got = _collect(b, task)
+        again = _collect(b, task)
+    finally:
+        b.close()
+    if ref is None:
+        ref = _reference(qs, ts, mode, task, k)
     for res_, tag in ((got, "first collection"), (again, "second collection")):
-        for f in _ALL:
-            a = res_[f] if res_[f] is not None else z
-            r = ref[f] if ref[f] is not None else z
-            assert np.array_equal(a, r), (mode, task, k, f, what, tag)
+        _compare(res_, ref, task, (mode, task, k, what, tag))
+    return st
 
 
 def _window_pairs(n, seed, m, win, sub=0.03, indel=0.01):
