@@ -49,19 +49,23 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
     a.chainIn = chain_.in; a.chainOut = chain_.out; a.chainSrc = chain_.src; a.chainInLanes = chain_.inLanes;
     a.chainBlocks = chain_.blocks; a.rowBase = chain_.rowBase;
     const bool chained = chain_.in != nullptr || chain_.out != nullptr;
-    static const bool dbg = getenv("EDLIB_AMD_DEBUG") != nullptr;
-    if (dbg) {
-        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
-        fprintf(stderr, "[edlib_amd] scanGroup nwords=%d mode=%d nlanes=%d S=%d segLen=%d warm=%d cap=%d kcap=%d slotmap=%p posOff=%p rows=%s\n",
-                g.nwords, mode, nlanes, numSegments, segLen, warm, cap, kcap, (const void*)d_slotmap, (const void*)posOff,
-                peqBottom > 1 ? "delay" : (peqBottom ? "bottom" : "top"));
-    }
-    scanTimerStart();
     // full-height HW scans (pass 2 over unrelated reads): scan_reads_kernel for four symbols (register-resident rows: 288 ms
     // per 1M-read step; the full-height kernel with LDS rows picked by M0 took 314 ms there, the banded kernel at full
     // height 325 ms: measured in round 2, the variants are gone), scan_reads_full_kernel above four symbols and for the
     // long word groups
     const bool longGroup = g.nwords > kMaxReadWords;                  // no plain kernel for 12 / 16 words
+    const bool fullHeight = banded_ && mode == EDLIB_MODE_HW && unbanded && (chained || syms_ > 4 || longGroup);
+    const bool bandedKernel = !fullHeight && banded_ && mode == EDLIB_MODE_HW && (!unbanded || syms_ > 4 || longGroup);
+    static const bool dbg = getenv("EDLIB_AMD_DEBUG") != nullptr;
+    if (dbg) {
+        // (the tests read this line; kernel= names the launcher taken below: tests/test_gpu_wide_rows.py)
+        EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+        fprintf(stderr, "[edlib_amd] scanGroup nwords=%d mode=%d nlanes=%d S=%d segLen=%d warm=%d cap=%d kcap=%d slotmap=%p posOff=%p rows=%s kernel=%s syms=%d\n",
+                g.nwords, mode, nlanes, numSegments, segLen, warm, cap, kcap, (const void*)d_slotmap, (const void*)posOff,
+                peqBottom > 1 ? "delay" : (peqBottom ? "bottom" : "top"),
+                fullHeight ? "full" : (bandedKernel ? "banded" : "plain"), syms_);
+    }
+    scanTimerStart();
     // columns a lane walks: the segments' own columns (a launch may cover a prefix of the target only) and their warm-ups
     // (a table of segments comes with its own sum)
     const long long colsScanned = segTable ? tableCols
@@ -79,8 +83,6 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
         a.waveClock = d_clk.p;
     }
 #endif
-    const bool fullHeight = banded_ && mode == EDLIB_MODE_HW && unbanded && (chained || syms_ > 4 || longGroup);
-    const bool bandedKernel = !fullHeight && banded_ && mode == EDLIB_MODE_HW && (!unbanded || syms_ > 4 || longGroup);
     if (peqBottom && (fullHeight || bandedKernel)) EDLIB_AMD_HIP(hipErrorInvalidValue);   // rows only scan_reads_kernel reads
     if (fullHeight) {
         EDLIB_AMD_HIP(launch_scan_reads_full(g.nwords, syms_, a, stream_));
