@@ -197,6 +197,9 @@ def lib():
         if hasattr(L, "edlibAmdBatchPairsSetSharedWindows"):
             L.edlibAmdBatchPairsSetSharedWindows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                              C.c_void_p, C.c_int]
+        if hasattr(L, "edlibAmdBatchPairsSetCells"):
+            L.edlibAmdBatchPairsSetCells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_int]
         if hasattr(L, "edlibAmdBatchCreateSelf"):
             L.edlibAmdBatchCreateSelf.restype = C.c_void_p
             L.edlibAmdBatchCreateSelf.argtypes = [C.c_void_p, C.c_void_p, C.c_int, AlignConfig, C.c_int]
@@ -629,7 +632,12 @@ class PairBatch(_Batch):
     (edlibAmdBatchPairsSetSharedWindows) makes it from (read, strand, window) tuples over a SharedBatch or a
     BothStrandsBatch: the reads and the target windows are gathered from the read batch's resident pools, so a distance
     run, first_hit_windows(), set_shared_windows, run gives start locations and CIGARs of the first hit of every read
-    that mapped, equal to the whole-target HW path answer."""
+    that mapped, equal to the whole-target HW path answer.
+    set_cells(batch, pair_query, pair_target, pair_start=None, pair_length=None, pair_strand=None)
+    (edlibAmdBatchPairsSetCells) makes it from (query, target, window, strand) tuples over a CrossBatch (any kind) or a
+    SelfBatch: the queries and the target windows are gathered from its resident query pool and 4-bit target pack -- the
+    loop set_targets, run, hits(), cell_windows(), set_cells, run gives the locations and CIGARs of the cells a cross
+    batch found without a read being sliced on the host or uploaded again."""
 
     def __init__(self, queries, targets, mode="NW", task="distance", k=-1, additionalEqualities=None, device=0):
         qd, qo = _pack(queries)
@@ -681,6 +689,90 @@ class PairBatch(_Batch):
                                                     None if st is None else st.ctypes.data, n) != 0:
             raise RuntimeError("edlib_amd: set_shared_windows failed: " + last_error())
         self.n = n
+
+
+    def set_cells(self, batch, pair_query, pair_target, pair_start=None, pair_length=None, pair_strand=None):
+        """Replace the pairs by pairs gathered on the device from a CrossBatch (dense, hits=True, occurrences=True,
+        strands="both") or a SelfBatch on the same device (edlibAmdBatchPairsSetCells): pair i is query pair_query[i] of
+        batch -- its reverse complement where pair_strand[i] == 1 -- against
+        targets[pair_target[i]][pair_start[i] : pair_start[i] + pair_length[i]]; pair_start and pair_length both None: every
+        pair takes its whole target.  Over a SelfBatch both indices name sequences of the one set, in any order.  The
+        batch is then what set_pairs over the materialised pairs would have made; the bytes are copied, so the source may
+        be given new targets, run or close afterwards, and it is itself left as it was, whether it has run or not.
+        cell_windows() makes the tuples of best cells (rows of hits(), cells of matrix(), best hits).  A target that is
+        not in the source's 4-bit pack (above 65,536 bases, or a set of more than 16 symbols) is refused by name: pass
+        those pairs through set_pairs.  Raises RuntimeError with last_error() on a refusal, which leaves the batch as it
+        was.  run() before the next results."""
+        if (pair_start is None) != (pair_length is None):
+            raise ValueError("pair_start and pair_length are given together or not at all")
+        pq, pt = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (pair_query, pair_target))
+        n = len(pq)
+        if len(pt) != n:
+            raise ValueError("pair_query and pair_target differ in length")
+        opt = []
+        for a, dt in ((pair_start, np.int32), (pair_length, np.int32), (pair_strand, np.uint8)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=dt).reshape(-1)
+                if len(a) != n:
+                    raise ValueError("the tuple arrays differ in length")
+                a = a if n else np.zeros(1, dtype=dt)
+            opt.append(a)
+        pq, pt = (a if n else np.zeros(1, dtype=np.int32) for a in (pq, pt))
+        if lib().edlibAmdBatchPairsSetCells(self._h, getattr(batch, "_h", None), pq.ctypes.data, pt.ctypes.data,
+                                            *(None if a is None else a.ctypes.data for a in opt), n) != 0:
+            raise RuntimeError("edlib_amd: set_cells failed: " + last_error())
+        self.n = n
+
+
+def cell_windows(mode, query, target, editDistance, endLocation, query_lengths, target_lengths, strand=None):
+    """The tuples PairBatch.set_cells (edlibAmdBatchPairsSetCells) takes for BEST CELLS of a cross batch (numpy only):
+    query / target / editDistance / endLocation are equally long arrays, one entry a cell -- the rows of
+    CrossBatch.hits() with the target of every row, cells of matrix(), or best hits --, with d the cell's distance and e
+    its first end location; query_lengths and target_lengths are the lengths of every query and target of the batch,
+    strand the cells' strand bytes of a both-strand batch (bit 0 is taken; None: all forward).  mode is the cross
+    batch's.  Returns (kept, pair_query, pair_target, pair_start, pair_length, pair_strand): kept the indices of the
+    cells that have a window (int64), the rest int32 / uint8 arrays over them (pair_strand None where none was given),
+    with the window, per target,
+      HW:  [max(0, e - m - d + 1), e]   (an alignment of cost d that ends at e starts at or behind e - m - d + 1)
+      SHW: [0, e]
+      NW:  the whole target.
+    Over that window the PATH answer of the pair batch's mode -- distance, first end, first start, alignment -- is the
+    whole target's, shifted by pair_start.  Left out: cells with distance -1, cells whose first end location is -1 (HW /
+    SHW: the whole query against the empty prefix) and cells of an empty target: a streamed pair set has no empty window.
+    It does NOT serve occurrence runs (CrossBatch.occurrences()): a neighbouring run of the same cell, of distance d',
+    may end within d + d' columns before this run's end e, lie wholly inside [e - m - d + 1, e] and tie with or beat d
+    there, so the window's answer would be the neighbour's.  For occurrences pass tuples of your own to set_cells."""
+    modes = {"NW": 0, "SHW": 1, "HW": 2}
+    if mode not in modes:
+        raise ValueError("mode must be 'NW', 'SHW' or 'HW'")
+    q, t, d, e = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (query, target, editDistance, endLocation))
+    if not (len(q) == len(t) == len(d) == len(e)):
+        raise ValueError("query, target, editDistance and endLocation differ in length")
+    ql = np.asarray(query_lengths, dtype=np.int64).reshape(-1)
+    tl = np.asarray(target_lengths, dtype=np.int64).reshape(-1)
+    m, T = ql[q], tl[t]
+    if mode == "NW":
+        keep = (d >= 0) & (T > 0)
+    else:
+        keep = (d >= 0) & (e >= 0) & (T > 0)
+    kept = np.flatnonzero(keep)
+    q, t, d, e, m, T = (a[kept] for a in (q, t, d, e, m, T))
+    if mode == "HW":
+        start = np.maximum(0, e - m - d + 1)
+        length = e + 1 - start
+    elif mode == "SHW":
+        start = np.zeros(len(kept), dtype=np.int64)
+        length = e + 1
+    else:
+        start = np.zeros(len(kept), dtype=np.int64)
+        length = T
+    st = None
+    if strand is not None:
+        st = np.asarray(strand, dtype=np.uint8).reshape(-1)
+        if len(st) != len(keep):
+            raise ValueError("strand and the cells differ in length")
+        st = np.ascontiguousarray(st[kept] & 1)
+    return kept, q.astype(np.int32), t.astype(np.int32), start.astype(np.int32), length.astype(np.int32), st
 
 
 def first_hit_windows(flat, read_lengths, strand=None):

@@ -473,6 +473,39 @@ EDLIB_API int edlibAmdBatchPairsSetSharedWindows(EdlibAmdBatch* pairs, EdlibAmdB
            }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+EDLIB_API int edlibAmdBatchPairsSetCells(EdlibAmdBatch* pairs, EdlibAmdBatch* cross, const int* pairQuery,
+                                         const int* pairTarget, const int* pairStart, const int* pairLength,
+                                         const unsigned char* pairStrand, int numPairs) {
+    static const char* const fn = "edlibAmdBatchPairsSetCells";
+    if (!pairs || !cross) {                       // (both handles before either is read)
+        set_error("%s: %s%s%s", fn, pairs ? "" : "null pair batch", !pairs && !cross ? " and " : "",
+                  cross ? "" : "null cross batch");
+        return EDLIB_STATUS_ERROR;
+    }
+    if (pairs->windows || pairs->cross || !pairs->impl.isPairs()) {
+        set_error("%s: not available on %s (only the pairs of a batch made by edlibAmdBatchCreatePairs can be replaced)", fn,
+                  kind_of(pairs));
+        return EDLIB_STATUS_ERROR;
+    }
+    if (!cross->cross) {
+        set_error("%s: the pairs cannot be gathered from %s (only from a cross, occurrence or self batch; a window batch has "
+                  "edlibAmdBatchPairsSetWindows, a read batch edlibAmdBatchPairsSetSharedWindows)", fn, kind_of(cross));
+        return EDLIB_STATUS_ERROR;
+    }
+    if (pairs->impl.device() != cross->cross->device()) {
+        set_error("%s: the pair batch is on device %d and %s on device %d: the gather does not cross devices", fn,
+                  pairs->impl.device(), kind_of(cross), cross->cross->device());
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded(fn, 1, [&] {
+               // (gatherSource waits for the source's stream -- its Create and SetTargets prepare asynchronously -- and
+               // changes nothing a caller can observe; the tuples and the envelope are then judged before the pair batch changes)
+               CellSource src;
+               if (cross->cross->gatherSource(fn, src)) return 1;
+               return pairs->impl.setCells(fn, src, pairQuery, pairTarget, pairStart, pairLength, pairStrand, numPairs);
+           }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 EDLIB_API int edlibAmdBatchWindowsSetUnits(EdlibAmdBatch* b, const char* queries, const long long* queryOffsets,
                                            int numQueries, const int* unitQuery, const int* unitStart,
                                            const int* unitLength, const unsigned char* unitStrand, int numUnits) {

@@ -185,6 +185,11 @@ public:
     // what a read batch (not a pair batch) lends to that gather: its query pool and its raw target, behind a wait for
     // init's upload (engine_flat.hip "pairs from a window batch")
     int gatherSource(const char* fn, WindowSource& out);
+    // the same with the pairs named as (query, target, window, strand) tuples over a cross or self batch and gathered from
+    // its query pool and its pack of targets (edlibAmdBatchPairsSetCells; engine_flat.hip "pairs from a cross batch");
+    // pairStart and pairLength both null: every pair takes its whole target
+    int setCells(const char* fn, const CellSource& src, const int* pairQuery, const int* pairTarget, const int* pairStart,
+                 const int* pairLength, const unsigned char* pairStrand, int n);
     bool isPairs() const { return pairsKind_; }
     int device() const { return device_; }
     bool isBothStrands() const { return strands_; }
@@ -498,6 +503,7 @@ private:
     int dropForStreamedSet(const FlatPlan& plan, std::vector<long long>& qnew, std::vector<long long>& tnew);
     int loadFlatSet(const FlatPlan& plan, const std::function<int()>& fill);
     DevBuf<int> d_gatherTuples_;                             // setWindows: pairQuery [n], pairStart [n], pairStrand (bytes)
+                                                             // setCells: the 64-bit bases [n], pairQuery, pairTarget, pairStart [n], pairStrand
     std::vector<long long> gatherQoff_;                      // gatherSource of a both-strand batch: the reads' n + 1 offsets
     DevBuf<uint8_t> d_tabs_; PinBuf h_tabs_;                 // tlut, idToByte, eqtbl of a streamed set
     // a Run (runPairsFlat) and its phases; every scan takes its arguments from flatScanArgs

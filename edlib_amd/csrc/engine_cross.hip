@@ -154,6 +154,12 @@ int CrossBatch::init(const char* queries, const long long* qoffIn, int nq, const
 
     // ---- the cross kernel's share
     const bool kernelShare = !inT.empty() && (int)longQ.size() < nq;
+    // (what a pair batch that gathers from this one is checked against: gatherSource)
+    tlenHost_.resize((size_t)nt);
+    for (int t = 0; t < nt; ++t) tlenHost_[t] = tlen(t);
+    inPack_.assign((size_t)nt, 0);
+    if (kernelShare)
+        for (int t : inT) inPack_[t] = 1;
     // (queries the kernel can take are resident even where this set leaves it nothing: a later setTargets finds them)
     if ((kernelShare || (nq > 0 && longQ.empty())) && uploadQueries(queries, qoff, strands_)) return 1;
     if (kernelShare && deviceSet) {
@@ -370,6 +376,7 @@ int CrossBatch::setTargets(const char* targets, const long long* toffIn, int nt)
     }
     // the host's share, linear in numTargets: the offsets checked, the longest target, the columns by length
     int maxLen = 0;
+    std::vector<int> tlens((size_t)nt);
     for (int t = 0; t < nt; ++t) {
         const long long n = toffIn[t + 1] - toffIn[t];
         if (n < 0) { set_error("%s: bad target offsets (target %d ends before it starts)", fn, t); return 1; }
@@ -379,6 +386,7 @@ int CrossBatch::setTargets(const char* targets, const long long* toffIn, int nt)
             return 1;
         }
         maxLen = std::max(maxLen, (int)n);
+        tlens[(size_t)t] = (int)n;
     }
     const long long tbytes = nt > 0 ? toffIn[nt] - toffIn[0] : 0;
     std::vector<long long> colsBelow;
@@ -407,6 +415,10 @@ int CrossBatch::setTargets(const char* targets, const long long* toffIn, int nt)
     EDLIB_AMD_HIP(hipMemcpyAsync(d_eqtbl_.p, tab_.eqtbl, 512, hipMemcpyHostToDevice, stream_));
     EDLIB_AMD_HIP(hipMemcpyAsync(d_presence_.p, tab_.presence, 32, hipMemcpyHostToDevice, stream_));
     if (adoptTargets(prep, nt)) return 1;
+    // (every target of a streamed set is in the pack; the places of the set before go with it: gatherSource)
+    tlenHost_.swap(tlens);
+    inPack_.assign((size_t)nt, 1);
+    placeReady_ = false;
     // the internal sessions of the set before are gone with it: a streamed set needs none
     outShared_.clear(); outTargets_.clear(); longPairs_.reset(); longCells_.clear(); otherCellIdx_.clear();
     otherCells_ = 0;
@@ -419,6 +431,36 @@ int CrossBatch::setTargets(const char* targets, const long long* toffIn, int nt)
     // (the raw pool and the scratch die here, the set before dies here: behind the pack)
     EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
     noTargets_ = false;
+    return 0;
+}
+
+int CrossBatch::gatherSource(const char* fn, CellSource& out)
+{
+    const char* const what = self_ ? "the self batch" : occ_ ? "the occurrence batch" : "the cross batch";
+    if (noTargets_) {
+        set_error("%s: %s has no targets (edlibAmdBatchCrossSetTargets failed on the device): set them again", fn, what);
+        return 1;
+    }
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    const bool packed = numSorted_ > 0 && d_tpk_.p && d_tdw_.p && d_tperm_.p && d_qpool_.p && d_qoff_.p;
+    if (packed && !placeReady_) {
+        EDLIB_AMD_HIP(d_place_.ensure((size_t)nt_));
+        EDLIB_AMD_HIP(launch_pack_places(d_tperm_.p, numSorted_, d_place_.p, nt_, stream_));
+    }
+    // (Create and SetTargets end with work of theirs in flight; the gather runs on the pair batch's stream)
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    if (packed) placeReady_ = true;
+    out = CellSource{};
+    out.what = what; out.self = self_;
+    out.numQueries = nq_; out.numTargets = nt_;
+    out.h_qlen = self_ ? tlenHost_.data() : qlen_.data();
+    out.h_tlen = tlenHost_.data();
+    out.h_inPack = packed ? inPack_.data() : nullptr;
+    out.d_qpool = d_qpool_.p; out.qpoolBytes = d_qpool_.n; out.d_qoff = d_qoff_.p; out.stranded = strands_;
+    out.d_pack = d_tpk_.p; out.packDwords = (long long)d_tpk_.n; out.d_tdw = d_tdw_.p; out.d_place = d_place_.p;
+    memcpy(out.idToByte, tab_.idToByte, 16);
     return 0;
 }
 

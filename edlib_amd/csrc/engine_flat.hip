@@ -552,6 +552,92 @@ int Batch::gatherSource(const char* fn, WindowSource& out)
     return 0;
 }
 
+// ------------------------------------------------------------ pairs from a cross batch
+
+// edlibAmdBatchPairsSetCells (DESIGN.md §4b "Pairs from a cross batch"): a streamed set whose pairs are (query, target,
+// window, strand) tuples over a cross or self batch `src` on the same device.  The host's pass checks the tuples against
+// the lengths the source keeps (CrossBatch::gatherSource) and builds the offsets of the two pools; they go through
+// planFlat like any streamed set.  The pools are gathered on the device from the source's query pool and its pack of
+// targets (pairs_gather.hip); the rest is setPairs'.  What is refused leaves the batch as it was.
+int Batch::setCells(const char* fn, const CellSource& src, const int* pairQuery, const int* pairTarget, const int* pairStart,
+                    const int* pairLength, const unsigned char* pairStrand, int n)
+{
+    if (n < 0) { set_error("%s: numPairs must be >= 0 (got %d)", fn, n); return 1; }
+    if (n > 0 && (!pairQuery || !pairTarget)) {
+        set_error("%s: pairQuery and pairTarget must not be NULL for %d pairs", fn, n);
+        return 1;
+    }
+    if ((pairStart == nullptr) != (pairLength == nullptr)) {
+        set_error("%s: pairStart and pairLength must both be given or both be NULL (both NULL: every pair takes its whole "
+                  "target); %s is NULL alone", fn, pairStart ? "pairLength" : "pairStart");
+        return 1;
+    }
+    if (flatScanMode() < 0) { set_error(kNoFlatForm, fn, (int)cfg_.mode); return 1; }
+    std::vector<long long> qnew((size_t)n + 1, 0), tnew((size_t)n + 1, 0);
+    for (int p = 0; p < n; ++p) {
+        const int q = pairQuery[p], t = pairTarget[p];
+        if (q < 0 || q >= src.numQueries) {
+            set_error("%s: pair %d names query %d, outside [0, %s = %d) of %s", fn, p, q,
+                      src.self ? "numSequences" : "numQueries", src.numQueries, src.what);
+            return 1;
+        }
+        if (t < 0 || t >= src.numTargets) {
+            set_error("%s: pair %d names target %d, outside [0, %s = %d) of %s", fn, p, t,
+                      src.self ? "numSequences" : "numTargets", src.numTargets, src.what);
+            return 1;
+        }
+        const int tlen = src.h_tlen[t];
+        const int start = pairStart ? pairStart[p] : 0, len = pairLength ? pairLength[p] : tlen;
+        if (start < 0) { set_error("%s: pair %d has a negative pairStart (%d)", fn, p, start); return 1; }
+        if (len < 0) { set_error("%s: pair %d has a negative pairLength (%d)", fn, p, len); return 1; }
+        if ((long long)start + (long long)len > (long long)tlen) {
+            set_error("%s: pair %d ends past target %d (pairStart %d + pairLength %d > its length %d)", fn, p, t, start, len, tlen);
+            return 1;
+        }
+        if (pairStrand && pairStrand[p] > 1) {
+            set_error("%s: pair %d has pairStrand %d (0: the query, 1: its reverse complement)", fn, p, (int)pairStrand[p]);
+            return 1;
+        }
+        if (!src.h_inPack || !src.h_inPack[t]) {
+            set_error("%s: pair %d names target %d (%s bases), which is not resident in the 4-bit pack of %s (a target above "
+                      "%s bases, a set of more than %d distinct symbols, or a set outside the kernel's envelope, ran through "
+                      "an internal session at Create): materialise those pairs and use edlibAmdBatchPairsSetPairs", fn, p, t,
+                      with_commas(tlen).c_str(), src.what, with_commas(kCrossMaxTarget).c_str(), kCrossMaxSyms);
+            return 1;
+        }
+        qnew[(size_t)p + 1] = qnew[p] + src.h_qlen[q];
+        tnew[(size_t)p + 1] = tnew[p] + len;
+    }
+    FlatPlan plan;
+    planFlat(qnew.data(), tnew.data(), n, false, plan, nullptr, nullptr);
+    // the tuples go up, the bases are planned, the pools are gathered
+    const int failed = replaceFlatSet(fn, plan, qnew, tnew, [&]() -> int {
+        const size_t np = (size_t)n;
+        EDLIB_AMD_HIP(d_gatherTuples_.ensure(2 * np + 3 * np + (np + 3) / 4));
+        long long* const dbase = reinterpret_cast<long long*>(d_gatherTuples_.p);        // (first: 8-byte aligned)
+        int* const dq = d_gatherTuples_.p + 2 * np; int* const dt = dq + np; int* const ds = dt + np;
+        uint8_t* const dst = reinterpret_cast<uint8_t*>(ds + np);
+        EDLIB_AMD_HIP(hipMemcpyAsync(dq, pairQuery, np * sizeof(int), hipMemcpyHostToDevice, stream_));
+        EDLIB_AMD_HIP(hipMemcpyAsync(dt, pairTarget, np * sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (pairStart) EDLIB_AMD_HIP(hipMemcpyAsync(ds, pairStart, np * sizeof(int), hipMemcpyHostToDevice, stream_));
+        if (pairStrand) EDLIB_AMD_HIP(hipMemcpyAsync(dst, pairStrand, np, hipMemcpyHostToDevice, stream_));
+        CellsGatherArgs a{};
+        a.pools.numPairs = n; a.pools.qoff = d_qoff_.p; a.pools.toff = d_toff_.p;
+        a.pools.qbytes = plan.qbytes; a.pools.tbytes = plan.tbytes;
+        a.pools.pairQuery = dq; a.pools.pairStart = pairStart ? ds : nullptr; a.pools.pairStrand = pairStrand ? dst : nullptr;
+        a.pools.qpool = d_qpool_.p; a.pools.tpool = d_tpool_.p;
+        a.pairTarget = dt; a.pairBase = dbase;
+        // The gather reads the source's query pool, its offsets, the pack, its dword offsets and the places from THIS
+        // batch's stream.  They are written by the source's Create and SetTargets and by its gatherSource (the places)
+        // only, and gatherSource has waited for the source's stream: nothing is in flight on them, a Run only reads them.
+        // prepareFlat's wait (loadFlatSet) ends the reads before this call returns: the source may change or go afterwards.
+        EDLIB_AMD_HIP(launch_pairs_gather_cells(src, a, stream_));
+        return 0;
+    });
+    if (failed == kSetLost) (void)hipStreamSynchronize(stream_);     // nothing of this batch's reads the source behind the call
+    return failed ? 1 : 0;
+}
+
 int Batch::noResults(const char* who)
 {
     if (noPairs_) set_error("pair batch: it has no pairs (edlibAmdBatchPairsSetPairs failed on the device): set them again");

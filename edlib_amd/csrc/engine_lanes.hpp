@@ -126,6 +126,13 @@ public:
     int occurrencesView(EdlibAmdCrossOccurrences* out);
     bool bothStrands() const { return strands_; }
     bool isOccurrences() const { return occ_; }
+    int device() const { return device_; }
+    // What a pair batch gathers its pairs from (edlibAmdBatchPairsSetCells, `fn` in the messages): the resident query pool
+    // and the pack of the targets the kernel takes, with the host's lengths of every query and target and which targets
+    // are in the pack.  Waits for the batch's stream (Create and SetTargets prepare asynchronously) and makes, once per
+    // target set, the place of every target in the pack's order.  1 with the error set for a batch a failed SetTargets
+    // left without targets.  Nothing a caller can observe changes.
+    int gatherSource(const char* fn, CellSource& out);
 
 private:
     struct Group : LaneGroup {                    // slots: whole tiles, padded with -1
@@ -163,6 +170,13 @@ private:
     int sizeResults();                            // the result buffers of nq_ x nt_ cells, made or grown
     int noResults();                              // the views': sets the error of a batch that has not run (or has no targets)
     int numSorted_ = 0;                           // targets on the cross kernel
+    // gatherSource's: the length of every target and whether it is in the pack (init, initSelf and setTargets keep them;
+    // a self batch's are its sequences', which are its queries too), and the inverse of d_tperm_ on the device, made at
+    // the first call after a target set arrived
+    std::vector<int> tlenHost_;
+    std::vector<uint8_t> inPack_;
+    DevBuf<int> d_place_;
+    bool placeReady_ = false;
     long long sortedCols_ = 0;                    // their columns
     DevBuf<int> d_tlen_;
     DevBuf<int> d_mat_;                           // [3][nt][nq]: editDistance, numLocations, endLocation

@@ -101,9 +101,15 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
         if (sizeHitList(std::max<long long>(1LL << 20, 2LL * n))) return 1;
     }
 
+    // (what a pair batch that gathers from this one is checked against: CrossBatch::gatherSource)
+    tlenHost_.resize((size_t)n);
+    for (int i = 0; i < n; ++i) tlenHost_[i] = len(i);
+    inPack_.assign((size_t)n, 0);
+
     // ---- the kernel's share
     if (inK.size() >= 2) {
         numSorted_ = (int)inK.size();
+        for (int i : inK) inPack_[i] = 1;
         std::vector<long long> colsBelow(numSorted_ + 1, 0);
         std::vector<int> tl(numSorted_);
         for (int r = 0; r < numSorted_; ++r) {

@@ -1,6 +1,8 @@
 // pairs_gather.hip -- the pools of a flat pair set gathered on the device from a window batch's resident query pool and
 // 4-bit target pack (edlibAmdBatchPairsSetWindows; DESIGN.md §4b "Pairs from a window batch"), or from a read batch's
-// query pool and raw target (edlibAmdBatchPairsSetSharedWindows; "Pairs from a read batch").  Pure data movement: a
+// query pool and raw target (edlibAmdBatchPairsSetSharedWindows; "Pairs from a read batch"), or from a cross or self
+// batch's query pool and its pack of many targets (edlibAmdBatchPairsSetCells; "Pairs from a cross batch": a plan kernel
+// writes every pair's 64-bit nibble position in that pack first).  Pure data movement: a
 // thread owns 16 aligned destination bytes (pairs_gather_core.hpp) and a wave stores 1 KiB of consecutive bytes per
 // instruction.  A block first narrows the offsets to the pairs its 4 KiB touch -- every wave searches the same two
 // positions, 64 probes a step -- so that a thread's own binary search runs over a handful of pairs.
@@ -111,6 +113,92 @@ gather_queries_kernel(const long long* __restrict__ qoff, int n, long long total
         r = query_run(d0, total, find_pair(qoff, lo, hi, d0), qoff, src, s_comp);
     }
     store_run(qpool, d0, total, r);
+}
+
+// ---- a cross or self batch's pack: many targets back to back (edlibAmdBatchPairsSetCells; "Pairs from a cross batch")
+
+// place[tperm[i]] = i: where every target lies in the pack's order (place was filled with -1)
+__global__ void __launch_bounds__(kBlockThreads)
+pack_places_kernel(const int* __restrict__ tperm, int numSorted, int* __restrict__ place)
+{
+    const int i = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (i < numSorted) place[tperm[i]] = i;
+}
+
+// the plan: one thread a pair, the 64-bit nibble position of its window's first column (pairStart null: column 0)
+__global__ void __launch_bounds__(kBlockThreads)
+plan_cells_kernel(const int* __restrict__ pairTarget, const int* __restrict__ pairStart, const int* __restrict__ place,
+                  const long long* __restrict__ tdw, int n, long long* __restrict__ base)
+{
+    const int p = blockIdx.x * kBlockThreads + threadIdx.x;
+    if (p < n) base[p] = cell_base(place, tdw, pairTarget[p], pairStart ? pairStart[p] : 0);
+}
+
+// gather_targets_kernel over that pack: the window of pair p starts at nibble src.pairBase[p]
+__global__ void __launch_bounds__(kBlockThreads)
+gather_targets_cells_kernel(const long long* __restrict__ toff, int n, long long total, TargetCellsSource src, IdToByte ids,
+                            uint8_t* __restrict__ tpool)
+{
+    __shared__ uint16_t s_tab2[256];
+    s_tab2[threadIdx.x] = (uint16_t)(ids.b[threadIdx.x & 15] | ids.b[threadIdx.x >> 4] << 8);
+    __syncthreads();
+    int lo, hi;
+    block_pairs(toff, n, total, lo, hi);                         // (every lane of every wave: before any of them leaves)
+    const long long d0 = ((long long)blockIdx.x * kBlockThreads + threadIdx.x) * kRun;
+    if (d0 >= total + 16) return;
+    Run r; r.w[0] = 0; r.w[1] = 0;
+    if (d0 < total) {
+        r = target_run_cells(d0, total, find_pair(toff, lo, hi, d0), toff, src, s_tab2);
+    }
+    store_run_words(tpool, d0, total, r.w[0], r.w[1]);
+}
+
+static unsigned gather_blocks(long long bytes) { return (unsigned)((bytes + 16 + kBlockBytes - 1) / kBlockBytes); }
+
+hipError_t launch_pack_places(const int* tperm, int numSorted, int* place, int numTargets, hipStream_t stream)
+{
+    if (numTargets < 1 || numSorted < 0 || numSorted > numTargets || !place || (numSorted > 0 && !tperm)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(place, 0xff, (size_t)numTargets * sizeof(int), stream);
+    if (e != hipSuccess || numSorted == 0) return e;
+    hipLaunchKernelGGL(pack_places_kernel, dim3((unsigned)((numSorted + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads),
+                       0, stream, tperm, numSorted, place);
+    return hipGetLastError();
+}
+
+hipError_t launch_pairs_gather_cells(const CellSource& c, const CellsGatherArgs& ca, hipStream_t stream)
+{
+    const PairsGatherArgs& a = ca.pools;
+    if (a.numPairs < 1 || a.qbytes < 1 || a.tbytes < 1) return hipErrorInvalidValue;
+    if (!c.d_qpool || !c.d_qoff || !c.d_pack || !c.d_tdw || !c.d_place || !ca.pairTarget || !ca.pairBase || c.packDwords < 1)
+        return hipErrorInvalidValue;
+    // the wide accesses: dwords of the sources, 128-bit stores into the pools, 64-bit bases
+    if ((reinterpret_cast<uintptr_t>(c.d_qpool) & 3) || (reinterpret_cast<uintptr_t>(c.d_pack) & 3) ||
+        (reinterpret_cast<uintptr_t>(ca.pairBase) & 7) ||
+        (reinterpret_cast<uintptr_t>(a.qpool) & 15) || (reinterpret_cast<uintptr_t>(a.tpool) & 15)) return hipErrorInvalidValue;
+    if ((a.qbytes + 16 + kBlockBytes - 1) / kBlockBytes > 0x7fffffffLL || (a.tbytes + 16 + kBlockBytes - 1) / kBlockBytes > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+
+    hipLaunchKernelGGL(plan_cells_kernel, dim3((unsigned)((a.numPairs + kBlockThreads - 1) / kBlockThreads)), dim3(kBlockThreads),
+                       0, stream, ca.pairTarget, a.pairStart, c.d_place, c.d_tdw, a.numPairs, ca.pairBase);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    TargetCellsSource ts{};
+    ts.pack = c.d_pack; ts.ndw = c.packDwords; ts.pairBase = ca.pairBase;
+    IdToByte ids;
+    for (int i = 0; i < 16; ++i) ids.b[i] = c.idToByte[i];
+    hipLaunchKernelGGL(gather_targets_cells_kernel, dim3(gather_blocks(a.tbytes)), dim3(kBlockThreads), 0, stream,
+                       a.toff, a.numPairs, a.tbytes, ts, ids, a.tpool);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+
+    QuerySource qs{};
+    qs.pool = reinterpret_cast<const u32*>(c.d_qpool); qs.ndw = (long long)(c.qpoolBytes / 4);
+    qs.off = c.d_qoff; qs.stranded = c.stranded ? 1 : 0;
+    qs.pairQuery = a.pairQuery; qs.pairStrand = a.pairStrand;
+    hipLaunchKernelGGL(gather_queries_kernel, dim3(gather_blocks(a.qbytes)), dim3(kBlockThreads), 0, stream,
+                       a.qoff, a.numPairs, a.qbytes, qs, a.qpool);
+    return hipGetLastError();
 }
 
 hipError_t launch_pairs_gather(const WindowSource& w, const PairsGatherArgs& a, hipStream_t stream)

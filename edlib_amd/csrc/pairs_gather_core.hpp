@@ -16,6 +16,9 @@
 //     256-entry table (revcomp8).
 //   target pool from a read batch (edlibAmdBatchPairsSetSharedWindows, "Pairs from a read batch"): the source is the raw
 //     target.  Sixteen bytes at any byte position are five dwords funnel-shifted (bytes16); at a pair boundary, bytes8.
+//   target pool from a cross or self batch (edlibAmdBatchPairsSetCells, "Pairs from a cross batch"): the source is the
+//     batch's pack of many targets, each from a dword of its own; a pair's window starts at a 64-bit nibble position
+//     (TargetCellsSource, target_run_cells), the rest is the window batch's codes8 / expand8.
 //
 // This header compiles for the device (pairs_gather.hip) AND for the host (tests/pairs_gather_host.cpp: the same code, the
 // runs walked one by one, checked against numpy slicing: tests/test_pairs_gather_model.py).
@@ -228,6 +231,42 @@ PG_FN Run target_run_bytes(long long d0, long long total, int p, const long long
         while (pos < stop) {
             const int cnt = stop - pos < 8 ? (int)(stop - pos) : 8;
             put(r, (int)(pos - d0), bytes8(src.bytes, src.ndw, s), cnt);
+            pos += cnt; s += cnt;
+        }
+        ++p;
+    }
+    return r;
+}
+
+// ---- targets that are resident back to back in one pack (edlibAmdBatchPairsSetCells: the 4-bit pack of a cross batch)
+
+// The source of the target pool where the pack holds many targets, each from a dword of its own: the pack as dwords (ndw of
+// them) and per pair the nibble position of its window's first column, 8 * (the target's first dword) + pairStart.  The
+// pack may pass 2^31 nibbles: the position is 64 bits wide
+struct TargetCellsSource {
+    const u32* pack; long long ndw;
+    const long long* pairBase;
+};
+
+// The nibble position of a window: target t lies at place[t] in the pack's order and starts at dword tdw[place[t]]
+PG_FN long long cell_base(const int* place, const long long* tdw, int target, int start)
+{
+    return 8 * tdw[place[target]] + (long long)start;
+}
+
+// The run [d0, d0 + 16) of the target pool from such a pack; total = toff[n], p = the pair of byte d0 (d0 < total)
+PG_FN Run target_run_cells(long long d0, long long total, int p, const long long* toff, const TargetCellsSource& src,
+                           const uint16_t* tab2)
+{
+    Run r; r.w[0] = 0; r.w[1] = 0;
+    const long long end = d0 + kRun < total ? d0 + kRun : total;
+    long long pos = d0;
+    while (pos < end) {
+        const long long first = toff[p], next = toff[p + 1], stop = next < end ? next : end;
+        long long s = src.pairBase[p] + (pos - first);
+        while (pos < stop) {
+            const int cnt = stop - pos < 8 ? (int)(stop - pos) : 8;
+            put(r, (int)(pos - d0), expand8(codes8(src.pack, src.ndw, s), tab2), cnt);
             pos += cnt; s += cnt;
         }
         ++p;

@@ -628,6 +628,47 @@ EDLIB_API int edlibAmdBatchPairsSetSharedWindows(EdlibAmdBatch* pairs, EdlibAmdB
     const int* pairQuery, const int* pairStart, const int* pairLength,
     const unsigned char* pairStrand /* NULL: all forward */, int numPairs);
 
+/* The same from a CROSS or SELF batch (start locations and paths for the cells a cross batch found, the alignments of the
+ * pairs within k of a self batch, without a sequence being sliced on the host or uploaded again): the query of pair i is
+ * query pairQuery[i] of `cross` -- its edlibAmdReverseComplement where pairStrand[i] == 1 -- and its target is
+ * target pairTarget[i] [pairStart[i] .. pairStart[i] + pairLength[i]), in the coordinates of that target; pairStart and
+ * pairLength both NULL: every pair takes its whole target.  Over a self batch "query" and "target" are both sequences of
+ * the one set, and any (i, j) is allowed, not only i < j.  Afterwards `pairs` is exactly the batch
+ * edlibAmdBatchPairsSetPairs would have made over these pairs materialised: everything that call keeps and resets this
+ * one keeps and resets, and Run, Results, ResultsFlat, ResultsView, CigarView and Stats follow as there.  Returns 0, or
+ * non-zero with edlibAmdLastError().
+ * The tuples are the caller's own: rows of EdlibAmdCrossHits, cells of the matrix, best hits, runs of an occurrence list,
+ * pairs of EdlibAmdSelfHits.  For a cell of HW distance d and first end location e >= 0 of a query of m bases, the window
+ * [max(0, e - m - d + 1), e] of its target gives the first start, the first end and the alignment of the whole-target
+ * HW / PATH answer, shifted by the window's start; SHW: [0, e]; NW: the whole target (DESIGN.md 4b "Pairs from a cross
+ * batch").
+ * The bytes are copied: when the call returns `pairs` depends on nothing in `cross`, which may be given new targets, run
+ * or destroyed.  `cross` is not changed in any way a caller can observe: its views, its next Run and its Stats stay.
+ * `pairs` is a batch of edlibAmdBatchCreatePairs in any state SetPairs accepts.  `cross` is a batch of
+ * edlibAmdBatchCreateCross, ...CrossHits, ...CrossOccurrences, ...CrossBothStrands, ...CrossHitsBothStrands,
+ * ...CreateSelf, ...SelfHits, ...SelfBothStrands or ...SelfHitsBothStrands in any state after Create or after a
+ * successful edlibAmdBatchCrossSetTargets (any number of Runs, none included).  Target bytes come from its resident 4-bit
+ * pack and its code -> byte table (up to 16 symbols, bytes >= 128 included), query bytes from its resident query pool:
+ * strand 1 of a both-strand batch reads the reverse complement the batch made at Create, from the other kinds it is
+ * reversed and complemented on the fly.  A query of any length the flat envelope takes (up to 1,024 bases) may be named,
+ * those above 256 bases that the cross kernel does not scan included.
+ * Refused, with this function and the reason named: a NULL handle ("null pair batch", "null cross batch"); another kind
+ * of batch on either side; batches on different devices; a batch left without targets by a failed SetTargets;
+ * numPairs < 0; a NULL pairQuery or pairTarget with a positive count; exactly one of pairStart and pairLength NULL (a
+ * NULL pairStrand is all forward).  Per pair, the first offender named with its values: a query or target index out of
+ * range, a negative pairStart or pairLength, pairStart + pairLength beyond that target's length, pairStrand > 1, and a
+ * target that is not in the pack -- one that ran through an internal session at Create because it has more than 65,536
+ * bases or because the union alphabet exceeds 16 symbols, or any sequence of a self set outside the kernel's envelope:
+ * materialise those pairs and use edlibAmdBatchPairsSetPairs.  Then the flat envelope of SetPairs with its messages: an
+ * empty query or window, a query above 1,024 bases, and under EDLIB_TASK_PATH the limits named there.  numPairs == 0 is
+ * valid.  Every refusal is decided on the host from the lengths alone, before either batch changes, and leaves `pairs` as
+ * it was.  Behind that point only a device error can fail the call; it leaves `pairs` without pairs, as a failed SetPairs
+ * does. */
+EDLIB_API int edlibAmdBatchPairsSetCells(EdlibAmdBatch* pairs, EdlibAmdBatch* cross,
+    const int* pairQuery, const int* pairTarget,
+    const int* pairStart, const int* pairLength,        /* both NULL: every pair takes its whole target */
+    const unsigned char* pairStrand /* NULL: all forward */, int numPairs);
+
 /* edlibFreeAlignResult() over results[0..n) (one call instead of n for binding languages). */
 EDLIB_API void edlibAmdFreeResults(EdlibAlignResult* results, int n);
 
