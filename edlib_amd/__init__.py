@@ -113,12 +113,19 @@ class SelfStrands(C.Structure):          # edlib_amd.h EdlibAmdSelfStrands
         (f, C.POINTER(C.c_ubyte)) for f in ("pairStrand", "hitStrand", "nearestStrand")]
 
 
+class SelfComponents(C.Structure):       # edlib_amd.h EdlibAmdSelfComponents
+    _fields_ = [("numSequences", C.c_int), ("numComponents", C.c_int)] + [
+        (f, C.POINTER(C.c_int)) for f in ("label", "componentSize", "componentOffsets", "members")]
+
+
 SELF_DISTANCES = 1                        # EDLIB_AMD_SELF_DISTANCES
 SELF_NEAREST = 2                          # EDLIB_AMD_SELF_NEAREST
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
 CROSS_BEST = 2                            # EDLIB_AMD_CROSS_BEST
 WINDOW_UNITS = 1                          # EDLIB_AMD_WINDOW_UNITS
 WINDOW_BEST = 2                           # EDLIB_AMD_WINDOW_BEST
+COMPONENT_LABELS = 1                      # EDLIB_AMD_COMPONENT_LABELS
+COMPONENT_MEMBERS = 2                     # EDLIB_AMD_COMPONENT_MEMBERS
 
 _lib = None
 
@@ -213,6 +220,8 @@ def lib():
             L.edlibAmdBatchCreateSelfHitsBothStrands.restype = C.c_void_p
             L.edlibAmdBatchCreateSelfHitsBothStrands.argtypes = L.edlibAmdBatchCreateSelf.argtypes
             L.edlibAmdBatchSelfStrands.argtypes = [C.c_void_p, C.c_int, C.POINTER(SelfStrands)]
+        if hasattr(L, "edlibAmdBatchSelfComponents"):
+            L.edlibAmdBatchSelfComponents.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SelfComponents)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -1159,6 +1168,27 @@ class SelfBatch(_Batch):
         out["nearestStrand"] = arr(v.nearestStrand, self.numSequences)
         return out
 
+    def components(self, max_distance=-1, members=False, copy=True):
+        """The connected components of the pairs within max_distance (< 0: the batch's k) of the last run(), labelled on
+        the device (edlibAmdBatchSelfComponents): label int32 [n], the smallest index in each sequence's component;
+        componentSize int32 [n]; numComponents; members=True: also componentOffsets int32 [numComponents + 1] and
+        members int32 [n], the components in ascending order of their labels with the members ascending inside each.
+        Any number of times per run(), at any level up to k.  copy=False: views of the batch's pinned memory, valid until
+        its next components() / run() / close()."""
+        v = SelfComponents()
+        what = COMPONENT_LABELS | (COMPONENT_MEMBERS if members else 0)
+        if lib().edlibAmdBatchSelfComponents(self._h, int(max_distance), what, C.byref(v)) != 0:
+            raise RuntimeError("edlib_amd: self components failed: " + last_error())
+        n, nc = self.numSequences, int(v.numComponents)
+
+        def arr(ptr, count):
+            return CrossBatch._arr(ptr, (count,), copy) if count else np.zeros(0, dtype=np.int32)
+        out = {"label": arr(v.label, n), "componentSize": arr(v.componentSize, n), "numComponents": nc}
+        if members:
+            out["componentOffsets"] = arr(v.componentOffsets, nc + 1)
+            out["members"] = arr(v.members, n)
+        return out
+
     def results(self, raw=True):
         raise RuntimeError("edlib_amd: a self batch has no per-unit results: use condensed() / hits() / nearest()")
 
@@ -1187,6 +1217,18 @@ def pairs_within(seqs, k, additionalEqualities=None, strands="forward"):
         if b.both_strands:
             out.update(b.strands())
         return out
+    finally:
+        b.close()
+
+
+def cluster_within(seqs, k, additionalEqualities=None, strands="forward"):
+    """Single linkage at k NW edits in one device batch: label int32 [n], the smallest index among the sequences that
+    sequence i reaches through pairs within k (strands="both": in either orientation).  The pairs stay on the device
+    (SelfBatch(..., hits=True).components())."""
+    b = SelfBatch(seqs, k, additionalEqualities, hits=True, strands=strands)
+    try:
+        b.run()
+        return b.components()["label"]
     finally:
         b.close()
 
@@ -1221,6 +1263,36 @@ def self_nearest_model(n, first, second, ed):
     has2[has2] = o[lead[has2] + 1] == o[lead[has2]]
     out["secondDistance"][o[lead[has2]]] = key[lead[has2] + 1] >> 32
     return out
+
+
+def self_components_model(n, rowOffsets, partner, editDistance, level):
+    """The component rules of a self batch stated in plain Python (what SelfBatch.components(level, members=True) must
+    equal): rowOffsets / partner / editDistance list pairs as hits() does (CSR by the first sequence; a condensed vector
+    goes in as rowOffsets = the triangle's).  A pair is an edge where its distance d is 0 <= d and, with level >= 0,
+    d <= level.  Union by minimum: the root of a component is its smallest index, whatever the order of the edges."""
+    off = np.asarray(rowOffsets, dtype=np.int64).reshape(-1)
+    p = np.asarray(partner, dtype=np.int64).reshape(-1)
+    d = np.asarray(editDistance, dtype=np.int64).reshape(-1)
+    row = np.repeat(np.arange(n, dtype=np.int64), np.diff(off)) if n else np.zeros(0, dtype=np.int64)
+    keep = (d >= 0) & ((d <= level) if level >= 0 else True)
+    parent = list(range(n))
+
+    def find(x):
+        while parent[x] != x:
+            parent[x] = parent[parent[x]]
+            x = parent[x]
+        return x
+    for a, b in zip(row[keep].tolist(), p[keep].tolist()):
+        a, b = find(a), find(b)
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+    label = np.array([find(x) for x in range(n)], dtype=np.int32)
+    count = np.bincount(label, minlength=n) if n else np.zeros(0, dtype=np.int64)
+    order = np.lexsort((np.arange(n), label)).astype(np.int32)           # by label, then by index
+    roots = np.flatnonzero(label == np.arange(n))
+    offsets = np.concatenate([[0], np.cumsum(count[roots])]).astype(np.int32)
+    return {"label": label, "componentSize": count[label].astype(np.int32), "numComponents": int(len(roots)),
+            "componentOffsets": offsets, "members": order}
 
 
 def window_best_model(unit_query, ed, numQueries):

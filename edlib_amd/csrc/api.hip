@@ -363,6 +363,23 @@ EDLIB_API int edlibAmdBatchSelfStrands(EdlibAmdBatch* b, int what, EdlibAmdSelfS
     return guarded("edlibAmdBatchSelfStrands", 1, [&] { return b->cross->selfStrandsView(what, out); }) ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+EDLIB_API int edlibAmdBatchSelfComponents(EdlibAmdBatch* b, int maxDistance, int what, EdlibAmdSelfComponents* out) {
+    // (the parts first: they are judged without a batch)
+    if (!what || (what & ~(EDLIB_AMD_COMPONENT_LABELS | EDLIB_AMD_COMPONENT_MEMBERS))) {
+        set_error("edlibAmdBatchSelfComponents: unknown parts %d (EDLIB_AMD_COMPONENT_LABELS, with or without "
+                  "EDLIB_AMD_COMPONENT_MEMBERS)", what);
+        return EDLIB_STATUS_ERROR;
+    }
+    if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
+    if (!b->cross || !b->cross->isSelf()) {
+        set_error("edlibAmdBatchSelfComponents: not a self batch (components are defined for self batches only: create one "
+                  "with edlibAmdBatchCreateSelf or edlibAmdBatchCreateSelfHits)");
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchSelfComponents", 1, [&] { return b->cross->selfComponents(maxDistance, what, out); })
+               ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 static EdlibAmdBatch* create_windows(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
                                      const char* target, int targetLength, const int* unitQuery, const int* unitStart,
                                      const int* unitLength, const unsigned char* unitStrand, int numUnits,

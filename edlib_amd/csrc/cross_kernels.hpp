@@ -148,6 +148,23 @@ hipError_t launch_self_nearest_strand_hits(const int* best, const uint8_t* bestS
                                            hipStream_t stream);
 // distances computed by other engines into the condensed vector: ed[cell[i]] = vals[i]
 hipError_t launch_self_scatter(const long long* cell, const int* vals, long long n, int* ed, hipStream_t stream);
+// the connected components of a self batch's pairs within a level (self_components.hip): views into one block of
+// ints(n) ints -- first what travels, back to back: label [n], size [n], numComponents (and a pad), offsets [n + 1],
+// members [n] (and a pad) -- then the work arrays
+struct SelfComponentsBuffers {
+    int *label, *size, *numComponents, *offsets, *members;
+    int *parent, *count, *iota, *slabel, *flag, *rank;
+    static size_t ints(int n);
+    static SelfComponentsBuffers carve(int* base, int n);
+};
+// bytes of scratch the members' sort and scan need for n sequences
+hipError_t self_components_scratch(int n, size_t* bytes);
+// init, hook, flatten, sizes and (members) the grouping, enqueued on the stream.  The edges are the finished hit list's
+// (cond == nullptr: the sorted keys (i << 32) | j, the partner and ed planes, [numHits] each) or the condensed vector's
+// (cond), each where its distance d is 0 <= d and, with level >= 0, d <= level.  n = 0: nothing
+hipError_t launch_self_components(const SelfComponentsBuffers& b, int n, const unsigned long long* skey, const int* partner,
+                                  const int* ed, long long numHits, const int* cond, int level, bool members,
+                                  void* scratch, size_t scratchBytes, hipStream_t stream);
 // per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are
 // best index / best distance / second distance
 hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,

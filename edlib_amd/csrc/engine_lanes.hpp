@@ -119,6 +119,10 @@ public:
     int selfView(int what, EdlibAmdSelfView* out);
     int selfHitsView(EdlibAmdSelfHits* out);
     int selfStrandsView(int what, EdlibAmdSelfStrands* out);
+    // The connected components of the pairs within maxDistance (< 0: the batch's k) of the last Run, labelled on the device
+    // from the finished hit list or the condensed vector as they lie there (DESIGN.md §4h "Components"); any number of
+    // times per Run.  A refusal leaves the batch and its other views as they were
+    int selfComponents(int maxDistance, int what, EdlibAmdSelfComponents* out);
     bool isSelf() const { return self_; }
     int view(int what, EdlibAmdCrossView* out);
     int hitsView(EdlibAmdCrossHits* out);
@@ -216,6 +220,9 @@ private:
     std::vector<int> selfEmptyVal_;
     DevBuf<int> d_near_;                          // [3][n]: nearest, nearestDistance, secondDistance
     PinnedPart near_;
+    // components: one block carved by SelfComponentsBuffers, made at the first call and kept; comp_ is fetched at every call
+    DevBuf<int> d_comp_;
+    PinnedPart comp_;
     // both-strand self batches: d_smat_ is the condensed strand vector, cellStrand_ its (or the hit list's) pinned part;
     // d_sbest_ is [2 n] for the hits finish, then [n] the strand byte of every nearest partner (bestStrand_); a pair of
     // selfOther_ behind the empty ones is the pairs 2c (forward) and 2c + 1 (the lower index reverse-complemented) of

@@ -382,4 +382,51 @@ int CrossBatch::selfStrandsView(int what, EdlibAmdSelfStrands* out)
     return 0;
 }
 
+int CrossBatch::selfComponents(int maxDistance, int what, EdlibAmdSelfComponents* out)
+{
+    if (!haveRun_) { set_error("self batch: no results (Run it first)"); return 1; }
+    if (!what || (what & ~(EDLIB_AMD_COMPONENT_LABELS | EDLIB_AMD_COMPONENT_MEMBERS))) {
+        set_error("self components: unknown parts %d", what);
+        return 1;
+    }
+    if (cfg_.k >= 0 && maxDistance > cfg_.k) {
+        set_error("self components: maxDistance %d is above the batch's k = %d: the batch kept no pairs beyond k (create it "
+                  "with a larger k)", maxDistance, cfg_.k);
+        return 1;
+    }
+    const int level = maxDistance >= 0 ? maxDistance : cfg_.k;       // (k < 0 too: every reported pair)
+    const bool members = (what & EDLIB_AMD_COMPONENT_MEMBERS) != 0;
+    const int n = nq_;
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    EDLIB_AMD_HIP(d_comp_.ensure(SelfComponentsBuffers::ints(n)));
+    const SelfComponentsBuffers b = SelfComponentsBuffers::carve(d_comp_.p, n);
+    size_t scratch = 0;
+    if (members && n > 0) {
+        EDLIB_AMD_HIP(self_components_scratch(n, &scratch));
+        EDLIB_AMD_HIP(hitList_.needScratch(scratch));
+    }
+    // the edges where the Run left them: the finished list's partner and distance planes with the sorted keys its finish
+    // leaves behind (their high half is the row), or the condensed vector
+    const long long numHits = hits_ ? hitList_.outN : 0;
+    EDLIB_AMD_HIP(launch_self_components(b, n, hits_ ? hitList_.skey.p : nullptr, hits_ ? hitList_.out() : nullptr,
+                                         hits_ ? hitList_.out() + (size_t)numHits : nullptr, numHits,
+                                         hits_ ? nullptr : d_mat_.p, level, members, hitList_.tmp.p, hitList_.tmp.n, stream_));
+    // label, componentSize, numComponents and -- behind them on the device -- the offsets and members: one copy
+    const size_t ints = n > 0 ? (members ? 4 * (size_t)n + 3 : 2 * (size_t)n + 1) : 0;
+    comp_.fetched = false;
+    EDLIB_AMD_HIP(comp_.fetch(d_comp_.p, ints * sizeof(int), stream_, 0, 4 * sizeof(int)));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    comp_.fetched = true;
+    if (n == 0) memset(comp_.h.p, 0, 4 * sizeof(int));             // no component: componentOffsets is {0}
+    const int* h = reinterpret_cast<const int*>(comp_.h.p);
+    memset(out, 0, sizeof *out);
+    out->numSequences = n;
+    out->numComponents = n > 0 ? h[2 * (size_t)n] : 0;
+    out->label = h; out->componentSize = h + n;
+    if (members) { out->componentOffsets = h + (b.offsets - b.label); out->members = h + (b.members - b.label); }
+    return 0;
+}
+
 }  // namespace edlib_amd

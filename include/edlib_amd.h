@@ -415,6 +415,37 @@ typedef struct {
 } EdlibAmdSelfStrands;
 EDLIB_API int edlibAmdBatchSelfStrands(EdlibAmdBatch* batch, int what, EdlibAmdSelfStrands* out);
 
+/* The connected components of the last Run of a self batch (single linkage: UMI / barcode collapsing, amplicon and OTU
+ * clustering, clonotype grouping, duplicate removal), labelled on the device from the pairs where the Run left them --
+ * the finished hit list or the condensed vector -- so that numSequences ints cross the link instead of the pairs.
+ * With L = maxDistance if it is >= 0, else the batch's k (and if that is < 0 too, every reported pair counts), the graph
+ * has the sequences as vertices and an edge {i, j} for every pair whose distance d, as edlibAmdBatchSelfView /
+ * edlibAmdBatchSelfHits report it (both strands: the combined distance), satisfies 0 <= d, and d <= L when L >= 0.  An
+ * empty sequence is reported at the other's length whatever k, so under d <= L it joins only sequences of length <= L:
+ * its true edit distance.  One Run at k serves every level up to k: call it any number of times per Run.
+ * label[i] is the SMALLEST index in i's component -- canonical, independent of the order in which the device meets the
+ * edges, equal bit for bit to a union-find on the host; numComponents is the number of i with label[i] == i;
+ * componentSize[i] the number of sequences in i's component.  With EDLIB_AMD_COMPONENT_MEMBERS the components are listed
+ * in ascending order of their labels, the members ascending inside each: component c is
+ * members[componentOffsets[c] .. componentOffsets[c + 1]), and label[members[componentOffsets[c]]] is the c-th smallest
+ * label.  The label parts are always filled.
+ * All four kinds of self batch are accepted, after a successful Run; numSequences 0 and 1 are valid (no component, one
+ * of size 1).  The pointers are pinned memory the batch owns, valid until the next edlibAmdBatchSelfComponents, Run or
+ * Destroy.  Refused with the reason in edlibAmdLastError(), the batch and its other views (and pointers a caller holds
+ * from them) left as they were: `what` 0 or with unknown bits, NULL batch or out, any other kind of batch, a batch that
+ * has not run, and maxDistance > k on a batch with k >= 0 (it kept no pairs beyond k).  Stats are untouched. */
+typedef struct {
+    int numSequences;
+    int numComponents;
+    const int* label;             /* [numSequences]      the LOWEST index in i's component            */
+    const int* componentSize;     /* [numSequences]      number of sequences in i's component         */
+    const int* componentOffsets;  /* [numComponents + 1] asked with EDLIB_AMD_COMPONENT_MEMBERS, else NULL */
+    const int* members;           /* [numSequences]      likewise: sequences grouped by component     */
+} EdlibAmdSelfComponents;
+#define EDLIB_AMD_COMPONENT_LABELS  1
+#define EDLIB_AMD_COMPONENT_MEMBERS 2
+EDLIB_API int edlibAmdBatchSelfComponents(EdlibAmdBatch* batch, int maxDistance, int what, EdlibAmdSelfComponents* out);
+
 /* A shared-target batch whose results are, per read, EVERY occurrence within k along the target -- the search question of
  * adapter / primer trimming, concatemer splitting, repeat finding and multi-mapping reads, which no choice of k makes
  * edlibAlign() answer (it keeps the columns of the single best score only).
