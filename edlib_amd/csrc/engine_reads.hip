@@ -64,6 +64,8 @@ int Batch::scanGroup(ReadGroup& g, int mode, const int* d_slotmap, int nlanes, i
                 g.nwords, mode, nlanes, numSegments, segLen, warm, cap, kcap, (const void*)d_slotmap, (const void*)posOff,
                 peqBottom > 1 ? "delay" : (peqBottom ? "bottom" : "top"),
                 fullHeight ? "full" : (bandedKernel ? "banded" : "plain"), syms_);
+        // (the line above is matched to its end by the tests: the depth of the delay rows goes on one of its own)
+        if (peqBottom > 1) fprintf(stderr, "[edlib_amd] scanGroup delayRows=%d\n", peqBottom - 1);
     }
     scanTimerStart();
     // columns a lane walks: the segments' own columns (a launch may cover a prefix of the target only) and their warm-ups
@@ -339,11 +341,12 @@ int Batch::runGroupScans(ReadGroup& g, bool fullOnly)
             // When the pass goes to the plain kernel (scanGroup: HW, four symbols, up to kMaxReadWords words, no chain), the
             // rebuilt rows are bottom-aligned: row m-1 at bit 31 of the last word, where the column reads the score's
             // delta with two full-rate shifts.  The pre-scan below shares them, on the same kernel.
-            // Where the group's longest read leaves three rows of its last word free, the rows carry delay rows above
-            // row m-1 and the score moves once per four columns (reads_kernels.hip: scan_reads_kernel<NWD, 2, true, true>).
+            // Where the group's longest read leaves seven rows of its last word free, the rows carry seven delay rows above
+            // row m-1 and the score moves once per eight columns; where it leaves three, three rows and once per four
+            // (reads_kernels.hip: scan_reads_kernel<NWD, 2, true, R>); else bottom-aligned rows without delay rows.
             const bool bottomOk = plain && mode == EDLIB_MODE_HW && syms_ == 4 && g.nwords <= kMaxReadWords &&
                                   chain_.in == nullptr && chain_.out == nullptr;
-            const int bottom = !bottomOk ? 0 : (delay_rows_fit(g.nwords, g.mMax) ? 1 + kDelayRows : 1);
+            const int bottom = !bottomOk ? 0 : 1 + delay_rows_for(g.nwords, g.mMax);
             // The main launch over the leftovers is eight rounds of resident workgroups at 1M reads, and with uniform segments
             // its end is ragged: for the time of up to one segment every workgroup that finishes leaves its slot empty.
             // Its segments taper instead (plan_segments_tapered): the uniform length while much is left, then ever shorter

@@ -162,42 +162,44 @@
     if constexpr (NA == 1) RC_COLUMN_ASM_NS(1, WORD0); if constexpr (NA == 2) RC_COLUMN_ASM_NS(2, WORD0); if constexpr (NA == 3) RC_COLUMN_ASM_NS(3, WORD0); \
     if constexpr (NA == 4) RC_COLUMN_ASM_NS(4, WORD0); if constexpr (NA == 5) RC_COLUMN_ASM_NS(5, WORD0); if constexpr (NA == 6) RC_COLUMN_ASM_NS(6, WORD0); \
     if constexpr (NA == 7) RC_COLUMN_ASM_NS(7, WORD0); if constexpr (NA == 8) RC_COLUMN_ASM_NS(8, WORD0);
-// Delay rows (scan_reads_kernel<NWD, 2, true, true>: rows built bottom-aligned with three all-match rows ABOVE row m-1, which
-// then sits at bit 28 of the last word).  An all-match row copies the row above it one column late, so bits
-// 28..31 of one column's Ph / Mh are the followed row's deltas of that column and the three before it, and the score moves
-// once per group of four columns, from two popcounts.  Three bodies per word count, in both forms of the column:
-//   NONE     the first three columns of a group: no score block at all (five words: 48 instructions);
-//   CAPTURE  the fourth: Ph >> 28 and Mh >> 28 of the last word to two outputs (two full-rate shifts), taken where the score
+// Delay rows (scan_reads_kernel<NWD, 2, true, R>, R = 3 or 7: rows built bottom-aligned with R all-match rows ABOVE row m-1,
+// which then sits at bit 31 - R of the last word).  An all-match row copies the row above it one column late, so
+// bits 31 - R .. 31 of one column's Ph / Mh are the followed row's deltas of that column and the R before it, and the score
+// moves once per group of R + 1 columns, from two popcounts.  Three bodies per word count, in both forms of the column; the
+// depth reaches them as two immediates, GSH = 32 - (R + 1) (28 or 24) and GBIT = 31 - R (28 or 24 as well: row m-1's own bit):
+//   NONE     the first R columns of a group: no score block at all (five words: 48 instructions);
+//   CAPTURE  the last: Ph >> GSH and Mh >> GSH of the last word to two outputs (two full-rate shifts), taken where the score
 //            block stood -- before the last word's registers are shifted in place, which drops bit 31 -- and behind them
 //            the group's update, score += popcount(nph) - popcount(nmh): two v_bcnt_u32_b32 (half rate; the first takes the
-//            old score as its addend) and a subtract.  Inside the statement, so that a group's nibbles die with it (left
-//            to the compiler, the popcounts of a whole 16-column word sank to its end: six registers, a wave at five
-//            words).  The old score stays in its register: the kernel's hit test reads both (scan_reads_kernel);
-//   BIT28    the ragged tail of the target (up to 15 columns of the last segment): the score every column, from bit 28.
+//            old score as its addend) and a subtract.  Inside the statement, so that a group's nibbles (bytes, at seven
+//            rows) die with it (left to the compiler, the popcounts of a whole 16-column word sank to its end: six
+//            registers, a wave at five words).  The old score stays in its register: the kernel's hit test reads both
+//            (scan_reads_kernel);
+//   BIT      the ragged tail of the target (up to 15 columns of the last segment): the score every column, from bit GBIT.
 #define RP_SC_NONE(PH, MH)
-#define RP_SC_CAPTURE(PH, MH) "v_lshrrev_b32_e64 %[nph], 28, " PH "\n\t" "v_lshrrev_b32_e64 %[nmh], 28, " MH "\n\t" RC_GROUP_UPDATE
-#define RP_SC_BIT28(PH, MH)   "v_bfe_u32 %[t], " PH ", 28, 1\n\t" "v_add_u32_e64 %[scoreN], %[score], %[t]\n\t" \
-                              "v_bfe_i32 %[t], " MH ", 28, 1\n\t" "v_add_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
-#define RP_COLUMN_ASM_D0(N) asm(RC_HEAD RP_BODY_##N(RP_SC_NONE) : RC_OUTS_##N, RP_TEMPS RP_XT_##N : RC_INS_##N RP_XI_##N)
+#define RP_SC_CAPTURE(PH, MH) "v_lshrrev_b32_e64 %[nph], %[gsh], " PH "\n\t" "v_lshrrev_b32_e64 %[nmh], %[gsh], " MH "\n\t" RC_GROUP_UPDATE
+#define RP_SC_BIT(PH, MH)     "v_bfe_u32 %[t], " PH ", %[gbit], 1\n\t" "v_add_u32_e64 %[scoreN], %[score], %[t]\n\t" \
+                              "v_bfe_i32 %[t], " MH ", %[gbit], 1\n\t" "v_add_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
+#define RP_COLUMN_ASM_D0(N, GSH, GBIT) asm(RC_HEAD RP_BODY_##N(RP_SC_NONE) : RC_OUTS_##N, RP_TEMPS RP_XT_##N : RC_INS_##N RP_XI_##N)
 #define RC_GROUP_UPDATE "v_bcnt_u32_b32 %[scoreN], %[nph], %[score]\n\t" "v_bcnt_u32_b32 %[t], %[nmh], 0\n\t" \
                         "v_sub_u32_e64 %[scoreN], %[scoreN], %[t]\n\t"
 #define RC_GROUP_OUTS [nph] "=&v"(nph), [nmh] "=&v"(nmh), [scoreN] "=&v"(scoreN)
-#define RP_COLUMN_ASM_D1(N) asm(RC_HEAD RP_BODY_##N(RP_SC_CAPTURE) : RC_OUTS_##N, RC_GROUP_OUTS, RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
-#define RP_COLUMN_ASM_D2(N) asm(RC_HEAD RP_BODY_##N(RP_SC_BIT28) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score) RP_XI_##N)
-#define RP_COLUMN_DISPATCH_D(F, NWD) \
-    if constexpr (NWD == 2) RP_COLUMN_ASM_D##F(2); if constexpr (NWD == 3) RP_COLUMN_ASM_D##F(3); \
-    if constexpr (NWD == 4) RP_COLUMN_ASM_D##F(4); if constexpr (NWD == 5) RP_COLUMN_ASM_D##F(5);
+#define RP_COLUMN_ASM_D1(N, GSH, GBIT) asm(RC_HEAD RP_BODY_##N(RP_SC_CAPTURE) : RC_OUTS_##N, RC_GROUP_OUTS, RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score), [gsh] "n"(GSH) RP_XI_##N)
+#define RP_COLUMN_ASM_D2(N, GSH, GBIT) asm(RC_HEAD RP_BODY_##N(RP_SC_BIT) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RP_TEMPS RP_XT_##N : RC_INS_##N, [score] "v"(score), [gbit] "n"(GBIT) RP_XI_##N)
+#define RP_COLUMN_DISPATCH_D(F, NWD, GSH, GBIT) \
+    if constexpr (NWD == 2) RP_COLUMN_ASM_D##F(2, GSH, GBIT); if constexpr (NWD == 3) RP_COLUMN_ASM_D##F(3, GSH, GBIT); \
+    if constexpr (NWD == 4) RP_COLUMN_ASM_D##F(4, GSH, GBIT); if constexpr (NWD == 5) RP_COLUMN_ASM_D##F(5, GSH, GBIT);
 // ... on the alignbit chain (one word, six to eight): the last word's Ph / Mh are not shifted in place there, the block stays last
-#define RC_SC_CAPTURE(c)  "v_lshrrev_b32_e64 %[nph], 28, %[ph" #c "]\n\t" "v_lshrrev_b32_e64 %[nmh], 28, %[mh" #c "]\n\t"
-#define RC_SC_BIT28(c)    "v_bfe_u32 %[t], %[ph" #c "], 28, 1\n\t" "v_bfe_i32 %[s], %[mh" #c "], 28, 1\n\t" "v_add3_u32 %[scoreN], %[score], %[t], %[s]\n\t"
+#define RC_SC_CAPTURE(c)  "v_lshrrev_b32_e64 %[nph], %[gsh], %[ph" #c "]\n\t" "v_lshrrev_b32_e64 %[nmh], %[gsh], %[mh" #c "]\n\t"
+#define RC_SC_BIT(c)      "v_bfe_u32 %[t], %[ph" #c "], %[gbit], 1\n\t" "v_bfe_i32 %[s], %[mh" #c "], %[gbit], 1\n\t" "v_add3_u32 %[scoreN], %[score], %[t], %[s]\n\t"
 #define RC_SC_CAPTURE_X(c) RC_SC_CAPTURE(c)
-#define RC_SC_BIT28_X(c) RC_SC_BIT28(c)
-#define RC_COLUMN_ASM_D0(N) RC_COLUMN_ASM_NS(N, RC_WORD0_HW)
-#define RC_COLUMN_ASM_D1(N) asm(RC_HEAD RC_WORD0_HW RC_REST_##N RC_SC_CAPTURE_X(RC_LAST_##N) RC_GROUP_UPDATE : RC_OUTS_##N, RC_GROUP_OUTS, RC_TEMPS : RC_INS_##N, [score] "v"(score))
-#define RC_COLUMN_ASM_D2(N) asm(RC_HEAD RC_WORD0_HW RC_REST_##N RC_SC_BIT28_X(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score))
-#define RC_COLUMN_DISPATCH_D(F, NWD) \
-    if constexpr (NWD == 1) RC_COLUMN_ASM_D##F(1); if constexpr (NWD == 6) RC_COLUMN_ASM_D##F(6); \
-    if constexpr (NWD == 7) RC_COLUMN_ASM_D##F(7); if constexpr (NWD == 8) RC_COLUMN_ASM_D##F(8);
+#define RC_SC_BIT_X(c) RC_SC_BIT(c)
+#define RC_COLUMN_ASM_D0(N, GSH, GBIT) RC_COLUMN_ASM_NS(N, RC_WORD0_HW)
+#define RC_COLUMN_ASM_D1(N, GSH, GBIT) asm(RC_HEAD RC_WORD0_HW RC_REST_##N RC_SC_CAPTURE_X(RC_LAST_##N) RC_GROUP_UPDATE : RC_OUTS_##N, RC_GROUP_OUTS, RC_TEMPS : RC_INS_##N, [score] "v"(score), [gsh] "n"(GSH))
+#define RC_COLUMN_ASM_D2(N, GSH, GBIT) asm(RC_HEAD RC_WORD0_HW RC_REST_##N RC_SC_BIT_X(RC_LAST_##N) : RC_OUTS_##N, [scoreN] "=&v"(scoreN), RC_TEMPS : RC_INS_##N, [score] "v"(score), [gbit] "n"(GBIT))
+#define RC_COLUMN_DISPATCH_D(F, NWD, GSH, GBIT) \
+    if constexpr (NWD == 1) RC_COLUMN_ASM_D##F(1, GSH, GBIT); if constexpr (NWD == 6) RC_COLUMN_ASM_D##F(6, GSH, GBIT); \
+    if constexpr (NWD == 7) RC_COLUMN_ASM_D##F(7, GSH, GBIT); if constexpr (NWD == 8) RC_COLUMN_ASM_D##F(8, GSH, GBIT);
 #define RC_COLUMN_DISPATCH_B(NWD, WORD0) \
     if constexpr (NWD == 1) RC_COLUMN_ASM_B(1, WORD0); if constexpr (NWD == 2) RC_COLUMN_ASM_B(2, WORD0); if constexpr (NWD == 3) RC_COLUMN_ASM_B(3, WORD0); \
     if constexpr (NWD == 4) RC_COLUMN_ASM_B(4, WORD0); if constexpr (NWD == 5) RC_COLUMN_ASM_B(5, WORD0); if constexpr (NWD == 6) RC_COLUMN_ASM_B(6, WORD0); \

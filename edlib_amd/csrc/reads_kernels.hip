@@ -121,7 +121,7 @@ hipError_t launch_pack_target_2bit(const uint8_t* raw, const uint8_t* lut, int T
 // row m-1 is bit 31 of the last word, and the pad bits below are set in the row of every symbol.  pad is below 32 for the
 // reads of a group (read_group_words: they reach into the last word); the padding slots of a list (m = 1) and any shorter
 // read get whole words of pad the same way, nothing here or in the scan's initial state assumes pad < 32.
-// bottomAlign = 1 + R (kDelayRows; scan_reads_kernel<NWD, 2, true, true>): R delay rows above row m-1, set in the row of every
+// bottomAlign = 1 + R (R = 3 or 7; scan_reads_kernel<NWD, 2, true, R>): R delay rows above row m-1, set in the row of every
 // symbol like the pads, and pad = 32 NWD - R - m: row m-1 is bit 31 - R of the last word.  The caller sees to m + R <= 32 NWD.
 template <int NWD>
 __global__ void __launch_bounds__(256)
@@ -224,7 +224,7 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
                                   int* alphaExtra, hipStream_t stream, int bottomAlign)
 {
     if (nslots == 0) return hipSuccess;
-    if (bottomAlign != 0 && bottomAlign != 1 && bottomAlign != 1 + kDelayRows) return hipErrorInvalidValue;
+    if (!bottom_align_valid(bottomAlign)) return hipErrorInvalidValue;
     if (syms != 4 && syms != 8 && syms != 16) return hipErrorInvalidValue;
     switch (nwords) {
 #define CASE(N) case N: return launch_build_peq_t<N>(reads, qoff, perm, nslots, syms, eqtbl, tpres, kcfg, peq, qlen, kinit, alphaExtra, stream, bottomAlign);
@@ -248,10 +248,10 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 
 #define EDLIB_AMD_DISPATCH_COLUMN_DELAY(FORM, sym)                                         \
     switch (sym) {                                                                         \
-        case 0:  column_step_delay<NWD, FORM>(E0, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym0"); break; \
-        case 1:  column_step_delay<NWD, FORM>(E1, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym1"); break; \
-        case 2:  column_step_delay<NWD, FORM>(E2, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym2"); break; \
-        default: column_step_delay<NWD, FORM>(E3, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym3"); break; \
+        case 0:  column_step_delay<NWD, FORM, R>(E0, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym0"); break; \
+        case 1:  column_step_delay<NWD, FORM, R>(E1, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym1"); break; \
+        case 2:  column_step_delay<NWD, FORM, R>(E2, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym2"); break; \
+        default: column_step_delay<NWD, FORM, R>(E3, Pv, Mv, score, nph, nmh, zr0, zr1); asm volatile("; sym3"); break; \
     }
 
 // Record column `col` if it ties or improves the best bottom-row score
@@ -267,17 +267,20 @@ hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, co
 // BOTTOM (HW): the Peq rows were built bottom-aligned (build_peq_reads_kernel), query row r at bit 32 NWD - m + r.  The
 // pad rows below bit 32 NWD - m match every symbol; with HW's zero row -1 they stay at D = 0 in every column, so the real
 // rows see the boundary they always saw, and the followed row m-1 is bit 31 of the last word in every lane.
-// DELAY (with BOTTOM): the rows carry kDelayRows all-match rows above row m-1 (bit 28 of the last word).  Each copies the row
-// above it one column late, so the top nibbles of the LAST column of a group of four are the followed row's deltas of the whole
-// group: three columns of a group carry no score code, the fourth hands out the two nibbles, and the score moves once per
-// group, by two popcounts (tests/delay_rows_model.py has the identity and its boundaries).
-template <int NWD, int MODE, bool BOTTOM = false, bool DELAY = false>
+// R > 0 (with BOTTOM): the rows carry R = 3 or 7 all-match rows above row m-1 (bit 31 - R of the last word).  Each copies the
+// row above it one column late, so the top R + 1 bits of the LAST column of a group of R + 1 are the followed row's deltas of
+// the whole group: R columns of a group carry no score code, the last hands out the two nibbles (bytes at R = 7), and the score
+// moves once per group, by two popcounts (tests/delay_rows_model.py and tests/delay_rows8_model.py have the identity and its
+// boundaries).
+template <int NWD, int MODE, bool BOTTOM = false, int R = 0>
 __global__ void __launch_bounds__(256)
 scan_reads_kernel(const ReadScanArgs a)
 {
+    constexpr bool DELAY = R > 0;
+    static_assert(R == 0 || R == kDelayRowsShallow || R == kDelayRowsDeep, "delay rows: none, three or seven");
     static_assert(!DELAY || (BOTTOM && MODE == 2), "delay rows: bottom-aligned HW rows");
-    constexpr int kHitGroup = 4;                                   // columns per hit test (divides 16)
-    static_assert(!DELAY || kHitGroup == kDelayRows + 1, "one nibble per group");
+    constexpr int kHitGroup = DELAY ? R + 1 : 4;                   // columns per hit test (divides 16): one nibble or byte per group
+    static_assert(16 % kHitGroup == 0, "no group straddles a 16-column target word");
     const int lane = threadIdx.x & 63;
     const int rblk = blockIdx.x * 4 + (threadIdx.x >> 6);          // 4 waves / workgroup
     const int seg = blockIdx.y;
@@ -310,7 +313,7 @@ scan_reads_kernel(const ReadScanArgs a)
         // column -1 of the pad rows is 0: Pv is clear on the 32 NWD - m low bits.  Reads of a group fill their last word
         // (read_group_words), so the pad is below 32 there; the padding slots of the rebuilt rows (m = 1) and anything
         // shorter still get whole words of pad.
-        const int pad = 32 * NWD - (DELAY ? kDelayRows : 0) - m;   // (delay rows: Pv = 1, D[i][-1] = i + 1 like the read's own)
+        const int pad = 32 * NWD - R - m;                          // (delay rows: Pv = 1, D[i][-1] = i + 1 like the read's own)
 #pragma unroll
         for (int d = 0; d < NWD; ++d) {
             const int lo = pad - 32 * d;
@@ -356,7 +359,7 @@ scan_reads_kernel(const ReadScanArgs a)
     cw &= ~15;
 
     // warm-up columns [cw, c0): state only, nothing is recorded (HW segments)
-    u32 nph = 0, nmh = 0;                                          // DELAY: the nibbles of the last group
+    u32 nph = 0, nmh = 0;                                          // DELAY: the nibbles / bytes of the last group
     for (int w = cw >> 4; w < (c0 >> 4); ++w) {
         const u32 tw = a.tpk[w];
 #pragma unroll
@@ -381,11 +384,12 @@ scan_reads_kernel(const ReadScanArgs a)
     int lim = best + (kHitGroup - 1);
     if constexpr (DELAY) {
         // The capture column leaves the score of the group's last column next to the one before the group.  With b and a
-        // the scores before and after a group, its column k = 1..4 scores at least max(b - k, a - (4 - k)) >= (a + b - 4) / 2,
-        // so a group may hold a hit only when a + b <= 2 best + 4: one add and one compare per group, and one unit tighter
-        // than a <= best + 3 for the reads that hover above their best.  It matters: a WAVE takes the slow path when any of
-        // its 64 lanes passes (three groups in ten at a <= best + 3).  There the four scores come out of the nibbles, bit 31
-        // the first column of the group, and the per-column test runs only if their least is a hit.
+        // the scores before and after a group of G = kHitGroup columns, its column k = 1..G scores at least
+        // max(b - k, a - (G - k)) >= (a + b - G) / 2, so a group may hold a hit only when a + b <= 2 best + G: one add and
+        // one compare per group, and tighter than a <= best + G - 1 for the reads that hover above their best.  It matters: a
+        // WAVE takes the slow path when any of its 64 lanes passes (at four columns, three groups in ten at a <= best + 3).
+        // There the G scores come out of the nibbles (bytes), bit 31 the first column of the group, and the per-column test
+        // runs only if their least is a hit.
         int lim2 = 2 * best + kHitGroup;
         for (int w0 = c0 >> 4; w0 < wend; w0 += kLiveBlocks) {
         if (livep) {
@@ -493,7 +497,8 @@ static hipError_t launch_scan_mode(int mode, const ReadScanArgs& a, hipStream_t 
     switch (mode) {
         case 0: hipLaunchKernelGGL((scan_reads_kernel<NWD, 0>), grid, block, 0, stream, a); break;
         case 1: hipLaunchKernelGGL((scan_reads_kernel<NWD, 1>), grid, block, 0, stream, a); break;
-        case 2: if (a.bottomAligned == 1 + kDelayRows) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true, true>), grid, block, 0, stream, a);
+        case 2: if (a.bottomAligned == 1 + kDelayRowsDeep) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true, kDelayRowsDeep>), grid, block, 0, stream, a);
+                else if (a.bottomAligned == 1 + kDelayRowsShallow) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true, kDelayRowsShallow>), grid, block, 0, stream, a);
                 else if (a.bottomAligned) hipLaunchKernelGGL((scan_reads_kernel<NWD, 2, true>), grid, block, 0, stream, a);
                 else hipLaunchKernelGGL((scan_reads_kernel<NWD, 2>), grid, block, 0, stream, a);
                 break;
@@ -506,7 +511,7 @@ hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStr
 {
     if (a.nlanes == 0) return hipSuccess;
     if (a.bottomAligned && mode != 2) return hipErrorInvalidValue;      // only HW keeps the pad rows at zero
-    if (a.bottomAligned != 0 && a.bottomAligned != 1 && a.bottomAligned != 1 + kDelayRows) return hipErrorInvalidValue;
+    if (!bottom_align_valid(a.bottomAligned)) return hipErrorInvalidValue;
     switch (nwords) {
 #define CASE(N) case N: return launch_scan_mode<N>(mode, a, stream);
         CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
@@ -518,7 +523,8 @@ hipError_t launch_scan_reads(int nwords, int mode, const ReadScanArgs& a, hipStr
 template <int NWD>
 static hipError_t resident_bottom(int bottomAligned, int* perCU)
 {
-    if (bottomAligned == 1 + kDelayRows) return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, scan_reads_kernel<NWD, 2, true, true>, 256, 0);
+    if (bottomAligned == 1 + kDelayRowsDeep) return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, scan_reads_kernel<NWD, 2, true, kDelayRowsDeep>, 256, 0);
+    if (bottomAligned == 1 + kDelayRowsShallow) return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, scan_reads_kernel<NWD, 2, true, kDelayRowsShallow>, 256, 0);
     return hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, scan_reads_kernel<NWD, 2, true>, 256, 0);
 }
 

@@ -17,10 +17,17 @@ constexpr int kMaxLongReadWords = 16;       // targets of 5..8 symbols
 constexpr int kMaxLongReadWords4 = 32;      // targets of up to 4 symbols
 constexpr int kFilterFromWords = 13;        // HW queries of this many words and more take the piece filter (long_reads.hip)
 inline int read_group_words(int m) { const int w = (m + 31) / 32; return w <= kMaxReadWords ? w : (w <= 10 ? 10 : (w <= 12 ? 12 : (w <= 14 ? 14 : (w <= 16 ? 16 : (w <= 24 ? 24 : 32))))); }
-// HW rows built bottom-aligned may carry this many all-match rows above row m-1 (reads_kernels.hip: the score of the plain
-// full-height scan then moves once per four columns): a group whose longest read leaves them room in its last word is eligible
-constexpr int kDelayRows = 3;
-constexpr bool delay_rows_fit(int nwords, int longest) { return nwords <= kMaxReadWords && longest >= 1 && longest + kDelayRows <= 32 * nwords; }
+// HW rows built bottom-aligned may carry R all-match rows above row m-1 (reads_kernels.hip: the score of the plain full-height
+// scan then moves once per R + 1 columns): a group whose longest read leaves them room in its last word is eligible.  Seven
+// rows (a byte per group of eight columns) where they fit, else three (a nibble per four), else none.
+constexpr int kDelayRowsDeep = 7, kDelayRowsShallow = 3;
+constexpr bool delay_rows_fit(int nwords, int longest, int rows) { return nwords <= kMaxReadWords && longest >= 1 && longest + rows <= 32 * nwords; }
+constexpr int delay_rows_for(int nwords, int longest)
+{
+    return delay_rows_fit(nwords, longest, kDelayRowsDeep) ? kDelayRowsDeep : (delay_rows_fit(nwords, longest, kDelayRowsShallow) ? kDelayRowsShallow : 0);
+}
+// bottomAlign values of the Peq builder and ReadScanArgs::bottomAligned: 0 top-aligned, 1 bottom-aligned, 1 + R with R delay rows
+constexpr bool bottom_align_valid(int b) { return b == 0 || b == 1 || b == 1 + kDelayRowsShallow || b == 1 + kDelayRowsDeep; }
 constexpr int kLanes = 64;            // wave64, hard-coded (gfx950)
 
 // Hit-list read batches (reads_hits.hip): the HITS scans append closed runs of columns scoring <= k to the
@@ -62,7 +69,7 @@ struct ReadScanArgs {
     HitList hits;             // HITS instantiation of the banded kernel only (launch_scan_reads_hits)
     int slotBase;             // ... the launch's group starts at this slot of the batch-wide slot table
     int bottomAligned;        // scan_reads_kernel, HW only: peq was built with this bottomAlign (1: row m-1 at bit 31 of the last
-                              // word; 1 + kDelayRows: at bit 28 under three delay rows)
+                              // word; 1 + R: at bit 31 - R under R = 3 or 7 delay rows)
     int* liveBest;            // scan_reads_kernel on bottom-aligned rows: optional [lanes] running best of the lane over ALL its
                               // segments, set to the lane's threshold before the launch (no slotmap).  The segments start
                               // from it, publish what they find and pick it up again every kLivePeriod columns.  Null: every
@@ -97,7 +104,7 @@ hipError_t launch_pack_target_rows(const uint8_t* raw, const uint8_t* lut, int t
 // 16-bit set of the target symbols a query byte equals),
 // the per-slot query length and the number of query byte values absent from the target.
 // bottomAlign 1: query row i at bit 32 nwords - m + i and the bits below set in every row (ReadScanArgs::bottomAligned);
-// 1 + kDelayRows: at bit 32 nwords - kDelayRows - m + i, the kDelayRows bits above row m-1 set in every row as well.
+// 1 + R (R = 3 or 7 delay rows): at bit 32 nwords - R - m + i, the R bits above row m-1 set in every row as well.
 hipError_t launch_build_peq_reads(int nwords, int syms, const uint8_t* reads, const long long* qoff,
                                   const int* perm, int nslots, const uint16_t* eqtbl,
                                   const uint32_t* targetPresence /*8 dwords*/, int kcfg,

@@ -84,28 +84,29 @@ __device__ __forceinline__ void column_step(const u32 (&Eq)[NWD], u32 (&Pv)[NWD]
     }
 }
 
-// The bottom-aligned HW column over rows built with delay rows (reads_column_asm.hpp: row m-1 at bit 28 of the last word, three
-// all-match rows above it).  FORM 0: no score at all; FORM 1: the top nibbles of the last word's Ph / Mh to nph / nmh (the
-// followed row's deltas of this column and the three before it, bit 31 the oldest) and score += popcount(nph) - popcount(nmh);
-// FORM 2: the score moves with bit 28.
-template <int NWD, int FORM>
+// The bottom-aligned HW column over rows built with R delay rows (reads_column_asm.hpp: row m-1 at bit 31 - R of the last word,
+// R all-match rows above it; R = 3 or 7).  FORM 0: no score at all; FORM 1: the top R + 1 bits of the last word's Ph / Mh to
+// nph / nmh (the followed row's deltas of this column and the R before it, bit 31 the oldest) and
+// score += popcount(nph) - popcount(nmh); FORM 2: the score moves with bit 31 - R.
+template <int NWD, int FORM, int R>
 __device__ __forceinline__ void column_step_delay(const u32 (&Eq)[NWD], u32 (&Pv)[NWD], u32 (&Mv)[NWD],
                                                   int& score, u32& nph, u32& nmh, const u32 zr0, const u32 zr1)
 {
     static_assert(NWD >= 1 && NWD <= 8 && FORM >= 0 && FORM <= 2, "delay rows: up to 8 words");
+    static_assert(R == kDelayRowsShallow || R == kDelayRowsDeep, "delay rows: a nibble or a byte per group");
     u32 Pn[NWD], Mn[NWD];
     int scoreN = score;
     unsigned long long cy_;
     if constexpr (NWD >= 2 && NWD <= 5) {
         u32 t_, ph0_, ph1_, mh0_, mh1_, phl_, mhl_, cp_, cm_;
-        if constexpr (FORM == 0) { RP_COLUMN_DISPATCH_D(0, NWD) }
-        if constexpr (FORM == 1) { RP_COLUMN_DISPATCH_D(1, NWD) }
-        if constexpr (FORM == 2) { RP_COLUMN_DISPATCH_D(2, NWD) }
+        if constexpr (FORM == 0) { RP_COLUMN_DISPATCH_D(0, NWD, 32 - (R + 1), 31 - R) }
+        if constexpr (FORM == 1) { RP_COLUMN_DISPATCH_D(1, NWD, 32 - (R + 1), 31 - R) }
+        if constexpr (FORM == 2) { RP_COLUMN_DISPATCH_D(2, NWD, 32 - (R + 1), 31 - R) }
     } else {
         u32 t_, s_, xh_, ph0_, ph1_, mh0_, mh1_, phs_, mhs_, xv_;
-        if constexpr (FORM == 0) { RC_COLUMN_DISPATCH_D(0, NWD) }
-        if constexpr (FORM == 1) { RC_COLUMN_DISPATCH_D(1, NWD) }
-        if constexpr (FORM == 2) { RC_COLUMN_DISPATCH_D(2, NWD) }
+        if constexpr (FORM == 0) { RC_COLUMN_DISPATCH_D(0, NWD, 32 - (R + 1), 31 - R) }
+        if constexpr (FORM == 1) { RC_COLUMN_DISPATCH_D(1, NWD, 32 - (R + 1), 31 - R) }
+        if constexpr (FORM == 2) { RC_COLUMN_DISPATCH_D(2, NWD, 32 - (R + 1), 31 - R) }
     }
 #pragma unroll
     for (int i = 0; i < NWD; ++i) { Pv[i] = Pn[i]; Mv[i] = Mn[i]; }

@@ -41,7 +41,7 @@ inline std::vector<Segment> uniform_segment_table(int T, int Lmax)
 // finishes leaves its slot to nothing, for as long as the longest one still has to go -- up to a whole segment.  Here every
 // segment is a fixed share of what is left when it is cut: remaining / (2 R) columns, R = resident / gridX the rows of
 // segments that are resident together, so that the work still queued behind a row is always about two rounds of rows like
-// it and the last rows are short.  Lengths are multiples of 16 (no group of four columns straddles a restart) between
+// it and the last rows are short.  Lengths are multiples of 16 (no group of four or eight columns straddles a restart) between
 // minCols (four warm-ups: a shorter segment pays more warm-up than that per column of its own) and Lmax (the uniform length);
 // the last segment takes the ragged rest.  Ascending in the target: the short segments are the END of the target, the
 // highest blockIdx.y.  Nothing depends on the order in which the device starts them; it only shortens the drain.
