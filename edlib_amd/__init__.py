@@ -118,6 +118,11 @@ class SelfComponents(C.Structure):       # edlib_amd.h EdlibAmdSelfComponents
         (f, C.POINTER(C.c_int)) for f in ("label", "componentSize", "componentOffsets", "members")]
 
 
+class Neighbors(C.Structure):            # edlib_amd.h EdlibAmdNeighbors
+    _fields_ = [("numRows", C.c_int), ("K", C.c_int)] + [
+        (f, C.POINTER(C.c_int)) for f in ("count", "neighbor", "distance")] + [("strand", C.POINTER(C.c_ubyte))]
+
+
 SELF_DISTANCES = 1                        # EDLIB_AMD_SELF_DISTANCES
 SELF_NEAREST = 2                          # EDLIB_AMD_SELF_NEAREST
 CROSS_MATRIX = 1                          # EDLIB_AMD_CROSS_MATRIX
@@ -222,6 +227,9 @@ def lib():
             L.edlibAmdBatchSelfStrands.argtypes = [C.c_void_p, C.c_int, C.POINTER(SelfStrands)]
         if hasattr(L, "edlibAmdBatchSelfComponents"):
             L.edlibAmdBatchSelfComponents.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SelfComponents)]
+        if hasattr(L, "edlibAmdBatchSelfNeighbors"):
+            L.edlibAmdBatchSelfNeighbors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Neighbors)]
+            L.edlibAmdBatchCrossNeighbors.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Neighbors)]
         L.edlibAmdBatchRun.argtypes = [C.c_void_p]
         L.edlibAmdBatchResults.argtypes = [C.c_void_p, C.POINTER(AlignResult)]
         L.edlibAmdBatchResultsFlat.argtypes = [C.c_void_p] + [C.c_void_p] * 9
@@ -960,8 +968,34 @@ class CrossBatch(_Batch):
         out["bestTargetStrand"] = arr(v.bestTargetStrand, (self.numQueries,))
         return out
 
+    def neighbors(self, K, max_distance=-1, copy=True):
+        """The K (1..64) nearest queries of every target within max_distance (< 0: every reported cell) of the last run(),
+        selected on the device (edlibAmdBatchCrossNeighbors): count int32 [numTargets], neighbor / distance int32
+        [numTargets, K] in ascending order of (distance, query), -1 past count; strands="both": also strand uint8
+        [numTargets, K], the cell's strand byte.  Any number of times per run().  copy=False: views of the batch's pinned
+        memory, valid until its next neighbors() / run() / set_targets() / close()."""
+        return _neighbors(lib().edlibAmdBatchCrossNeighbors, "cross", self, K, max_distance, copy)
+
     def results(self, raw=True):
         raise RuntimeError("edlib_amd: a cross batch has no per-unit results: use matrix() / best()")
+
+
+def _neighbors(call, kind, batch, K, max_distance, copy):
+    """A neighbours call of a self or cross batch as a dict of numpy arrays (strand: both-strand batches only)."""
+    v = Neighbors()
+    if call(batch._h, int(K), int(max_distance), C.byref(v)) != 0:
+        raise RuntimeError("edlib_amd: %s neighbors failed: %s" % (kind, last_error()))
+    rows, K = int(v.numRows), int(v.K)
+    out = {"count": CrossBatch._arr(v.count, (rows,), copy)}
+    for f in ("neighbor", "distance"):
+        out[f] = CrossBatch._arr(getattr(v, f), (rows, K), copy)
+    if batch.both_strands:
+        if rows == 0 or not v.strand:
+            out["strand"] = np.zeros((rows, K), dtype=np.uint8)
+        else:
+            a = np.ctypeslib.as_array(v.strand, shape=(rows, K))
+            out["strand"] = a.copy() if copy else a
+    return out
 
 
 def align_cross(queries, targets, mode="HW", k=-1, additionalEqualities=None, hits=False, strands="forward"):
@@ -1189,6 +1223,14 @@ class SelfBatch(_Batch):
             out["members"] = arr(v.members, n)
         return out
 
+    def neighbors(self, K, max_distance=-1, copy=True):
+        """The K (1..64) nearest other sequences of every sequence within max_distance (< 0: every reported pair) of the last
+        run(), selected on the device (edlibAmdBatchSelfNeighbors): count int32 [n], neighbor / distance int32 [n, K] in
+        ascending order of (distance, index), -1 past count; strands="both": also strand uint8 [n, K], the pair's strand
+        byte.  With max_distance=-1 the columns 0 and 1 repeat nearest().  Any number of times per run().  copy=False:
+        views of the batch's pinned memory, valid until its next neighbors() / run() / close()."""
+        return _neighbors(lib().edlibAmdBatchSelfNeighbors, "self", self, K, max_distance, copy)
+
     def results(self, raw=True):
         raise RuntimeError("edlib_amd: a self batch has no per-unit results: use condensed() / hits() / nearest()")
 
@@ -1229,6 +1271,18 @@ def cluster_within(seqs, k, additionalEqualities=None, strands="forward"):
     try:
         b.run()
         return b.components()["label"]
+    finally:
+        b.close()
+
+
+def knn(seqs, K, k=-1, additionalEqualities=None, strands="forward"):
+    """The K nearest other sequences of every sequence of seqs by NW edit distance, in one device batch: the neighbors()
+    arrays of SelfBatch.  k >= 0: only partners within k count, through the hit-list batch (no condensed vector is kept);
+    k < 0: over all pairs, through the dense batch.  strands="both": every pair in its better orientation."""
+    b = SelfBatch(seqs, k, additionalEqualities, hits=k >= 0, strands=strands)
+    try:
+        b.run()
+        return b.neighbors(K)
     finally:
         b.close()
 
@@ -1293,6 +1347,29 @@ def self_components_model(n, rowOffsets, partner, editDistance, level):
     offsets = np.concatenate([[0], np.cumsum(count[roots])]).astype(np.int32)
     return {"label": label, "componentSize": count[label].astype(np.int32), "numComponents": int(len(roots)),
             "componentOffsets": offsets, "members": order}
+
+
+def neighbors_model(numRows, row, partner, distance, K, level):
+    """The neighbour rules of a self or cross batch stated in numpy (what neighbors(K, level) must equal): row / partner /
+    distance list the candidates, entry e a candidate `partner[e]` of row `row[e]` (a self batch's pair goes in twice, once
+    under each end; a partner at most once per row).  A candidate takes part where its distance d is 0 <= d and, with
+    level >= 0, d <= level; a row reports its K smallest keys (distance << 32) | partner in ascending order.
+    {count [numRows], neighbor [numRows, K], distance [numRows, K]}, -1 past count."""
+    r = np.asarray(row, dtype=np.int64).reshape(-1)
+    p = np.asarray(partner, dtype=np.int64).reshape(-1)
+    d = np.asarray(distance, dtype=np.int64).reshape(-1)
+    keep = (d >= 0) & ((d <= level) if level >= 0 else True)
+    r, p, d = r[keep], p[keep], d[keep]
+    order = np.lexsort((p, d, r))                       # by row, then by distance, then by partner
+    r, p, d = r[order], p[order], d[order]
+    start = np.searchsorted(r, np.arange(numRows))      # the first entry of every row
+    rank = np.arange(len(r)) - start[r] if len(r) else np.zeros(0, dtype=np.int64)
+    out = {"count": np.minimum(np.bincount(r, minlength=numRows), K).astype(np.int32) if numRows else np.zeros(0, dtype=np.int32),
+           "neighbor": np.full((numRows, K), -1, dtype=np.int32), "distance": np.full((numRows, K), -1, dtype=np.int32)}
+    top = rank < K
+    out["neighbor"][r[top], rank[top]] = p[top]
+    out["distance"][r[top], rank[top]] = d[top]
+    return out
 
 
 def window_best_model(unit_query, ed, numQueries):

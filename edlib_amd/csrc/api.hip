@@ -380,6 +380,35 @@ EDLIB_API int edlibAmdBatchSelfComponents(EdlibAmdBatch* b, int maxDistance, int
                ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
 }
 
+// (K first: it is judged without a batch)
+static bool bad_neighbors_call(const char* fn, const EdlibAmdBatch* b, int K, const EdlibAmdNeighbors* out) {
+    if (K < 1 || K > 64) { set_error("%s: K must be 1..64 (got %d)", fn, K); return true; }
+    if (!b || !out) { set_error("%s: null argument", fn); return true; }
+    return false;
+}
+
+EDLIB_API int edlibAmdBatchSelfNeighbors(EdlibAmdBatch* b, int K, int maxDistance, EdlibAmdNeighbors* out) {
+    if (bad_neighbors_call("edlibAmdBatchSelfNeighbors", b, K, out)) return EDLIB_STATUS_ERROR;
+    if (!b->cross || !b->cross->isSelf()) {
+        set_error("edlibAmdBatchSelfNeighbors: not a self batch (create one with edlibAmdBatchCreateSelf or "
+                  "edlibAmdBatchCreateSelfHits; a cross batch has edlibAmdBatchCrossNeighbors)");
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchSelfNeighbors", 1, [&] { return b->cross->selfNeighbors(K, maxDistance, out); })
+               ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
+EDLIB_API int edlibAmdBatchCrossNeighbors(EdlibAmdBatch* b, int K, int maxDistance, EdlibAmdNeighbors* out) {
+    if (bad_neighbors_call("edlibAmdBatchCrossNeighbors", b, K, out)) return EDLIB_STATUS_ERROR;
+    if (!b->cross || b->cross->isSelf()) {
+        set_error("edlibAmdBatchCrossNeighbors: not a cross batch (create one with edlibAmdBatchCreateCross or "
+                  "edlibAmdBatchCreateCrossHits; a self batch has edlibAmdBatchSelfNeighbors)");
+        return EDLIB_STATUS_ERROR;
+    }
+    return guarded("edlibAmdBatchCrossNeighbors", 1, [&] { return b->cross->crossNeighbors(K, maxDistance, out); })
+               ? EDLIB_STATUS_ERROR : EDLIB_STATUS_OK;
+}
+
 static EdlibAmdBatch* create_windows(const char* where, const char* queries, const long long* queryOffsets, int numQueries,
                                      const char* target, int targetLength, const int* unitQuery, const int* unitStart,
                                      const int* unitLength, const unsigned char* unitStrand, int numUnits,

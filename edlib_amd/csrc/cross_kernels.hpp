@@ -165,6 +165,47 @@ hipError_t self_components_scratch(int n, size_t* bytes);
 hipError_t launch_self_components(const SelfComponentsBuffers& b, int n, const unsigned long long* skey, const int* partner,
                                   const int* ed, long long numHits, const int* cond, int level, bool members,
                                   void* scratch, size_t scratchBytes, hipStream_t stream);
+// the K nearest neighbours of every row (neighbors.hip, DESIGN.md §4h "Neighbours").  Where a row's candidates lie:
+//   kMatrix     row t is ed[t * rowLength ..], the index implicit (a dense cross batch: rowLength = numQueries)
+//   kCondensed  row i is the n - 1 cells of the condensed vector `ed` that name i (a dense self batch: rowLength = n)
+//   kCsr        row r is the entries [off[r], off[r + 1]) of the partner and distance planes; position[e] (nullptr: e
+//               itself) is where entry e lies in its source, which is where its strand byte is
+// strand (nullptr: none): the strand bytes by source position -- the cell of the matrix or of the condensed vector, or the
+// position above
+struct NeighborsSource {
+    enum { kMatrix = 0, kCondensed = 1, kCsr = 2 };
+    int kind, numRows, rowLength;
+    const int* ed;
+    const long long* off;
+    const int* partner;
+    const int* distance;
+    const uint32_t* position;
+    const uint8_t* strand;
+};
+// views into one block of ints(rows, K) ints, what travels back to back: count [rows], neighbor [rows][K],
+// distance [rows][K], strand bytes [rows][K]
+struct NeighborsBuffers {
+    int *count, *neighbor, *distance;
+    uint8_t* strand;
+    static size_t ints(int rows, int K);
+    static NeighborsBuffers carve(int* base, int rows, int K);
+};
+// the symmetric CSR of a self hit list (each pair under both its ends), views into one block of bytes(n, numHits) bytes
+struct NeighborsMirror {
+    long long* off;                         // [n + 1]
+    int *degree, *cursor;                   // [n + 1], [n]
+    int *partner, *distance;                // [2 numHits]
+    uint32_t* position;                     // [2 numHits] the hit's place in the finished list
+    static size_t bytes(int n, long long numHits);
+    static NeighborsMirror carve(uint8_t* base, int n, long long numHits);
+};
+hipError_t neighbors_mirror_scratch(int n, size_t* bytes);       // of the scan over n + 1 degrees
+// degree count, exclusive scan and scatter of the finished list (sorted keys (i << 32) | j, partner and ed planes)
+hipError_t launch_neighbors_mirror(const NeighborsMirror& m, int n, const unsigned long long* skey, const int* partner,
+                                   const int* ed, long long numHits, void* scratch, size_t scratchBytes, hipStream_t stream);
+// a wave per row: the K (1..64) smallest keys (distance << 32) | index among the row's candidates whose distance d is
+// 0 <= d and, with level >= 0, d <= level; -1 / -1 / 0 behind count[row]
+hipError_t launch_neighbors_select(const NeighborsSource& s, int K, int level, const NeighborsBuffers& out, hipStream_t stream);
 // per target over its queries (rows of the matrix) and per query over the targets (columns); out arrays are
 // best index / best distance / second distance
 hipError_t launch_cross_best(const int* ed, int numQueries, int numTargets,

@@ -719,4 +719,68 @@ int CrossBatch::strandsView(int what, EdlibAmdCrossStrands* out)
     return 0;
 }
 
+int CrossBatch::neighborsLevel(const char* who, int K, int maxDistance, int* level)
+{
+    if (K < 1 || K > 64) { set_error("%s: K must be 1..64 (got %d)", who, K); return 1; }
+    if (cfg_.k >= 0 && maxDistance > cfg_.k) {
+        set_error("%s: maxDistance %d is above the batch's k = %d: the batch kept nothing beyond k (create it with a "
+                  "larger k)", who, maxDistance, cfg_.k);
+        return 1;
+    }
+    // (< 0: every distance the batch reports -- an empty sequence's pairs are reported at the other's length whatever k,
+    // and the nearest / best views count them: so do the neighbours)
+    *level = maxDistance >= 0 ? maxDistance : -1;
+    return 0;
+}
+
+int CrossBatch::selectNeighbors(const NeighborsSource& src, int K, int level, EdlibAmdNeighbors* out)
+{
+    const int rows = src.numRows;
+    const size_t cells = (size_t)rows * (size_t)K;
+    EDLIB_AMD_HIP(d_nbr_.ensure(NeighborsBuffers::ints(rows, K)));
+    const NeighborsBuffers b = NeighborsBuffers::carve(d_nbr_.p, rows, K);
+    EDLIB_AMD_HIP(launch_neighbors_select(src, K, level, b, stream_));
+    // count, neighbor, distance and -- behind them on the device -- the strand bytes: one copy
+    const size_t bytes = ((size_t)rows + 2 * cells) * sizeof(int) + (strands_ ? cells : 0);
+    nbr_.fetched = false;
+    EDLIB_AMD_HIP(nbr_.fetch(d_nbr_.p, bytes, stream_, 0, 4 * sizeof(int)));
+    EDLIB_AMD_HIP(hipStreamSynchronize(stream_));
+    nbr_.fetched = true;
+    const int* h = reinterpret_cast<const int*>(nbr_.h.p);
+    memset(out, 0, sizeof *out);
+    out->numRows = rows; out->K = K;
+    out->count = h; out->neighbor = h + rows; out->distance = h + rows + cells;
+    if (strands_) out->strand = reinterpret_cast<const unsigned char*>(h + rows + 2 * cells);
+    return 0;
+}
+
+int CrossBatch::crossNeighbors(int K, int maxDistance, EdlibAmdNeighbors* out)
+{
+    int level = -1;
+    if (occ_) {
+        set_error("edlibAmdBatchCrossNeighbors: not available on an occurrence batch (its entries are runs of columns, not "
+                  "cells: take edlibAmdBatchCrossOccurrences, or create a hit-list batch)");
+        return 1;
+    }
+    if (!haveRun_) return noResults();
+    if (neighborsLevel("cross neighbors", K, maxDistance, &level)) return 1;
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    NeighborsSource src{};
+    src.numRows = nt_; src.rowLength = nq_;
+    if (!hits_) {
+        // row t of the matrix: the distances of its queries, the index implicit
+        src.kind = NeighborsSource::kMatrix;
+        src.ed = d_mat_.p;
+        src.strand = strands_ ? d_smat_.p : nullptr;
+    } else {
+        // the finished list is the CSR by target itself: plane 0 the query, plane 1 the distance
+        src.kind = NeighborsSource::kCsr;
+        src.off = hitList_.off(); src.partner = hitList_.out(); src.distance = hitList_.out() + (size_t)hitList_.outN;
+        src.strand = strands_ ? hitList_.byteOut.p : nullptr;
+    }
+    return selectNeighbors(src, K, level, out);
+}
+
 }  // namespace edlib_amd

@@ -123,6 +123,11 @@ public:
     // from the finished hit list or the condensed vector as they lie there (DESIGN.md §4h "Components"); any number of
     // times per Run.  A refusal leaves the batch and its other views as they were
     int selfComponents(int maxDistance, int what, EdlibAmdSelfComponents* out);
+    // The K nearest other sequences of every sequence (self batches) / nearest queries of every target (cross batches)
+    // within maxDistance (< 0: every reported distance) of the last Run, selected on the device from the results as they lie there
+    // (DESIGN.md §4h "Neighbours"); any number of times per Run.  A refusal leaves the batch and its other views as they were
+    int selfNeighbors(int K, int maxDistance, EdlibAmdNeighbors* out);
+    int crossNeighbors(int K, int maxDistance, EdlibAmdNeighbors* out);
     bool isSelf() const { return self_; }
     int view(int what, EdlibAmdCrossView* out);
     int hitsView(EdlibAmdCrossHits* out);
@@ -223,6 +228,15 @@ private:
     // components: one block carved by SelfComponentsBuffers, made at the first call and kept; comp_ is fetched at every call
     DevBuf<int> d_comp_;
     PinnedPart comp_;
+    // neighbours: the block carved by NeighborsBuffers and, for a self hit list, the one carved by NeighborsMirror, made
+    // at the first call and kept (grow-only); nbr_ is fetched at every call
+    DevBuf<int> d_nbr_;
+    DevBuf<uint8_t> d_mirror_;
+    PinnedPart nbr_;
+    // `who` names the call in the messages; the checks every neighbours call shares, then level = maxDistance, -1 where it is < 0
+    int neighborsLevel(const char* who, int K, int maxDistance, int* level);
+    // the selection over `src` into d_nbr_, the block back in one copy, `out` filled
+    int selectNeighbors(const NeighborsSource& src, int K, int level, EdlibAmdNeighbors* out);
     // both-strand self batches: d_smat_ is the condensed strand vector, cellStrand_ its (or the hit list's) pinned part;
     // d_sbest_ is [2 n] for the hits finish, then [n] the strand byte of every nearest partner (bestStrand_); a pair of
     // selfOther_ behind the empty ones is the pairs 2c (forward) and 2c + 1 (the lower index reverse-complemented) of

@@ -429,4 +429,39 @@ int CrossBatch::selfComponents(int maxDistance, int what, EdlibAmdSelfComponents
     return 0;
 }
 
+int CrossBatch::selfNeighbors(int K, int maxDistance, EdlibAmdNeighbors* out)
+{
+    int level = -1;
+    if (!haveRun_) { set_error("self batch: no results (Run it first)"); return 1; }
+    if (neighborsLevel("self neighbors", K, maxDistance, &level)) return 1;
+    const int n = nq_;
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    NeighborsSource src{};
+    src.numRows = n; src.rowLength = n;
+    if (!hits_) {
+        // the condensed vector as it lies there: row i is its stretch of row i and one cell of every row above
+        src.kind = NeighborsSource::kCondensed;
+        src.ed = d_mat_.p;
+        src.strand = strands_ ? d_smat_.p : nullptr;
+    } else {
+        // the finished list holds a pair once, under its lower index: mirrored into a CSR with every pair under both ends
+        const long long numHits = hitList_.outN;
+        size_t scratch = 0;
+        if (n > 0) {
+            EDLIB_AMD_HIP(neighbors_mirror_scratch(n, &scratch));
+            EDLIB_AMD_HIP(hitList_.needScratch(scratch));
+        }
+        EDLIB_AMD_HIP(d_mirror_.ensure(NeighborsMirror::bytes(n, numHits)));
+        const NeighborsMirror m = NeighborsMirror::carve(d_mirror_.p, n, numHits);
+        EDLIB_AMD_HIP(launch_neighbors_mirror(m, n, hitList_.skey.p, hitList_.out(), hitList_.out() + (size_t)numHits, numHits,
+                                              hitList_.tmp.p, hitList_.tmp.n, stream_));
+        src.kind = NeighborsSource::kCsr;
+        src.off = m.off; src.partner = m.partner; src.distance = m.distance; src.position = m.position;
+        src.strand = strands_ ? hitList_.byteOut.p : nullptr;
+    }
+    return selectNeighbors(src, K, level, out);
+}
+
 }  // namespace edlib_amd

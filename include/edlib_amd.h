@@ -446,6 +446,38 @@ typedef struct {
 #define EDLIB_AMD_COMPONENT_MEMBERS 2
 EDLIB_API int edlibAmdBatchSelfComponents(EdlibAmdBatch* batch, int maxDistance, int what, EdlibAmdSelfComponents* out);
 
+/* The K nearest neighbours per row of the last Run, selected on the device from the results where the Run left them --
+ * the condensed vector, the matrix or the finished hit list -- so that numRows x K entries cross the link instead of the
+ * pairs or cells (kNN graphs for clustering, the few candidate barcodes of an ambiguous read, the K closest references).
+ * edlibAmdBatchSelfNeighbors: a row is a sequence i of a self batch (all four kinds), its candidates the OTHER sequences
+ * j != i on both sides of the triangle, at the distance edlibAmdBatchSelfView / edlibAmdBatchSelfHits report for the pair.
+ * edlibAmdBatchCrossNeighbors: a row is a target t of a cross batch (dense or hit list, one strand or both), its
+ * candidates the queries, at the distance of cell (t, q).  Neighbours of the queries are not offered.
+ * A candidate takes part where its distance d satisfies 0 <= d and, with maxDistance >= 0, d <= maxDistance; with
+ * maxDistance < 0 every distance the batch reports counts (also the pairs of an empty sequence, which a self batch
+ * reports at the other's length whatever k).  A row lists its count[row] <= K
+ * nearest candidates in ascending order of the key (distance << 32) | index: the smaller distance first, ties to the
+ * lower index -- the rule of the nearest / best views, so with maxDistance = -1 neighbor[row][0], distance[row][0] and
+ * distance[row][1] equal nearest, nearestDistance and secondDistance (bestQuery, bestQueryDistance, secondQueryDistance).
+ * Entries past count[row] are -1 / -1 / strand 0.  strand[row][r] (both-strand batches) is the strand byte of that pair
+ * or cell as edlibAmdBatchSelfStrands / edlibAmdBatchCrossStrands report it.
+ * K is 1..64.  Valid after a successful Run, any number of times per Run; numRows 0, a single sequence and numQueries 0
+ * are valid (no rows / count 0).  The pointers are pinned memory the batch owns, valid until the next Neighbors call,
+ * Run, edlibAmdBatchCrossSetTargets or Destroy.  Refused with the reason in edlibAmdLastError(), the batch and its other
+ * views (and pointers a caller holds from them) left as they were: K out of range, NULL batch or out, the other kind of
+ * batch, an occurrence batch (its entries are runs, not cells), a batch that has not run (a cross batch that took new
+ * targets since its last Run has not), and maxDistance > k on a batch with k >= 0.  Stats are untouched. */
+typedef struct {
+    int numRows;                 /* sequences (self) or targets (cross)                         */
+    int K;
+    const int* count;            /* [numRows]     neighbours reported for the row, 0..K         */
+    const int* neighbor;         /* [numRows][K]  ascending by (distance, index); -1 past count */
+    const int* distance;         /* [numRows][K]  -1 past count                                 */
+    const unsigned char* strand; /* [numRows][K]  both-strand batches only, else NULL; 0 past count */
+} EdlibAmdNeighbors;
+EDLIB_API int edlibAmdBatchSelfNeighbors(EdlibAmdBatch* batch, int K, int maxDistance, EdlibAmdNeighbors* out);
+EDLIB_API int edlibAmdBatchCrossNeighbors(EdlibAmdBatch* batch, int K, int maxDistance, EdlibAmdNeighbors* out);
+
 /* A shared-target batch whose results are, per read, EVERY occurrence within k along the target -- the search question of
  * adapter / primer trimming, concatemer splitting, repeat finding and multi-mapping reads, which no choice of k makes
  * edlibAlign() answer (it keeps the columns of the single best score only).
