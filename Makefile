@@ -9,7 +9,7 @@ OBJDIR  := build/obj
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fvisibility=hidden -Iinclude -Wall -Wno-unused-function \
             -mllvm -disable-promote-alloca-to-vector
 
-SRCS := $(CSRC)/reads_kernels.hip $(CSRC)/reads_kernels_long.hip $(CSRC)/reads_seed.hip $(CSRC)/reads_hits.hip $(CSRC)/strands.hip $(CSRC)/pair_kernels.hip $(CSRC)/wide_kernels.hip $(CSRC)/ring32_kernels.hip $(CSRC)/lanepair_kernels.hip $(CSRC)/lanepair_kernels42.hip $(CSRC)/lanepair_kernels24.hip $(CSRC)/flat_results.hip $(CSRC)/flat_pairs_prepare.hip $(CSRC)/pairs_gather.hip $(CSRC)/runtime.hip $(CSRC)/engine.hip $(CSRC)/engine_reads.hip $(CSRC)/engine_pairs.hip $(CSRC)/engine_paths.hip $(CSRC)/engine_flat.hip $(CSRC)/long_reads.hip $(CSRC)/one_pair.hip $(CSRC)/cross_kernels.hip $(CSRC)/cross_kernels_strands.hip $(CSRC)/cross_kernels_self.hip $(CSRC)/cross_kernels_self_strands.hip $(CSRC)/cross_kernels_occ.hip $(CSRC)/hit_list.hip $(CSRC)/cross_hits.hip $(CSRC)/cross_targets.hip $(CSRC)/engine_lanes.hip $(CSRC)/engine_cross.hip $(CSRC)/engine_self.hip $(CSRC)/self_components.hip $(CSRC)/neighbors.hip $(CSRC)/window_kernels.hip $(CSRC)/window_units.hip $(CSRC)/engine_windows.hip $(CSRC)/api.hip
+SRCS := $(CSRC)/reads_kernels.hip $(CSRC)/reads_kernels_long.hip $(CSRC)/reads_seed.hip $(CSRC)/reads_hits.hip $(CSRC)/strands.hip $(CSRC)/pair_kernels.hip $(CSRC)/wide_kernels.hip $(CSRC)/ring32_kernels.hip $(CSRC)/lanepair_kernels.hip $(CSRC)/lanepair_kernels42.hip $(CSRC)/lanepair_kernels24.hip $(CSRC)/flat_results.hip $(CSRC)/flat_pairs_prepare.hip $(CSRC)/pairs_gather.hip $(CSRC)/runtime.hip $(CSRC)/engine.hip $(CSRC)/engine_reads.hip $(CSRC)/engine_pairs.hip $(CSRC)/engine_paths.hip $(CSRC)/engine_flat.hip $(CSRC)/long_reads.hip $(CSRC)/one_pair.hip $(CSRC)/cross_kernels.hip $(CSRC)/cross_kernels_strands.hip $(CSRC)/cross_kernels_self.hip $(CSRC)/cross_kernels_self_strands.hip $(CSRC)/cross_kernels_self_groups.hip $(CSRC)/cross_kernels_occ.hip $(CSRC)/hit_list.hip $(CSRC)/cross_hits.hip $(CSRC)/cross_targets.hip $(CSRC)/engine_lanes.hip $(CSRC)/engine_cross.hip $(CSRC)/engine_self.hip $(CSRC)/self_components.hip $(CSRC)/neighbors.hip $(CSRC)/window_kernels.hip $(CSRC)/window_units.hip $(CSRC)/engine_windows.hip $(CSRC)/api.hip
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 
 all: edlib_amd/libedlib.so build/edlib-aligner-batch build/latency build/cu_hog build/libcu_hog.so

@@ -219,6 +219,9 @@ def lib():
             L.edlibAmdBatchCreateSelfHits.argtypes = L.edlibAmdBatchCreateSelf.argtypes
             L.edlibAmdBatchSelfView.argtypes = [C.c_void_p, C.c_int, C.POINTER(SelfView)]
             L.edlibAmdBatchSelfHits.argtypes = [C.c_void_p, C.POINTER(SelfHits)]
+        if hasattr(L, "edlibAmdBatchCreateSelfHitsGrouped"):
+            L.edlibAmdBatchCreateSelfHitsGrouped.restype = C.c_void_p
+            L.edlibAmdBatchCreateSelfHitsGrouped.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, AlignConfig, C.c_int]
         if hasattr(L, "edlibAmdBatchSelfStrands"):
             L.edlibAmdBatchCreateSelfBothStrands.restype = C.c_void_p
             L.edlibAmdBatchCreateSelfBothStrands.argtypes = L.edlibAmdBatchCreateSelf.argtypes
@@ -1124,13 +1127,20 @@ class SelfBatch(_Batch):
     lists the pairs i < j within k.
     strands="both" (edlibAmdBatchCreateSelfBothStrands / ...HitsBothStrands): pair (i, j), i < j, is the better of seqs[i]
     and reverse_complement(seqs[i]) against seqs[j] (ties: forward); condensed(), hits() and nearest() describe these
-    combined distances, and strands() says which orientation each reports."""
+    combined distances, and strands() says which orientation each reports.
+    groups= (hits=True, k >= 0; edlibAmdBatchCreateSelfHitsGrouped): an int label per sequence; only the pairs of
+    sequences with equal labels exist, and hits(), nearest(), components(), neighbors() and a pair batch's set_cells()
+    report what a SelfBatch(hits=True) over each group alone would, in the indices of the whole set."""
 
     both_strands = False
+    grouped = False
 
-    def __init__(self, seqs, k=-1, additionalEqualities=None, device=0, hits=False, strands="forward"):
+    def __init__(self, seqs, k=-1, additionalEqualities=None, device=0, hits=False, strands="forward", groups=None):
         if strands not in ("forward", "both"):
             raise ValueError("strands must be 'forward' or 'both'")
+        if groups is not None:
+            self._init_grouped(seqs, k, additionalEqualities, device, hits, strands, groups)
+            return
         sd, so = _pack(seqs)
         cfg, keep = _make_config("NW", "distance", k, additionalEqualities)
         self.numSequences = len(so) - 1
@@ -1144,6 +1154,30 @@ class SelfBatch(_Batch):
         h = create(sd.ctypes.data, so.ctypes.data, self.numSequences, cfg, device)
         super().__init__(h, self.numPairs, keep)
 
+    def _init_grouped(self, seqs, k, additionalEqualities, device, hits, strands, groups):
+        if not hits:
+            raise ValueError("groups= needs hits=True: there is no dense grouped form (a condensed vector has no meaning "
+                             "across groups)")
+        if k is None or k < 0:
+            raise ValueError("groups= needs k >= 0: a grouped self batch is a hit list of the pairs within k")
+        if strands != "forward":
+            raise ValueError("groups= is one-strand: run a SelfBatch(strands='both') per group")
+        sd, so = _pack(seqs)
+        labels = np.asarray(groups)
+        if labels.ndim != 1 or len(labels) != len(so) - 1 or (len(labels) and labels.dtype.kind not in "iu"):
+            raise ValueError("groups must be a 1-D int array with one label per sequence")
+        if len(labels) and (labels.min() < -2**31 or labels.max() > 2**31 - 1):
+            raise ValueError("groups: labels must fit an int32 (relabel them with np.unique(groups, return_inverse=True))")
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        cfg, keep = _make_config("NW", "distance", k, additionalEqualities)
+        self.numSequences = len(so) - 1
+        size = np.unique(labels, return_counts=True)[1].astype(np.int64)
+        self.numPairs = int((size * (size - 1) // 2).sum())            # the pairs inside groups
+        self.is_hits, self.both_strands, self.grouped = True, False, True
+        h = lib().edlibAmdBatchCreateSelfHitsGrouped(sd.ctypes.data, so.ctypes.data, self.numSequences,
+                                                     labels.ctypes.data if len(labels) else None, cfg, device)
+        _Batch.__init__(self, h, self.numPairs, keep)
+
     def _view(self, what):
         v = SelfView()
         if lib().edlibAmdBatchSelfView(self._h, what, C.byref(v)) != 0:
@@ -1153,6 +1187,9 @@ class SelfBatch(_Batch):
     def condensed(self, copy=True):
         """The distances of the pairs i < j, int32 [n (n - 1) / 2], pair (i, j) at condensed_index(n, i, j).
         copy=False: a view of the batch's pinned memory, valid until its next run() / close()."""
+        if self.grouped:
+            raise RuntimeError("edlib_amd: condensed(): a grouped self batch keeps no condensed vector (it has no meaning "
+                               "across groups): use hits()")
         if self.is_hits:
             raise RuntimeError("edlib_amd: a hit-list self batch keeps no condensed vector: use hits(), or create the "
                                "batch without hits=True")
@@ -1263,11 +1300,11 @@ def pairs_within(seqs, k, additionalEqualities=None, strands="forward"):
         b.close()
 
 
-def cluster_within(seqs, k, additionalEqualities=None, strands="forward"):
+def cluster_within(seqs, k, additionalEqualities=None, strands="forward", groups=None):
     """Single linkage at k NW edits in one device batch: label int32 [n], the smallest index among the sequences that
     sequence i reaches through pairs within k (strands="both": in either orientation).  The pairs stay on the device
-    (SelfBatch(..., hits=True).components())."""
-    b = SelfBatch(seqs, k, additionalEqualities, hits=True, strands=strands)
+    (SelfBatch(..., hits=True).components()).  groups=: an int label per sequence; only pairs inside a group link."""
+    b = SelfBatch(seqs, k, additionalEqualities, hits=True, strands=strands, groups=groups)
     try:
         b.run()
         return b.components()["label"]
@@ -1275,11 +1312,14 @@ def cluster_within(seqs, k, additionalEqualities=None, strands="forward"):
         b.close()
 
 
-def knn(seqs, K, k=-1, additionalEqualities=None, strands="forward"):
+def knn(seqs, K, k=-1, additionalEqualities=None, strands="forward", groups=None):
     """The K nearest other sequences of every sequence of seqs by NW edit distance, in one device batch: the neighbors()
     arrays of SelfBatch.  k >= 0: only partners within k count, through the hit-list batch (no condensed vector is kept);
-    k < 0: over all pairs, through the dense batch.  strands="both": every pair in its better orientation."""
-    b = SelfBatch(seqs, k, additionalEqualities, hits=k >= 0, strands=strands)
+    k < 0: over all pairs, through the dense batch.  strands="both": every pair in its better orientation.
+    groups=: an int label per sequence; only the other sequences of its own group count, and k must be >= 0."""
+    if groups is not None and k < 0:
+        raise ValueError("knn(groups=...) needs k >= 0: k < 0 would take the dense form, which a grouped batch does not have")
+    b = SelfBatch(seqs, k, additionalEqualities, hits=k >= 0, strands=strands, groups=groups)
     try:
         b.run()
         return b.neighbors(K)
@@ -1317,6 +1357,32 @@ def self_nearest_model(n, first, second, ed):
     has2[has2] = o[lead[has2] + 1] == o[lead[has2]]
     out["secondDistance"][o[lead[has2]]] = key[lead[has2] + 1] >> 32
     return out
+
+
+def grouped_hits_model(groups, per_group_hits):
+    """The index mapping of a grouped self batch stated in numpy (what SelfBatch(groups=...).hits() must equal): groups is
+    the label array [n]; per_group_hits maps a label to the hits() dictionary of a SelfBatch(hits=True) over
+    seqs[np.flatnonzero(groups == label)] alone (a missing label: no hits).  Member x of that group is sequence
+    np.flatnonzero(groups == label)[x] of the whole set; members ascend, so a row's partners stay ascending."""
+    g = np.asarray(groups).reshape(-1)
+    n = len(g)
+    rows, partner, ed = [], [], []
+    for label in np.unique(g):
+        h = per_group_hits.get(int(label))
+        if h is None:
+            continue
+        member = np.flatnonzero(g == label)
+        off = np.asarray(h["rowOffsets"], dtype=np.int64)
+        rows.append(member[np.repeat(np.arange(len(member)), np.diff(off))])
+        partner.append(member[np.asarray(h["partner"], dtype=np.int64)])
+        ed.append(np.asarray(h["editDistance"], dtype=np.int32))
+    rows = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+    partner = np.concatenate(partner) if partner else np.zeros(0, dtype=np.int64)
+    ed = np.concatenate(ed) if ed else np.zeros(0, dtype=np.int32)
+    order = np.lexsort((partner, rows))
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=n), out=off[1:])
+    return {"rowOffsets": off, "partner": partner[order].astype(np.int32), "editDistance": ed[order].astype(np.int32)}
 
 
 def self_components_model(n, rowOffsets, partner, editDistance, level):

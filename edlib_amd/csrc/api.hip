@@ -332,6 +332,13 @@ EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHits(const char* seqs, const lon
     return create_self("edlibAmdBatchCreateSelfHits", seqs, offsets, numSequences, config, device, true);
 }
 
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHitsGrouped(const char* seqs, const long long* offsets, int numSequences,
+                                                            const int* groups, EdlibAlignConfig config, int device) {
+    return create_batch("edlibAmdBatchCreateSelfHitsGrouped", [&](EdlibAmdBatch& b) {
+        b.cross.reset(new CrossBatch);
+        return b.cross->initSelfGrouped(seqs, offsets, numSequences, groups, config, device); });
+}
+
 EDLIB_API int edlibAmdBatchSelfView(EdlibAmdBatch* b, int what, EdlibAmdSelfView* out) {
     if (!b || !out) { set_error("null argument"); return EDLIB_STATUS_ERROR; }
     if (not_on_occurrences(b, "edlibAmdBatchSelfView")) return EDLIB_STATUS_ERROR;

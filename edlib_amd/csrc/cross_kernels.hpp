@@ -114,6 +114,9 @@ struct CrossScanArgs {
     const int* qrank;           // [slots] rank of the slot's sequence, -1 for a padding slot
     const int* items;           // [3][numItems] as triples
     int numItems;
+    // grouped self batches (launch_scan_cross_self_groups; DESIGN.md §4h "Grouped self batches"): the order is (group,
+    // length, index), and a lane scans cell (slot, ts) only where qrank[slot] < ts < qend[slot]
+    const int* qend;            // [slots] one past the last rank of the group of the slot's sequence, -1 for a padding slot
 };
 
 hipError_t launch_pack_cross_targets(const uint8_t* raw, const long long* toff, const int* tperm, const long long* tdw,
@@ -133,6 +136,8 @@ hipError_t launch_scan_cross_occ(int nwords, int syms, const CrossScanArgs& a, i
 hipError_t launch_scan_cross_self(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
 // the self scan over both strands of the row sequence (cross_kernels_self_strands.hip): the combined pair per mate pair
 hipError_t launch_scan_cross_self_strands(int nwords, int syms, bool hits, const CrossScanArgs& a, hipStream_t stream);
+// the grouped self scan (cross_kernels_self_groups.hip): NW, hit list, one strand, one block per work item
+hipError_t launch_scan_cross_self_groups(int nwords, int syms, const CrossScanArgs& a, hipStream_t stream);
 // nearest other sequence of each of n sequences from the condensed vector: out [3][n] = nearest, nearestDistance,
 // secondDistance (the key rule of CrossBest2 over all partners on either side of the triangle)
 hipError_t launch_self_nearest_dense(const int* ed, int n, int* out, hipStream_t stream);

@@ -1,10 +1,12 @@
 // cross_scan.hpp -- the lane-per-cell scan of cross batches (DESIGN.md "Cross batches"): the kernel template and its
 // launch ladders, included by the translation units that instantiate it -- cross_kernels.hip (one strand) and
 // cross_kernels_strands.hip (both strands), each half of the cross instantiations, and cross_kernels_self.hip /
-// cross_kernels_self_strands.hip (self batches, NW only, one strand / both).
+// cross_kernels_self_strands.hip (self batches, NW only, one strand / both) and cross_kernels_self_groups.hip (grouped
+// self batches, hit list, one strand).
 #pragma once
 #include "cross_kernels.hpp"
 #include "cross_column.hpp"
+#include "self_groups_layout.hpp"
 #include "strands.hpp"
 
 namespace edlib_amd {
@@ -30,11 +32,15 @@ typedef unsigned long long u64;
 // SELF with STRANDS: a tile of qt slots holds qt / 2 sequences, mates carry the same qrank (so the same `live`), the
 // targets are the forward copies; the row sequence is the one that is reverse-complemented, which the host allows only
 // where that equals the definition by index (engine_self.hip, complement condition).
-template <int NWD, int S, int MODE, bool HITS, bool STRANDS, bool SELF = false>
+// GROUPS (SELF, HITS, one strand; DESIGN.md §4h "Grouped self batches"): the order is (group, length, index), a lane is
+// live only where its target's rank is also below qend[slot], the end of its query's group (self_groups_lane(), shared
+// with the host layout), and a trip in which no lane of the wave is live is skipped whole.
+template <int NWD, int S, int MODE, bool HITS, bool STRANDS, bool SELF = false, bool GROUPS = false>
 __global__ void __launch_bounds__(64)
 scan_cross_kernel(CrossScanArgs a)
 {
     static_assert(!SELF || MODE == 0, "self batches are NW");
+    static_assert(!GROUPS || (SELF && HITS && !STRANDS), "grouped self batches are one-strand hit lists");
     __shared__ u32 s_peq[S * NWD * 64];                 // [symbol][word][query of the tile]
     const int lane = threadIdx.x;
     const int qt = a.qt;
@@ -57,12 +63,19 @@ scan_cross_kernel(CrossScanArgs a)
     const int sh = (m - 1) & 31;
     if (!HITS && q < 0) return;                         // (no barrier or ballot below)
     const int rank = SELF ? a.qrank[slot] : 0;
+    const int gend = GROUPS ? a.qend[slot] : 0;
     const int ttFirst = SELF ? a.items[3 * blockIdx.x + 1] : (int)blockIdx.y;
     const int ttStep = SELF ? 1 : (int)gridDim.y;
     const int numTT = SELF ? ttFirst + a.items[3 * blockIdx.x + 2] : (a.numSorted + tpt - 1) / tpt;
     for (int tt = ttFirst; tt < numTT; tt += ttStep) {         // wave-uniform trip count
-        const int ts = tt * tpt + ti;
-        const bool live = q >= 0 && ts < a.numSorted && (!SELF || ts > rank);
+        int ts = tt * tpt + ti;
+        bool live = q >= 0 && ts < a.numSorted && (!SELF || ts > rank);
+        if (GROUPS) {
+            int qiSame;
+            live = self_groups_lane(qt, lane, tt, rank, gend, a.numSorted, qiSame, ts);     // (padding: rank = end = -1)
+            // wave-uniform, in front of the append every lane reaches: the tile's other runs own this trip
+            if (__builtin_amdgcn_ballot_w64(live) == 0ull) continue;
+        }
         int ed = -1, nloc = 0, end = -1;
         if (live) {
             const int n = a.tlen[ts];

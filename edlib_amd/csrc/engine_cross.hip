@@ -503,7 +503,11 @@ int CrossBatch::scanGroups()
             // (the condensed vector is one plane: numLocations and endLocation are 1 and length - 1 for NW)
             a.nloc = a.end = nullptr;
             a.qrank = g->d_rank.p; a.items = g->d_items.p; a.numItems = g->numItems;
-            EDLIB_AMD_HIP((strands_ ? launch_scan_cross_self_strands : launch_scan_cross_self)(g->words, syms_, hits_, a, stream_));
+            if (grouped_) {
+                a.qend = g->d_end.p;
+                EDLIB_AMD_HIP(launch_scan_cross_self_groups(g->words, syms_, a, stream_));
+            } else
+                EDLIB_AMD_HIP((strands_ ? launch_scan_cross_self_strands : launch_scan_cross_self)(g->words, syms_, hits_, a, stream_));
             if (g->numItems > 0) ++stats.scan_launches;
             stats.word_steps += g->wordSteps;
             continue;

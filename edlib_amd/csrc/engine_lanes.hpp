@@ -112,6 +112,9 @@ public:
              EdlibAlignConfig cfg, int device, bool hits = false, bool strands = false, bool occ = false);
     int initSelf(const char* seqs, const long long* off, int n, EdlibAlignConfig cfg, int device, bool hits,
                  bool strands = false);
+    // A hit-list self batch whose pair (i, j) exists only where groups[i] == groups[j] (DESIGN.md §4h "Grouped self
+    // batches"): one strand, k >= 0; every view reports what a hit-list self batch over each group alone would
+    int initSelfGrouped(const char* seqs, const long long* off, int n, const int* groups, EdlibAlignConfig cfg, int device);
     // Another target set for the resident queries (DESIGN.md §4h "Streamed targets"): prepared on the device into fresh
     // buffers and swapped in once it is known to lie inside the kernel's envelope; a refusal leaves the batch as it was
     int setTargets(const char* targets, const long long* toff, int nt);
@@ -147,7 +150,8 @@ private:
     struct Group : LaneGroup {                    // slots: whole tiles, padded with -1
         int qt = 64, tiles = 0, ysplit = 1;       // wordSteps: of its scanned cells (NW, k >= 0: inside the length window)
         // self batches: the rank of every slot, and the work items (query tile, first target tile, trips) of its launch
-        DevBuf<int> d_rank, d_items;
+        // (grouped self batches: d_end, one past the last rank of every slot's group)
+        DevBuf<int> d_rank, d_items, d_end;
         int numItems = 0;
         int syms = 0;                             // Peq rows per word its buffers were allocated for
     };
@@ -221,6 +225,7 @@ private:
     // kernel's envelope; selfOther_ the keys (i << 32) | j of the pairs answered off the kernel -- first the selfEmpty_
     // pairs with an empty sequence (distance: the other's length), then the pairs of longPairs_
     bool self_ = false;
+    bool grouped_ = false;                        // initSelfGrouped: only the pairs inside a group exist (cells_ counts them)
     std::vector<unsigned long long> selfOther_;
     std::vector<int> selfEmptyVal_;
     DevBuf<int> d_near_;                          // [3][n]: nearest, nearestDistance, secondDistance

@@ -9,9 +9,11 @@
 // kernel reverse-complements the row sequence, the shorter one, which is the same only under the complement condition
 // below; a set that fails it goes through the pair batch whole, in index order.
 #include "engine_lanes.hpp"
+#include "self_groups_layout.hpp"
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 namespace edlib_amd {
 
@@ -252,6 +254,164 @@ int CrossBatch::initSelf(const char* seqs, const long long* offIn, int n, EdlibA
             EDLIB_AMD_HIP(d_cells_.alloc((size_t)otherCells_)); EDLIB_AMD_HIP(d_vals_.alloc((size_t)otherCells_));
             EDLIB_AMD_HIP(hipMemcpy(d_cells_.p, cellIdx.data(), (size_t)otherCells_ * sizeof(long long), hipMemcpyHostToDevice));
         }
+    }
+    return 0;
+}
+
+// A grouped self batch: the checks and the routes of a hit-list self batch, every route restricted to the pairs inside a
+// group.  The kernel's order, word groups and work items are self_groups_layout.hpp's; the host's share is that sort, a
+// sort of the indices by (group, index) for the other routes, and linear passes.
+int CrossBatch::initSelfGrouped(const char* seqs, const long long* offIn, int n, const int* groups, EdlibAlignConfig cfg,
+                                int device)
+{
+    if (!groups && n > 0) {
+        set_error("grouped self batch: groups is NULL (one int label per sequence; a set without groups is "
+                  "edlibAmdBatchCreateSelfHits)");
+        return 1;
+    }
+    if (cfg.task != EDLIB_TASK_DISTANCE) {
+        set_error("self batches compute distances only (EDLIB_TASK_DISTANCE): align the chosen pairs with a pair batch "
+                  "for locations or paths");
+        return 1;
+    }
+    if (cfg.mode == EDLIB_MODE_HW || cfg.mode == EDLIB_MODE_SHW) {
+        set_error("self batches are global (EDLIB_MODE_NW): %s distances are not symmetric, pass the set as queries and "
+                  "as targets of a cross batch", cfg.mode == EDLIB_MODE_HW ? "HW" : "SHW");
+        return 1;
+    }
+    if (cfg.mode != EDLIB_MODE_NW) { set_error("unknown mode"); return 1; }
+    if (cfg.k < 0) {
+        set_error("grouped self batches are hit lists and need config.k >= 0 (got %d; there is no dense grouped form: the "
+                  "condensed vector has no meaning across groups -- pass a k that bounds the distances wanted)", cfg.k);
+        return 1;
+    }
+    if (n < 0 || (n > 0 && !offIn)) { set_error("bad batch shape"); return 1; }
+    std::vector<long long> off;
+    if (copy_offsets(offIn, n, "sequence", off) || check_device(device)) return 1;
+    keep_config(cfg, cfg_, eqs_);
+    device_ = device; nq_ = nt_ = n; hits_ = true; strands_ = false; self_ = true; grouped_ = true;
+    const long long base = off[0], bytes = off[n] - base;
+    auto len = [&](int i) { return (int)(off[i + 1] - off[i]); };
+    auto key = [](int i, int j) { return ((u64)(uint32_t)std::min(i, j) << 32) | (uint32_t)std::max(i, j); };
+    auto inWindow = [&](int a, int b) {
+        const long long d = (long long)len(a) - len(b);
+        return (d < 0 ? -d : d) <= cfg.k;
+    };
+    // the members of every group, ascending: byGroup[memberOff[g] .. memberOff[g + 1]), groupOf[i] = g
+    std::vector<int> byGroup(n), groupOf(n), memberOff(1, 0);
+    for (int i = 0; i < n; ++i) byGroup[i] = i;
+    std::sort(byGroup.begin(), byGroup.end(), [&](int a, int b) { return groups[a] != groups[b] ? groups[a] < groups[b] : a < b; });
+    stats = EdlibAmdBatchStats{};
+    {   // per group: its pairs, and the sum over i < j of m_i m_j = ((sum m)^2 - sum m^2) / 2
+        long long pairs = 0;
+        unsigned __int128 cells = 0;
+        for (int a = 0; a < n;) {
+            int b = a;
+            unsigned __int128 sum = 0, sq = 0;
+            for (; b < n && groups[byGroup[b]] == groups[byGroup[a]]; ++b) {
+                groupOf[byGroup[b]] = (int)memberOff.size() - 1;
+                sum += (unsigned __int128)len(byGroup[b]);
+                sq += (unsigned __int128)len(byGroup[b]) * (unsigned __int128)len(byGroup[b]);
+            }
+            pairs += (long long)(b - a) * (b - a - 1) / 2;
+            cells += (sum * sum - sq) / 2;
+            memberOff.push_back(b);
+            a = b;
+        }
+        cells_ = (size_t)pairs;
+        stats.cells = (long long)cells;
+    }
+
+    build_tables(tab_, reinterpret_cast<const uint8_t*>(seqs) + base, bytes, eqs_.data(), (int)eqs_.size());
+    const bool wide = tab_.sigmaT > kCrossMaxSyms;
+    syms_ = peq_syms(tab_.sigmaT);
+    std::vector<int> inK, empties, outK;
+    for (int i = 0; i < n; ++i) {
+        if (len(i) == 0) empties.push_back(i);
+        else if (!wide && len(i) <= 32 * kCrossMaxQueryWords) inK.push_back(i);
+        else outK.push_back(i);
+    }
+
+    pool_quarantine(false);
+    DeviceGuard guard(device_);
+    EDLIB_AMD_HIP(guard.status);
+    if (openStream()) return 1;
+    EDLIB_AMD_HIP(d_near_.alloc(3 * (size_t)n));
+    EDLIB_AMD_HIP(d_best_.alloc(6 * (size_t)n));
+    EDLIB_AMD_HIP(d_bkey_.alloc(4 * (size_t)n));
+    if (sizeHitList(std::max<long long>(1LL << 20, 2LL * n))) return 1;
+
+    // (what a pair batch that gathers from this one is checked against: CrossBatch::gatherSource)
+    tlenHost_.resize((size_t)n);
+    for (int i = 0; i < n; ++i) tlenHost_[i] = len(i);
+    inPack_.assign((size_t)n, 0);
+
+    // ---- the kernel's share
+    if (inK.size() >= 2) {
+        SelfGroupsLayout lay = self_groups_layout(std::move(inK), [&](int i) { return groups[i]; }, len, cfg.k,
+                                                  kCrossMaxQueryWords);
+        numSorted_ = (int)lay.order.size();
+        for (int i : lay.order) inPack_[i] = 1;
+        for (int m : lay.tlen) sortedCols_ += m;
+        // the pool goes up once: the pack reads it as the targets, the Peq build as the queries
+        if (uploadQueries(seqs, off, false) || packTargets(d_qpool_.p, d_qoff_.p, lay.order, lay.tlen)) return 1;
+        EDLIB_AMD_HIP(d_tlen_.alloc(numSorted_));
+        EDLIB_AMD_HIP(hipMemcpy(d_tlen_.p, lay.tlen.data(), numSorted_ * sizeof(int), hipMemcpyHostToDevice));
+        for (SelfGroupsWordGroup& w : lay.wordGroups) {
+            std::unique_ptr<Group> g(new Group);
+            g->words = w.words; g->qt = w.qt; g->tiles = w.tiles; g->wordSteps = w.wordSteps;
+            g->numItems = (int)(w.items.size() / 3);
+            if (allocGroup(*g, w.perm)) return 1;
+            EDLIB_AMD_HIP(g->d_rank.alloc(g->slots)); EDLIB_AMD_HIP(g->d_end.alloc(g->slots));
+            EDLIB_AMD_HIP(g->d_items.alloc(std::max<size_t>(w.items.size(), 3)));
+            EDLIB_AMD_HIP(hipMemcpy(g->d_rank.p, w.rank.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(g->d_end.p, w.end.data(), g->slots * sizeof(int), hipMemcpyHostToDevice));
+            EDLIB_AMD_HIP(hipMemcpy(g->d_items.p, w.items.data(), w.items.size() * sizeof(int), hipMemcpyHostToDevice));
+            groups_.push_back(std::move(g));
+        }
+    }
+
+    // ---- the pairs answered off the kernel, inside their groups: those with an empty sequence here, the rest by one pair batch
+    auto members = [&](int i) { return std::make_pair(byGroup.begin() + memberOff[groupOf[i]], byGroup.begin() + memberOff[groupOf[i] + 1]); };
+    for (int e : empties) {
+        const auto m = members(e);
+        for (auto it = m.first; it != m.second; ++it) {
+            const int x = *it;
+            if (x == e || (len(x) == 0 && x < e)) continue;          // two empty sequences: once
+            selfOther_.push_back(key(e, x));
+            selfEmptyVal_.push_back(len(x));
+        }
+    }
+    {
+        PairPool pool;
+        long long np = 0;
+        std::vector<char> isOut(n, 0);
+        for (int i : outK) isOut[i] = 1;
+        for (int i : outK) {
+            const auto m = members(i);
+            for (auto it = m.first; it != m.second && np <= 0x7fffffffLL; ++it) {
+                const int x = *it;
+                if (x == i || len(x) == 0 || (isOut[x] && x < i)) continue;   // two such sequences: once
+                if (!inWindow(i, x) || ++np > 0x7fffffffLL) continue;
+                const int lo = std::min(i, x), hi = std::max(i, x);
+                pool.add(seqs + off[lo], len(lo), false, seqs + off[hi], len(hi));
+                selfOther_.push_back(key(lo, hi));
+            }
+        }
+        if (np > 0x7fffffffLL) {
+            set_error("grouped self batch: too many pairs outside the kernel's envelope (more than 2^31 - 1): sequences above "
+                      "%d bases or a set with more than %d symbols", 32 * kCrossMaxQueryWords, kCrossMaxSyms);
+            return 1;
+        }
+        if (np > 0) {
+            longPairs_.reset(new Batch);
+            if (pool.init(*longPairs_, cfg_, device)) return 1;
+        }
+    }
+    otherCells_ = (long long)selfOther_.size();
+    if (otherCells_ > 0) {
+        EDLIB_AMD_HIP(h_vals_.alloc((size_t)otherCells_ * sizeof(int)));
+        std::copy(selfEmptyVal_.begin(), selfEmptyVal_.end(), reinterpret_cast<int*>(h_vals_.p));
     }
     return 0;
 }

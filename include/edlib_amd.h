@@ -376,6 +376,26 @@ typedef struct {
 } EdlibAmdSelfHits;
 EDLIB_API int edlibAmdBatchSelfHits(EdlibAmdBatch* batch, EdlibAmdSelfHits* out);
 
+/* A hit-list self batch over a partitioned set (UMIs per cell and gene, clonotypes per V/J gene or sample, duplicates per
+ * locus): groups[i] is any int label of sequence i, negative values included; sequences with equal labels form a group,
+ * which need not be contiguous in the input.  Pair (i, j), i < j, exists only where groups[i] == groups[j], and every view
+ * -- edlibAmdBatchSelfHits, edlibAmdBatchSelfView with EDLIB_AMD_SELF_NEAREST, edlibAmdBatchSelfComponents,
+ * edlibAmdBatchSelfNeighbors, a pair batch filled by edlibAmdBatchPairsSetCells -- reports exactly what
+ * edlibAmdBatchCreateSelfHits over each group alone would, with that group's indices mapped back to the whole set:
+ * partners ascend inside a row, the key rule of nearest and neighbours is unchanged, and a pair with an empty sequence is
+ * the other's length whatever k, inside a group only.  One Create, one upload and one launch sequence whatever the number
+ * of groups; pairs across groups are neither scanned nor listed.
+ * Accepted: what edlibAmdBatchCreateSelfHits accepts (NW, DISTANCE, k >= 0, additionalEqualities); groups == NULL is
+ * refused and names edlibAmdBatchCreateSelfHits.  There is no dense grouped form (a condensed vector has no meaning across
+ * groups: EdlibAmdSelfView.editDistance stays NULL, numPairs counts the pairs inside groups) and no both-strand one.
+ * Routing is a self batch's, inside groups: sequences up to 256 bases over at most 16 symbols in the whole set on the
+ * grouped instantiation of the self kernel (Stats.path bit 3), same-group pairs with a longer sequence and every
+ * same-group pair of a set with more symbols through one internal pair batch (bit 1; at most 2^31 - 1 pairs).
+ * Stats.cells is the sum over groups of the sum of length i * length j over i < j; Stats.word_steps the sum of
+ * ceil(min / 32) * max over the same-group pairs the kernel scans (both with bases, both <= 256, lengths within k). */
+EDLIB_API EdlibAmdBatch* edlibAmdBatchCreateSelfHitsGrouped(
+    const char* seqs, const long long* offsets, int numSequences, const int* groups, EdlibAlignConfig config, int device);
+
 /* Self batches on both strands (sequences of unknown orientation: amplicons, UMIs, barcodes, k-mer sets): the same
  * arguments, routing and refusals as the two Creates above -- checked before the device is looked for, with the same
  * messages, and numSequences above 0x3fffffff is refused too -- but pair (i, j), i < j, is the better of
